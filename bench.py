@@ -10,8 +10,15 @@ cross-GPU mail is exchanged with RCCL once per superstep.
 A "step" is one BSP superstep (one Mailbox.run round over every actor with
 mail) = 1M deliveries per GPU.  Inputs are resident in HBM before timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: build the ring, `--warmup` untimed
+supersteps, `--steps` timed ones, the result line.  `--dump-outputs DIR` also writes what the
+timed supersteps left behind (actor state and counters after the last timed one) as
+DIR/<name>.npy; the inputs are the same from run to run, so two builds can be compared array
+for array.  `--full` adds everything else to the line: the per-kernel profile and roofline of
+the headline, the 100M-actor point, the other BASELINE configs and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -36,6 +43,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--actors-per-gpu", type=int, default=N_PER_GPU)
     ap.add_argument("--hops", type=int, default=256)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed supersteps left (after the last one) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel profile and roofline, the "
+                         "100M-actor point, the other BASELINE configs, the CPU baseline (the options below)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--large-actors", type=int, default=100_000_000,
                     help="whole-job actor count of the second operating point (0 = skip)")
@@ -370,6 +382,61 @@ def summary(out: dict) -> dict:
     return s
 
 
+DUMP_BUDGET = 48 << 20  # bytes of actor state written by --dump-outputs (the whole dump stays under 64 MB)
+
+
+def dump_outputs(eng, out_dir: str, world: int, rank: int) -> None:
+    """What a caller of the timed path holds after its last superstep: every actor's state words
+    (u64 -> float64, exact below 2^53), its alive flag (float32) and the engine's counters
+    (float64, in the order of COUNTERS), as <out_dir>/<name>.npy.  Above DUMP_BUDGET the actors
+    written are a fixed sample (sorted rows of a seeded choice; `actor_ids` names them)."""
+    import numpy as np
+    d = pathlib.Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    words, alive = eng.read_state()
+    n = words.shape[0]
+    rows = DUMP_BUDGET // (8 * words.shape[1] + 4 + 8)
+    ids = np.arange(n, dtype=np.int64)
+    if n > rows:
+        ids = np.sort(np.random.default_rng(20240607).choice(n, size=rows, replace=False))
+    st = eng.stats()
+    suffix = f"_rank{rank}" if world > 1 else ""
+    np.save(d / f"state_words{suffix}.npy", words[ids].astype(np.float64))
+    np.save(d / f"alive{suffix}.npy", alive[ids].astype(np.float32))
+    np.save(d / f"actor_ids{suffix}.npy", ids.astype(np.float64))
+    np.save(d / f"counters{suffix}.npy", np.array([getattr(st, k) for k in COUNTERS], dtype=np.float64))
+
+
+COUNTERS = ("delivered", "dead_letters", "unhandled", "emitted", "staged", "supersteps", "in_flight")
+
+
+def headline(args, world: int, value: float, step_time: float, n_total: int, hops: int, steps_done: int,
+             cfg_words: int) -> dict:
+    """The result line of a plain run (a --full run adds its other objects to it)."""
+    superstep_bytes = (12 + 12 + 16 * cfg_words + 2) * args.actors_per_gpu
+    return {
+        "metric": "messages delivered/sec (whole node) at 1M and 100M actors; % HBM roofline",
+        "value": value,
+        "unit": "msg/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": step_time * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic (deterministic SplitMix64-seeded token ring; integer payloads)",
+        "config": {"workload": "C2 token ring, 1M actors/GPU, 1 token/actor, RING behaviour, throughput=5, "
+                               "unbounded mailbox" + (", hash-sharded (ShardRegion extractShardId), RCCL exchange"
+                                                      if world > 1 else ""),
+                   "actors": n_total, "actors_per_gpu": args.actors_per_gpu, "hop_budget": hops,
+                   "supersteps_timed": int(steps_done), "parallelism": f"shard{world}"},
+        "roofline": {"bound": "hbm", "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                     "superstep_frac": superstep_bytes / step_time / 1e9 / PEAK_HBM_GBS},
+    }
+
+
 def reduce_ranks(elapsed: float, delivered: int, world: int):
     """MAX elapsed and SUM delivered over ranks."""
     if world == 1:
@@ -408,6 +475,18 @@ def main():
     eng, elapsed, delivered, steps_done = timed_ring(n_total, hops, args.warmup, args.steps, world, rank, local,
                                                      msg_capacity=int(2 * args.actors_per_gpu * 1.25) if world > 1 else 0,
                                                      keep=True)
+    if args.dump_outputs:  # (before the profiled supersteps of --full move the state on)
+        dump_outputs(eng, args.dump_outputs, world, rank)
+    if not args.full:
+        cfg_words = eng.cfg.n_words
+        eng.close()
+        elapsed, delivered = reduce_ranks(elapsed, delivered, world)
+        if rank == 0:
+            print(json.dumps(headline(args, world, delivered / elapsed, elapsed / max(args.steps, 1), n_total, hops,
+                                      steps_done, cfg_words)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # per-kernel HIP-event timing on the engine's stream (eager launches: the
     # event pairs bracket every kernel); kernel durations are launch-mode independent
@@ -501,27 +580,10 @@ def main():
             traffic = None
     step_time = elapsed / max(args.steps, 1)
     superstep_bytes = (12 + 12 + 16 * cfg_words + 2) * local_msgs_per_step
-    out = {
-        "metric": "messages delivered/sec (whole node) at 1M and 100M actors; % HBM roofline",
-        "value": value,
-        "unit": "msg/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": step_time * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (deterministic SplitMix64-seeded token ring; integer payloads)",
-        "config": {"workload": "C2 token ring, 1M actors/GPU, 1 token/actor, RING behaviour, throughput=5, "
-                               "unbounded mailbox" + (", hash-sharded (ShardRegion extractShardId), RCCL exchange"
-                                                      if world > 1 else ""),
-                   "actors": n_total, "actors_per_gpu": args.actors_per_gpu, "hop_budget": hops,
-                   "supersteps_timed": int(steps_done), "profiled_supersteps": prof_steps,
-                   "parallelism": f"shard{world}"},
-        "kernel_ms": {k: {"total_ms": round(v["total_ms"], 4), "launches": v["launches"]} for k, v in prof.items()},
-    }
+    out = headline(args, world, value, step_time, n_total, hops, steps_done, cfg_words)
+    del out["roofline"]  # (the full object goes last, below)
+    out["config"]["profiled_supersteps"] = prof_steps
+    out["kernel_ms"] = {k: {"total_ms": round(v["total_ms"], 4), "launches": v["launches"]} for k, v in prof.items()}
     if world == 1 and not args.no_configs:
         try:
             out["configs"] = other_configs(args.quick_configs)

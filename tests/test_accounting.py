@@ -71,6 +71,27 @@ def test_bench_kernel_rooflines():
     assert "bucket_apply" not in r  # (no launches: no roofline)
 
 
+def test_bench_plain_line(monkeypatch):
+    """A plain run's result line: the headline fields, ms_per_step = the timed seconds / --steps, and
+    nothing that needs a run of its own (those objects come with --full, off by default)."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 20
+    elapsed = 20 * 14e-6
+    line = bench.headline(args, 1, 20 * 1_000_000 / elapsed, elapsed / args.steps, 1_000_000, 256, 20, 1)
+    assert line["ms_per_step"] == pytest.approx(0.014) and line["steps"] == 20 and line["warmup"] == 5
+    assert line["unit"] == "msg/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["value"] == pytest.approx(1_000_000 / 14e-6)
+    assert line["roofline"]["superstep_frac"] == pytest.approx(42e6 / 14e-6 / 1e9 / bench.PEAK_HBM_GBS)
+    assert not {"kernel_ms", "configs", "cpu_baseline", "at_100M_actors", "summary"} & set(line)
+    json.dumps(line)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
+
+
 def test_bench_rooflines_after_a_dense_launch():
     """At 100M the block launch follows the dense launch and returns at entry when it took every
     bucket -- as the device's dense_left flags say (agx_profile_read items: the profiled dense launches

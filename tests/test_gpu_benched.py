@@ -303,3 +303,37 @@ def test_c1_ping_pong_as_benched(built):
     _assert_same(sg, so, a, b, "C1")
     sg, so, a, b = _run_both(w, msg_capacity=1 << 20, bucket_actors=2048)
     _assert_same(sg, so, a, b, "C1")
+
+
+# ------------------------------------------------------------------ the benchmark's own outputs
+def test_bench_plain_run_dumps_what_it_computed(built, tmp_path):
+    """A plain `bench.py` run (no --full) with --dump-outputs: the line carries ms_per_step for
+    exactly --steps timed supersteps and none of the --full objects, and the arrays it writes are
+    the ring after warmup + steps supersteps, bit for bit the BSP oracle's (float64 holds these
+    counts exactly).  5000 actors: three 2048-actor buckets, the last one partial."""
+    import subprocess
+    import sys
+    from oracle import BspOracle
+    root = pathlib.Path(__file__).resolve().parents[1]
+    n, warm, steps = 5000, 2, 3
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warm), "--actors-per-gpu", str(n), "--dump-outputs", str(out)],
+                       cwd=root, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["config"]["supersteps_timed"] == steps and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(n / (line["ms_per_step"] * 1e-3))
+    assert not {"kernel_ms", "configs", "cpu_baseline", "at_100M_actors", "summary"} & set(line)
+    w = wl.token_ring(n, line["config"]["hop_budget"])
+    ref = BspOracle(**w.engine_kwargs())
+    w.apply_to(ref)
+    so = ref.run(warm + steps)
+    wo, ao = ref.read_state()
+    ref.close()
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert sorted(got) == ["actor_ids", "alive", "counters", "state_words"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["actor_ids"], np.arange(n))
+    assert np.array_equal(got["state_words"], wo.astype(np.float64)) and np.array_equal(got["alive"], ao)
+    assert got["counters"].tolist() == [float(so[k]) for k in COUNT_KEYS]

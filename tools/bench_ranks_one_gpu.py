@@ -5,7 +5,8 @@ so RCCL accepts several ranks on one device (socket transport on loopback).  Che
 multi-rank bench path runs end to end and prints one JSON line; its numbers are not multi-GPU
 numbers (the ranks share one GPU).
 
-    python tools/bench_ranks_one_gpu.py --world 2 -- --steps 5 --warmup 2 --large-actors 0
+    python tools/bench_ranks_one_gpu.py --world 2 -- --steps 5 --warmup 2
+    python tools/bench_ranks_one_gpu.py --world 2 -- --steps 5 --warmup 2 --full --large-actors 0   (with the exchange figures)
 """
 import os
 import socket

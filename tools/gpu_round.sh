@@ -6,7 +6,8 @@ set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${1:-r01}
-B1M="--no-cpu-baseline --large-actors 0 --no-configs"
+B1M="--full --no-cpu-baseline --large-actors 0 --no-configs"
+BENCH_ARGS="--full ${BENCH_ARGS}"
 fail() { echo "$1 failed"; tail -30 "$2"; exit 1; }
 
 if [ -z "$SKIP_TESTS" ]; then

@@ -2,15 +2,19 @@
 # One GPU session on an MI355X box (tools/gpu_run.sh TAG).  Steps are chosen by environment:
 #   BUILD=1   rebuild libakka_gpu.so on the box from the sources (proves build() there; logs time)
 #   TESTS=1   pytest -m gpu (TEST_ARGS: extra pytest arguments, e.g. -k expr)
-#   BENCH=1   bench.py ${BENCH_ARGS} -> TAG_bench.json
+#   BENCH=1   bench.py --full ${BENCH_ARGS} -> TAG_bench.json
 #   PROF=1    rocprofv3 --kernel-trace --stats of bench.py ${PROF_ARGS}
 #   PMC="FETCH_SIZE WRITE_SIZE"  one rocprofv3 --pmc pass per group (PMC_ARGS = bench.py arguments)
+#   (PROF_ARGS / PMC_ARGS default to the --full ring points, 1M and 100M, without configs and CPU baseline)
 #   CMD="..." any extra command (run last, under its own time limit)
 # Every GPU step has its own time limit; the first failure ends the script.
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${1:-run}
+BENCH_ARGS="--full ${BENCH_ARGS}"
+PROF_ARGS=${PROF_ARGS:---full --no-cpu-baseline --no-configs}
+PMC_ARGS=${PMC_ARGS:---full --no-cpu-baseline --no-configs --steps 40 --warmup 4}
 fail() { echo "$1 failed"; tail -40 "$2"; exit 1; }
 if [ -n "$BUILD" ]; then
   t0=$(date +%s)
