@@ -23,6 +23,14 @@ hipError_t agx_launch_apply_g4(uint32_t, uint32_t, bool, dim3, hipStream_t, cons
 hipError_t agx_launch_apply_g5(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_apply_g6(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_apply_g7(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_prio_g0(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_prio_g1(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_prio_g2(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_prio_g3(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_prio_g4(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_prio_g5(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_prio_g6(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_prio_g7(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_tiny_g0(uint32_t, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_tiny_g1(uint32_t, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_tiny_g2(uint32_t, dim3, hipStream_t, const BucketArgs&);
@@ -85,6 +93,27 @@ hipError_t group_dispatch(uint32_t vid, uint32_t mode, bool skew, dim3 g, hipStr
     if constexpr (kVariantGroup[V] == AGX_VGROUP)
       if (vid == V) return launch_v<V>(mode, skew, g, s, ba);
     return group_dispatch<V + 1>(vid, mode, skew, g, s, ba);
+  }
+}
+
+// the prioritised fast launch (k_bucket_apply<.., kPrio>) of the catch-all plain variants of this group
+template <uint32_t V>
+hipError_t prio_dispatch(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
+  if constexpr (V >= V_N) {
+    return hipErrorInvalidValue;
+  } else {
+    if constexpr (kVariantGroup[V] == AGX_VGROUP && (V == V_ALL || V == V_ALL_COMPILED))
+      if (vid == V) {
+        constexpr uint32_t M = kVariants[V].km;
+        if (mode == M_FUSED)
+          hipLaunchKernelGGL((k_bucket_apply<false, M, true, false, false, true>), g, dim3(kBThreads), 0, s, ba);
+        else if (mode == M_BYPASS)
+          hipLaunchKernelGGL((k_bucket_apply<false, M, false, false, false, true>), g, dim3(kBThreads), 0, s, ba);
+        else
+          return hipErrorInvalidValue;
+        return hipGetLastError();
+      }
+    return prio_dispatch<V + 1>(vid, mode, g, s, ba);
   }
 }
 
@@ -177,6 +206,11 @@ hipError_t AGX_GROUP_FN(uint32_t vid, uint32_t mode, bool skew, dim3 g, hipStrea
   return group_dispatch<0>(vid, mode, skew, g, s, ba);
 }
 
+hipError_t AGX_CAT(agx_launch_apply_prio_g, AGX_VGROUP)(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s,
+                                                        const BucketArgs& ba) {
+  return prio_dispatch<0>(vid, mode, g, s, ba);
+}
+
 #if AGX_VGROUP == 0
 hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 g, hipStream_t s, const BucketArgs& ba) {
   if (vid >= V_N) return hipErrorInvalidValue;
@@ -189,6 +223,19 @@ hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 g, hipS
     case 5: return agx_launch_apply_g5(vid, mode, skew, g, s, ba);
     case 6: return agx_launch_apply_g6(vid, mode, skew, g, s, ba);
     default: return agx_launch_apply_g7(vid, mode, skew, g, s, ba);
+  }
+}
+hipError_t agx_launch_apply_prio(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
+  if (vid != V_ALL && vid != V_ALL_COMPILED) return hipErrorInvalidValue;
+  switch (kVariantGroup[vid]) {
+    case 0: return agx_launch_apply_prio_g0(vid, mode, g, s, ba);
+    case 1: return agx_launch_apply_prio_g1(vid, mode, g, s, ba);
+    case 2: return agx_launch_apply_prio_g2(vid, mode, g, s, ba);
+    case 3: return agx_launch_apply_prio_g3(vid, mode, g, s, ba);
+    case 4: return agx_launch_apply_prio_g4(vid, mode, g, s, ba);
+    case 5: return agx_launch_apply_prio_g5(vid, mode, g, s, ba);
+    case 6: return agx_launch_apply_prio_g6(vid, mode, g, s, ba);
+    default: return agx_launch_apply_prio_g7(vid, mode, g, s, ba);
   }
 }
 hipError_t agx_launch_ring(uint32_t vid, bool tiny, dim3 g, hipStream_t s, const BucketArgs& ba, const RingArgs& ra) {

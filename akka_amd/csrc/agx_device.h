@@ -36,11 +36,20 @@ struct DevParams {
   // actor-major pairs of a two-word engine (sa 2, sw 1: one line holds both words of 8 actors, so
   // a sparse superstep touches one state line per activation instead of two)
   uint32_t sa, sw;
+  // priority mailboxes (agx_set_mailbox_priority): bit c = mailbox class c has a priority table (ptab below)
+  uint32_t pmask;
   // CRDT state gossips (agx_crdt.h): snapshot rows, row-major, `pw` u32 each.
   // heap = 2 x heap_rows rows (ping-pong by superstep parity); rx = rows
   // received from other ranks this superstep (handle - heap_rows).
   uint32_t* heap;
-  const uint32_t* rx;
+  // (an engine has CRDT kinds or priority mailboxes, never both -- agx_set_mailbox_priority: one slot)
+  union {
+    const uint32_t* rx;
+    // priority mailboxes, read only by the prioritised k_bucket_apply instantiations: the classes' tables
+    // ptab[class * 256 + tag] (lower = dequeued first), then one byte per bucket, != 0 when the bucket
+    // holds an actor of a prioritised class (kPrioBucketOff; written on the host when mailboxes are bound)
+    const uint8_t* ptab;
+  };
   uint32_t* heap_top;       // [2] rows allocated in heap[parity]
   const uint32_t* step;     // superstep counter (bumped by the first kernel of a step)
   uint32_t heap_rows, pw, gossip_f;
@@ -83,6 +92,17 @@ __device__ __forceinline__ void mbox_limits(const DevParams& P, uint32_t abyte, 
   }
   C = P.mcap[(abyte >> 1) & (AGX_MAX_MAILBOX_CLASSES - 1)];
   T = C && P.Tr > C ? C : P.Tr;
+}
+
+constexpr uint32_t kPrioBucketOff = AGX_MAX_MAILBOX_CLASSES * 256u;  // DevParams.ptab: the per-bucket marks
+// Does the actor's mailbox class carry a priority table (P.pmask; class 0 when no classes are set)?
+__device__ __forceinline__ bool mbox_prioritised(const DevParams& P, uint32_t abyte) {
+  return (P.pmask >> ((abyte >> 1) & (AGX_MAX_MAILBOX_CLASSES - 1))) & 1u;
+}
+// The priority of a message in that class's queue: the table entry of its tag (payload >> 24);
+// lower is dequeued first (PriorityGenerator, Mailbox.scala:726-816; control-aware: 0 / 1, :867-1025)
+__device__ __forceinline__ uint32_t mbox_priority(const DevParams& P, uint32_t abyte, uint32_t pay) {
+  return P.ptab[((abyte >> 1) & (AGX_MAX_MAILBOX_CLASSES - 1)) * 256u + (pay >> 24)];
 }
 
 // A tell to a host-side actor (agx_set_outbound): appended to the outbox (when `write`); returns

@@ -120,6 +120,13 @@ struct agx_engine {
   uint32_t mcap[AGX_MAX_MAILBOX_CLASSES] = {0};
   uint32_t mclass_set = 1u;  // bit c: class c configured (class 0 always)
   bool mclasses = false;     // some class other than 0 configured: kernels look up per-actor limits
+  // priority tables (agx_set_mailbox_priority): bit c of prio_mask = class c has one.  An engine with a
+  // table launches the prioritised catch-all variants (apply_variant, launch_apply) and no wave / ring /
+  // dense / persistent launch
+  uint32_t prio_mask = 0;
+  std::vector<uint8_t> prio_tab = std::vector<uint8_t>(AGX_MAX_MAILBOX_CLASSES * 256u, 0);
+  uint8_t* d_ptab = nullptr;  // [classes][256] tables, then the [nb] bucket marks (DevParams.ptab)
+  bool prio_dirty = false;   // the tables or the actors' classes changed since the last upload
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -422,6 +429,7 @@ DevParams make_params(agx_engine* e) {
   P.Tr = e->Traw;
   P.nmc = e->mclasses ? 1u : 0u;
   for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) P.mcap[c] = e->mcap[c];
+  P.pmask = e->prio_mask;
   P.host_lo = e->host_lo;
   P.host_n = e->host_n;
   P.outbox = e->d_outbox;
@@ -451,6 +459,7 @@ DevParams make_params(agx_engine* e) {
   P.nstop = e->d_nstop;
   P.heap = e->d_heap;
   P.rx = e->d_rx;
+  if (e->prio_mask) P.ptab = e->d_ptab;  // (shares rx's slot: no CRDT kinds on an engine with priority tables)
   P.heap_top = e->d_heap_top;
   P.step = e->d_step;
   P.heap_rows = (uint32_t)e->heap_rows;
@@ -614,6 +623,8 @@ void skew_prepass(agx_engine* e, const BucketArgs& ba, const SkewArgs& ska) {
 // the k_bucket_apply variant for the registered behaviour kinds (agx_variants.h)
 uint32_t apply_variant(const agx_engine* e) {
   const uint32_t km = e->kinds_mask & ~kb(AGX_KIND_NONE);
+  if (e->prio_mask)  // priority mailboxes: the catch-all plain variants carry the order step (kPrio)
+    return (km & kb(AGX_KIND_COMPILED)) ? V_ALL_COMPILED : V_ALL;
   if (e->pw && e->delta_max) {  // delta-CRDT replication: the variants that carry the delta code
     if (km == kb(AGX_KIND_GCOUNTER)) return V_GC_DELTA;
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN_DELTA;
@@ -643,7 +654,7 @@ bool dense_on(const agx_engine* e, uint32_t vid) {
   // (k_dense_fused reads a fused bucket's table row one sender bucket per thread: nb <= 512, which
   // the fused superstep's <= 2^20 actors guarantee)
   if (e->fused && e->nb > (uint32_t)kDenseThreads) return false;
-  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live &&
+  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask &&
          (e->dense_launch == 1 || (e->dense_launch < 0 && vid == V_RING));
 }
 
@@ -825,7 +836,9 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       HIP_TRY(hipGetLastError());
       return AGX_OK;
     }
-    const bool tl = mode == M_BYPASS && !kVariants[vid].wide && e->tiny_launch && e->tiny_max && !e->skew_only;
+    // (priority mailboxes: the wave path drains in arrival order -- every bucket takes the block launch)
+    const bool tl = mode == M_BYPASS && !kVariants[vid].wide && e->tiny_launch && e->tiny_max && !e->skew_only &&
+                    !e->prio_mask;
     if (tl) {  // wave-per-bucket launch first; the block launch then takes the buckets it marked
       ba.blist = e->d_blist;
       ba.dense_first = dl ? 1u : 0u;
@@ -839,7 +852,12 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       Scope s(e, K_APPLY);
       BucketArgs bf = ba;
       if (e->stamps_skew) bf.dbg = nullptr;  // (diagnostic: stamps of the skew launch only)
-      HIP_TRY(agx_launch_apply(vid, mode, false, g, e->stream, bf));
+      if (e->prio_mask) {
+        if (mode == M_OWNER) return set_err(AGX_ESTATE, "priority mailboxes need a single-rank engine");
+        HIP_TRY(agx_launch_apply_prio(vid, mode, g, e->stream, bf));
+      } else {
+        HIP_TRY(agx_launch_apply(vid, mode, false, g, e->stream, bf));
+      }
     }
     if (!(mode == M_FUSED && e->strict_cap)) {
       if (!kVariants[vid].wide && mode == M_BYPASS) {
@@ -875,7 +893,7 @@ agx_status launch_staged_chunk(agx_engine* e) {
 // behaviours, every configured mailbox class bounded by <= kRingMaxC); from then on the classes
 // are fixed (agx_set_mailbox_class refuses a capacity the rings cannot hold).
 agx_status setup_rings(agx_engine* e) {
-  if (e->ring_live || !e->ring_res || e->pw) return AGX_OK;
+  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask) return AGX_OK;  // (a ring drains in arrival order)
   uint32_t cmax = 0;
   for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) {
     if (!((e->mclass_set >> c) & 1u)) continue;
@@ -919,7 +937,7 @@ agx_status setup_rings(agx_engine* e) {
 constexpr uint32_t kRingAutoC = 256;  // ring apply by default from this mailbox capacity up (setup_ring_apply)
 agx_status setup_ring_apply(agx_engine* e) {
   if (e->started || e->rg_on || e->ring_live || e->ring_res) return AGX_OK;
-  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0) return AGX_OK;
+  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask) return AGX_OK;
   // AGX_RING_APPLY=1 / 0 forces rings on / off; unset: on when the largest bounded capacity is at
   // least kRingAutoC.  Deep queues are where re-copying the backlog every superstep costs most (C3,
   // BoundedMailbox(1000): 4.67e8 -> 6.7e8 msg/s with rings, the sparse buckets a wave each); at
@@ -1014,6 +1032,20 @@ agx_status prepare_run(agx_engine* e) {
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->actors_dirty = false;
+    e->prio_dirty = e->prio_mask != 0;  // (mailboxes bound since: the per-bucket marks below)
+  }
+  if (e->prio_dirty) {  // priority tables and the buckets that hold an actor of a prioritised class
+    std::vector<uint8_t> pb(e->prio_tab);  // tables, then the bucket marks (kPrioBucketOff)
+    pb.resize(kPrioBucketOff + e->nb, 0);
+    for (uint64_t l = 0; l < e->n_local; ++l)
+      if ((e->prio_mask >> ((e->h_alive[l] >> 1) & (AGX_MAX_MAILBOX_CLASSES - 1))) & 1u) pb[kPrioBucketOff + (l >> e->bb)] = 1;
+    if (!e->d_ptab) {
+      AGX_TRY(dalloc(&e->d_ptab, pb.size()));
+      drop_graphs(e);  // (a kernel argument of the captured supersteps)
+    }
+    HIP_TRY(hipMemcpyAsync(e->d_ptab, pb.data(), pb.size(), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->prio_dirty = false;
   }
   if (e->fused && !e->hs_key.empty()) {
     // staged tells still on the device (a run of 0 supersteps) come first: staging order
@@ -1237,6 +1269,10 @@ agx_status read_counters(agx_engine* e, uint64_t* s) {
 agx_status error_status(const agx_engine* e, uint64_t err) {
   if (err & kErrRange)
     return set_err(AGX_ERANGE, "a GCounter/PNCounter slot exceeded 2^64 - 1 (u64 slots; the reference uses BigInt)");
+  if (err & kErrPrioTile)
+    return set_err(AGX_ECAPACITY, "a bucket of %u actors that holds a priority-mailbox actor received more than one "
+                   "tile of %d messages (backlog included): a prioritised actor's queue is ordered within one tile "
+                   "(smaller agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
   if (err & kErrCapacity)
     return set_err(AGX_ECAPACITY, "in-flight messages exceeded engine capacity (msg_capacity=%llu)",
                    (unsigned long long)e->cap);
@@ -1309,7 +1345,7 @@ bool persist_ok(agx_engine* e) {
       e->persist = (uint64_t)e->nb <= (uint64_t)per_cu * (uint64_t)ncu ? 1 : 0;
     (void)hipGetLastError();
   }
-  return e->persist == 1 && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
+  return e->persist == 1 && !e->prio_mask && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
          !e->recover_dense;
 }
 
@@ -2035,6 +2071,9 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
   const uint32_t pw = ru > kRowAlign ? (ru + kRowAlign - 1) / kRowAlign * kRowAlign : ru;
   if (pw <= e->pw) return AGX_OK;
   if (e->started) return set_err(AGX_ESTATE, "register CRDT kinds before the first agx_run");
+  if (e->prio_mask)
+    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a priority mailbox "
+                   "(agx_set_mailbox_priority): a state gossip's snapshot handle carries no message tag");
   const uint64_t rows = ((uint64_t)e->nb << e->bb) + e->cap;
   if (rows + e->cap > kHandleMask) return set_err(AGX_EINVAL, "CRDT kinds need msg_capacity < 2^28 - n_actors");
   hipFree(e->d_heap);
@@ -2448,6 +2487,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_rg_dp);
   hipFree(e->d_ring_next); hipFree(e->d_ring_free); hipFree(e->d_ring_total);
   hipFree(e->d_orw); hipFree(e->d_orm); hipFree(e->d_orw_n);
+  hipFree(e->d_ptab);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -2543,6 +2583,34 @@ agx_status agx_set_mailbox(agx_engine* e, uint64_t first_id, uint64_t count, uin
     e->h_alive[l] = (uint8_t)((e->h_alive[l] & 1u) | (cls << 1));
   }
   e->actors_dirty = true;
+  return AGX_OK;
+}
+
+// Mailbox.scala:726-816 (priority / stable priority), :867-1025 (control-aware)
+agx_status agx_set_mailbox_priority(agx_engine* e, uint32_t cls, const uint8_t prio[256]) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (e->R > 1)
+    return set_err(AGX_EINVAL, "priority mailboxes need a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
+  if (e->pw)
+    return set_err(AGX_EINVAL, "priority mailboxes need an engine without CRDT kinds (one is registered): a state "
+                   "gossip's snapshot handle carries no message tag");
+  if (cls >= AGX_MAX_MAILBOX_CLASSES || !((e->mclass_set >> cls) & 1u))
+    return set_err(AGX_EINVAL, "mailbox class %u is not configured (agx_set_mailbox_class; classes 0..%u)", cls,
+                   AGX_MAX_MAILBOX_CLASSES - 1);
+  if (e->ring_live || e->rg_on)
+    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, drained in "
+                   "arrival order: set priority tables before the first run", e->ring_live ? e->ring_c : e->rg_c);
+  if (e->started) return set_err(AGX_ESTATE, "set mailbox priorities before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  if (prio) {
+    memcpy(e->prio_tab.data() + cls * 256u, prio, 256);
+    e->prio_mask |= 1u << cls;
+  } else {
+    memset(e->prio_tab.data() + cls * 256u, 0, 256);
+    e->prio_mask &= ~(1u << cls);
+  }
+  e->prio_dirty = e->prio_mask != 0;
+  drop_graphs(e);  // the variant and the tables are captured in the superstep graphs
   return AGX_OK;
 }
 

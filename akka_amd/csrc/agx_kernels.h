@@ -53,6 +53,7 @@ enum { ST_DELIVERED = 0, ST_DEAD = 1, ST_UNHANDLED = 2, ST_EMITTED = 3, ST_STEPS
 constexpr uint64_t kErrCapacity = 1;
 constexpr uint64_t kErrRange = 2;  // a counter slot wrapped past 2^64 - 1 (AGX_ERANGE)
 constexpr uint64_t kErrBarrier = 4;  // a persistent superstep launch's grid barrier timed out (AGX_EDEVICE)
+constexpr uint64_t kErrPrioTile = 8;  // a bucket with a priority-mailbox actor exceeded one LDS tile (AGX_ECAPACITY)
 // per-block counters of k_bucket_apply: delivered, dead, unhandled, emitted, active
 constexpr int kBStats = 5;
 constexpr uint32_t kMaxApplyGrid = 4096;
@@ -4040,12 +4041,77 @@ static __global__ void __launch_bounds__(kBThreads) k_skew_scatter(BucketArgs a,
   }
 }
 
+// Priority mailboxes (agx_set_mailbox_priority; Mailbox.scala:726-816, 867-1025): the
+// order step of a prioritised actor's superstep.  The bucket's inbox is in LDS sorted by actor, each
+// actor's segment in arrival position order (backlog -- already in priority order from the previous
+// superstep -- then arrivals, then staged tells).  Admission goes by that position (the first `keep`
+// of the segment, bucket_finish's rule); here the admitted messages [s0, s0 + keep) of every actor
+// whose class has a table are stably re-ranked by (priority, position): a message's new slot is s0 +
+// the number of admitted messages of its actor that precede it in that order (a counting rank over
+// the 8-bit priorities kept in LDS; quadratic in the queue, which one tile bounds).  The
+// non-admitted tail [s0 + keep, s0 + len) and every FIFO actor's segment stay where they are, so
+// bucket_finish drains, queues and counts dead letters by position exactly as without a table.
+__device__ __forceinline__ void prio_rerank(const BucketArgs& a, const BucketLds& L, uint32_t cnt) {
+  const DevParams& P = a.P;
+  const int tid = threadIdx.x;
+  const uint32_t amask = (1u << a.bb) - 1u;
+  uint8_t* const pr = reinterpret_cast<uint8_t*>(L.U);  // [kBucket] priority of inbox slot q (U is free here)
+  uint32_t sv[kBIpt], pv[kBIpt], s0[kBIpt], keep[kBIpt];
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) {
+    const uint32_t q = r * kBThreads + tid;
+    keep[r] = 0;
+    s0[r] = 0;
+    sv[r] = pv[r] = 0;
+    if (q < cnt) {
+      const uint32_t la = L.key[q] & amask, ab = L.alive[la];
+      if (mbox_prioritised(P, ab)) {
+        sv[r] = L.src[q];
+        pv[r] = L.pay[q];
+        pr[q] = (uint8_t)mbox_priority(P, ab, pv[r]);
+        const uint32_t b0 = L.seg[la], len = L.seg[la + 1] - b0;
+        uint32_t C, T;
+        mbox_limits(P, ab, C, T);
+        const uint32_t k = (C == 0 || len < C) ? len : C;  // admitted by arrival position
+        s0[r] = b0;
+        keep[r] = q - b0 < k ? k : 0u;
+      }
+    }
+  }
+  __syncthreads();
+  uint32_t to[kBIpt];
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) {
+    const uint32_t q = r * kBThreads + tid;
+    to[r] = q;
+    if (keep[r] > 1) {
+      const uint32_t mine = pr[q];
+      uint32_t rank = 0;
+      for (uint32_t i = s0[r]; i < s0[r] + keep[r]; ++i) {
+        const uint32_t x = pr[i];
+        rank += (x < mine || (x == mine && i < q)) ? 1u : 0u;
+      }
+      to[r] = s0[r] + rank;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r)  // (every moved message was read into registers before the barrier)
+    if (keep[r] > 1) {
+      L.src[to[r]] = sv[r];
+      L.pay[to[r]] = pv[r];
+    }
+  __syncthreads();
+}
+
 #ifndef AGX_WIDE_WPE
 #define AGX_WIDE_WPE 4  // CRDT (wide) variants: minimum waves per SIMD (4: 128 VGPRs; 2: 256, one block per CU)
 #endif
-template <bool kWide, uint32_t KM, bool kGather, bool kSkew, bool kOwner = false>
+// kPrio: priority mailboxes (prio_rerank above) -- the fast launches of the catch-all plain variants
+// of a single-rank engine with a priority table; every other instantiation compiles without it.
+template <bool kWide, uint32_t KM, bool kGather, bool kSkew, bool kOwner = false, bool kPrio = false>
 static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_bucket_apply(BucketArgs a) {
   constexpr bool kDefer = !kSkew;  // large inboxes are appended to the skew list
+  static_assert(!kPrio || (!kWide && !kSkew && !kOwner), "priority mailboxes: single-rank fast launches, plain behaviours");
   if (kOwner && a.halt && a.halt[0]) return;  // (device-resident multi-rank replay stopped)
   // key/src/pay carved from one array: group_tells reuses key+src as a 16 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t s_ksp[3 * kBucket];
@@ -4170,6 +4236,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           s_hi = a.bstart[b + 1];
         }
         s_g[5] = s_hi - s_lo > (uint32_t)kBucket || (kBypass && a.ring_of && a.ring_of[b]);  // (a ring bucket: skew path)
+        if constexpr (kPrio)  // the skew launches cannot keep a prioritised actor's order: loud, never wrong
+          if (s_g[5] && P.ptab[kPrioBucketOff + b]) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrPrioTile);
         if (kDefer && s_g[5]) a.skew_list[atomicAdd(skew_n, 1u)] = b;
       }
     } else {
@@ -4213,6 +4281,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         s_g[4] = ns;
         const uint32_t cnt = blc + tt + s_g[2];
         s_g[5] = cnt > (uint32_t)kBucket;
+        if constexpr (kPrio)  // (as the multi-pass launch above)
+          if (s_g[5] && P.ptab[kPrioBucketOff + b]) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrPrioTile);
         if (kDefer && s_g[5]) {
           a.skew_list[atomicAdd(skew_n, 1u)] = b;
           if (a.abort) a.abort[wpar] = a.slot + 1u;  // strict replay: the rest of it is void
@@ -4448,6 +4518,7 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         __syncthreads();
       }
       AGX_STAMP(a, 2);
+      if constexpr (kPrio) prio_rerank(a, L, cnt);
       bucket_finish<true, kWide, KM, kGather, kOwner>(a, L, b, lo, cnt, a0, na, wpar, 0u, acc, 0xFFFFFFFFu,
                                                       kEarly ? ex0 : nullptr, kEarly ? ex1 : nullptr);
     } else {

@@ -47,6 +47,10 @@ constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 
 // launch k_bucket_apply<variant vid, mode, skew> with `grid` x kBThreads threads on `s`
 // (defined in agx_apply.hip; returns hipErrorInvalidValue for an unknown combination)
 hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 grid, hipStream_t s, const BucketArgs& ba);
+// launch the prioritised fast launch k_bucket_apply<variant vid, mode, no skew, kPrio> (priority mailboxes,
+// agx_set_mailbox_priority): only the catch-all plain variants V_ALL / V_ALL_COMPILED in the modes M_FUSED /
+// M_BYPASS are instantiated (hipErrorInvalidValue otherwise)
+hipError_t agx_launch_apply_prio(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
 // launch k_tiny_apply<variant vid's kinds> (plain / compiled variants only: hipErrorInvalidValue otherwise)
 hipError_t agx_launch_tiny(uint32_t vid, dim3 grid, hipStream_t s, const BucketArgs& ba);
 // launch k_dense_apply<variant vid's kinds> (mode M_FUSED / M_OWNER: k_dense_fused) (plain / compiled variants only)

@@ -101,7 +101,99 @@ class NonBlockingBoundedMailbox(MailboxType):
     capacity: int
 
 
+def _no_push_timeout(name: str, push_timeout_s: float) -> None:
+    if push_timeout_s > 0:
+        raise ConfigurationException(
+            f"GPU mailboxes never block the sender: set mailbox-push-timeout-time = 0 "
+            f"({name} with pushTimeOut > 0 would block; Mailboxes.scala:238-249)")
+
+
+def priority_table(priority_by_tag) -> bytes:
+    """The engine's 256-entry u8 table (agx_set_mailbox_priority) of a PriorityGenerator
+    (Mailbox.scala:726-816 use it as the queue's comparator): `priority_by_tag` is a function
+    tag -> Int, a dict {tag: Int} (missing tags share the lowest priority, after every given one) or
+    a sequence of 256 Ints.  The Ints are replaced by their dense ranks -- the comparator's order and
+    its ties are all a priority queue uses -- so any Int range (Int.MaxValue included) fits 8 bits."""
+    if callable(priority_by_tag):
+        v = [int(priority_by_tag(t)) for t in range(256)]
+    elif isinstance(priority_by_tag, dict):
+        if any(not 0 <= int(t) <= 255 for t in priority_by_tag):
+            raise ConfigurationException("message tags are 8 bits (payload >> 24)")
+        last = max([int(x) for x in priority_by_tag.values()], default=0) + 1
+        v = [int(priority_by_tag.get(t, last)) for t in range(256)]
+    else:
+        v = [int(x) for x in priority_by_tag]
+        if len(v) != 256:
+            raise ConfigurationException("a priority table has one entry per message tag (256)")
+    rank = {x: i for i, x in enumerate(sorted(set(v)))}
+    return bytes(rank[x] for x in v)
+
+
+class UnboundedStablePriorityMailbox(MailboxType):
+    """UnboundedStablePriorityMailbox(cmp) (Mailbox.scala:779-794): lower priority first, FIFO among
+    equal priorities.  `priority_by_tag`: see priority_table."""
+
+    def __init__(self, priority_by_tag):
+        self.capacity = 0
+        self.priority_table = priority_table(priority_by_tag)
+
+    def __repr__(self):
+        return f"{type(self).__name__}(capacity={self.capacity})"
+
+
+class BoundedStablePriorityMailbox(UnboundedStablePriorityMailbox):
+    """BoundedStablePriorityMailbox(cmp, capacity, pushTimeOut) (Mailbox.scala:796-816): offer fails
+    (a DeadLetter) when the queue holds `capacity` messages, whatever the priority."""
+
+    def __init__(self, priority_by_tag, capacity: int, push_timeout_s: float = 0.0):
+        super().__init__(priority_by_tag)
+        if capacity < 0:
+            raise ValueError(f"The capacity for {type(self).__name__} can not be negative")
+        _no_push_timeout(type(self).__name__, push_timeout_s)
+        self.capacity = int(capacity)
+
+
+class UnboundedPriorityMailbox(UnboundedStablePriorityMailbox):
+    """UnboundedPriorityMailbox(cmp) (Mailbox.scala:726-742).  The reference leaves the order among
+    equal priorities unspecified; the engine's stable order is one legal order."""
+
+
+class BoundedPriorityMailbox(BoundedStablePriorityMailbox):
+    """BoundedPriorityMailbox(cmp, capacity, pushTimeOut) (Mailbox.scala:744-766)."""
+
+
+class UnboundedControlAwareMailbox(UnboundedStablePriorityMailbox):
+    """UnboundedControlAwareMailbox (Mailbox.scala:867-900): messages that extend ControlMessage --
+    here: whose tag is in `control_tags` -- are handed out before all others; two FIFO queues."""
+
+    def __init__(self, control_tags=()):
+        tags = {int(t) for t in control_tags}
+        if any(not 0 <= t <= 255 for t in tags):
+            raise ConfigurationException("control-tags are message tags (payload >> 24): 0..255")
+        super().__init__(lambda t: 0 if t in tags else 1)
+        self.control_tags = tuple(sorted(tags))
+
+
+class BoundedControlAwareMailbox(UnboundedControlAwareMailbox):
+    """BoundedControlAwareMailbox(capacity, pushTimeOut) (Mailbox.scala:902-1025): one capacity
+    over both queues."""
+
+    def __init__(self, capacity: int, control_tags=(), push_timeout_s: float = 0.0):
+        super().__init__(control_tags)
+        if capacity < 0:
+            raise ValueError("The capacity for BoundedControlAwareMailbox can not be negative")
+        _no_push_timeout("BoundedControlAwareMailbox", push_timeout_s)
+        self.capacity = int(capacity)
+
+
+def _control_tags(c: Config):
+    return c.get_value("gpu.control-tags") if c.has_path("gpu.control-tags") else ()
+
+
 _MAILBOX_FQCN = {
+    "akka.dispatch.UnboundedControlAwareMailbox": lambda c: UnboundedControlAwareMailbox(_control_tags(c)),
+    "akka.dispatch.BoundedControlAwareMailbox": lambda c: BoundedControlAwareMailbox(
+        c.get_int("mailbox-capacity"), _control_tags(c), c.get_duration_s("mailbox-push-timeout-time")),
     "akka.dispatch.UnboundedMailbox": lambda c: UnboundedMailbox(),
     "akka.dispatch.SingleConsumerOnlyUnboundedMailbox": lambda c: SingleConsumerOnlyUnboundedMailbox(),
     "akka.dispatch.BoundedMailbox": lambda c: BoundedMailbox(c.get_int("mailbox-capacity"),
@@ -138,16 +230,33 @@ class Mailboxes:
         self._cache[mailbox_id] = mt
         return mt
 
+    # The priority mailbox types are abstract in the reference: the user subclasses them with a
+    # comparator and names the subclass in `mailbox-type` (Mailboxes.scala:222-236 instantiates it with
+    # (ActorSystem.Settings, Config)).  Here the subclass is registered: fqcn -> factory(config).
+    _registry: dict = {}
+
+    @classmethod
+    def register(cls, fqcn: str, factory) -> None:
+        """Make `mailbox-type = "<fqcn>"` resolve to factory(config) -> MailboxType, e.g.
+        Mailboxes.register("com.example.MyPrio", lambda c: BoundedStablePriorityMailbox(
+            {1: 0, 2: 5}, c.get_int("mailbox-capacity"), c.get_duration_s("mailbox-push-timeout-time")))."""
+        if fqcn in _MAILBOX_FQCN:
+            raise ConfigurationException(f"[{fqcn}] is a built-in mailbox type")
+        cls._registry[fqcn] = factory
+
     @staticmethod
     def from_config(conf: Config, fqcn: str, where: str = "") -> MailboxType:
         if fqcn == "":
             raise ConfigurationException(f"The setting mailbox-type, defined in [{where}] is empty")
-        ctor = _MAILBOX_FQCN.get(fqcn)
+        ctor = _MAILBOX_FQCN.get(fqcn) or Mailboxes._registry.get(fqcn)
         if ctor is None:
             raise ConfigurationException(
                 f"Cannot instantiate MailboxType [{fqcn}], defined in [{where}]: not supported by the GPU dispatcher "
-                f"(supported: {sorted(_MAILBOX_FQCN)})")
-        return ctor(conf.with_fallback(REFERENCE_CONF.get_config("akka.actor.default-mailbox")))
+                f"(supported: {sorted(_MAILBOX_FQCN)}, and the types registered with Mailboxes.register)")
+        mt = ctor(conf.with_fallback(REFERENCE_CONF.get_config("akka.actor.default-mailbox")))
+        if not isinstance(mt, MailboxType):
+            raise ConfigurationException(f"the factory registered for [{fqcn}] did not return a MailboxType")
+        return mt
 
 
 # ------------------------------------------------------------------ typed behaviours
@@ -282,6 +391,9 @@ class GpuDispatcher:
             raise RuntimeError(f"dispatcher [{self.id}] is shut down")
         if self._engine is None:
             self._engine = GpuEngine(self._cfg)  # created lazily, like the executor service
+            table = getattr(self.mailbox_type, "priority_table", None)
+            if table is not None:  # a priority / control-aware mailbox type: the dispatcher's class 0
+                self._engine.set_mailbox_priority(0, table)
         return self._engine
 
     def is_throughput_deadline_time_defined(self) -> bool:
@@ -292,7 +404,8 @@ class GpuDispatcher:
         """actorOf for `count` actors with one behaviour: a contiguous ActorRef id range."""
         if mailbox is not None:
             mb = (mailboxes or self._cfg_mailboxes()).lookup(mailbox)
-            if mb.capacity != self.mailbox_type.capacity:
+            if mb.capacity != self.mailbox_type.capacity or \
+                    getattr(mb, "priority_table", None) != getattr(self.mailbox_type, "priority_table", None):
                 raise ConfigurationException(
                     f"dispatcher [{self.id}] runs one mailbox semantics (capacity {self.mailbox_type.capacity}); "
                     f"props asked for {mb}")

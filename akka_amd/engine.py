@@ -108,6 +108,14 @@ def _u32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.uint32))
 
 
+def priority_table(table) -> np.ndarray:
+    """256 u8 priorities by message tag from bytes or any sequence of 256 integers in [0, 255]."""
+    t = np.frombuffer(bytes(table), np.uint8) if isinstance(table, (bytes, bytearray)) else np.asarray(table)
+    if t.shape != (256,) or (np.asarray(t, np.int64) < 0).any() or (np.asarray(t, np.int64) > 255).any():
+        raise ValueError("a mailbox priority table is 256 values in [0, 255], one per message tag")
+    return np.ascontiguousarray(t.astype(np.uint8))
+
+
 def _ptr(a: np.ndarray, ty):
     return a.ctypes.data_as(ctypes.POINTER(ty))
 
@@ -168,6 +176,17 @@ class GpuEngine:
     def set_mailbox(self, first: int, count: int, cls: int) -> None:
         """Bind actors [first, first + count) to mailbox class `cls` (agx_set_mailbox)."""
         check(self.lib.agx_set_mailbox(self._h, first, count, cls))
+
+    def set_mailbox_priority(self, cls: int, table) -> None:
+        """A priority table for mailbox class `cls` (agx_set_mailbox_priority): 256 u8, the priority of
+        a message is table[payload >> 24], lower is dequeued first, equal priorities stay FIFO
+        (Unbounded/BoundedStablePriorityMailbox, Mailbox.scala:726-816; a control-aware mailbox is the
+        table 0 / 1, Mailbox.scala:867-1025).  None clears the table (FIFO)."""
+        if table is None:
+            check(self.lib.agx_set_mailbox_priority(self._h, cls, None))
+            return
+        t = priority_table(table)
+        check(self.lib.agx_set_mailbox_priority(self._h, cls, _ptr(t, ctypes.c_uint8)))
 
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox

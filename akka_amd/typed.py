@@ -426,6 +426,35 @@ def library(ring_stride: int = 1) -> dict:
     return {"counter": counter, "ring": ring, "stop_after": stop_after, "ping_pong": ping_pong}
 
 
+def echo(host_id: int) -> Behavior:
+    """The observer of the reference's mailbox specs (`case x => testActor ! x`,
+    akka-actor-tests/src/test/scala/akka/dispatch/ControlAwareDispatcherSpec.scala:50-52): every
+    message is told on, payload unchanged, to the host-side actor `host_id` (agx_set_outbound), so
+    the outbox shows the order in which the mailbox handed the messages out."""
+    st = State("count", "last")
+    return (ReceiveBuilder.create(st)
+            .on_any_message(lambda m, s: [s.count.inc(), s.last.set(m.payload), actor_ref(host_id).tell(m.payload),
+                                          Behaviors.same])
+            .build("echo"))
+
+
+def forwarder(n_actors: int, hop: int, stop_tag: int) -> Behavior:
+    """A tagged-message relay: a message with tag `stop_tag` stops the actor; a message from a
+    host-side sender (id >= n_actors) is echoed to it; any other message with a hop count (its
+    24-bit argument) above 0 goes on to the actor `hop` ids further with one hop less, tag kept.
+    State: messages handled, the last payload handled (order-sensitive)."""
+    st = State("count", "last")
+    seen = lambda m, s: [s.count.inc(), s.last.set(m.payload)]
+    return (ReceiveBuilder.create(st)
+            .on_any_message(lambda m, s: [s.count.inc(), Behaviors.stopped], test=lambda m: m.tag == stop_tag)
+            .on_any_message(lambda m, s: seen(m, s) + [m.sender.tell(m.payload), Behaviors.same],
+                            test=lambda m: m.sender.dst >= n_actors)
+            .on_any_message(lambda m, s: seen(m, s) + [self_ref(hop).tell(m.payload - 1), Behaviors.same],
+                            test=lambda m: m.arg > 0)
+            .on_any_message(lambda m, s: seen(m, s) + [Behaviors.same])
+            .build(f"forwarder{hop}"))
+
+
 SWITCH_ON, SWITCH_OFF, PING = MessageType("SwitchOn", 1), MessageType("SwitchOff", 2), MessageType("Ping", 3)
 
 

@@ -46,6 +46,8 @@ class Workload:
     mailbox_classes: dict = field(default_factory=dict)  # class -> capacity (agx_set_mailbox_class)
     mailboxes: list = field(default_factory=list)         # (first, count, class) (agx_set_mailbox)
     outbound: tuple | None = None                         # (first_host_id, n_host) (agx_set_outbound)
+    # class -> 256 priorities by message tag, bytes or a sequence (agx_set_mailbox_priority)
+    mailbox_priorities: dict = field(default_factory=dict)
 
     def engine_kwargs(self) -> dict:
         """Semantic parameters (shared by the GPU engine and the CPU oracles)."""
@@ -63,6 +65,8 @@ class Workload:
             target.set_mailbox_class(cls, cap)
         for first, count, cls in self.mailboxes:
             target.set_mailbox(first, count, cls)
+        for cls, table in self.mailbox_priorities.items():  # (empty: targets without the call are unaffected)
+            target.set_mailbox_priority(cls, table)
         if self.outbound is not None:
             target.set_outbound(*self.outbound)
         if self.ring_stride is not None:
@@ -460,3 +464,41 @@ def mailbox_mix(n: int = 4096, seed: int = 7, throughput: int = 3, capacity: int
         # host senders to every kind; the PINGPONG range answers them
         w.tells = (np.concatenate([dst, hd]), np.concatenate([src, hs]), np.concatenate([pay, hp]))
     return w
+
+
+# ------------------------------------------------------------------ priority and control-aware mailboxes
+PRIORITY_MIX_STOP_TAG = 9
+
+
+def priority_mix(n: int = 2048, seed: int = 1, throughput: int = 3, n_host: int = 8, tells_per_actor: float = 0.7,
+                 tables: bool = True) -> Workload:
+    """Four mailbox types in one dispatcher, two of them prioritised (agx_set_mailbox_priority;
+    Unbounded/BoundedStablePriorityMailbox, Mailbox.scala:726-816): quarters of the population on
+    class 1 (prioritised, unbounded), class 2 (prioritised, capacity 4), class 3 (FIFO, capacity 2)
+    and class 0 (FIFO, unbounded).  The actors are compiled relays (typed.forwarder, hops 1 and 5)
+    that pass tagged messages on with one hop less, echo the messages of host-side senders through
+    the outbox and stop on tag PRIORITY_MIX_STOP_TAG.  Destinations are skewed inside groups of 64
+    actors (offset 64 u^3), so many actors hold 2-40 messages while a bucket's load stays near
+    `tells_per_actor` per actor.  `tables=False`: the same population with every class FIFO."""
+    from . import typed
+    rng = np.random.default_rng(seed)
+    fa, fb = typed.forwarder(n, 1, PRIORITY_MIX_STOP_TAG), typed.forwarder(n, 5, PRIORITY_MIX_STOP_TAG)
+    tb = typed.compile_behaviors([fa, fb], max_emit=1)
+    h = n // 2
+    ranges = [(0, h, tb.kind_of(fa), None), (h, n - h, tb.kind_of(fb), None)]
+    m = max(1, int(n * tells_per_actor))
+    group = (rng.integers(0, max(1, n // 64), m) * 64).astype(np.int64)
+    dst = np.minimum(group + (64 * rng.random(m) ** 3).astype(np.int64), n - 1).astype(np.uint32)
+    src = rng.integers(0, n, m).astype(np.uint32)
+    if n_host:
+        hs = rng.random(m) < 0.15
+        src[hs] = rng.integers(n, n + n_host, int(hs.sum())).astype(np.uint32)
+    tag = rng.integers(1, 8, m).astype(np.uint32)
+    tag[rng.random(m) < 0.03] = PRIORITY_MIX_STOP_TAG
+    pay = (tag << np.uint32(24)) | rng.integers(0, 6, m).astype(np.uint32)
+    prio = bytes([3, 0, 2, 1, 2, 0, 3, 1][t % 8] for t in range(256))  # (the stop tag overtakes: priority 0)
+    q = n // 4
+    return Workload("priority_mix", n, 2, 1, throughput, 0, ranges, behaviors=tb, tells=(dst, src, pay),
+                    mailbox_classes={1: 0, 2: 4, 3: 2}, mailboxes=[(0, q, 1), (q, q, 2), (2 * q, q, 3)],
+                    outbound=(n, n_host) if n_host else None,
+                    mailbox_priorities={1: prio, 2: prio} if tables else {})

@@ -31,6 +31,10 @@
  *   agx_set_mailbox_class / agx_set_mailbox
  *                       <- Mailboxes.lookupConfigurator / getMailboxType per actor
  *                          (akka-actor/.../dispatch/Mailboxes.scala:140-191,204-260)
+ *   agx_set_mailbox_priority
+ *                       <- UnboundedPriorityMailbox / UnboundedStablePriorityMailbox and their bounded
+ *                          forms, UnboundedControlAwareMailbox / BoundedControlAwareMailbox
+ *                          (akka-actor/.../dispatch/Mailbox.scala:726-816, 867-1025)
  *   agx_set_outbound / agx_take_outbound
  *                       <- sender() ! reply to a JVM actor (akka-actor/.../actor/ActorCell.scala:583-587):
  *                          GPU tells to host-side actors leave the engine through an outbox
@@ -373,6 +377,25 @@ agx_status agx_persist_info(agx_engine* eng, uint64_t out[2]);
 #define AGX_MAX_MAILBOX_CLASSES 8u
 agx_status agx_set_mailbox_class(agx_engine* eng, uint32_t mailbox_class, uint32_t capacity);
 agx_status agx_set_mailbox(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t mailbox_class);
+/* Mailbox.scala:726-816 (priority / stable priority), :867-1025 (control-aware)
+ * A mailbox class may carry a priority table: the priority of a message is prio[payload >> 24] (the
+ * message tag), a lower value is dequeued first (PriorityGenerator's comparator), equal priorities stay
+ * in arrival order across supersteps (StablePriorityBlockingQueue's (priority, sequence number)).
+ * Admission is unchanged and goes by arrival position (a bounded priority queue's offer fails when
+ * the queue is full, whatever the priority: Mailbox.scala:761-766, 810-815); the admitted messages
+ * of an actor are then stably sorted by priority, the first min(len, throughput) are drained and
+ * the rest is the backlog, kept in that order.  A control-aware mailbox is the
+ * table 0 for control tags, 1 for all others.  prio == NULL clears the class's table; a class
+ * without a table is FIFO.  The class must be configured (class 0 always is); call before the first
+ * agx_run (AGX_ESTATE afterwards).  AGX_EINVAL: an engine with n_ranks > 1, an engine with a CRDT
+ * kind registered (a snapshot handle has no tag; registering one after this call is refused the
+ * same way), an unconfigured class, an engine whose bounded-mailbox ring pool exists.
+ * The one bounded difference from the reference: a prioritised actor's whole queue must be seen
+ * by one workgroup, so a bucket (agx_cfg.bucket_actors actors) that holds an actor of a prioritised
+ * class and whose inbox -- backlog included -- exceeds one 2048-message tile makes agx_run return
+ * AGX_ECAPACITY (sticky; never a silently wrong order).  Buckets without such an actor are not
+ * limited. */
+agx_status agx_set_mailbox_priority(agx_engine* eng, uint32_t mailbox_class, const uint8_t prio[256]);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --

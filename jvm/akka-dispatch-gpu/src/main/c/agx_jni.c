@@ -123,6 +123,23 @@ JNIEXPORT void JNICALL Java_akka_dispatch_gpu_AgxJni_setMailboxClass(JNIEnv* env
   raise(env, agx_set_mailbox_class(ENG(eng), (uint32_t)cls, (uint32_t)capacity));
 }
 
+/* agx_set_mailbox_priority: prio = 256 bytes (priority by message tag), or null to clear the class's table */
+JNIEXPORT void JNICALL Java_akka_dispatch_gpu_AgxJni_setMailboxPriority(JNIEnv* env, jclass k, jlong eng, jint cls,
+                                                                        jbyteArray prio) {
+  (void)k;
+  if (!prio) {
+    raise(env, agx_set_mailbox_priority(ENG(eng), (uint32_t)cls, NULL));
+    return;
+  }
+  if ((*env)->GetArrayLength(env, prio) != 256) {
+    raise(env, AGX_EINVAL);
+    return;
+  }
+  uint8_t t[256];
+  (*env)->GetByteArrayRegion(env, prio, 0, 256, (jbyte*)t);
+  raise(env, agx_set_mailbox_priority(ENG(eng), (uint32_t)cls, t));
+}
+
 JNIEXPORT void JNICALL Java_akka_dispatch_gpu_AgxJni_setMailbox(JNIEnv* env, jclass k, jlong eng, jlong first,
                                                                 jlong count, jint cls) {
   (void)k;

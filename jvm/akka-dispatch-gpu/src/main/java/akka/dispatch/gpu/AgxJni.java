@@ -41,6 +41,10 @@ public final class AgxJni {
 
   public static native void setMailbox(long engine, long first, long count, int mailboxClass);
 
+  /** agx_set_mailbox_priority: the class's priority by message tag (256 bytes, lower first; null clears it):
+   *  priority / stable-priority and control-aware mailboxes (Mailbox.scala:726-816, 867-1025). */
+  public static native void setMailboxPriority(long engine, int mailboxClass, byte[] prio);
+
   public static native void setRing(long engine, int stride);
 
   public static native void setGossip(long engine, int fanout, long seed);

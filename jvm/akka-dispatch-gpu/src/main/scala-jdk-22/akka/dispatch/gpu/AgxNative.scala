@@ -48,6 +48,8 @@ object AgxNative {
   val setMailboxClass: MethodHandle = h("agx_set_mailbox_class", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT))
   val setMailbox: MethodHandle =
     h("agx_set_mailbox", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_LONG, JAVA_LONG, JAVA_INT))
+  val setMailboxPriority: MethodHandle =
+    h("agx_set_mailbox_priority", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, ADDRESS))
   val setBehaviors: MethodHandle = h(
     "agx_set_behaviors",
     FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT))
@@ -123,6 +125,15 @@ object PanamaBackend extends AgxBackend {
     check(AgxNative.setMailboxClass.invokeExact(seg(engine), mailboxClass, capacity).asInstanceOf[Int])
   def setMailbox(engine: Long, first: Long, count: Long, mailboxClass: Int): Unit =
     check(AgxNative.setMailbox.invokeExact(seg(engine), first, count, mailboxClass).asInstanceOf[Int])
+  def setMailboxPriority(engine: Long, mailboxClass: Int, prio: Array[Byte]): Unit = {
+    val a = Arena.ofConfined()
+    try {
+      if (prio != null && prio.length != 256)
+        throw new akka.ConfigurationException("a mailbox priority table has 256 entries (one per message tag)")
+      val t = if (prio == null) MemorySegment.NULL else a.allocateFrom(JAVA_BYTE, prio: _*)
+      check(AgxNative.setMailboxPriority.invokeExact(seg(engine), mailboxClass, t).asInstanceOf[Int])
+    } finally a.close()
+  }
   def setBehaviors(engine: Long, t: GpuBehaviors.Tables): Unit = {
     val a = Arena.ofConfined()
     try {

@@ -19,6 +19,8 @@ trait AgxBackend {
   def registerRange(engine: Long, first: Long, count: Long, kind: Int, init: Array[Long], stateWords: Int): Unit
   def setMailboxClass(engine: Long, mailboxClass: Int, capacity: Int): Unit
   def setMailbox(engine: Long, first: Long, count: Long, mailboxClass: Int): Unit
+  /** agx_set_mailbox_priority: 256 priorities by message tag (lower first), or null to clear */
+  def setMailboxPriority(engine: Long, mailboxClass: Int, prio: Array[Byte]): Unit
   def setBehaviors(engine: Long, t: GpuBehaviors.Tables): Unit
   def setOutbound(engine: Long, firstHostId: Int, nHost: Int, capacity: Long): Unit
   def takeOutbound(engine: Long, dst: Array[Int], src: Array[Int], payload: Array[Int], cap: Int): Int
@@ -67,6 +69,8 @@ object JniBackend extends AgxBackend {
     AgxJni.setMailboxClass(engine, mailboxClass, capacity)
   def setMailbox(engine: Long, first: Long, count: Long, mailboxClass: Int): Unit =
     AgxJni.setMailbox(engine, first, count, mailboxClass)
+  def setMailboxPriority(engine: Long, mailboxClass: Int, prio: Array[Byte]): Unit =
+    AgxJni.setMailboxPriority(engine, mailboxClass, prio)
   def setBehaviors(engine: Long, t: GpuBehaviors.Tables): Unit =
     AgxJni.setBehaviors(engine, t.cases, t.nCases, t.acts, t.nActs, t.first, t.behaviors.size)
   def setOutbound(engine: Long, firstHostId: Int, nHost: Int, capacity: Long): Unit =

@@ -46,20 +46,24 @@ final class GpuEngine(val dispatcherId: String, config: Config, throughput: Int)
 
   // ---------------------------------------------------------------- mailbox types (per actor)
   // Mailboxes.lookupConfigurator resolves a mailbox per actor (Mailboxes.scala:204-260): each distinct
-  // capacity among this dispatcher's GPU mailbox types becomes one engine mailbox class (class 0 =
-  // gpu.mailbox-capacity; at most Agx.MaxMailboxClasses - 1 further ones).
-  private val classes = new ConcurrentHashMap[Integer, Integer]()
-  classes.put(defaultCapacity, 0)
-  def mailboxClass(capacity: Int): Int = synchronized {
-    val c = classes.get(capacity)
+  // (capacity, priority table) among this dispatcher's GPU mailbox types becomes one engine mailbox class
+  // (class 0 = gpu.mailbox-capacity, FIFO; at most Agx.MaxMailboxClasses - 1 further ones).  A priority
+  // table (GpuPriorityMailboxType / GpuControlAwareMailboxType: 256 priorities by message tag, lower
+  // first) is bound with agx_set_mailbox_priority -- before the first run: the engine refuses it later.
+  private val classes = new ConcurrentHashMap[(Int, Option[Seq[Byte]]), Integer]()
+  classes.put((defaultCapacity, None), 0)
+  def mailboxClass(capacity: Int, priority: Array[Byte] = null): Int = synchronized {
+    val key = (capacity, Option(priority).map(_.toSeq))
+    val c = classes.get(key)
     if (c != null) c.intValue
     else {
       val cls = classes.size
       if (cls >= Agx.MaxMailboxClasses)
         throw new akka.ConfigurationException(
-          s"GPU dispatcher [$dispatcherId]: more than ${Agx.MaxMailboxClasses} distinct mailbox capacities")
+          s"GPU dispatcher [$dispatcherId]: more than ${Agx.MaxMailboxClasses} distinct mailbox types")
       native.setMailboxClass(handle, cls, capacity)
-      classes.put(capacity, cls)
+      if (priority != null) native.setMailboxPriority(handle, cls, priority)
+      classes.put(key, cls)
       cls
     }
   }
@@ -80,10 +84,10 @@ final class GpuEngine(val dispatcherId: String, config: Config, throughput: Int)
   private val hostRefs = new ConcurrentHashMap[Integer, ActorRef]()
 
   /** actorOf: one fixed-layout actor (GpuMailboxType.create) with its mailbox class */
-  def register(ref: ActorRef, kind: Int, init: Array[Long], mailboxCapacity: Int): Int = {
+  def register(ref: ActorRef, kind: Int, init: Array[Long], mailboxCapacity: Int, priority: Array[Byte] = null): Int = {
     val id = nextId.getAndIncrement()
     if (id >= maxActors) throw new IllegalStateException(s"GPU dispatcher [$dispatcherId] is full ($maxActors actors)")
-    val cls = mailboxClass(mailboxCapacity)
+    val cls = mailboxClass(mailboxCapacity, priority)
     synchronized {
       native.registerRange(handle, id.toLong, 1L, kind, init, stateWords)
       if (cls != 0) native.setMailbox(handle, id.toLong, 1L, cls)

@@ -13,6 +13,13 @@
  * the type's marker (Mailboxes.scala:122-135,164-175), so an actor that requires bounded semantics
  * must be given the bounded type.  A GpuMailboxType with mailbox-capacity > 0 still tail-drops at
  * that capacity and its queues are GpuBoundedMessageQueue at run time.
+ *
+ * Priority and control-aware mailboxes (Mailbox.scala:726-816, 867-1025): GpuPriorityMailboxType
+ * (gpu.priority-by-tag) and GpuControlAwareMailboxType (gpu.control-tags) bind a priority table by
+ * message tag (payload >>> 24) to their engine mailbox class (agx_set_mailbox_priority): lower first,
+ * FIFO among equal priorities, admission by arrival position at mailbox-capacity.  The reference's
+ * priority mailboxes take a Comparator[Envelope] from a user subclass; a GPU actor's messages are
+ * fixed-layout payloads, so the comparator is given as data in the mailbox's config block.
  */
 package akka.dispatch.gpu
 
@@ -56,10 +63,13 @@ abstract class GpuMailboxTypeBase(settings: ActorSystem.Settings, config: Config
     throw new akka.ConfigurationException(
       "GpuMailboxType is a non-blocking bounded mailbox: mailbox-push-timeout-time must be 0")
 
+  /** The class's priority by message tag (256 bytes, lower first), or null: FIFO. */
+  protected def priorityTable: Array[Byte] = null
+
   override def create(owner: Option[ActorRef], system: Option[ActorSystem]): MessageQueue = {
     val engine = GpuEngine.forDispatcher(dispatcherId)
     val id = owner match {
-      case Some(ref) => engine.register(ref, kind, Array.fill(engine.stateWords)(0L), capacity)
+      case Some(ref) => engine.register(ref, kind, Array.fill(engine.stateWords)(0L), capacity, priorityTable)
       case None      => Agx.NoSender // the dummy queue of a top-level actor under construction
     }
     val q: GpuQueue =
@@ -81,6 +91,55 @@ class GpuBoundedMailboxType(settings: ActorSystem.Settings, config: Config)
     with ProducesMessageQueue[GpuBoundedMessageQueue] {
   if (capacity <= 0)
     throw new IllegalArgumentException("The capacity for GpuBoundedMailboxType must be positive (mailbox-capacity)")
+}
+
+/** mailbox-type = "akka.dispatch.gpu.GpuControlAwareMailboxType": Unbounded / BoundedControlAwareMailbox
+ *  (Mailbox.scala:867-1025) -- messages whose tag is listed in `gpu.control-tags = [..]` (the
+ *  ControlMessage marker of a fixed-layout payload) are handed out before all others, each group
+ *  FIFO; mailbox-capacity > 0 bounds both together. */
+class GpuControlAwareMailboxType(settings: ActorSystem.Settings, config: Config)
+    extends GpuMailboxTypeBase(settings, config)
+    with ProducesMessageQueue[GpuMessageQueue] {
+  private val table: Array[Byte] = {
+    val t = Array.fill[Byte](256)(1)
+    if (config.hasPath("gpu.control-tags")) {
+      val it = config.getIntList("gpu.control-tags").iterator()
+      while (it.hasNext) {
+        val tag = it.next().intValue
+        if (tag < 0 || tag > 255) throw new akka.ConfigurationException(s"gpu.control-tags: [$tag] is not a message tag (0..255)")
+        t(tag) = 0
+      }
+    }
+    t
+  }
+  override protected def priorityTable: Array[Byte] = table
+}
+
+/** mailbox-type = "akka.dispatch.gpu.GpuPriorityMailboxType": Unbounded / BoundedStablePriorityMailbox
+ *  (Mailbox.scala:779-816; the unstable types' order among equal priorities is unspecified, and the
+ *  stable one is a legal instance, :726-766).  `gpu.priority-by-tag { "<tag>" = <Int>, .. }` is the
+ *  PriorityGenerator as data: lower is handed out first; tags not listed come after every listed one.
+ *  The Ints are replaced by their dense ranks (a priority queue uses only their order), so any Int fits. */
+class GpuPriorityMailboxType(settings: ActorSystem.Settings, config: Config)
+    extends GpuMailboxTypeBase(settings, config)
+    with ProducesMessageQueue[GpuMessageQueue] {
+  private val table: Array[Byte] = {
+    val given = new java.util.TreeMap[Integer, java.lang.Long]()
+    if (config.hasPath("gpu.priority-by-tag")) {
+      val it = config.getConfig("gpu.priority-by-tag").entrySet().iterator()
+      while (it.hasNext) {
+        val e = it.next()
+        val tag = e.getKey.replace("\"", "").toInt
+        if (tag < 0 || tag > 255) throw new akka.ConfigurationException(s"gpu.priority-by-tag: [$tag] is not a message tag (0..255)")
+        given.put(tag, e.getValue.unwrapped().asInstanceOf[Number].longValue)
+      }
+    }
+    val last: Long = if (given.isEmpty) 0L else java.util.Collections.max(given.values()).longValue + 1
+    val value = Array.tabulate[Long](256)(t => if (given.containsKey(t)) given.get(t).longValue else last)
+    val ranks = value.distinct.sorted.zipWithIndex.toMap
+    value.map(v => ranks(v).toByte)
+  }
+  override protected def priorityTable: Array[Byte] = table
 }
 
 /** The device-side mailbox of one actor.  enqueue hands the tell to the engine through the
