@@ -49,6 +49,9 @@ struct DevParams {
     // ptab[class * 256 + tag] (lower = dequeued first), then one byte per bucket, != 0 when the bucket
     // holds an actor of a prioritised class (kPrioBucketOff; written on the host when mailboxes are bound)
     const uint8_t* ptab;
+    // deque-based mailboxes (agx_set_stash), read and written only by the stash k_bucket_apply instantiations:
+    // the per-actor stash buffers and their bookkeeping (StashDev below)
+    uint32_t* stash;
   };
   uint32_t* heap_top;       // [2] rows allocated in heap[parity]
   const uint32_t* step;     // superstep counter (bumped by the first kernel of a step)
@@ -103,6 +106,50 @@ __device__ __forceinline__ bool mbox_prioritised(const DevParams& P, uint32_t ab
 // lower is dequeued first (PriorityGenerator, Mailbox.scala:726-816; control-aware: 0 / 1, :867-1025)
 __device__ __forceinline__ uint32_t mbox_priority(const DevParams& P, uint32_t abyte, uint32_t pay) {
   return P.ptab[((abyte >> 1) & (AGX_MAX_MAILBOX_CLASSES - 1)) * 256u + (pay >> 24)];
+}
+
+// ---- deque-based mailboxes: the stash (agx_set_stash; StashBufferImpl.scala:61-79,131-218)
+// DevParams.stash, u32 units:
+//   [0..7]   stash capacity S of mailbox class c (0: the class has none)
+//   [8]      Smax = the largest S: buffer slots per actor   [9] Pmax: park slots per actor
+//   [16..21] three u64 counters: stashed, unstashed, overflows
+//   [kStashBucketOff + b]       pending: buffered / parked messages bucket b processes next superstep
+//                               (counted into the bucket's backlog count, read at the bucket's entry)
+//   [kStashBucketOff + nb + b]  != 0: bucket b holds an actor of a class with a stash (host-written)
+//   then, 8-byte aligned, one uint2 header per actor (nb << bb of them):
+//     x = head | released << 8 | size << 16   (the buffer: a ring of Smax slots starting at head)
+//     y = park head | parked << 16            (the park: slots Smax.., consumed from the front)
+//   then Smax + Pmax uint2 envelopes (sender, payload) per actor.
+constexpr uint32_t kStashBucketOff = 32;
+constexpr uint32_t kStashCtr = 16;
+struct StashDev {
+  uint32_t* base;
+  uint2* hdr;
+  uint2* slots;
+  uint32_t smax, per;  // per = Smax + Pmax envelope slots per actor
+  __device__ __forceinline__ uint2* of(uint32_t l) const { return slots + (size_t)l * per; }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kStashCtr) + i;
+  }
+};
+__device__ __forceinline__ StashDev stash_dev(const DevParams& P, uint32_t nb, uint32_t bb) {
+  StashDev s;
+  s.base = P.stash;
+  s.smax = P.stash[8];
+  s.per = s.smax + P.stash[9];
+  const size_t ho = ((size_t)kStashBucketOff + 2u * nb + 1u) & ~(size_t)1;
+  s.hdr = reinterpret_cast<uint2*>(P.stash + ho);
+  s.slots = s.hdr + ((size_t)nb << bb);
+  return s;
+}
+__device__ __forceinline__ uint32_t stash_cap(const DevParams& P, uint32_t abyte) {
+  return P.stash[(abyte >> 1) & (AGX_MAX_MAILBOX_CLASSES - 1)];
+}
+// the messages a superstep takes from the buffer / the park instead of the mailbox (the source rule):
+// the first min(released, T) buffer entries, else the first min(parked, T) parked ones, else none
+__device__ __forceinline__ uint32_t stash_window(uint2 h, uint32_t T) {
+  const uint32_t rel = (h.x >> 8) & 0xFFu, pc = h.y >> 16;
+  return rel ? min(rel, T) : min(pc, T);
 }
 
 // A tell to a host-side actor (agx_set_outbound): appended to the outbox (when `write`); returns
@@ -262,13 +309,21 @@ constexpr uint32_t kb(uint32_t k) { return 1u << (k < AGX_KIND_COMPILED ? k : AG
 // KM flag (not a kind): the variant runs delta-CRDT replication (agx_set_delta_crdt).  Variants
 // without it compile the delta code out (its registers would spill the full-state merges).
 constexpr uint32_t kDeltaKM = 1u << 31;
+// KM flag (not a kind): the variant knows the stash of deque-based mailboxes (agx_set_stash).  A flag of KM,
+// not a template parameter of its own, so every other instantiation keeps its name and compiles as before.
+constexpr uint32_t kStashKM = 1u << 30;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
 // ---- compiled behaviours (include/akka_gpu.h "compiled behaviours"; akka_amd/typed.py lowers them)
+// (kStash: the stash instantiations know AGX_V_STASH, the size of the actor's stash buffer; every other
+// instantiation compiles as before)
+template <bool kStash = false>
 __device__ __forceinline__ uint64_t cb_operand(uint32_t src, uint32_t word, int64_t k, uint32_t pay, const uint64_t* w,
-                                               uint32_t sender, uint32_t self) {
+                                               uint32_t sender, uint32_t self, uint32_t nstash = 0) {
   uint64_t b = 0;
+  if constexpr (kStash)
+    if (src == AGX_V_STASH) return (uint64_t)nstash + (uint64_t)k;
   switch (src) {
     case AGX_V_PAYLOAD: b = pay; break;
     case AGX_V_TAG: b = pay >> 24; break;
@@ -292,23 +347,23 @@ __device__ __forceinline__ bool cb_cmp(uint32_t op, uint64_t a, uint64_t b) {
   }
 }
 // ReceiveBuilder.receive (TY/javadsl/ReceiveBuilder.scala:209-218): the first case whose tests hold
-template <typename Emit>
+template <bool kStash = false, typename Emit>
 __device__ __forceinline__ uint32_t compiled_apply(const DevParams& P, uint32_t& kind, uint32_t self, uint64_t* w,
-                                                uint32_t src, uint32_t pay, Emit& emit) {
+                                                uint32_t src, uint32_t pay, Emit& emit, uint32_t nstash = 0) {
   const uint32_t b = kind - AGX_KIND_COMPILED;
   if (b >= P.n_beh) return AGX_RES_UNHANDLED;
   const uint32_t c1 = P.bfirst[b + 1];
   for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
     const agx_case C = P.bcase[c];
-    if (!cb_cmp(C.cmp1, cb_operand(C.src1, C.word1, C.k1, pay, w, src, self),
-                cb_operand(C.src2, C.word2, C.k2, pay, w, src, self)))
+    if (!cb_cmp(C.cmp1, cb_operand<kStash>(C.src1, C.word1, C.k1, pay, w, src, self, nstash),
+                cb_operand<kStash>(C.src2, C.word2, C.k2, pay, w, src, self, nstash)))
       continue;
-    if (!cb_cmp(C.cmp2, cb_operand(C.src3, C.word3, C.k3, pay, w, src, self),
-                cb_operand(C.src4, C.word4, C.k4, pay, w, src, self)))
+    if (!cb_cmp(C.cmp2, cb_operand<kStash>(C.src3, C.word3, C.k3, pay, w, src, self, nstash),
+                cb_operand<kStash>(C.src4, C.word4, C.k4, pay, w, src, self, nstash)))
       continue;
     for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
       const agx_act A = P.bact[i];
-      const uint64_t v = cb_operand(A.src, A.sword, A.k, pay, w, src, self);
+      const uint64_t v = cb_operand<kStash>(A.src, A.sword, A.k, pay, w, src, self, nstash);
       switch (A.op) {
         case AGX_A_SET: w[A.word & 1u] = v; break;
         case AGX_A_ADD: w[A.word & 1u] += v; break;
@@ -320,7 +375,7 @@ __device__ __forceinline__ uint32_t compiled_apply(const DevParams& P, uint32_t&
             int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
             d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
           } else {
-            d = cb_operand(A.dsrc, A.dword, A.dk, pay, w, src, self);
+            d = cb_operand<kStash>(A.dsrc, A.dword, A.dk, pay, w, src, self, nstash);
           }
           emit(d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d, A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v);
           break;
@@ -332,6 +387,8 @@ __device__ __forceinline__ uint32_t compiled_apply(const DevParams& P, uint32_t&
       kind = AGX_KIND_COMPILED + C.next;
       return AGX_RES_SAME;
     }
+    if constexpr (kStash)  // unstash_all(next): the become here, the release by the caller
+      if (C.result == AGX_RES_UNSTASH_ALL && C.next != AGX_NEXT_SAME) kind = AGX_KIND_COMPILED + C.next;
     return C.result;
   }
   return AGX_RES_UNHANDLED;
@@ -341,14 +398,15 @@ __device__ __forceinline__ uint32_t compiled_apply(const DevParams& P, uint32_t&
 // keeps it for the rest of the drain and stores it back).
 template <uint32_t KM, typename Emit>
 __device__ __forceinline__ uint32_t apply_msg(const DevParams& P, uint32_t& kind_io, uint32_t self, uint32_t local,
-                                              uint64_t* w, uint32_t src, uint32_t pay, Emit&& emit) {
+                                              uint64_t* w, uint32_t src, uint32_t pay, Emit&& emit, uint32_t nstash = 0) {
+  constexpr bool kStash = (KM & kStashKM) != 0;
   uint32_t kind = kind_io;
   if constexpr (KM == kb(AGX_KIND_RING)) kind = AGX_KIND_RING;  // single-kind specialisations: no dispatch
   if constexpr (KM == kb(AGX_KIND_FORWARD_RR)) kind = AGX_KIND_FORWARD_RR;
   if constexpr (KM == kb(AGX_KIND_FANOUT)) kind = AGX_KIND_FANOUT;
   if constexpr (KM == kb(AGX_KIND_COUNTER)) kind = AGX_KIND_COUNTER;
   if constexpr ((KM & kb(AGX_KIND_COMPILED)) != 0)
-    if (kind >= AGX_KIND_COMPILED) return compiled_apply(P, kind_io, self, w, src, pay, emit);
+    if (kind >= AGX_KIND_COMPILED) return compiled_apply<kStash>(P, kind_io, self, w, src, pay, emit, nstash);
   switch (kind) {
     case AGX_KIND_COUNTER:
       if constexpr ((KM & kb(AGX_KIND_COUNTER)) != 0) {

@@ -127,6 +127,15 @@ struct agx_engine {
   std::vector<uint8_t> prio_tab = std::vector<uint8_t>(AGX_MAX_MAILBOX_CLASSES * 256u, 0);
   uint8_t* d_ptab = nullptr;  // [classes][256] tables, then the [nb] bucket marks (DevParams.ptab)
   bool prio_dirty = false;   // the tables or the actors' classes changed since the last upload
+  // deque-based mailboxes (agx_set_stash): the classes' stash capacities.  An engine with one launches the
+  // stash instantiation of the compiled catch-all variant and no wave / ring / dense / persistent launch
+  uint32_t stash_cap[AGX_MAX_MAILBOX_CLASSES] = {0};
+  bool stash_on = false;
+  uint32_t* d_stash = nullptr;  // DevParams.stash (agx_device.h StashDev): sized at the first run
+  uint32_t stash_smax = 0, stash_pmax = 0;
+  size_t stash_hdr_off = 0, stash_slot_off = 0;  // u32 offsets of the headers / envelopes in d_stash
+  bool stash_dirty = false;  // the capacities or the actors' classes changed since the last upload
+  bool beh_stash = false;    // the compiled tables hold a stash / unstash_all result (agx_set_behaviors)
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -460,6 +469,7 @@ DevParams make_params(agx_engine* e) {
   P.heap = e->d_heap;
   P.rx = e->d_rx;
   if (e->prio_mask) P.ptab = e->d_ptab;  // (shares rx's slot: no CRDT kinds on an engine with priority tables)
+  if (e->stash_on) P.stash = e->d_stash;  // (the same slot: neither CRDT kinds nor priority tables with a stash)
   P.heap_top = e->d_heap_top;
   P.step = e->d_step;
   P.heap_rows = (uint32_t)e->heap_rows;
@@ -625,6 +635,7 @@ uint32_t apply_variant(const agx_engine* e) {
   const uint32_t km = e->kinds_mask & ~kb(AGX_KIND_NONE);
   if (e->prio_mask)  // priority mailboxes: the catch-all plain variants carry the order step (kPrio)
     return (km & kb(AGX_KIND_COMPILED)) ? V_ALL_COMPILED : V_ALL;
+  if (e->stash_on) return V_ALL_COMPILED;  // deque-based mailboxes: the compiled catch-all carries the stash (kStash)
   if (e->pw && e->delta_max) {  // delta-CRDT replication: the variants that carry the delta code
     if (km == kb(AGX_KIND_GCOUNTER)) return V_GC_DELTA;
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN_DELTA;
@@ -654,7 +665,7 @@ bool dense_on(const agx_engine* e, uint32_t vid) {
   // (k_dense_fused reads a fused bucket's table row one sender bucket per thread: nb <= 512, which
   // the fused superstep's <= 2^20 actors guarantee)
   if (e->fused && e->nb > (uint32_t)kDenseThreads) return false;
-  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask &&
+  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask && !e->stash_on &&
          (e->dense_launch == 1 || (e->dense_launch < 0 && vid == V_RING));
 }
 
@@ -838,7 +849,7 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
     }
     // (priority mailboxes: the wave path drains in arrival order -- every bucket takes the block launch)
     const bool tl = mode == M_BYPASS && !kVariants[vid].wide && e->tiny_launch && e->tiny_max && !e->skew_only &&
-                    !e->prio_mask;
+                    !e->prio_mask && !e->stash_on;
     if (tl) {  // wave-per-bucket launch first; the block launch then takes the buckets it marked
       ba.blist = e->d_blist;
       ba.dense_first = dl ? 1u : 0u;
@@ -855,6 +866,9 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       if (e->prio_mask) {
         if (mode == M_OWNER) return set_err(AGX_ESTATE, "priority mailboxes need a single-rank engine");
         HIP_TRY(agx_launch_apply_prio(vid, mode, g, e->stream, bf));
+      } else if (e->stash_on) {
+        if (mode == M_OWNER) return set_err(AGX_ESTATE, "deque-based mailboxes need a single-rank engine");
+        HIP_TRY(agx_launch_apply_stash(vid, mode, g, e->stream, bf));
       } else {
         HIP_TRY(agx_launch_apply(vid, mode, false, g, e->stream, bf));
       }
@@ -893,7 +907,7 @@ agx_status launch_staged_chunk(agx_engine* e) {
 // behaviours, every configured mailbox class bounded by <= kRingMaxC); from then on the classes
 // are fixed (agx_set_mailbox_class refuses a capacity the rings cannot hold).
 agx_status setup_rings(agx_engine* e) {
-  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask) return AGX_OK;  // (a ring drains in arrival order)
+  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask || e->stash_on) return AGX_OK;  // (a ring drains in arrival order)
   uint32_t cmax = 0;
   for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) {
     if (!((e->mclass_set >> c) & 1u)) continue;
@@ -937,7 +951,7 @@ agx_status setup_rings(agx_engine* e) {
 constexpr uint32_t kRingAutoC = 256;  // ring apply by default from this mailbox capacity up (setup_ring_apply)
 agx_status setup_ring_apply(agx_engine* e) {
   if (e->started || e->rg_on || e->ring_live || e->ring_res) return AGX_OK;
-  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask) return AGX_OK;
+  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask || e->stash_on) return AGX_OK;
   // AGX_RING_APPLY=1 / 0 forces rings on / off; unset: on when the largest bounded capacity is at
   // least kRingAutoC.  Deep queues are where re-copying the backlog every superstep costs most (C3,
   // BoundedMailbox(1000): 4.67e8 -> 6.7e8 msg/s with rings, the sparse buckets a wave each); at
@@ -999,8 +1013,86 @@ agx_status setup_orset(agx_engine* e) {
   return AGX_OK;
 }
 
+agx_status copy_sync(agx_engine* e, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+
+// the drain limit of mailbox class c (mbox_limits on the device)
+uint32_t class_throughput(const agx_engine* e, uint32_t c) {
+  if (!e->mclasses) return std::max<uint32_t>(e->T, 1u);
+  const uint32_t C = e->mcap[c], T = std::max<uint32_t>(e->Traw, 1u);
+  return C && T > C ? C : T;
+}
+
+// Deque-based mailboxes (agx_set_stash): the stash storage (agx_device.h StashDev) -- allocated and
+// zeroed once, sized by n_local: every actor has a header, Smax buffer slots and Pmax park slots, so an
+// actor's slot needs no indirection and a class can be bound to any actor later; then the classes'
+// capacities and the marks of the buckets that hold an actor of a stash class.
+agx_status upload_stash(agx_engine* e) {
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  if (!e->d_stash) {
+    uint32_t smax = 1, tmax = 1;
+    for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) {
+      if (!((e->mclass_set >> c) & 1u)) continue;
+      smax = std::max(smax, e->stash_cap[c]);
+      tmax = std::max(tmax, class_throughput(e, c));
+    }
+    const uint32_t pmax = std::min<uint32_t>(tmax - 1u, (uint32_t)kBucket - 1u);  // (a park is the rest of one drain window)
+    const uint64_t hoff = ((uint64_t)kStashBucketOff + 2ull * e->nb + 1ull) & ~1ull;
+    const uint64_t soff = hoff + 2ull * npad;
+    const uint64_t total = soff + 2ull * npad * ((uint64_t)smax + pmax);
+    if (hipMalloc((void**)&e->d_stash, total * 4ull) != hipSuccess) {
+      (void)hipGetLastError();
+      e->d_stash = nullptr;
+      return set_err(AGX_ENOMEM, "the stash buffers of %llu actors (%u buffer + %u park envelopes each, %llu MB) do not "
+                     "fit on the device", (unsigned long long)npad, smax, pmax, (unsigned long long)(total >> 18));
+    }
+    // (headers, pending counts and counters start at zero; the envelopes need no initial value)
+    HIP_TRY(hipMemsetAsync(e->d_stash, 0, soff * 4ull, e->stream));
+    e->stash_smax = smax;
+    e->stash_pmax = pmax;
+    e->stash_hdr_off = hoff;
+    e->stash_slot_off = soff;
+    drop_graphs(e);  // (a kernel argument of the captured supersteps)
+  }
+  uint32_t head[16] = {0};
+  for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) head[c] = e->stash_cap[c];
+  head[8] = e->stash_smax;
+  head[9] = e->stash_pmax;
+  std::vector<uint32_t> marks(e->nb, 0);
+  for (uint64_t l = 0; l < e->n_local; ++l)
+    if (e->stash_cap[(e->h_alive[l] >> 1) & (AGX_MAX_MAILBOX_CLASSES - 1)]) marks[l >> e->bb] = 1;
+  HIP_TRY(hipMemcpyAsync(e->d_stash, head, sizeof(head), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_stash + kStashBucketOff + e->nb, marks.data(), marks.size() * 4ull, hipMemcpyHostToDevice,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->stash_dirty = false;
+  return AGX_OK;
+}
+
+// The stash headers of every actor, read back: buffered messages not released (held), released or
+// parked ones still to be processed (pending), and how many of the pending ones the buckets' backlog
+// counts already carry (the next superstep's windows: counted by the device's in-flight sum).
+agx_status stash_scan(agx_engine* e, uint64_t* held, uint64_t* pending, uint64_t* windows) {
+  *held = *pending = *windows = 0;
+  if (!e->d_stash) return AGX_OK;
+  std::vector<uint32_t> h(2ull * e->n_local);
+  AGX_TRY(copy_sync(e, h.data(), e->d_stash + e->stash_hdr_off, h.size() * 4ull, hipMemcpyDeviceToHost));
+  for (uint64_t l = 0; l < e->n_local; ++l) {
+    const uint32_t x = h[2 * l], y = h[2 * l + 1];
+    const uint32_t rel = (x >> 8) & 0xFFu, size = (x >> 16) & 0xFFu, pc = y >> 16;
+    if (!size && !pc) continue;
+    const uint32_t T = class_throughput(e, (e->h_alive[l] >> 1) & (AGX_MAX_MAILBOX_CLASSES - 1));
+    *held += size - rel;
+    *pending += rel + pc;
+    *windows += rel ? std::min(rel, T) : std::min(pc, T);
+  }
+  return AGX_OK;
+}
+
 // upload host mirrors / staged tells before a run
 agx_status prepare_run(agx_engine* e) {
+  if (e->beh_stash && !e->stash_on)  // (only the stash variant interprets those results: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours stash or unstash_all, but no mailbox class of this engine has a "
+                   "stash capacity (agx_set_stash): without one every stash would overflow");
   if (e->actors_dirty) {
     HIP_TRY(hipMemcpyAsync(e->d_kind, e->h_kind.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
@@ -1033,7 +1125,9 @@ agx_status prepare_run(agx_engine* e) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->actors_dirty = false;
     e->prio_dirty = e->prio_mask != 0;  // (mailboxes bound since: the per-bucket marks below)
+    e->stash_dirty = e->stash_on;
   }
+  if (e->stash_dirty) AGX_TRY(upload_stash(e));
   if (e->prio_dirty) {  // priority tables and the buckets that hold an actor of a prioritised class
     std::vector<uint8_t> pb(e->prio_tab);  // tables, then the bucket marks (kPrioBucketOff)
     pb.resize(kPrioBucketOff + e->nb, 0);
@@ -1273,6 +1367,10 @@ agx_status error_status(const agx_engine* e, uint64_t err) {
     return set_err(AGX_ECAPACITY, "a bucket of %u actors that holds a priority-mailbox actor received more than one "
                    "tile of %d messages (backlog included): a prioritised actor's queue is ordered within one tile "
                    "(smaller agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
+  if (err & kErrStashTile)
+    return set_err(AGX_ECAPACITY, "a bucket of %u actors that holds an actor of a deque-based mailbox class received "
+                   "more than one tile of %d messages (backlog and released stash messages included): a stash is "
+                   "drained within one tile (smaller agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
   if (err & kErrCapacity)
     return set_err(AGX_ECAPACITY, "in-flight messages exceeded engine capacity (msg_capacity=%llu)",
                    (unsigned long long)e->cap);
@@ -1300,6 +1398,11 @@ agx_status collect_stats(agx_engine* e, agx_stats* out, bool check) {
   st.supersteps = s[ST_STEPS] + e->host_steps;
   // backlog + tells produced by the last apply, plus host tells not yet consumed
   st.in_flight = s[kStatInfl] + e->n_staged_dev + e->hs_key.size();
+  if (e->stash_on) {  // every buffered and parked message is in flight; the next windows are in the backlog counts
+    uint64_t held, pending, windows;
+    AGX_TRY(stash_scan(e, &held, &pending, &windows));
+    st.in_flight += held + pending - windows;
+  }
   // B = E_in + f_out*E_out + 2*S*(A/M); kind+alive bytes read per activation.
   // S = the state words a behaviour touches: words 0-1 (plain and compiled behaviours), a CRDT's
   // data words (a full-state merge reads and writes all of them), or with delta-CRDT replication
@@ -1345,7 +1448,7 @@ bool persist_ok(agx_engine* e) {
       e->persist = (uint64_t)e->nb <= (uint64_t)per_cu * (uint64_t)ncu ? 1 : 0;
     (void)hipGetLastError();
   }
-  return e->persist == 1 && !e->prio_mask && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
+  return e->persist == 1 && !e->prio_mask && !e->stash_on && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
          !e->recover_dense;
 }
 
@@ -2074,6 +2177,9 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
   if (e->prio_mask)
     return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a priority mailbox "
                    "(agx_set_mailbox_priority): a state gossip's snapshot handle carries no message tag");
+  if (e->stash_on)
+    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a deque-based mailbox "
+                   "(agx_set_stash): a state gossip's snapshot row does not outlive its superstep in a stash");
   const uint64_t rows = ((uint64_t)e->nb << e->bb) + e->cap;
   if (rows + e->cap > kHandleMask) return set_err(AGX_EINVAL, "CRDT kinds need msg_capacity < 2^28 - n_actors");
   hipFree(e->d_heap);
@@ -2488,6 +2594,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_ring_next); hipFree(e->d_ring_free); hipFree(e->d_ring_total);
   hipFree(e->d_orw); hipFree(e->d_orm); hipFree(e->d_orw_n);
   hipFree(e->d_ptab);
+  hipFree(e->d_stash);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -2600,6 +2707,8 @@ agx_status agx_set_mailbox_priority(agx_engine* e, uint32_t cls, const uint8_t p
   if (e->ring_live || e->rg_on)
     return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, drained in "
                    "arrival order: set priority tables before the first run", e->ring_live ? e->ring_c : e->rg_c);
+  if (e->stash_on)
+    return set_err(AGX_EINVAL, "priority mailboxes need an engine without a deque-based mailbox class (agx_set_stash)");
   if (e->started) return set_err(AGX_ESTATE, "set mailbox priorities before the first agx_run");
   AGX_TRY(ensure_dev(e));
   if (prio) {
@@ -2611,6 +2720,94 @@ agx_status agx_set_mailbox_priority(agx_engine* e, uint32_t cls, const uint8_t p
   }
   e->prio_dirty = e->prio_mask != 0;
   drop_graphs(e);  // the variant and the tables are captured in the superstep graphs
+  return AGX_OK;
+}
+
+// Stash.scala (classic `stash-capacity`, *DequeBasedMailbox); TY/internal/StashBufferImpl.scala:61-79,131-218
+agx_status agx_set_stash(agx_engine* e, uint32_t cls, uint32_t capacity) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (e->R > 1)
+    return set_err(AGX_EINVAL, "deque-based mailboxes need a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
+  if (e->pw)
+    return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without CRDT kinds (one is registered): a state "
+                   "gossip's snapshot row does not outlive its superstep in a stash");
+  if (e->prio_mask)
+    return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without priority tables (agx_set_mailbox_priority)");
+  if (cls >= AGX_MAX_MAILBOX_CLASSES || !((e->mclass_set >> cls) & 1u))
+    return set_err(AGX_EINVAL, "mailbox class %u is not configured (agx_set_mailbox_class; classes 0..%u)", cls,
+                   AGX_MAX_MAILBOX_CLASSES - 1);
+  if (capacity == 0 || capacity > 255u)
+    return set_err(AGX_EINVAL, "stash capacity %u: a stash holds 1..255 messages (there is no unbounded stash: "
+                   "stash-capacity = -1 is not supported)", capacity);
+  if (e->kmax != 1)
+    return set_err(AGX_EINVAL, "deque-based mailboxes need max_emit = 1 (it is %u): a stash drain stages at most one "
+                   "tell per message", e->kmax);
+  if (e->ring_live || e->rg_on)
+    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, which know no "
+                   "stash: set stash capacities before the first run", e->ring_live ? e->ring_c : e->rg_c);
+  if (e->started) return set_err(AGX_ESTATE, "set stash capacities before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  e->stash_cap[cls] = capacity;
+  e->stash_on = true;
+  e->stash_dirty = true;
+  drop_graphs(e);  // the variant and the stash storage are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_stash_info(agx_engine* e, uint64_t* stashed, uint64_t* unstashed, uint64_t* overflows, uint64_t* held,
+                          uint64_t* pending) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[3] = {0, 0, 0}, h = 0, p = 0, w = 0;
+  if (e->d_stash) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(copy_sync(e, c, e->d_stash + kStashCtr, sizeof(c), hipMemcpyDeviceToHost));
+    AGX_TRY(stash_scan(e, &h, &p, &w));
+  }
+  if (stashed) *stashed = c[0];
+  if (unstashed) *unstashed = c[1];
+  if (overflows) *overflows = c[2];
+  if (held) *held = h;
+  if (pending) *pending = p;
+  return AGX_OK;
+}
+
+agx_status agx_read_stash(agx_engine* e, uint64_t actor_id, uint32_t* src, uint32_t* payload, uint32_t cap,
+                          uint32_t* n_released, uint32_t* n) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (actor_id >= e->n_global) return set_err(AGX_EINVAL, "bad actor id");
+  if (n) *n = 0;
+  if (n_released) *n_released = 0;
+  if (!e->d_stash) return AGX_OK;
+  AGX_TRY(ensure_dev(e));
+  const uint64_t l = actor_id;  // (single rank: local = global)
+  uint32_t h[2];
+  AGX_TRY(copy_sync(e, h, e->d_stash + e->stash_hdr_off + 2ull * l, sizeof(h), hipMemcpyDeviceToHost));
+  const uint32_t head = h[0] & 0xFFu, rel = (h[0] >> 8) & 0xFFu, size = (h[0] >> 16) & 0xFFu;
+  if (n) *n = size;
+  if (n_released) *n_released = rel;
+  if (!size) return AGX_OK;
+  const uint64_t per = (uint64_t)e->stash_smax + e->stash_pmax;
+  std::vector<uint32_t> sl(2ull * e->stash_smax);
+  AGX_TRY(copy_sync(e, sl.data(), e->d_stash + e->stash_slot_off + 2ull * l * per, sl.size() * 4ull, hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < size && i < cap; ++i) {
+    const uint32_t x = (head + i) % e->stash_smax;
+    if (src) src[i] = sl[2 * x];
+    if (payload) payload[i] = sl[2 * x + 1];
+  }
+  return AGX_OK;
+}
+
+// the behaviour kind of each actor now (a compiled behaviour's become and unstash_all change it)
+agx_status agx_read_kinds(agx_engine* e, uint64_t first_id, uint64_t count, uint8_t* kinds) {
+  if (!e || !kinds) return set_err(AGX_EINVAL, "null argument");
+  if (e->R > 1) return set_err(AGX_EINVAL, "agx_read_kinds needs a single-rank engine");
+  if (first_id + count > e->n_global) return set_err(AGX_EINVAL, "bad actor range");
+  AGX_TRY(ensure_dev(e));
+  if (e->actors_dirty) {  // the host mirror is newer than the device
+    memcpy(kinds, e->h_kind.data() + first_id, count);
+    return AGX_OK;
+  }
+  if (count) AGX_TRY(copy_sync(e, kinds, e->d_kind + first_id, count, hipMemcpyDeviceToHost));
   return AGX_OK;
 }
 
@@ -2682,12 +2879,13 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   if (first[0] != 0 || first[n_beh] != n_cases) return set_err(AGX_EINVAL, "first[] must run from 0 to n_cases");
   for (uint32_t b = 0; b < n_beh; ++b)
     if (first[b] > first[b + 1]) return set_err(AGX_EINVAL, "first[] must be non-decreasing");
-  auto opnd_ok = [](uint32_t src, uint32_t word) { return src <= AGX_V_SELF && word <= 1u; };
+  auto opnd_ok = [](uint32_t src, uint32_t word) { return src <= AGX_V_STASH && word <= 1u; };
   for (uint32_t c = 0; c < n_cases; ++c) {
     const agx_case& C = cases[c];
     if (!opnd_ok(C.src1, C.word1) || !opnd_ok(C.src2, C.word2) || !opnd_ok(C.src3, C.word3) ||
-        !opnd_ok(C.src4, C.word4) || C.cmp1 > AGX_CMP_GE || C.cmp2 > AGX_CMP_GE || C.result > AGX_RES_BECOME ||
-        (C.result == AGX_RES_BECOME && C.next >= n_beh) || (uint32_t)C.act_first + C.act_count > n_acts)
+        !opnd_ok(C.src4, C.word4) || C.cmp1 > AGX_CMP_GE || C.cmp2 > AGX_CMP_GE || C.result > AGX_RES_UNSTASH_ALL ||
+        (C.result == AGX_RES_BECOME && C.next >= n_beh) ||
+        (C.result == AGX_RES_UNSTASH_ALL && C.next >= n_beh && C.next != AGX_NEXT_SAME) || (uint32_t)C.act_first + C.act_count > n_acts)
       return set_err(AGX_EINVAL, "compiled behaviours: bad case %u", c);
   }
   for (uint32_t i = 0; i < n_acts; ++i) {
@@ -2721,6 +2919,8 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   if (n_acts) AGX_TRY(copy_sync(e, e->d_bact, acts, n_acts * sizeof(agx_act), hipMemcpyHostToDevice));
   AGX_TRY(copy_sync(e, e->d_bfirst, first, (n_beh + 1) * 4ull, hipMemcpyHostToDevice));
   e->n_beh = n_beh;
+  e->beh_stash = false;
+  for (uint32_t c = 0; c < n_cases; ++c) e->beh_stash |= cases[c].result >= AGX_RES_STASH;
   drop_graphs(e);  // the tables are kernel parameters captured in the superstep graphs
   return AGX_OK;
 }

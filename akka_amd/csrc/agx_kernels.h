@@ -54,6 +54,7 @@ constexpr uint64_t kErrCapacity = 1;
 constexpr uint64_t kErrRange = 2;  // a counter slot wrapped past 2^64 - 1 (AGX_ERANGE)
 constexpr uint64_t kErrBarrier = 4;  // a persistent superstep launch's grid barrier timed out (AGX_EDEVICE)
 constexpr uint64_t kErrPrioTile = 8;  // a bucket with a priority-mailbox actor exceeded one LDS tile (AGX_ECAPACITY)
+constexpr uint64_t kErrStashTile = 16;  // a bucket with an actor of a stash class exceeded one LDS tile (AGX_ECAPACITY)
 // per-block counters of k_bucket_apply: delivered, dead, unhandled, emitted, active
 constexpr int kBStats = 5;
 constexpr uint32_t kMaxApplyGrid = 4096;
@@ -1318,13 +1319,23 @@ __device__ __forceinline__ void flush_stats(const BucketArgs& a, const uint32_t 
 constexpr uint32_t kWaveRowU32 = 64;  // (multi-rank packing) rows of at least this many u32 are copied by a whole wave
 
 
+// kStash: deque-based mailboxes (agx_set_stash).  The inbox segment of an actor then
+// starts with its window: the buffered / parked messages this superstep processes instead of mailbox
+// mail (stash_window; k_bucket_apply put them there).  With a window every admitted mailbox message
+// is queued; the drain (sp_actor) stashes, releases and parks from registers, and the bucket's
+// backlog count carries the next superstep's windows, so a bucket with pending messages has mail.
 template <bool kLds, bool kWide, uint32_t KM, bool kGather, bool kOwner>
 __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketLds& L, uint32_t b, uint32_t lo,
                                               uint32_t cnt, uint32_t a0, uint32_t na, uint32_t w, uint32_t ndead0,
                                               uint32_t (&acc)[kBStats], uint32_t bl_given = 0xFFFFFFFFu,
                                               const uint64_t* pre0 = nullptr, const uint64_t* pre1 = nullptr) {
+  constexpr bool kStash = (KM & kStashKM) != 0;
+  static_assert(!kStash || (kLds && !kWide && !kOwner), "stash: single-rank fast launches, plain behaviours");
   const DevParams& P = a.P;
   const int tid = threadIdx.x;
+  StashDev SD{};
+  if constexpr (kStash) SD = stash_dev(P, a.nb, a.bb);
+  uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
   auto ikey = [&](uint32_t q) -> uint32_t { return kLds ? L.key[q] : a.scr.key[lo + q]; };
   auto isrc = [&](uint32_t q) -> uint32_t { return kLds ? L.src[q] : a.scr.src[lo + q]; };
@@ -1351,6 +1362,25 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     const uint32_t la = tid * kBAct + j;
     const uint32_t len = L.seg[la + 1] - L.seg[la];
     uint32_t q = 0;
+    if constexpr (kStash) {  // [window][mailbox mail]: admission and the backlog concern the mail only
+      uint32_t win = 0;
+      if (len) {
+        const uint32_t ab = L.alive[la];
+        if (!(ab & 1u)) {
+          ndead += len;  // (a stopped actor has no window: its buffers were emptied when it stopped)
+        } else {
+          uint32_t C, T;
+          mbox_limits(P, ab, C, T);
+          win = la < na ? stash_window(SD.hdr[a0 + la], T) : 0u;
+          win = min(win, len);
+          const uint32_t mail = len - win;
+          const uint32_t keep = (C == 0 || mail < C) ? mail : C;
+          ndead += mail - keep;
+          q = win ? keep : (keep > T ? keep - T : 0u);
+        }
+      }
+      winl[la] = win;
+    } else
     if (len) {
       const uint32_t ab = L.alive[la];
       if (!(ab & 1u)) {
@@ -1400,8 +1430,15 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       const uint32_t ab = L.alive[la];
       uint32_t C, T;
       mbox_limits(P, ab, C, T);
-      const uint32_t keep = (C == 0 || len < C) ? len : C;
-      const bool queued = valid && (ab & 1u) && p >= T && p < keep;
+      uint32_t keep = (C == 0 || len < C) ? len : C;
+      bool queued = valid && (ab & 1u) && p >= T && p < keep;
+      uint32_t qoff = p - T;  // the message's place in its actor's backlog
+      if constexpr (kStash) {
+        const uint32_t win = winl[la], mail = len - win, pm = p - win;  // (pm wraps for a window entry: never queued)
+        keep = (C == 0 || mail < C) ? mail : C;
+        queued = valid && (ab & 1u) && p >= win && pm < keep && (win != 0u || pm >= T);
+        qoff = win ? pm : pm - T;
+      }
       const uint32_t sv = valid ? isrc(q) : 0u;
       uint32_t pv = valid ? ipay(q) : 0u;
       if (kWide) {  // a queued state gossip outlives its row's superstep: copy the row forward
@@ -1443,7 +1480,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         }
       }
       if (queued) {
-        const uint32_t o = lo + blpre[la] + (p - T);
+        const uint32_t o = lo + blpre[la] + qoff;
         blw.key[o] = key;
         blw.src[o] = sv;
         blw.pay[o] = pv;
@@ -1616,8 +1653,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     }
   }
   uint32_t ndel = 0, nunh = 0, nall = 0, nact = 0, emtot = 0;
+  uint32_t npn = 0;  // kStash: the next superstep's windows of this thread's actors
   const uint64_t embase = (uint64_t)lo * a.kmax;  // this bucket's slice of the tell arena
-  if (!kWide && a.kmax == 1) {
+  if (!kWide && (kStash || a.kmax == 1)) {  // (a stash engine has max_emit 1: agx_set_stash)
     // ---- single pass (each message emits <= 1 tell): drain + apply; tells are staged over the
     // actor's own, already consumed, inbox slots (tell e of an actor <= message index q that made it):
     // in LDS (fast path) or in the bucket's scratch copy (skew launch)
@@ -1744,6 +1782,80 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           }
         }
       }
+      if constexpr (kStash) {
+        // the drain of DESIGN.md §2.2: the window (segment head) if the actor has one, else the first
+        // min(mail, T) mailbox messages.  A message is read into registers first: a stashed or parked
+        // envelope goes to HBM from there, before a tell is staged over its slot.
+        uint2 h = SD.hdr[l];
+        const uint2 h0 = h;
+        uint32_t head = h.x & 0xFFu, rel = (h.x >> 8) & 0xFFu, size = (h.x >> 16) & 0xFFu;
+        uint32_t ph = h.y & 0xFFFFu, pc = h.y >> 16;
+        const uint32_t scap = stash_cap(P, L.alive[la]);
+        const uint32_t mode = rel ? 1u : pc ? 2u : 0u;  // the source: 1 the buffer, 2 the park, 0 the mailbox
+        const uint32_t win = min(stash_window(h, Ta), len);
+        const uint32_t nds = win ? win : nd;
+        uint2* const sl = SD.of(l);
+        uint32_t nst = 0, nun = 0, nov = 0;
+        for (uint32_t q = 0; q < nds; ++q) {
+          const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          if (mode == 1u) {  // removed from its source, then processed
+            head = head + 1u >= SD.smax ? 0u : head + 1u;
+            --rel;
+            --size;
+          } else if (mode == 2u) {
+            ++ph;
+            --pc;
+          }
+          uint32_t r = apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em, size);
+          if (r == AGX_RES_STASH) {
+            if (size >= scap) {  // StashOverflowException: the actor fails and stops
+              r = AGX_RES_STOPPED;
+              ++nov;
+            } else {
+              uint32_t t = head + size;
+              if (t >= SD.smax) t -= SD.smax;
+              sl[t] = make_uint2(sv, pv);
+              ++size;
+              ++nst;
+            }
+          }
+          if (r != AGX_RES_STASH) ++ndel;
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            // the rest of a mailbox window, and everything buffered or parked (the rest of a buffer /
+            // park window is still in there): dead letters
+            ndead += (mode ? 0u : nds - q - 1u) + size + pc;
+            head = rel = size = ph = pc = 0u;
+            break;
+          }
+          if (r == AGX_RES_UNSTASH_ALL && size) {  // release what is buffered now; the drain ends
+            nun += size - rel;
+            rel = size;
+            if (mode == 0u) {  // the unprocessed rest of the mailbox window is parked (the park is empty)
+              ph = 0u;
+              for (uint32_t i = q + 1u; i < nds; ++i) {
+                if (SD.smax + pc < SD.per) {
+                  sl[SD.smax + pc] = make_uint2(sts[s0 + i], stp[s0 + i]);
+                  ++pc;
+                } else {  // (the park holds throughput - 1 envelopes: only a drain limit raised since)
+                  atomicOr(P.err, (unsigned long long)kErrCapacity);
+                  ++ndead;
+                }
+              }
+            }
+            break;
+          }
+        }
+        h.x = head | (rel << 8) | (size << 16);
+        h.y = ph | (pc << 16);
+        if (h.x != h0.x || h.y != h0.y) SD.hdr[l] = h;
+        npn += stash_window(h, Ta);  // this actor's window of the next superstep
+        if (nst) atomicAdd(SD.ctr(0), (unsigned long long)nst);
+        if (nun) atomicAdd(SD.ctr(1), (unsigned long long)nun);
+        if (nov) atomicAdd(SD.ctr(2), (unsigned long long)nov);
+      } else
       for (uint32_t q = 0; q < nd; ++q) {
         const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
         uint32_t r;
@@ -1805,6 +1917,18 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       for (int j = 0; j < kBAct; ++j) sp_actor(j);
     }
     __syncthreads();
+    if constexpr (kStash) {
+      // the bucket's pending count (read at its entry next superstep) joins its backlog count: the
+      // next inbox has room for the windows, the bucket is visited and the run goes on while any
+      // released or parked message waits
+      uint32_t nptot;
+      block_excl_sum<kBThreads>(npn, L.scratch, &nptot);
+      if (tid == 0) {
+        SD.base[kStashBucketOff + b] = nptot;
+        if constexpr (kGather) a.g.blc[w][b] = bltot + nptot;
+        else a.chunk_cnt[b] = bltot + nptot;
+      }
+    }
     AGX_STAMP(a, 5);
     {  // exclusive scan of tell counts in actor (= sender) order
       uint32_t ec[kBAct], run = 0;
@@ -4108,10 +4232,16 @@ __device__ __forceinline__ void prio_rerank(const BucketArgs& a, const BucketLds
 #endif
 // kPrio: priority mailboxes (prio_rerank above) -- the fast launches of the catch-all plain variants
 // of a single-rank engine with a priority table; every other instantiation compiles without it.
+// kStash: deque-based mailboxes (agx_set_stash) -- the fast launches of the compiled
+// catch-all variant of a single-rank engine with a stash class.  A bucket's inbox then starts with its
+// pending messages (the windows of its actors' buffers and parks, read from the stash storage), its
+// backlog count carries their number (bucket_finish), and the drain knows the stash results.
 template <bool kWide, uint32_t KM, bool kGather, bool kSkew, bool kOwner = false, bool kPrio = false>
 static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_bucket_apply(BucketArgs a) {
   constexpr bool kDefer = !kSkew;  // large inboxes are appended to the skew list
   static_assert(!kPrio || (!kWide && !kSkew && !kOwner), "priority mailboxes: single-rank fast launches, plain behaviours");
+  constexpr bool kStash = (KM & kStashKM) != 0;  // (a flag of KM: agx_device.h)
+  static_assert(!kStash || (!kWide && !kSkew && !kOwner && !kPrio), "stash: single-rank fast launches, plain behaviours");
   if (kOwner && a.halt && a.halt[0]) return;  // (device-resident multi-rank replay stopped)
   // key/src/pay carved from one array: group_tells reuses key+src as a 16 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t s_ksp[3 * kBucket];
@@ -4128,6 +4258,9 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
   __shared__ uint32_t s_lo, s_hi, s_g[6], s_rowtop, s_flags;
   __shared__ unsigned long long s_stat[5];
   const BucketLds L{s_key, s_src, s_pay, U, s_seg, s_ecnt, s_alive, s_kind, s_nh, scratch, s_stat, &s_rowtop};
+  // (kStash: s_rowtop holds the bucket's pending count -- plain behaviours allocate no snapshot rows.  The stash
+  // code below lives in `if constexpr (kStash)` bodies of its own, and every line the other instantiations
+  // compile is textually the one they compiled before: they must keep their register allocation)
   uint16_t* whist = reinterpret_cast<uint16_t*>(U);  // [kBWaves][kBucket]
 
   const DevParams& P = a.P;
@@ -4226,6 +4359,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
             s_g[3] = bs;
             s_lo = bs + bp;
             s_hi = bs + bp + blc + (be - bs);
+            if constexpr (kStash) {  // the backlog count carries the pending windows: [windows][backlog][mail]
+              const uint32_t np = min(P.stash[kStashBucketOff + b], blc);
+              s_rowtop = np;
+              s_g[0] = blc - np;
+            }
           }
           if ((uint64_t)s_hi > a.cap) {  // mail + backlog over the message capacity: report, drop
             atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
@@ -4238,6 +4376,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         s_g[5] = s_hi - s_lo > (uint32_t)kBucket || (kBypass && a.ring_of && a.ring_of[b]);  // (a ring bucket: skew path)
         if constexpr (kPrio)  // the skew launches cannot keep a prioritised actor's order: loud, never wrong
           if (s_g[5] && P.ptab[kPrioBucketOff + b]) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrPrioTile);
+        if constexpr (kStash)  // ... nor do they know a stash: loud, never wrong
+          if (s_g[5] && P.stash[kStashBucketOff + a.nb + b]) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrStashTile);
         if (kDefer && s_g[5]) a.skew_list[atomicAdd(skew_n, 1u)] = b;
       }
     } else {
@@ -4264,6 +4404,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
       }
       if (tid == 0) {  // (the staged count is zeroed once the bucket is processed)
         s_g[0] = g.blc[rpar][b];
+        if constexpr (kStash) {  // (as the multi-pass launch above)
+          const uint32_t np = min(P.stash[kStashBucketOff + b], s_g[0]);
+          s_rowtop = np;
+          s_g[0] -= np;
+        }
         s_g[1] = g.blo[rpar][b];
         s_g[2] = g.stg_cnt[b];
         s_g[3] = g.stg_off[b];
@@ -4279,10 +4424,13 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
       if (tid == 0) {
         segp[ns] = blc + tt;  // staged segment
         s_g[4] = ns;
+        if constexpr (kStash) tt += s_rowtop;  // (the pending windows are part of the inbox; tt is not read again)
         const uint32_t cnt = blc + tt + s_g[2];
         s_g[5] = cnt > (uint32_t)kBucket;
         if constexpr (kPrio)  // (as the multi-pass launch above)
           if (s_g[5] && P.ptab[kPrioBucketOff + b]) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrPrioTile);
+        if constexpr (kStash)
+          if (s_g[5] && P.stash[kStashBucketOff + a.nb + b]) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrStashTile);
         if (kDefer && s_g[5]) {
           a.skew_list[atomicAdd(skew_n, 1u)] = b;
           if (a.abort) a.abort[wpar] = a.slot + 1u;  // strict replay: the rest of it is void
@@ -4360,6 +4508,61 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
       // ---- fast path: the whole bucket in one LDS tile
       uint32_t k[kBIpt], sv[kBIpt], pv[kBIpt], rk[kBIpt];
       const uint32_t wbase = w * (kBIpt * kWave);
+      // kStash: the inbox's first np items are the pending windows of the bucket's actors, in actor
+      // order (so each lands at the head of its actor's segment), staged here from the stash storage
+      if constexpr (kStash) {
+        const uint32_t np = s_rowtop;
+        uint32_t* const wk = reinterpret_cast<uint32_t*>(U);  // [3][kBucket] staged window items
+        if (np) {  // (block-uniform)
+          const StashDev SD = stash_dev(P, a.nb, a.bb);
+          uint32_t wn[kBAct], tot = 0;
+          uint2 hh[kBAct];
+#pragma unroll
+          for (int j = 0; j < kBAct; ++j) {
+            const uint32_t la = tid * kBAct + j, ab = (alive4 >> (8 * j)) & 0xFFu;
+            wn[j] = 0;
+            hh[j] = make_uint2(0u, 0u);
+            if (la < na && (ab & 1u)) {
+              uint32_t Cw, Tw;
+              mbox_limits(P, ab, Cw, Tw);
+              hh[j] = SD.hdr[a0 + la];
+              wn[j] = stash_window(hh[j], Tw);
+            }
+            tot += wn[j];
+          }
+          uint32_t t;
+          uint32_t ex = block_excl_sum<kBThreads>(tot, scratch, &t);
+          if (t < np) {
+            // fewer window messages than the pending count the bucket's backlog count carries (an actor
+            // re-bound to a class with another drain limit since): loud, and the missing items defined
+            if (tid == 0) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
+            for (uint32_t i = t + tid; i < np; i += kBThreads) {
+              wk[i] = a0;
+              wk[kBucket + i] = AGX_NO_SENDER;
+              wk[2 * kBucket + i] = 0u;
+            }
+          }
+#pragma unroll 1
+          for (int j = 0; j < kBAct; ++j) {
+            if (!wn[j]) continue;
+            const uint32_t l = a0 + tid * kBAct + j;
+            const uint32_t head = hh[j].x & 0xFFu, rel = (hh[j].x >> 8) & 0xFFu, ph = hh[j].y & 0xFFFFu;
+            const uint2* sl = SD.of(l);
+            for (uint32_t i = 0; i < wn[j]; ++i, ++ex) {
+              uint32_t x = head + i;
+              if (x >= SD.smax) x -= SD.smax;
+              if (!rel) x = SD.smax + ph + i;
+              if (ex < np && x < SD.per) {
+                const uint2 e = sl[x];
+                wk[ex] = l;
+                wk[kBucket + ex] = e.x;
+                wk[2 * kBucket + ex] = e.y;
+              }
+            }
+          }
+          __syncthreads();
+        }
+      }
       {  // locate every item first (LDS only), then issue all 3 x kBIpt loads back to back: selected
          // base pointers and no branches around the loads (per-item if/else made the compiler wait
          // for each item's loads before the next item's: 8 dependent round trips instead of 1)
@@ -4369,6 +4572,20 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           const uint32_t q = wbase + r * kWave + lane;
           sel[r] = 0;
           idx[r] = 0;
+          if constexpr (kStash) {  // (the first s_rowtop items are the windows, filled in below)
+            const uint32_t np = s_rowtop;
+            if (q < cnt && q >= np) {
+              const uint32_t qm = q - np;
+              if (kGather) {
+                idx[r] = gv.locate(qm, sel[r]);
+              } else if (qm < xblc) {
+                idx[r] = xblo + qm;
+              } else {
+                sel[r] = 1;
+                idx[r] = iv.at(xbst + qm - xblc);
+              }
+            }
+          } else
           if (q < cnt) {
             if (kGather) {
               idx[r] = gv.locate(q, sel[r]);
@@ -4416,6 +4633,19 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
 #pragma unroll
         for (int r = 0; r < kBIpt; ++r)
           if (wbase + r * kWave + lane >= cnt) k[r] = 0xFFFFFFFFu;
+        if constexpr (kStash) {
+          const uint32_t np = s_rowtop;
+          const uint32_t* const wk = reinterpret_cast<const uint32_t*>(U);
+#pragma unroll
+          for (int r = 0; r < kBIpt; ++r) {
+            const uint32_t q = wbase + r * kWave + lane;
+            if (q < np) {
+              k[r] = wk[q];
+              sv[r] = wk[kBucket + q];
+              pv[r] = wk[2 * kBucket + q];
+            }
+          }
+        }
       }
       if (kLateAlive) reinterpret_cast<uint32_t*>(s_alive)[tid] = alive4;
       __syncthreads();  // (fused) the segment list in s_pay is read before the items overwrite it
@@ -4450,6 +4680,7 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
 #else
       const bool presorted = !(flags & 1u);
 #endif
+      if constexpr (!kStash)  // (a stash drain is not the dense rule)
       if (kDense && !(flags & 2u) && a.kmax == 1) {
         dense_finish<KM, kGather, kOwner>(a, L, b, lo, cnt, a0, wpar, acc, kEarly ? ex0 : nullptr, kEarly ? ex1 : nullptr);
         continue;

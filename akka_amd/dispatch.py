@@ -55,6 +55,13 @@ akka.actor.default-mailbox {
   mailbox-type = "akka.dispatch.UnboundedMailbox"
   mailbox-capacity = 1000
   mailbox-push-timeout-time = 10s
+  stash-capacity = -1
+}
+akka.actor.mailbox.unbounded-deque-based {
+  mailbox-type = "akka.dispatch.UnboundedDequeBasedMailbox"
+}
+akka.actor.mailbox.bounded-deque-based {
+  mailbox-type = "akka.dispatch.BoundedDequeBasedMailbox"
 }
 akka.actor.typed.default-mailbox {
   mailbox-type = "akka.dispatch.SingleConsumerOnlyUnboundedMailbox"
@@ -186,6 +193,46 @@ class BoundedControlAwareMailbox(UnboundedControlAwareMailbox):
         self.capacity = int(capacity)
 
 
+MAX_STASH_CAPACITY = 255
+
+
+def _stash_capacity(n) -> int:
+    """`stash-capacity` of a deque-based mailbox (Stash.scala; reference.conf default-mailbox): the GPU
+    stash is a fixed per-actor buffer, so the reference's default -1 (unbounded) is refused."""
+    n = int(n)
+    if n < 0:
+        raise ConfigurationException(
+            f"stash-capacity = {n}: the GPU stash is bounded -- set stash-capacity to 1..{MAX_STASH_CAPACITY} "
+            "(the reference's default -1, an unbounded stash, is not supported)")
+    if not 1 <= n <= MAX_STASH_CAPACITY:
+        raise ConfigurationException(f"stash-capacity = {n}: a GPU stash holds 1..{MAX_STASH_CAPACITY} messages")
+    return n
+
+
+class UnboundedDequeBasedMailbox(MailboxType):
+    """UnboundedDequeBasedMailbox (Mailbox.scala) with the classic `stash-capacity` (Stash.scala): the
+    actors may stash (typed.Behaviors.with_stash); agx_set_stash on the dispatcher's mailbox class."""
+    capacity = 0
+
+    def __init__(self, stash_capacity: int):
+        self.stash_capacity = _stash_capacity(stash_capacity)
+
+    def __repr__(self):
+        return f"{type(self).__name__}(capacity={self.capacity}, stash_capacity={self.stash_capacity})"
+
+
+class BoundedDequeBasedMailbox(UnboundedDequeBasedMailbox):
+    """BoundedDequeBasedMailbox(capacity, pushTimeOut) (Mailbox.scala); the stash does not count towards
+    the capacity."""
+
+    def __init__(self, capacity: int, stash_capacity: int, push_timeout_s: float = 0.0):
+        super().__init__(stash_capacity)
+        if capacity < 0:
+            raise ValueError("The capacity for BoundedDequeBasedMailbox can not be negative")
+        _no_push_timeout("BoundedDequeBasedMailbox", push_timeout_s)
+        self.capacity = int(capacity)
+
+
 def _control_tags(c: Config):
     return c.get_value("gpu.control-tags") if c.has_path("gpu.control-tags") else ()
 
@@ -194,6 +241,9 @@ _MAILBOX_FQCN = {
     "akka.dispatch.UnboundedControlAwareMailbox": lambda c: UnboundedControlAwareMailbox(_control_tags(c)),
     "akka.dispatch.BoundedControlAwareMailbox": lambda c: BoundedControlAwareMailbox(
         c.get_int("mailbox-capacity"), _control_tags(c), c.get_duration_s("mailbox-push-timeout-time")),
+    "akka.dispatch.UnboundedDequeBasedMailbox": lambda c: UnboundedDequeBasedMailbox(c.get_int("stash-capacity")),
+    "akka.dispatch.BoundedDequeBasedMailbox": lambda c: BoundedDequeBasedMailbox(
+        c.get_int("mailbox-capacity"), c.get_int("stash-capacity"), c.get_duration_s("mailbox-push-timeout-time")),
     "akka.dispatch.UnboundedMailbox": lambda c: UnboundedMailbox(),
     "akka.dispatch.SingleConsumerOnlyUnboundedMailbox": lambda c: SingleConsumerOnlyUnboundedMailbox(),
     "akka.dispatch.BoundedMailbox": lambda c: BoundedMailbox(c.get_int("mailbox-capacity"),
@@ -212,7 +262,12 @@ class Mailboxes:
     def lookup(self, mailbox_id: str) -> MailboxType:
         if mailbox_id in self._cache:
             return self._cache[mailbox_id]
-        if mailbox_id == "unbounded":
+        if mailbox_id in ("unbounded-deque-based", "bounded-deque-based"):  # the reference's mailbox ids
+            mailbox_id_path = "akka.actor.mailbox." + mailbox_id
+            conf = self.config.get_config(mailbox_id_path).with_fallback(
+                self.config.get_config("akka.actor.default-mailbox"))
+            mt = self.from_config(conf, conf.get_string("mailbox-type"), mailbox_id_path)
+        elif mailbox_id == "unbounded":
             mt = UnboundedMailbox()
         elif mailbox_id == "bounded":
             # Mailboxes.scala:211 builds a BoundedMailbox from default-mailbox; the GPU mailbox
@@ -394,6 +449,9 @@ class GpuDispatcher:
             table = getattr(self.mailbox_type, "priority_table", None)
             if table is not None:  # a priority / control-aware mailbox type: the dispatcher's class 0
                 self._engine.set_mailbox_priority(0, table)
+            stash = getattr(self.mailbox_type, "stash_capacity", None)
+            if stash is not None:  # a deque-based mailbox type: the dispatcher's class 0 carries its stash
+                self._engine.set_stash(0, stash)
         return self._engine
 
     def is_throughput_deadline_time_defined(self) -> bool:
@@ -405,7 +463,8 @@ class GpuDispatcher:
         if mailbox is not None:
             mb = (mailboxes or self._cfg_mailboxes()).lookup(mailbox)
             if mb.capacity != self.mailbox_type.capacity or \
-                    getattr(mb, "priority_table", None) != getattr(self.mailbox_type, "priority_table", None):
+                    getattr(mb, "priority_table", None) != getattr(self.mailbox_type, "priority_table", None) or \
+                    getattr(mb, "stash_capacity", None) != getattr(self.mailbox_type, "stash_capacity", None):
                 raise ConfigurationException(
                     f"dispatcher [{self.id}] runs one mailbox semantics (capacity {self.mailbox_type.capacity}); "
                     f"props asked for {mb}")

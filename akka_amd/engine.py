@@ -188,6 +188,37 @@ class GpuEngine:
         t = priority_table(table)
         check(self.lib.agx_set_mailbox_priority(self._h, cls, _ptr(t, ctypes.c_uint8)))
 
+    def set_stash(self, cls: int, capacity: int) -> None:
+        """A stash of `capacity` (1..255) messages for every actor of mailbox class `cls` (agx_set_stash): the
+        class is a deque-based mailbox (Unbounded/BoundedDequeBasedMailbox, classic `stash-capacity`), its
+        actors' compiled behaviours may stash and unstash_all (typed.Behaviors.with_stash; StashBuffer,
+        TY/internal/StashBufferImpl.scala:61-79,131-218)."""
+        check(self.lib.agx_set_stash(self._h, cls, capacity))
+
+    def stash_info(self) -> dict:
+        """agx_stash_info: totals stashed / unstashed / overflows, and the messages held / pending now."""
+        v = [ctypes.c_uint64() for _ in range(5)]
+        check(self.lib.agx_stash_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(("stashed", "unstashed", "overflows", "held", "pending"), (int(x.value) for x in v)))
+
+    def read_stash(self, actor_id: int, cap: int = 255):
+        """agx_read_stash: (senders, payloads, released) -- one actor's stash buffer in order and how
+        many of its first entries are released."""
+        s, p = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        rel, n = ctypes.c_uint32(), ctypes.c_uint32()
+        check(self.lib.agx_read_stash(self._h, actor_id, _ptr(s, ctypes.c_uint32), _ptr(p, ctypes.c_uint32), cap,
+                                      ctypes.byref(rel), ctypes.byref(n)))
+        k = min(int(n.value), cap)
+        return s[:k], p[:k], int(rel.value)
+
+    def read_kinds(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """agx_read_kinds: each actor's behaviour kind now (become / unstash_all change it)."""
+        if count is None:
+            count = self.cfg.n_actors - first
+        k = np.zeros(count, np.uint8)
+        check(self.lib.agx_read_kinds(self._h, first, count, _ptr(k, ctypes.c_uint8)))
+        return k
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""

@@ -15,6 +15,11 @@ What lowers:
   * messages are u32 payloads; a ``MessageType`` owns a tag (payload >> 24) and carries a 24-bit
     argument, ``m.payload`` / ``m.tag`` / ``m.arg`` / ``m.sender`` are the message's fields;
   * state is at most two u64 fields (the actor's state words 0 and 1);
+  * ``Behaviors.with_stash(capacity, lambda buffer: ...)`` (TY/scaladsl/Behaviors.scala withStash; StashBuffer,
+    TY/internal/StashBufferImpl.scala): ``buffer.stash()`` as a case's last effect keeps the message,
+    ``buffer.unstash_all(behavior)`` as its result releases the buffered messages into `behavior`,
+    ``buffer.size`` / ``is_empty`` / ``is_full`` are usable in tests and values; the actors' mailbox class
+    carries the capacity (``Tables.stash_capacity`` -> engine.set_stash);
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -36,10 +41,12 @@ import numpy as np
 KIND_COMPILED = 16
 MAX_BEHAVIORS, MAX_CASES, MAX_ACTS = 64, 1024, 4096
 
-V_CONST, V_PAYLOAD, V_TAG, V_ARG, V_WORD, V_SENDER, V_SELF = range(7)
+V_CONST, V_PAYLOAD, V_TAG, V_ARG, V_WORD, V_SENDER, V_SELF, V_STASH = range(8)
 CMP_ANY, CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(7)
 A_SET, A_ADD, A_MAX, A_MIN, A_TELL = 1, 2, 3, 4, 5
-RES_SAME, RES_STOPPED, RES_UNHANDLED, RES_BECOME = 0, 1, 2, 3
+RES_SAME, RES_STOPPED, RES_UNHANDLED, RES_BECOME, RES_STASH, RES_UNSTASH_ALL = 0, 1, 2, 3, 4, 5
+NEXT_SAME = 0xFF  # agx_case.next of RES_UNSTASH_ALL: the behaviour stays
+MAX_STASH = 255
 
 
 class AgxCase(ctypes.Structure):
@@ -235,11 +242,67 @@ class _Result:
     name: str
 
 
+@dataclass(frozen=True, eq=False)
+class _StashEffect:
+    """buffer.stash(msg): the last effect of a case (the message is kept, the behaviour stays)."""
+    buffer: "StashBuffer"
+
+
+@dataclass(frozen=True, eq=False)
+class _UnstashAll:
+    """buffer.unstashAll(behavior) as a case's result."""
+    buffer: "StashBuffer"
+    target: object  # Behavior or Behaviors.same
+
+
+class StashBuffer:
+    """StashBuffer[T] (TY/scaladsl/StashBuffer.scala; StashBufferImpl.scala:61-79 stash / capacity,
+    :131-218 unstashAll) of the actor running the behaviour, symbolic.  The engine enforces the stash
+    capacity of the actor's mailbox class (engine.set_stash), not this number: `capacity` only feeds
+    `is_full` and Tables.stash_capacity, so bind such behaviours to a class with the same capacity wherever
+    a case tests `is_full` (a smaller class capacity overflows earlier than `is_full` says)."""
+
+    def __init__(self, capacity: int):
+        if not isinstance(capacity, int) or not 1 <= capacity <= MAX_STASH:
+            raise CompileError(f"a stash holds 1..{MAX_STASH} messages (no unbounded stash), not {capacity!r}")
+        self.capacity = capacity
+        self.size = Operand(V_STASH)
+
+    def stash(self) -> _StashEffect:
+        return _StashEffect(self)
+
+    def unstash_all(self, behavior) -> _UnstashAll:
+        if not (isinstance(behavior, Behavior) or behavior is Behaviors.same):
+            raise CompileError("unstash_all takes a Behavior or Behaviors.same")
+        return _UnstashAll(self, behavior)
+
+    @property
+    def is_empty(self) -> Test:
+        return self.size == 0
+
+    @property
+    def non_empty(self) -> Test:
+        return self.size > 0
+
+    @property
+    def is_full(self) -> Test:
+        return self.size >= self.capacity
+
+
 class Behaviors:
-    """Behaviors.same / stopped / unhandled (TY/scaladsl/Behaviors.scala) and receiveMessage."""
+    """Behaviors.same / stopped / unhandled (TY/scaladsl/Behaviors.scala), receiveMessage and withStash."""
     same = _Result(RES_SAME, "same")
     stopped = _Result(RES_STOPPED, "stopped")
     unhandled = _Result(RES_UNHANDLED, "unhandled")
+
+    @staticmethod
+    def with_stash(capacity: int, factory) -> "Behavior":
+        """Behaviors.withStash(capacity)(factory): `factory(buffer)` builds the behaviour(s) around one
+        StashBuffer; the actors running it need a mailbox class with a stash of at least `capacity`."""
+        b = factory(StashBuffer(capacity))
+        if not isinstance(b, Behavior):
+            raise CompileError("with_stash's factory must return a Behavior")
+        return b
 
     @staticmethod
     def receive_message(state: State, *handlers, name: str = "behavior") -> "Behavior":
@@ -255,7 +318,7 @@ class Behaviors:
 class _Case:
     tests: list
     effects: list
-    result: object  # _Result or Behavior
+    result: object  # _Result, Behavior, _StashEffect (stash, then same) or _UnstashAll
 
 
 @dataclass(eq=False)
@@ -284,8 +347,21 @@ class ReceiveBuilder:
         if not isinstance(out, (list, tuple)):
             out = [out]
         effects, result = list(out[:-1]), out[-1]
-        if not isinstance(result, (_Result, Behavior)):
-            raise CompileError("a handler's last element must be Behaviors.same/stopped/unhandled or a Behavior")
+        if isinstance(result, _StashEffect):
+            raise CompileError("buffer.stash() is an effect: end the case with Behaviors.same")
+        if not isinstance(result, (_Result, Behavior, _UnstashAll)):
+            raise CompileError("a handler's last element must be Behaviors.same/stopped/unhandled, a Behavior "
+                               "or buffer.unstash_all(...)")
+        if effects and isinstance(effects[-1], _StashEffect):  # the message is kept: the behaviour stays
+            if isinstance(result, _UnstashAll):
+                raise CompileError("a case cannot stash its message and unstash_all")
+            if result is not Behaviors.same:
+                raise CompileError("a case that stashes its message ends with Behaviors.same (not stopped, "
+                                   "unhandled or another behaviour)")
+            result = effects.pop()
+        for e in effects:
+            if isinstance(e, _StashEffect):
+                raise CompileError("buffer.stash() must be the last effect of a case")
         for e in effects:
             if not isinstance(e, Action):
                 raise CompileError(f"not an effect: {e!r}")
@@ -341,6 +417,13 @@ class Tables:
         return max((sum(1 for i in range(c.act_first, c.act_first + c.act_count) if self.acts[i].op == A_TELL)
                     for c in self.cases[:int(self.first[-1])]), default=0)
 
+    @property
+    def stash_capacity(self) -> int:
+        """The largest capacity of the stash buffers these behaviours use (0: none): the stash the
+        actors' mailbox class needs (engine.set_stash)."""
+        return max((c.result.buffer.capacity for b in self.behaviors for c in b.cases
+                    if isinstance(c.result, (_StashEffect, _UnstashAll))), default=0)
+
     def kind_of(self, b: Behavior) -> int:
         """The actor kind that starts in behaviour `b`."""
         for i, x in enumerate(self.behaviors):
@@ -359,6 +442,8 @@ def _reachable(roots) -> list:
         seen.add(id(b))
         order.append(b)
         todo.extend(c.result for c in b.cases if isinstance(c.result, Behavior))
+        todo.extend(c.result.target for c in b.cases
+                    if isinstance(c.result, _UnstashAll) and isinstance(c.result.target, Behavior))
     return order
 
 
@@ -375,7 +460,14 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
         for c in b.cases:
             t = c.tests + [ALWAYS] * (2 - len(c.tests))
             res = c.result
-            code, nxt = (RES_BECOME, index[id(res)]) if isinstance(res, Behavior) else (res.code, 0)
+            if isinstance(res, Behavior):
+                code, nxt = RES_BECOME, index[id(res)]
+            elif isinstance(res, _StashEffect):
+                code, nxt = RES_STASH, 0
+            elif isinstance(res, _UnstashAll):
+                code, nxt = RES_UNSTASH_ALL, (index[id(res.target)] if isinstance(res.target, Behavior) else NEXT_SAME)
+            else:
+                code, nxt = res.code, 0
             if len(acts) + len(c.effects) > 0xFFFF:
                 raise CompileError("too many actions")
             cases.append(AgxCase(src1=t[0].lhs.src, word1=t[0].lhs.word, k1=t[0].lhs.k, cmp1=t[0].cmp,

@@ -48,6 +48,7 @@ class Workload:
     outbound: tuple | None = None                         # (first_host_id, n_host) (agx_set_outbound)
     # class -> 256 priorities by message tag, bytes or a sequence (agx_set_mailbox_priority)
     mailbox_priorities: dict = field(default_factory=dict)
+    stash: dict = field(default_factory=dict)  # class -> stash capacity (agx_set_stash: a deque-based mailbox)
 
     def engine_kwargs(self) -> dict:
         """Semantic parameters (shared by the GPU engine and the CPU oracles)."""
@@ -67,6 +68,8 @@ class Workload:
             target.set_mailbox(first, count, cls)
         for cls, table in self.mailbox_priorities.items():  # (empty: targets without the call are unaffected)
             target.set_mailbox_priority(cls, table)
+        for cls, cap in self.stash.items():  # (empty: targets without the call are unaffected)
+            target.set_stash(cls, cap)
         if self.outbound is not None:
             target.set_outbound(*self.outbound)
         if self.ring_stride is not None:
@@ -502,3 +505,82 @@ def priority_mix(n: int = 2048, seed: int = 1, throughput: int = 3, n_host: int 
                     mailbox_classes={1: 0, 2: 4, 3: 2}, mailboxes=[(0, q, 1), (q, q, 2), (2 * q, q, 3)],
                     outbound=(n, n_host) if n_host else None,
                     mailbox_priorities={1: prio, 2: prio} if tables else {})
+
+
+# ------------------------------------------------------------------ deque-based mailboxes: the stash
+GATE_OPEN, GATE_CLOSE, GATE_DATA, GATE_STOP = 1, 2, 3, 4
+STASH_GATE_HOP = 67
+
+
+def gate(n_actors: int, capacity: int, hop: int = STASH_GATE_HOP):
+    """(closed, open): a gate as two behaviours around one StashBuffer (Behaviors.withStash; "buffer until
+    initialised, then replay", the first pattern of the reference's stash documentation).  Closed, it
+    stashes every data message; Open releases them into the open gate (unstash_all) and Close shuts it
+    again.  Open, a data message of a host-side sender is echoed to it, any other one with a hop count
+    above 0 goes on to the actor `hop` ids further with one hop less; a second Open releases what was
+    stashed meanwhile.  Stop stops the gate.  State: messages seen (a stashed one twice), the last
+    payload handled while open."""
+    from . import typed
+    st = typed.State("count", "last")
+    tag = lambda t: (lambda m: m.tag == t)
+
+    def build(buf):
+        closed, opened = typed.Behavior("closed", st), typed.Behavior("open", st)
+        seen = lambda m, s: [s.count.inc(), s.last.set(m.payload)]
+        (typed.ReceiveBuilder.create(st)
+         .on_any_message(lambda m, s: [s.count.inc(), buf.unstash_all(opened)], test=tag(GATE_OPEN))
+         .on_any_message(lambda m, s: [typed.Behaviors.same], test=tag(GATE_CLOSE))
+         .on_any_message(lambda m, s: [s.count.inc(), typed.Behaviors.stopped], test=tag(GATE_STOP))
+         .on_any_message(lambda m, s: [s.count.inc(), buf.stash(), typed.Behaviors.same])
+         .build(into=closed))
+        (typed.ReceiveBuilder.create(st)
+         .on_any_message(lambda m, s: [closed], test=tag(GATE_CLOSE))
+         .on_any_message(lambda m, s: [s.count.inc(), buf.unstash_all(typed.Behaviors.same)], test=tag(GATE_OPEN))
+         .on_any_message(lambda m, s: [s.count.inc(), typed.Behaviors.stopped], test=tag(GATE_STOP))
+         .on_any_message(lambda m, s: seen(m, s) + [m.sender.tell(m.payload), typed.Behaviors.same],
+                         test=lambda m: m.sender.dst >= n_actors)
+         .on_any_message(lambda m, s: seen(m, s) + [typed.self_ref(hop).tell(m.payload - 1), typed.Behaviors.same],
+                         test=lambda m: m.arg > 0)
+         .on_any_message(lambda m, s: seen(m, s) + [typed.Behaviors.same])
+         .build(into=opened))
+        return closed
+
+    closed = typed.Behaviors.with_stash(capacity, build)
+    return closed, closed.cases[0].result.target
+
+
+def stash_gate(n: int = 2048, seed: int = 1, throughput: int = 3, n_host: int = 8, tells_per_actor: float = 0.9,
+               all_open: bool = False) -> Workload:
+    """A population of gates (gate() above) on four mailbox types: halves of the population start closed
+    and open; quarters are bound to class 1 (unbounded deque-based, stash-capacity 12), class 2
+    (bounded-capacity 4, deque-based, stash-capacity 3), class 3 (bounded-capacity 8, no stash: a gate
+    of it that stashes fails at once) and class 0 (the dispatcher default, stash-capacity 2).  Host
+    tells: data messages with hop counts (some from host-side senders, echoed through the outbox: the
+    order observable), Open, Close and a few Stop, skewed inside groups of 64 actors as priority_mix.
+    `all_open`: every gate starts open and no Close is sent -- the same traffic without a stash in use."""
+    from . import typed
+    rng = np.random.default_rng(seed)
+    closed, opened = gate(n, 12)
+    tb = typed.compile_behaviors([closed, opened], max_emit=1)
+    h = n // 2
+    ranges = [(0, h, tb.kind_of(opened if all_open else closed), None), (h, n - h, tb.kind_of(opened), None)]
+    m = max(1, int(n * tells_per_actor))
+    group = (rng.integers(0, max(1, n // 64), m) * 64).astype(np.int64)
+    dst = np.minimum(group + (64 * rng.random(m) ** 3).astype(np.int64), n - 1).astype(np.uint32)
+    src = rng.integers(0, n, m).astype(np.uint32)
+    if n_host:
+        hs = rng.random(m) < 0.3
+        src[hs] = rng.integers(n, n + n_host, int(hs.sum())).astype(np.uint32)
+    u = rng.random(m)
+    tag = np.full(m, GATE_DATA, np.uint32)
+    tag[u < 0.24] = GATE_OPEN
+    tag[u < 0.10] = GATE_DATA if all_open else GATE_CLOSE
+    tag[u < 0.02] = GATE_STOP
+    pay = (tag << np.uint32(24)) | rng.integers(0, 7, m).astype(np.uint32)
+    late = np.argsort(tag == GATE_OPEN, kind="stable")  # the Opens are told last: a closed gate has buffered by then
+    dst, src, pay = dst[late], src[late], pay[late]
+    q = n // 4
+    return Workload("stash_gate", n, 2, 1, throughput, 0, ranges, behaviors=tb, tells=(dst, src, pay),
+                    mailbox_classes={1: 0, 2: 4, 3: 8}, mailboxes=[(0, q, 1), (q, q, 2), (2 * q, q, 3)],
+                    outbound=(n, n_host) if n_host else None, bucket_actors=128,
+                    stash={0: 2, 1: 12, 2: 3})

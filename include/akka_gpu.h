@@ -95,6 +95,15 @@ enum agx_behavior_kind {
 #define AGX_RES_STOPPED 1u
 #define AGX_RES_UNHANDLED 2u
 #define AGX_RES_BECOME 3u /* compiled behaviours: the next behaviour is agx_case.next */
+/* compiled behaviours of a deque-based mailbox class (agx_set_stash; StashBuffer, TY/internal/
+ * StashBufferImpl.scala:61-79,131-218):
+ *   AGX_RES_STASH        the case's actions run, then the message is appended to the actor's stash
+ *                        buffer (buffer.stash(msg); a full buffer is StashOverflowException: the actor stops);
+ *   AGX_RES_UNSTASH_ALL  buffer.unstashAll(next): the behaviour becomes agx_case.next
+ *                        (AGX_NEXT_SAME: it stays) and the buffered messages are released.            */
+#define AGX_RES_STASH 4u
+#define AGX_RES_UNSTASH_ALL 5u
+#define AGX_NEXT_SAME 0xFFu /* agx_case.next of AGX_RES_UNSTASH_ALL: Behaviors.same */
 
 /* --- compiled behaviours ------------------------------------------------------
  * A typed Behaviors.receiveMessage / javadsl ReceiveBuilder subset lowered to tables
@@ -113,7 +122,9 @@ enum agx_behavior_kind {
 #define AGX_MAX_CASES 1024u
 #define AGX_MAX_ACTS 4096u
 enum agx_operand { AGX_V_CONST = 0, AGX_V_PAYLOAD = 1, AGX_V_TAG = 2, AGX_V_ARG = 3, AGX_V_WORD = 4,
-                   AGX_V_SENDER = 5, AGX_V_SELF = 6 };
+                   AGX_V_SENDER = 5, AGX_V_SELF = 6,
+                   AGX_V_STASH = 7 /* the size of the actor's stash buffer (StashBuffer.size); 0 on an
+                                      engine without a deque-based mailbox class (agx_set_stash) */ };
 enum agx_cmp { AGX_CMP_ANY = 0, AGX_CMP_EQ = 1, AGX_CMP_NE = 2, AGX_CMP_LT = 3, AGX_CMP_LE = 4, AGX_CMP_GT = 5,
                AGX_CMP_GE = 6 };
 enum agx_action_op {
@@ -396,6 +407,45 @@ agx_status agx_set_mailbox(agx_engine* eng, uint64_t first_id, uint64_t count, u
  * AGX_ECAPACITY (sticky; never a silently wrong order).  Buckets without such an actor are not
  * limited. */
 agx_status agx_set_mailbox_priority(agx_engine* eng, uint32_t mailbox_class, const uint8_t prio[256]);
+/* Deque-based mailboxes and the stash (Unbounded/BoundedDequeBasedMailbox, Mailbox.scala; classic
+ * Stash.scala `stash-capacity`; typed StashBuffer, TY/internal/StashBufferImpl.scala:61-79,131-218).
+ * A mailbox class with a stash capacity S (1..255) gives each of its actors a stash buffer of at most
+ * S envelopes outside its mailbox: it never counts towards the mailbox capacity.  A compiled case with
+ * result AGX_RES_STASH appends the message to the buffer (sender and payload kept; not counted
+ * delivered; a full buffer stops the actor, StashOverflowException under typed's default supervision);
+ * AGX_RES_UNSTASH_ALL releases what the buffer holds at that point: the drain ends there, and the
+ * following supersteps process the released messages, up to `throughput` each, before any mailbox
+ * message (mail that arrives meanwhile is queued; the unprocessed rest of that drain is parked and
+ * comes next).  Messages stashed while released ones are processed go behind them and stay held
+ * (DESIGN.md 2.2).  A stopping actor's buffered and parked messages are dead letters.  Held messages
+ * do not keep agx_run going; agx_stats.in_flight includes every buffered and parked message.
+ * The class must be configured; call before the first agx_run (AGX_ESTATE afterwards).  AGX_EINVAL:
+ * capacity 0 or above 255 (there is no unbounded stash: stash-capacity = -1 is not supported), an
+ * engine with n_ranks > 1, with a CRDT kind or a priority table (either call order), with max_emit
+ * above 1, an unconfigured class, an engine whose bounded-mailbox ring pool exists.  AGX_ENOMEM: the
+ * per-actor buffers (n_actors x (largest S + throughput - 1) envelopes) do not fit.
+ * The one bounded difference from the reference: a bucket (agx_cfg.bucket_actors actors) that holds an
+ * actor of such a class and whose inbox -- backlog and the released messages due this superstep
+ * included -- exceeds one 2048-message tile makes agx_run return AGX_ECAPACITY (sticky).  Buckets
+ * without such an actor are not limited. */
+agx_status agx_set_stash(agx_engine* eng, uint32_t mailbox_class, uint32_t capacity);
+/* Totals since agx_create: messages stashed, released by unstash_all, StashOverflowExceptions; and
+ * right now: buffered messages not released (held), released or parked messages still to be
+ * processed (pending).  Any pointer may be NULL. */
+agx_status agx_stash_info(agx_engine* eng, uint64_t* stashed, uint64_t* unstashed, uint64_t* overflows,
+                          uint64_t* held, uint64_t* pending);
+/* One actor's stash buffer in order (for tests and tools): up to `cap` envelopes into src / payload,
+ * *n = the buffer's size, *n_released = how many of its first entries are released. */
+agx_status agx_read_stash(agx_engine* eng, uint64_t actor_id, uint32_t* src, uint32_t* payload, uint32_t cap,
+                          uint32_t* n_released, uint32_t* n);
+/* The behaviour kind of actors [first_id, first_id + count) now, one byte each: a compiled behaviour's become
+ * and unstash_all(next) change it (AGX_KIND_COMPILED + behaviour).  Single-rank engines (for tests and tools). */
+agx_status agx_read_kinds(agx_engine* eng, uint64_t first_id, uint64_t count, uint8_t* kinds);
+/* Compiled tables with a stash / unstash_all result on an engine without any stash class make agx_run
+ * return AGX_EINVAL.  On an engine with one, an actor of a class without a capacity that runs a stash
+ * case overflows and stops -- except in a bucket without any actor of a stash class whose inbox exceeds
+ * one tile: that bucket takes the skew launch, which does not interpret the stash results (the message
+ * is handled as Behaviors.same); keep such actors off behaviours that stash. */
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
