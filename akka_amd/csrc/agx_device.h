@@ -52,6 +52,9 @@ struct DevParams {
     // deque-based mailboxes (agx_set_stash), read and written only by the stash k_bucket_apply instantiations:
     // the per-actor stash buffers and their bookkeeping (StashDev below)
     uint32_t* stash;
+    // timers (agx_set_timers), read and written only by the timer k_bucket_apply instantiations: the
+    // per-actor timer slots and their bookkeeping (TimerDev below)
+    uint32_t* timers;
   };
   uint32_t* heap_top;       // [2] rows allocated in heap[parity]
   const uint32_t* step;     // superstep counter (bumped by the first kernel of a step)
@@ -150,6 +153,82 @@ __device__ __forceinline__ uint32_t stash_cap(const DevParams& P, uint32_t abyte
 __device__ __forceinline__ uint32_t stash_window(uint2 h, uint32_t T) {
   const uint32_t rel = (h.x >> 8) & 0xFFu, pc = h.y >> 16;
   return rel ? min(rel, T) : min(pc, T);
+}
+
+// ---- timers (agx_set_timers; TY/internal/TimerSchedulerImpl.scala:61-172)
+// One superstep is one tick.  DevParams.timers, u32 units:
+//   [0]      n_keys: timer slots per actor (1..4)
+//   [2]      the last tick at whose entry a bucket had mail or a pending timer (atomicMax; the host's
+//            quiescence poll of the multi-pass pipeline and the `ticks` count read it)
+//   [4..7]   two u64 counters: fired, discarded
+//   [kTmBucketOff + b]           earliest: the tick of bucket b's next fire, kTmNone when no timer is pending
+//                                (exact at the end of every tick: a bucket with nothing due reads this word only)
+//   [kTmBucketOff + nb + b]      due: the fires of the next tick (counted into the bucket's backlog count, so
+//                                the next inbox has room for their TimerMsgs; read at the bucket's entry)
+//   [kTmBucketOff + 2 * nb + b]  clock: the ticks bucket b has run (every bucket runs every tick: all equal)
+//   then, 16-byte aligned and slot-major ([key][actor], np = nb << bb actors, so a scan of one key over a
+//   bucket is coalesced):
+//     next[key][np]  the tick of the slot's next fire, kTmNone when none is to come
+//     per[key][np]   the period (0: a single timer) | kTmActive
+//     gen[key][np]   the slot's generation          pay[key][np]  the message payload
+//   then agen[np]: the actor's generation counter minus 1 (the reference's timerGen starts at 1).
+// Generations are compared mod 2^22 (the TimerMsg payload carries 22 bits of them).
+constexpr uint32_t kTmBucketOff = 16;
+constexpr uint32_t kTmLastAct = 2, kTmCtr = 4;
+constexpr uint32_t kTmNone = 0xFFFFFFFFu, kTmActive = 0x80000000u, kTmGenMask = 0x3FFFFFu;
+constexpr uint32_t kTmMaxDelay = 0x7FFFFFFFu;
+__host__ __device__ __forceinline__ size_t tm_slot_off(uint32_t nb) {
+  return ((size_t)kTmBucketOff + 3u * (size_t)nb + 3u) & ~(size_t)3;
+}
+struct TimerDev {
+  uint32_t* base;
+  uint32_t *next, *per, *gen, *pay, *agen;  // [key * np + l]
+  uint32_t nk, np, nb;
+  __device__ __forceinline__ uint32_t& earliest(uint32_t b) const { return base[kTmBucketOff + b]; }
+  __device__ __forceinline__ uint32_t& due(uint32_t b) const { return base[kTmBucketOff + nb + b]; }
+  __device__ __forceinline__ uint32_t& clock(uint32_t b) const { return base[kTmBucketOff + 2u * nb + b]; }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kTmCtr) + i;
+  }
+  __device__ __forceinline__ size_t at(uint32_t key, uint32_t l) const { return (size_t)key * np + l; }
+  // cancel: the slot is inactive and nothing of it is to come; the bucket rescans its slots at the end of the tick
+  __device__ __forceinline__ void cancel(uint32_t key, uint32_t l, uint32_t b) const {
+    const size_t i = at(key, l);
+    if (per[i] & kTmActive) {
+      per[i] = 0u;
+      next[i] = kTmNone;
+      atomicMin(&earliest(b), 0u);
+    }
+  }
+  // start: cancel, the actor's next generation, active with the next fire at now + delay (delay in 1..2^31 - 1)
+  __device__ __forceinline__ void start(uint32_t key, uint32_t l, uint32_t b, uint32_t now, uint32_t delay, bool periodic,
+                                        uint32_t payload) const {
+    const size_t i = at(key, l);
+    const uint32_t g = agen[l] + 1u;
+    agen[l] = g;
+    gen[i] = g;
+    pay[i] = payload;
+    per[i] = (periodic ? delay : 0u) | kTmActive;
+    next[i] = now + delay;
+    atomicMin(&earliest(b), now + delay);
+  }
+};
+__device__ __forceinline__ TimerDev timer_dev(const DevParams& P, uint32_t nb, uint32_t bb) {
+  TimerDev t;
+  t.base = P.timers;
+  t.nk = P.timers[0];
+  t.nb = nb;
+  t.np = nb << bb;
+  t.next = P.timers + tm_slot_off(nb);
+  t.per = t.next + (size_t)t.nk * t.np;
+  t.gen = t.per + (size_t)t.nk * t.np;
+  t.pay = t.gen + (size_t)t.nk * t.np;
+  t.agen = t.pay + (size_t)t.nk * t.np;
+  return t;
+}
+// a computed delay: below 1 counts as 1, above 2^31 - 1 is clamped (the operand is a wrapped 64-bit sum)
+__device__ __forceinline__ uint32_t tm_delay(uint64_t d) {
+  return (int64_t)d < 1 ? 1u : d > (uint64_t)kTmMaxDelay ? kTmMaxDelay : (uint32_t)d;
 }
 
 // A tell to a host-side actor (agx_set_outbound): appended to the outbox (when `write`); returns
@@ -312,6 +391,8 @@ constexpr uint32_t kDeltaKM = 1u << 31;
 // KM flag (not a kind): the variant knows the stash of deque-based mailboxes (agx_set_stash).  A flag of KM,
 // not a template parameter of its own, so every other instantiation keeps its name and compiles as before.
 constexpr uint32_t kStashKM = 1u << 30;
+// KM flag (not a kind): the variant knows timers (agx_set_timers).  A flag of KM for the same reason.
+constexpr uint32_t kTimersKM = 1u << 29;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -389,6 +470,75 @@ __device__ __forceinline__ uint32_t compiled_apply(const DevParams& P, uint32_t&
     }
     if constexpr (kStash)  // unstash_all(next): the become here, the release by the caller
       if (C.result == AGX_RES_UNSTASH_ALL && C.next != AGX_NEXT_SAME) kind = AGX_KIND_COMPILED + C.next;
+    return C.result;
+  }
+  return AGX_RES_UNHANDLED;
+}
+
+// compiled_apply of the timer instantiations (agx_set_timers): the same rule, with AGX_V_TIMER
+// (isTimerActive) among the operands and the timer actions, run in order with the others, against the
+// actor's slots.  A function of its own: every other instantiation compiles compiled_apply as before.
+__device__ __forceinline__ uint64_t tm_operand(const TimerDev& TD, uint32_t l, uint32_t src, uint32_t word, int64_t k,
+                                               uint32_t pay, const uint64_t* w, uint32_t sender, uint32_t self) {
+  if (src == AGX_V_TIMER)
+    return (uint64_t)((word < TD.nk && (TD.per[TD.at(word, l)] & kTmActive)) ? 1u : 0u) + (uint64_t)k;
+  return cb_operand(src, word, k, pay, w, sender, self);
+}
+template <typename Emit>
+__device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const TimerDev& TD, uint32_t l, uint32_t bkt,
+                                                      uint32_t now, uint32_t& kind, uint32_t self, uint64_t* w,
+                                                      uint32_t src, uint32_t pay, Emit& emit) {
+  const uint32_t b = kind - AGX_KIND_COMPILED;
+  if (b >= P.n_beh) return AGX_RES_UNHANDLED;
+  const uint32_t c1 = P.bfirst[b + 1];
+  for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
+    const agx_case C = P.bcase[c];
+    if (!cb_cmp(C.cmp1, tm_operand(TD, l, C.src1, C.word1, C.k1, pay, w, src, self),
+                tm_operand(TD, l, C.src2, C.word2, C.k2, pay, w, src, self)))
+      continue;
+    if (!cb_cmp(C.cmp2, tm_operand(TD, l, C.src3, C.word3, C.k3, pay, w, src, self),
+                tm_operand(TD, l, C.src4, C.word4, C.k4, pay, w, src, self)))
+      continue;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      const agx_act A = P.bact[i];
+      const uint64_t v = tm_operand(TD, l, A.src, A.sword, A.k, pay, w, src, self);
+      switch (A.op) {
+        case AGX_A_SET: w[A.word & 1u] = v; break;
+        case AGX_A_ADD: w[A.word & 1u] += v; break;
+        case AGX_A_MAX: w[A.word & 1u] = v > w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_MIN: w[A.word & 1u] = v < w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_TELL: {
+          uint64_t d;
+          if (A.dsrc == AGX_V_SELF) {  // (self + dk) mod n: ring neighbours
+            int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+            d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+          } else {
+            d = tm_operand(TD, l, A.dsrc, A.dword, A.dk, pay, w, src, self);
+          }
+          emit(d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d, A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v);
+          break;
+        }
+        case AGX_A_TIMER_SINGLE:
+        case AGX_A_TIMER_PERIODIC:
+          if (A.word < TD.nk) {  // (a key past n_keys is refused at agx_run)
+            TD.cancel(A.word, l, bkt);
+            TD.start(A.word, l, bkt, now, tm_delay(tm_operand(TD, l, A.dsrc, A.dword, A.dk, pay, w, src, self)),
+                     A.op == AGX_A_TIMER_PERIODIC, A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v);
+          }
+          break;
+        case AGX_A_TIMER_CANCEL:
+          if (A.word < TD.nk) TD.cancel(A.word, l, bkt);
+          break;
+        case AGX_A_TIMER_CANCEL_ALL:
+          for (uint32_t k = 0; k < TD.nk; ++k) TD.cancel(k, l, bkt);
+          break;
+        default: break;
+      }
+    }
+    if (C.result == AGX_RES_BECOME) {
+      kind = AGX_KIND_COMPILED + C.next;
+      return AGX_RES_SAME;
+    }
     return C.result;
   }
   return AGX_RES_UNHANDLED;

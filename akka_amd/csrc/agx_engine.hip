@@ -136,6 +136,20 @@ struct agx_engine {
   size_t stash_hdr_off = 0, stash_slot_off = 0;  // u32 offsets of the headers / envelopes in d_stash
   bool stash_dirty = false;  // the capacities or the actors' classes changed since the last upload
   bool beh_stash = false;    // the compiled tables hold a stash / unstash_all result (agx_set_behaviors)
+  // timers (agx_set_timers): n_keys slots per actor.  An engine with timers launches the timer instantiation of
+  // the compiled catch-all variant and no wave / ring / dense / persistent launch
+  uint32_t tm_keys = 0;
+  uint32_t* d_timers = nullptr;  // DevParams.timers (agx_device.h TimerDev): sized at the first run
+  uint32_t beh_tm_keys = 0;      // the compiled tables use timer keys below this (0: no timer action / AGX_V_TIMER)
+  bool tm_bad_start = false;     // agx_start_timers was called on an engine without timers: agx_run refuses
+  uint64_t tm_ticks = 0;         // supersteps that ran while the engine was not quiescent
+  uint32_t tm_clock = 0;         // the device clock after the last run (every bucket's tick count)
+  struct TimerStart {
+    uint64_t first, count;
+    uint32_t key, periodic, delay, payload;
+    std::vector<uint32_t> delays;
+  };
+  std::vector<TimerStart> tm_starts;  // agx_start_timers calls not yet applied on the device (prepare_run)
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -470,6 +484,7 @@ DevParams make_params(agx_engine* e) {
   P.rx = e->d_rx;
   if (e->prio_mask) P.ptab = e->d_ptab;  // (shares rx's slot: no CRDT kinds on an engine with priority tables)
   if (e->stash_on) P.stash = e->d_stash;  // (the same slot: neither CRDT kinds nor priority tables with a stash)
+  if (e->tm_keys) P.timers = e->d_timers;  // (the same slot: none of the three on an engine with timers)
   P.heap_top = e->d_heap_top;
   P.step = e->d_step;
   P.heap_rows = (uint32_t)e->heap_rows;
@@ -636,6 +651,7 @@ uint32_t apply_variant(const agx_engine* e) {
   if (e->prio_mask)  // priority mailboxes: the catch-all plain variants carry the order step (kPrio)
     return (km & kb(AGX_KIND_COMPILED)) ? V_ALL_COMPILED : V_ALL;
   if (e->stash_on) return V_ALL_COMPILED;  // deque-based mailboxes: the compiled catch-all carries the stash (kStash)
+  if (e->tm_keys) return V_ALL_COMPILED;   // timers: the compiled catch-all carries them (kTimers)
   if (e->pw && e->delta_max) {  // delta-CRDT replication: the variants that carry the delta code
     if (km == kb(AGX_KIND_GCOUNTER)) return V_GC_DELTA;
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN_DELTA;
@@ -665,7 +681,7 @@ bool dense_on(const agx_engine* e, uint32_t vid) {
   // (k_dense_fused reads a fused bucket's table row one sender bucket per thread: nb <= 512, which
   // the fused superstep's <= 2^20 actors guarantee)
   if (e->fused && e->nb > (uint32_t)kDenseThreads) return false;
-  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask && !e->stash_on &&
+  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask && !e->stash_on && !e->tm_keys &&
          (e->dense_launch == 1 || (e->dense_launch < 0 && vid == V_RING));
 }
 
@@ -849,7 +865,7 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
     }
     // (priority mailboxes: the wave path drains in arrival order -- every bucket takes the block launch)
     const bool tl = mode == M_BYPASS && !kVariants[vid].wide && e->tiny_launch && e->tiny_max && !e->skew_only &&
-                    !e->prio_mask && !e->stash_on;
+                    !e->prio_mask && !e->stash_on && !e->tm_keys;
     if (tl) {  // wave-per-bucket launch first; the block launch then takes the buckets it marked
       ba.blist = e->d_blist;
       ba.dense_first = dl ? 1u : 0u;
@@ -869,6 +885,9 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       } else if (e->stash_on) {
         if (mode == M_OWNER) return set_err(AGX_ESTATE, "deque-based mailboxes need a single-rank engine");
         HIP_TRY(agx_launch_apply_stash(vid, mode, g, e->stream, bf));
+      } else if (e->tm_keys) {
+        if (mode == M_OWNER) return set_err(AGX_ESTATE, "timers need a single-rank engine");
+        HIP_TRY(agx_launch_apply_timers(vid, mode, g, e->stream, bf));
       } else {
         HIP_TRY(agx_launch_apply(vid, mode, false, g, e->stream, bf));
       }
@@ -907,7 +926,7 @@ agx_status launch_staged_chunk(agx_engine* e) {
 // behaviours, every configured mailbox class bounded by <= kRingMaxC); from then on the classes
 // are fixed (agx_set_mailbox_class refuses a capacity the rings cannot hold).
 agx_status setup_rings(agx_engine* e) {
-  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask || e->stash_on) return AGX_OK;  // (a ring drains in arrival order)
+  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask || e->stash_on || e->tm_keys) return AGX_OK;  // (a ring drains in arrival order)
   uint32_t cmax = 0;
   for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) {
     if (!((e->mclass_set >> c) & 1u)) continue;
@@ -951,7 +970,7 @@ agx_status setup_rings(agx_engine* e) {
 constexpr uint32_t kRingAutoC = 256;  // ring apply by default from this mailbox capacity up (setup_ring_apply)
 agx_status setup_ring_apply(agx_engine* e) {
   if (e->started || e->rg_on || e->ring_live || e->ring_res) return AGX_OK;
-  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask || e->stash_on) return AGX_OK;
+  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask || e->stash_on || e->tm_keys) return AGX_OK;
   // AGX_RING_APPLY=1 / 0 forces rings on / off; unset: on when the largest bounded capacity is at
   // least kRingAutoC.  Deep queues are where re-copying the backlog every superstep costs most (C3,
   // BoundedMailbox(1000): 4.67e8 -> 6.7e8 msg/s with rings, the sparse buckets a wave each); at
@@ -1088,8 +1107,147 @@ agx_status stash_scan(agx_engine* e, uint64_t* held, uint64_t* pending, uint64_t
   return AGX_OK;
 }
 
+// ---- timers (agx_set_timers)
+// agx_start_timers on the device: one thread per actor of the range starts slot `key` at its bucket's clock
+static __global__ void __launch_bounds__(kThreads) k_timer_start(uint32_t* tm, const uint8_t* alive, uint32_t nb, uint32_t bb,
+                                                                uint32_t first, uint32_t count, uint32_t key, uint32_t periodic,
+                                                                uint32_t delay, const uint32_t* delays, uint32_t payload) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t l = first + i, np = nb << bb;
+  if (!(alive[l] & 1u)) return;  // (a stopped actor has no timers)
+  const uint32_t nk = tm[0];
+  uint32_t* const next = tm + tm_slot_off(nb);
+  uint32_t *const per = next + (size_t)nk * np, *const gen = per + (size_t)nk * np, *const pay = gen + (size_t)nk * np,
+           *const agen = pay + (size_t)nk * np;
+  // the first fire after delays[i] ticks (`delay` without the array); a periodic timer's period is `delay`
+  auto clamp = [](uint32_t x) { return x < 1u ? 1u : x > kTmMaxDelay ? kTmMaxDelay : x; };
+  const uint32_t d = clamp(delays ? delays[i] : delay), pd = clamp(delay);
+  const size_t x = (size_t)key * np + l;
+  const uint32_t g = agen[l] + 1u;
+  agen[l] = g;
+  gen[x] = g;
+  pay[x] = payload;
+  per[x] = (periodic ? pd : 0u) | kTmActive;
+  next[x] = tm[kTmBucketOff + 2u * nb + (l >> bb)] + d;
+}
+// after host-side starts: every bucket's earliest fire and the fires of its next tick, whose count replaces
+// the old one in the bucket's backlog count (one block per bucket)
+static __global__ void __launch_bounds__(kThreads) k_timer_sync(uint32_t* tm, const uint8_t* alive, uint32_t nb, uint32_t bb,
+                                                               uint32_t n_local, uint32_t* blc) {
+  __shared__ uint32_t s_min, s_due;
+  const uint32_t b = blockIdx.x, np = nb << bb, nk = tm[0];
+  if (threadIdx.x == 0) {
+    s_min = kTmNone;
+    s_due = 0u;
+  }
+  __syncthreads();
+  const uint32_t* next = tm + tm_slot_off(nb);
+  const uint32_t now = tm[kTmBucketOff + 2u * nb + b];
+  const uint32_t a0 = b << bb, na = min(1u << bb, n_local - a0);
+  uint32_t mn = kTmNone, nd = 0;
+  for (uint32_t k = 0; k < nk; ++k)
+    for (uint32_t la = threadIdx.x; la < na; la += kThreads) {
+      const uint32_t n = next[(size_t)k * np + a0 + la];
+      if (n != kTmNone && (alive[a0 + la] & 1u)) {
+        mn = min(mn, n);
+        nd += n == now + 1u ? 1u : 0u;
+      }
+    }
+  if (mn != kTmNone) atomicMin(&s_min, mn);
+  if (nd) atomicAdd(&s_due, nd);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    tm[kTmBucketOff + b] = s_min;
+    blc[b] = blc[b] - min(tm[kTmBucketOff + nb + b], blc[b]) + s_due;
+    tm[kTmBucketOff + nb + b] = s_due;
+  }
+}
+
+size_t timers_words(const agx_engine* e) {
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  return tm_slot_off(e->nb) + (4ull * e->tm_keys + 1ull) * npad;
+}
+
+// The timer storage (agx_device.h TimerDev) -- allocated once, sized by n_local: counters, clocks and due counts
+// zero, every bucket's earliest fire and every slot's next fire "none", the slots inactive.
+agx_status alloc_timers(agx_engine* e) {
+  if (e->d_timers) return AGX_OK;
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  const size_t total = timers_words(e), soff = tm_slot_off(e->nb);
+  if (hipMalloc((void**)&e->d_timers, total * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_timers = nullptr;
+    return set_err(AGX_ENOMEM, "the timer slots of %llu actors (%u keys each, %llu MB) do not fit on the device",
+                   (unsigned long long)npad, e->tm_keys, (unsigned long long)(total >> 18));
+  }
+  HIP_TRY(hipMemsetAsync(e->d_timers, 0, total * 4ull, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_timers + kTmBucketOff, 0xFF, (size_t)e->nb * 4ull, e->stream));       // earliest
+  HIP_TRY(hipMemsetAsync(e->d_timers + soff, 0xFF, (size_t)e->tm_keys * npad * 4ull, e->stream));  // next
+  const uint32_t nk = e->tm_keys;
+  HIP_TRY(hipMemcpyAsync(e->d_timers, &nk, 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  drop_graphs(e);  // (a kernel argument of the captured supersteps)
+  return AGX_OK;
+}
+
+// the backlog counts the next superstep reads (fused: the read parity's; multi-pass: the chunk counts)
+uint32_t* next_backlog_counts(agx_engine* e) { return e->fused ? e->d_blc[e->par ^ 1u] : e->d_chunk_cnt; }
+
+// apply the recorded agx_start_timers calls (the actors' flags are on the device: prepare_run)
+agx_status flush_timer_starts(agx_engine* e) {
+  if (e->tm_starts.empty()) return AGX_OK;
+  if (e->actors_dirty)  // (a query before the run: the host's flags are the newer ones; prepare_run uploads the rest)
+    HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
+  for (const auto& ts : e->tm_starts) {
+    uint32_t* d_del = nullptr;
+    if (!ts.delays.empty()) {
+      AGX_TRY(dalloc(&d_del, ts.delays.size()));
+      HIP_TRY(hipMemcpyAsync(d_del, ts.delays.data(), ts.delays.size() * 4ull, hipMemcpyHostToDevice, e->stream));
+    }
+    if (ts.count)
+      hipLaunchKernelGGL(k_timer_start, dim3((uint32_t)((ts.count + kThreads - 1) / kThreads)), dim3(kThreads), 0, e->stream,
+                         e->d_timers, e->d_alive, e->nb, e->bb, (uint32_t)ts.first, (uint32_t)ts.count, ts.key, ts.periodic,
+                         ts.delay, d_del, ts.payload);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (d_del) hipFree(d_del);
+  }
+  e->tm_starts.clear();
+  hipLaunchKernelGGL(k_timer_sync, dim3(e->nb), dim3(kThreads), 0, e->stream, e->d_timers, e->d_alive, e->nb, e->bb,
+                     (uint32_t)e->n_local, next_backlog_counts(e));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->inflight_known = false;
+  return AGX_OK;
+}
+
+// the bookkeeping words of the timer storage: [0, kTmBucketOff) then earliest / due / clock per bucket
+agx_status read_timer_head(agx_engine* e, std::vector<uint32_t>& h) {
+  h.assign(kTmBucketOff + 3ull * e->nb, 0u);
+  return copy_sync(e, h.data(), e->d_timers, h.size() * 4ull, hipMemcpyDeviceToHost);
+}
+
+// after a run: the ticks that passed while the engine was not quiescent (the device's last active tick against
+// the clock before the run), and the clock now
+agx_status timers_after_run(agx_engine* e) {
+  if (!e->d_timers) return AGX_OK;
+  uint32_t la = 0, clk = 0;
+  AGX_TRY(copy_sync(e, &la, e->d_timers + kTmLastAct, 4, hipMemcpyDeviceToHost));
+  AGX_TRY(copy_sync(e, &clk, e->d_timers + kTmBucketOff + 2ull * e->nb, 4, hipMemcpyDeviceToHost));
+  if (la > e->tm_clock) e->tm_ticks += la - e->tm_clock;
+  e->tm_clock = clk;
+  return AGX_OK;
+}
+
 // upload host mirrors / staged tells before a run
 agx_status prepare_run(agx_engine* e) {
+  if (e->tm_bad_start)
+    return set_err(AGX_EINVAL, "agx_start_timers was called on an engine without timers (agx_set_timers)");
+  if (e->beh_tm_keys > e->tm_keys)  // (only the timer variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, e->tm_keys ? "the compiled behaviours use timer key %u, but the engine has %u timer slots per "
+                   "actor (agx_set_timers)" : "the compiled behaviours use timers (key %u), but the engine has none "
+                   "(agx_set_timers; it has %u slots)", e->beh_tm_keys - 1u, e->tm_keys);
   if (e->beh_stash && !e->stash_on)  // (only the stash variant interprets those results: loud, never wrong)
     return set_err(AGX_EINVAL, "the compiled behaviours stash or unstash_all, but no mailbox class of this engine has a "
                    "stash capacity (agx_set_stash): without one every stash would overflow");
@@ -1128,6 +1286,10 @@ agx_status prepare_run(agx_engine* e) {
     e->stash_dirty = e->stash_on;
   }
   if (e->stash_dirty) AGX_TRY(upload_stash(e));
+  if (e->tm_keys) {
+    AGX_TRY(alloc_timers(e));
+    AGX_TRY(flush_timer_starts(e));
+  }
   if (e->prio_dirty) {  // priority tables and the buckets that hold an actor of a prioritised class
     std::vector<uint8_t> pb(e->prio_tab);  // tables, then the bucket marks (kPrioBucketOff)
     pb.resize(kPrioBucketOff + e->nb, 0);
@@ -1371,6 +1533,10 @@ agx_status error_status(const agx_engine* e, uint64_t err) {
     return set_err(AGX_ECAPACITY, "a bucket of %u actors that holds an actor of a deque-based mailbox class received "
                    "more than one tile of %d messages (backlog and released stash messages included): a stash is "
                    "drained within one tile (smaller agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
+  if (err & kErrTimerTile)
+    return set_err(AGX_ECAPACITY, "a bucket of %u actors of an engine with timers received more than one tile of %d "
+                   "messages (backlog and the tick's timer messages included): the launches for larger inboxes know "
+                   "no timers (smaller agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
   if (err & kErrCapacity)
     return set_err(AGX_ECAPACITY, "in-flight messages exceeded engine capacity (msg_capacity=%llu)",
                    (unsigned long long)e->cap);
@@ -1402,6 +1568,11 @@ agx_status collect_stats(agx_engine* e, agx_stats* out, bool check) {
     uint64_t held, pending, windows;
     AGX_TRY(stash_scan(e, &held, &pending, &windows));
     st.in_flight += held + pending - windows;
+  }
+  if (e->d_timers) {  // the backlog counts carry the next tick's fires: not sent yet, not in flight
+    std::vector<uint32_t> h;
+    AGX_TRY(read_timer_head(e, h));
+    for (uint32_t b = 0; b < e->nb; ++b) st.in_flight -= std::min<uint64_t>(st.in_flight, h[kTmBucketOff + e->nb + b]);
   }
   // B = E_in + f_out*E_out + 2*S*(A/M); kind+alive bytes read per activation.
   // S = the state words a behaviour touches: words 0-1 (plain and compiled behaviours), a CRDT's
@@ -1448,7 +1619,7 @@ bool persist_ok(agx_engine* e) {
       e->persist = (uint64_t)e->nb <= (uint64_t)per_cu * (uint64_t)ncu ? 1 : 0;
     (void)hipGetLastError();
   }
-  return e->persist == 1 && !e->prio_mask && !e->stash_on && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
+  return e->persist == 1 && !e->prio_mask && !e->stash_on && !e->tm_keys && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
          !e->recover_dense;
 }
 
@@ -1571,14 +1742,19 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
     for (uint32_t i = 0; i < rep_steps[slot]; ++i) {
       uint64_t t = 0;
       bool skew = false;  // a bucket's inbox over one LDS tile (it took the skew launch)
+      bool tpend = false;  // timers: bit 31 of an entry = the bucket had a pending timer at the tick's entry
       for (uint32_t b = 0; b < e->nb; ++b) {
-        const uint32_t v = h[(size_t)i * e->nb + b];
+        uint32_t v = h[(size_t)i * e->nb + b];
+        if (e->tm_keys) {
+          tpend |= (v >> 31) != 0u;
+          v &= 0x7FFFFFFFu;
+        }
         t += v;
         skew |= v > (uint32_t)kBucket;
       }
       if (t) ++e->host_steps;
       e->clean_steps = skew ? 0u : e->clean_steps + 1u;
-      last_empty = t == 0;
+      last_empty = t == 0 && !tpend;
     }
     rep_steps[slot] = 0;
     return last_empty;
@@ -1672,7 +1848,8 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
           strict = true;
           e->strict_ok = true;
         }
-      } else if (e->h_pin[slot] == 0) {
+      } else if (e->tm_keys ? e->h_pin[8 + 2 * slot] != e->h_pin[9 + 2 * slot] : e->h_pin[slot] == 0) {
+        // (timers: the last tick with mail or a pending timer at its entry is not that replay's last tick)
         break;  // that replay ended on a superstep with no mail: quiescent
       }
     }
@@ -1726,6 +1903,10 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
       }
     } else {  // inbox total (sorted + backlog) of the replay's last superstep
       hipMemcpyAsync(&e->h_pin[slot], e->d_ninbox, 4, hipMemcpyDeviceToHost, e->stream);
+      if (e->tm_keys) {  // the last active tick and the clock after this replay
+        hipMemcpyAsync(&e->h_pin[8 + 2 * slot], e->d_timers + kTmLastAct, 4, hipMemcpyDeviceToHost, e->stream);
+        hipMemcpyAsync(&e->h_pin[9 + 2 * slot], e->d_timers + kTmBucketOff + 2ull * e->nb, 4, hipMemcpyDeviceToHost, e->stream);
+      }
     }
     launched_steps += cnt;
     hipEventRecord(ev[slot], e->stream);
@@ -2177,6 +2358,8 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
   if (e->prio_mask)
     return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a priority mailbox "
                    "(agx_set_mailbox_priority): a state gossip's snapshot handle carries no message tag");
+  if (e->tm_keys)
+    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with timers (agx_set_timers)");
   if (e->stash_on)
     return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a deque-based mailbox "
                    "(agx_set_stash): a state gossip's snapshot row does not outlive its superstep in a stash");
@@ -2595,6 +2778,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_orw); hipFree(e->d_orm); hipFree(e->d_orw_n);
   hipFree(e->d_ptab);
   hipFree(e->d_stash);
+  hipFree(e->d_timers);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -2709,6 +2893,7 @@ agx_status agx_set_mailbox_priority(agx_engine* e, uint32_t cls, const uint8_t p
                    "arrival order: set priority tables before the first run", e->ring_live ? e->ring_c : e->rg_c);
   if (e->stash_on)
     return set_err(AGX_EINVAL, "priority mailboxes need an engine without a deque-based mailbox class (agx_set_stash)");
+  if (e->tm_keys) return set_err(AGX_EINVAL, "priority mailboxes need an engine without timers (agx_set_timers)");
   if (e->started) return set_err(AGX_ESTATE, "set mailbox priorities before the first agx_run");
   AGX_TRY(ensure_dev(e));
   if (prio) {
@@ -2733,6 +2918,7 @@ agx_status agx_set_stash(agx_engine* e, uint32_t cls, uint32_t capacity) {
                    "gossip's snapshot row does not outlive its superstep in a stash");
   if (e->prio_mask)
     return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without priority tables (agx_set_mailbox_priority)");
+  if (e->tm_keys) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without timers (agx_set_timers)");
   if (cls >= AGX_MAX_MAILBOX_CLASSES || !((e->mclass_set >> cls) & 1u))
     return set_err(AGX_EINVAL, "mailbox class %u is not configured (agx_set_mailbox_class; classes 0..%u)", cls,
                    AGX_MAX_MAILBOX_CLASSES - 1);
@@ -2811,6 +2997,115 @@ agx_status agx_read_kinds(agx_engine* e, uint64_t first_id, uint64_t count, uint
   return AGX_OK;
 }
 
+// TY/internal/TimerSchedulerImpl.scala:61-172 (classic dungeon/TimerSchedulerImpl.scala: the same rule)
+agx_status agx_set_timers(agx_engine* e, uint32_t n_keys) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (n_keys < 1u || n_keys > AGX_MAX_TIMER_KEYS)
+    return set_err(AGX_EINVAL, "timers: %u keys per actor (1..%u)", n_keys, AGX_MAX_TIMER_KEYS);
+  if (e->R > 1) return set_err(AGX_EINVAL, "timers need a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
+  if (e->pw) return set_err(AGX_EINVAL, "timers need an engine without CRDT kinds (one is registered)");
+  if (e->prio_mask) return set_err(AGX_EINVAL, "timers need an engine without priority tables (agx_set_mailbox_priority)");
+  if (e->stash_on) return set_err(AGX_EINVAL, "timers need an engine without a deque-based mailbox class (agx_set_stash)");
+  if (e->kmax != 1)
+    return set_err(AGX_EINVAL, "timers need max_emit = 1 (it is %u): the drain for more evaluates a case more than once, "
+                   "and a timer action must take effect once", e->kmax);
+  if (e->ring_live || e->rg_on)
+    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, which know no "
+                   "timers: set timers before the first run", e->ring_live ? e->ring_c : e->rg_c);
+  if (e->started) return set_err(AGX_ESTATE, "set timers before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  if (e->d_timers && n_keys != e->tm_keys) {
+    hipFree(e->d_timers);
+    e->d_timers = nullptr;
+    e->tm_starts.clear();
+  }
+  e->tm_keys = n_keys;
+  e->tm_bad_start = false;  // (an agx_start_timers refused before this call no longer stands in the way of agx_run)
+  AGX_TRY(alloc_timers(e));  // (now: AGX_ENOMEM is this call's)
+  drop_graphs(e);  // the variant and the timer storage are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_start_timers(agx_engine* e, uint64_t first_id, uint64_t count, uint32_t key, int32_t periodic, uint32_t delay,
+                            const uint32_t* delays, uint32_t payload) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->tm_keys) {
+    e->tm_bad_start = true;  // (agx_run refuses too: the rule for tables with timer actions)
+    return set_err(AGX_EINVAL, "agx_start_timers needs an engine with timers (agx_set_timers)");
+  }
+  if (key >= e->tm_keys) return set_err(AGX_EINVAL, "timer key %u: the engine has %u slots per actor", key, e->tm_keys);
+  if (first_id + count > e->n_global || first_id + count < first_id) return set_err(AGX_EINVAL, "bad actor range");
+  agx_engine::TimerStart ts;
+  ts.first = first_id;
+  ts.count = count;
+  ts.key = key;
+  ts.periodic = periodic ? 1u : 0u;
+  ts.delay = delay;
+  ts.payload = payload;
+  if (delays) ts.delays.assign(delays, delays + count);
+  e->tm_starts.push_back(std::move(ts));
+  return AGX_OK;
+}
+
+agx_status agx_timer_info(agx_engine* e, uint64_t* fired, uint64_t* discarded, uint64_t* active, uint64_t* pending,
+                          uint64_t* ticks) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[2] = {0, 0}, na = 0, npd = 0;
+  if (e->d_timers) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(flush_timer_starts(e));  // (starts recorded since the last run: applied now, nothing else is uploaded)
+    AGX_TRY(copy_sync(e, c, e->d_timers + kTmCtr, sizeof(c), hipMemcpyDeviceToHost));
+    const uint64_t npad = (uint64_t)e->nb << e->bb;
+    std::vector<uint32_t> sl(2ull * e->tm_keys * npad);  // next, per
+    AGX_TRY(copy_sync(e, sl.data(), e->d_timers + tm_slot_off(e->nb), sl.size() * 4ull, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < e->tm_keys; ++k)
+      for (uint64_t l = 0; l < e->n_local; ++l) {
+        if (!(sl[((uint64_t)e->tm_keys + k) * npad + l] & kTmActive)) continue;
+        ++na;
+        npd += sl[k * npad + l] != kTmNone;
+      }
+  }
+  if (fired) *fired = c[0];
+  if (discarded) *discarded = c[1];
+  if (active) *active = na;
+  if (pending) *pending = npd;
+  if (ticks) *ticks = e->tm_ticks;
+  return AGX_OK;
+}
+
+agx_status agx_read_timers(agx_engine* e, uint64_t actor_id, uint32_t active[4], uint32_t remaining[4], uint32_t period[4],
+                           uint32_t payload[4], uint32_t generation[4]) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (actor_id >= e->n_global) return set_err(AGX_EINVAL, "bad actor id");
+  for (uint32_t k = 0; k < AGX_MAX_TIMER_KEYS; ++k) {
+    if (active) active[k] = 0;
+    if (remaining) remaining[k] = 0xFFFFFFFFu;
+    if (period) period[k] = 0;
+    if (payload) payload[k] = 0;
+    if (generation) generation[k] = 0;
+  }
+  if (!e->d_timers) return AGX_OK;
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_timer_starts(e));  // (starts recorded since the last run: applied now, nothing else is uploaded)
+  const uint64_t npad = (uint64_t)e->nb << e->bb, l = actor_id;  // (single rank: local = global)
+  uint32_t clk = 0;
+  AGX_TRY(copy_sync(e, &clk, e->d_timers + kTmBucketOff + 2ull * e->nb + (l >> e->bb), 4, hipMemcpyDeviceToHost));
+  // the actor's column of the [field][key][actor] arrays in one strided copy: row f * n_keys + k = field f of key k
+  uint32_t col[4 * AGX_MAX_TIMER_KEYS];
+  HIP_TRY(hipMemcpy2DAsync(col, 4, e->d_timers + tm_slot_off(e->nb) + l, npad * 4ull, 4, 4ull * e->tm_keys,
+                           hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t k = 0; k < e->tm_keys; ++k) {
+    const uint32_t v[4] = {col[k], col[e->tm_keys + k], col[2 * e->tm_keys + k], col[3 * e->tm_keys + k]};
+    if (active) active[k] = (v[1] & kTmActive) ? 1u : 0u;
+    if (remaining) remaining[k] = v[0] == kTmNone ? 0xFFFFFFFFu : v[0] - clk;
+    if (period) period[k] = v[1] & ~kTmActive;
+    if (payload) payload[k] = v[3];
+    if (generation) generation[k] = v[2];
+  }
+  return AGX_OK;
+}
+
 agx_status agx_set_outbound(agx_engine* e, uint32_t first_host_id, uint32_t n_host, uint64_t capacity) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (n_host && (first_host_id < e->n_global || (uint64_t)first_host_id + n_host > (1ull << 31)))
@@ -2879,7 +3174,9 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   if (first[0] != 0 || first[n_beh] != n_cases) return set_err(AGX_EINVAL, "first[] must run from 0 to n_cases");
   for (uint32_t b = 0; b < n_beh; ++b)
     if (first[b] > first[b + 1]) return set_err(AGX_EINVAL, "first[] must be non-decreasing");
-  auto opnd_ok = [](uint32_t src, uint32_t word) { return src <= AGX_V_STASH && word <= 1u; };
+  auto opnd_ok = [](uint32_t src, uint32_t word) {
+    return src == AGX_V_TIMER ? word < AGX_MAX_TIMER_KEYS : src <= AGX_V_STASH && word <= 1u;
+  };
   for (uint32_t c = 0; c < n_cases; ++c) {
     const agx_case& C = cases[c];
     if (!opnd_ok(C.src1, C.word1) || !opnd_ok(C.src2, C.word2) || !opnd_ok(C.src3, C.word3) ||
@@ -2890,9 +3187,11 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   }
   for (uint32_t i = 0; i < n_acts; ++i) {
     const agx_act& A = acts[i];
-    if (A.op < AGX_A_SET || A.op > AGX_A_TELL || A.word > 1u || !opnd_ok(A.src, A.sword) ||
-        (A.op == AGX_A_TELL && !opnd_ok(A.dsrc, A.dword)))
-      return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (state words 0..1)", i);
+    const bool tmop = A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL;  // (`word` is the key)
+    if (A.op < AGX_A_SET || A.op > AGX_A_TIMER_CANCEL_ALL || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+        !opnd_ok(A.src, A.sword) ||
+        ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC) && !opnd_ok(A.dsrc, A.dword)))
+      return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (state words 0..1, timer keys 0..3)", i);
   }
   // the apply kernels reserve kmax tell slots per message (single pass: the tell overwrites the
   // message's own consumed LDS slot; otherwise a bucket's tells live in [lo*kmax, (lo+cnt)*kmax)):
@@ -2921,6 +3220,22 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   e->n_beh = n_beh;
   e->beh_stash = false;
   for (uint32_t c = 0; c < n_cases; ++c) e->beh_stash |= cases[c].result >= AGX_RES_STASH;
+  e->beh_tm_keys = 0;  // the timer keys the tables use (checked against agx_set_timers at agx_run)
+  auto tm_use = [&](uint32_t src, uint32_t word) {
+    if (src == AGX_V_TIMER) e->beh_tm_keys = std::max(e->beh_tm_keys, word + 1u);
+  };
+  for (uint32_t c = 0; c < n_cases; ++c) {
+    tm_use(cases[c].src1, cases[c].word1);
+    tm_use(cases[c].src2, cases[c].word2);
+    tm_use(cases[c].src3, cases[c].word3);
+    tm_use(cases[c].src4, cases[c].word4);
+  }
+  for (uint32_t i = 0; i < n_acts; ++i) {
+    tm_use(acts[i].src, acts[i].sword);
+    tm_use(acts[i].dsrc, acts[i].dword);
+    if (acts[i].op == AGX_A_TIMER_CANCEL_ALL) e->beh_tm_keys = std::max(e->beh_tm_keys, 1u);
+    else if (acts[i].op >= AGX_A_TIMER_SINGLE) e->beh_tm_keys = std::max<uint32_t>(e->beh_tm_keys, acts[i].word + 1u);
+  }
   drop_graphs(e);  // the tables are kernel parameters captured in the superstep graphs
   return AGX_OK;
 }
@@ -3067,6 +3382,8 @@ agx_status agx_stage_tells(agx_engine* e, const uint32_t* dst, const uint32_t* s
     const uint32_t sv = src ? src[i] : AGX_NO_SENDER;
     if ((sv & AGX_WIDE_BIT) && sv != AGX_NO_SENDER)
       return set_err(AGX_EINVAL, "tell %zu: sender %u is not an actor id (bit 31 tags CRDT state gossips)", i, sv);
+    if (e->tm_keys && (payload[i] >> 24) == AGX_TAG_TIMER)
+      return set_err(AGX_EINVAL, "tell %zu: message tag 0xFF is reserved for timer messages on an engine with timers", i);
     ++take;
   }
   if (take) {
@@ -3145,6 +3462,8 @@ agx_status agx_tell(agx_engine* e, uint32_t dst, uint32_t src, uint32_t payload,
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if ((src & AGX_WIDE_BIT) && src != AGX_NO_SENDER)
     return set_err(AGX_EINVAL, "tell: sender %u is not an actor id (bit 31 tags CRDT state gossips)", src);
+  if (e->tm_keys && (payload >> 24) == AGX_TAG_TIMER)
+    return set_err(AGX_EINVAL, "tell: message tag 0xFF is reserved for timer messages on an engine with timers");
   const bool sched = e->tq.tell(dst, src, payload);
   if (schedule) *schedule = sched ? 1 : 0;
   return AGX_OK;
@@ -3163,6 +3482,11 @@ agx_status agx_pump_idle(agx_engine* e, int32_t* reschedule) {
     uint64_t infl = 0;
     AGX_TRY(in_flight_now(e, &infl));
     again = infl > 0;  // (status stays "scheduled": this pump hands over to the next)
+    if (!again && e->d_timers) {  // a pending timer keeps the engine scheduled
+      std::vector<uint32_t> h;
+      AGX_TRY(read_timer_head(e, h));
+      for (uint32_t b = 0; b < e->nb; ++b) again |= h[kTmBucketOff + b] != kTmNone;
+    }
   }
   if (!again) again = e->tq.pump_idle();
   if (reschedule) *reschedule = again ? 1 : 0;
@@ -3191,6 +3515,7 @@ agx_status agx_run(agx_engine* e, uint32_t max_supersteps, agx_stats* out) {
     AGX_TRY(run_multi_rccl(e, max_supersteps));
   } else {
     AGX_TRY(run_single(e, max_supersteps));
+    AGX_TRY(timers_after_run(e));
   }
   prof_collect(e);
   if (e->ident_on && getenv("AGX_IDENT_DEBUG")) {  // diagnostic: the last superstep's slice summaries

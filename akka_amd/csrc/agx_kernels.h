@@ -55,6 +55,7 @@ constexpr uint64_t kErrRange = 2;  // a counter slot wrapped past 2^64 - 1 (AGX_
 constexpr uint64_t kErrBarrier = 4;  // a persistent superstep launch's grid barrier timed out (AGX_EDEVICE)
 constexpr uint64_t kErrPrioTile = 8;  // a bucket with a priority-mailbox actor exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrStashTile = 16;  // a bucket with an actor of a stash class exceeded one LDS tile (AGX_ECAPACITY)
+constexpr uint64_t kErrTimerTile = 32;  // a bucket of an engine with timers exceeded one LDS tile (AGX_ECAPACITY)
 // per-block counters of k_bucket_apply: delivered, dead, unhandled, emitted, active
 constexpr int kBStats = 5;
 constexpr uint32_t kMaxApplyGrid = 4096;
@@ -1319,6 +1320,69 @@ __device__ __forceinline__ void flush_stats(const BucketArgs& a, const uint32_t 
 constexpr uint32_t kWaveRowU32 = 64;  // (multi-rank packing) rows of at least this many u32 are copied by a whole wave
 
 
+// ---- timers (agx_set_timers): the end of tick `now` in bucket b, by the bucket's own block.
+// If the bucket's earliest fire says a fire is due at now + 1 -- or a slot was cancelled this tick (the
+// cancel set it to 0) -- the block scans the bucket's next-fire ticks (slot-major: coalesced), counts the
+// fires of now + 1 and finds the exact earliest fire; else it reads that one word.  The count joins the
+// bucket's backlog count: the next inbox has room for the TimerMsgs.  `alive`: the bucket's flags in LDS.
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+  for (int d = kWave / 2; d > 0; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d, kWave));
+  return v;
+}
+template <bool kGather>
+__device__ __forceinline__ void timer_tick_end(const BucketArgs& a, const TimerDev& TD, uint32_t b, uint32_t a0,
+                                               uint32_t na, uint32_t now, uint32_t bltot, uint32_t w,
+                                               const uint8_t* alive, uint32_t* scratch) {
+  const int tid = threadIdx.x;
+  const uint32_t e = __hip_atomic_load(&TD.earliest(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();  // (every thread has read it)
+  uint32_t nd = 0;
+  if (e <= now + 1u) {  // (block-uniform)
+    if (tid == 0) __hip_atomic_store(&TD.earliest(b), kTmNone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    uint32_t mn = kTmNone;
+    for (uint32_t k = 0; k < TD.nk; ++k) {
+      uint4 n4 = make_uint4(kTmNone, kTmNone, kTmNone, kTmNone);  // (one 16-byte load: a0 is a multiple of 32)
+      if ((uint32_t)tid * kBAct < na) n4 = *reinterpret_cast<const uint4*>(TD.next + TD.at(k, a0 + tid * kBAct));
+      const uint32_t nx[kBAct] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+      for (int j = 0; j < kBAct; ++j) {
+        const uint32_t la = tid * kBAct + j;
+        if (la < na && (alive[la] & 1u) && nx[j] != kTmNone) {
+          uint32_t nv = nx[j];
+          if (nv <= now) {
+            // a fire of this tick that was not sent (the bucket's inbox was over one tile: kErrTimerTile, or
+            // more fires than the backlog count carried): the slot moves on as if it had fired, so the state
+            // stays defined -- a periodic slot fires again a period from now, a single slot has none to come
+            const size_t i = TD.at(k, a0 + la);
+            const uint32_t pr = TD.per[i] & ~kTmActive;
+            nv = pr ? now + pr : kTmNone;
+            TD.next[i] = nv;
+          }
+          if (nv != kTmNone) {
+            nd += nv == now + 1u ? 1u : 0u;
+            mn = min(mn, nv);
+          }
+        }
+      }
+    }
+    mn = wave_min_u32(mn);
+    if (lane_id() == 0 && mn != kTmNone) atomicMin(&TD.earliest(b), mn);
+    uint32_t tot;
+    block_excl_sum<kBThreads>(nd, scratch, &tot);
+    nd = tot;
+  }
+  if (tid == 0) {
+    TD.due(b) = nd;
+    if (nd) {
+      if constexpr (kGather) a.g.blc[w][b] = bltot + nd;
+      else a.chunk_cnt[b] = bltot + nd;
+    }
+    TD.clock(b) = now;
+  }
+}
+
 // kStash: deque-based mailboxes (agx_set_stash).  The inbox segment of an actor then
 // starts with its window: the buffered / parked messages this superstep processes instead of mailbox
 // mail (stash_window; k_bucket_apply put them there).  With a window every admitted mailbox message
@@ -1331,10 +1395,21 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
                                               const uint64_t* pre0 = nullptr, const uint64_t* pre1 = nullptr) {
   constexpr bool kStash = (KM & kStashKM) != 0;
   static_assert(!kStash || (kLds && !kWide && !kOwner), "stash: single-rank fast launches, plain behaviours");
+  // kTm: timers (agx_set_timers).  The tick's TimerMsgs are the inbox's last items
+  // (k_bucket_apply put them there); the drain intercepts them, compiled cases run the timer actions
+  // against the slots, and the end of the tick counts the next tick's fires into the backlog count.
+  constexpr bool kTm = (KM & kTimersKM) != 0;
+  static_assert(!kTm || (kLds && !kWide && !kOwner && !kStash), "timers: single-rank fast launches, plain behaviours");
   const DevParams& P = a.P;
   const int tid = threadIdx.x;
   StashDev SD{};
   if constexpr (kStash) SD = stash_dev(P, a.nb, a.bb);
+  TimerDev TD{};
+  uint32_t tnow = 0;  // kTm: this tick
+  if constexpr (kTm) {
+    TD = timer_dev(P, a.nb, a.bb);
+    tnow = TD.clock(b) + 1u;
+  }
   uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
   auto ikey = [&](uint32_t q) -> uint32_t { return kLds ? L.key[q] : a.scr.key[lo + q]; };
@@ -1855,6 +1930,38 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         if (nst) atomicAdd(SD.ctr(0), (unsigned long long)nst);
         if (nun) atomicAdd(SD.ctr(1), (unsigned long long)nun);
         if (nov) atomicAdd(SD.ctr(2), (unsigned long long)nov);
+      } else if constexpr (kTm) {
+        // the drain with interceptTimerMsg (TimerSchedulerImpl.scala:145-172): a TimerMsg takes a drain
+        // slot and counts as delivered; a stale one is discarded, else the behaviour runs on the slot's
+        // stored payload with the actor itself as the sender
+        uint32_t ndisc = 0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          ++ndel;
+          if ((pv >> 24) == AGX_TAG_TIMER) {
+            const uint32_t key = (pv >> 22) & 3u;
+            const size_t i = TD.at(key < TD.nk ? key : 0u, l);
+            const uint32_t pr = key < TD.nk ? TD.per[i] : 0u;
+            if (!(pr & kTmActive) || ((TD.gen[i] ^ pv) & kTmGenMask)) {
+              ++ndisc;
+              continue;
+            }
+            if (!(pr & ~kTmActive)) TD.per[i] = 0u;  // a single timer: inactive now (nothing of it is to come)
+            sv = self;
+            pv = TD.pay[i];
+          }
+          const uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_tm(P, TD, l, b, tnow, kcur, self, wv, sv, pv, em)
+                                                       : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            for (uint32_t k = 0; k < TD.nk; ++k) TD.cancel(k, l, b);  // cancelAll on PostStop
+            break;
+          }
+        }
+        if (ndisc) atomicAdd(TD.ctr(1), (unsigned long long)ndisc);
       } else
       for (uint32_t q = 0; q < nd; ++q) {
         const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
@@ -1929,6 +2036,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         else a.chunk_cnt[b] = bltot + nptot;
       }
     }
+    if constexpr (kTm) timer_tick_end<kGather>(a, TD, b, a0, na, tnow, bltot, w, L.alive, L.scratch);
     AGX_STAMP(a, 5);
     {  // exclusive scan of tell counts in actor (= sender) order
       uint32_t ec[kBAct], run = 0;
@@ -4242,6 +4350,12 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
   static_assert(!kPrio || (!kWide && !kSkew && !kOwner), "priority mailboxes: single-rank fast launches, plain behaviours");
   constexpr bool kStash = (KM & kStashKM) != 0;  // (a flag of KM: agx_device.h)
   static_assert(!kStash || (!kWide && !kSkew && !kOwner && !kPrio), "stash: single-rank fast launches, plain behaviours");
+  // kTm: timers (agx_set_timers) -- the fast launches of the compiled catch-all variant of a
+  // single-rank engine with timers.  A bucket's inbox then ends with the tick's TimerMsgs (written here from
+  // the slots, in (actor, key) order), its backlog count carries their number (timer_tick_end), every
+  // bucket runs every tick (its clock is the tick count), and a bucket never takes the skew launch.
+  constexpr bool kTm = (KM & kTimersKM) != 0;  // (a flag of KM: agx_device.h)
+  static_assert(!kTm || (!kWide && !kSkew && !kOwner && !kPrio && !kStash), "timers: single-rank fast launches, plain behaviours");
   if (kOwner && a.halt && a.halt[0]) return;  // (device-resident multi-rank replay stopped)
   // key/src/pay carved from one array: group_tells reuses key+src as a 16 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t s_ksp[3 * kBucket];
@@ -4331,6 +4445,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
     if (tid < 5) s_stat[tid] = 0;
     if (tid == 0) s_rowtop = 0;
     if (tid == 0) s_flags = 0;
+    if constexpr (kTm)  // (a timer drain is not the dense rule: the flag that keeps a bucket off dense_finish)
+      if (tid == 0) s_flags = 2u;
     for (uint32_t d = tid; d < kRadix; d += kBThreads) s_nh[d] = 0;
     uint32_t* my_tc = nullptr;  // (fused) this thread's table entry, zeroed once the bucket is processed
     // fused fast path, plain behaviours: state words 0 / 1 of the bucket's actors are loaded here,
@@ -4364,6 +4480,16 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
               s_rowtop = np;
               s_g[0] = blc - np;
             }
+            if constexpr (kTm) {  // the backlog count carries the tick's fires: [backlog][mail][TimerMsgs]
+              const uint32_t np = min(P.timers[kTmBucketOff + a.nb + b], blc);
+              s_rowtop = np;
+              s_g[0] = blc - np;
+              if (s_hi - s_lo > (uint32_t)kBucket) {  // the skew launches know no timers: loud, the bucket's mail dropped
+                atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrTimerTile);
+                s_lo = s_hi = 0u;
+                s_rowtop = 0u;
+              }
+            }
           }
           if ((uint64_t)s_hi > a.cap) {  // mail + backlog over the message capacity: report, drop
             atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
@@ -4378,6 +4504,10 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           if (s_g[5] && P.ptab[kPrioBucketOff + b]) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrPrioTile);
         if constexpr (kStash)  // ... nor do they know a stash: loud, never wrong
           if (s_g[5] && P.stash[kStashBucketOff + a.nb + b]) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrStashTile);
+        if constexpr (kTm) {  // mail or a pending timer at the entry of this tick: the engine is not quiescent
+          if (s_hi != s_lo || __hip_atomic_load(&P.timers[kTmBucketOff + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kTmNone)
+            atomicMax(&P.timers[kTmLastAct], P.timers[kTmBucketOff + 2u * a.nb + b] + 1u);
+        }
         if (kDefer && s_g[5]) a.skew_list[atomicAdd(skew_n, 1u)] = b;
       }
     } else {
@@ -4409,6 +4539,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           s_rowtop = np;
           s_g[0] -= np;
         }
+        if constexpr (kTm) {  // (as the multi-pass launch above)
+          const uint32_t np = min(P.timers[kTmBucketOff + a.nb + b], s_g[0]);
+          s_rowtop = np;
+          s_g[0] -= np;
+        }
         s_g[1] = g.blo[rpar][b];
         s_g[2] = g.stg_cnt[b];
         s_g[3] = g.stg_off[b];
@@ -4425,6 +4560,14 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         segp[ns] = blc + tt;  // staged segment
         s_g[4] = ns;
         if constexpr (kStash) tt += s_rowtop;  // (the pending windows are part of the inbox; tt is not read again)
+        if constexpr (kTm) {  // (the tick's TimerMsgs are part of the inbox; tt is not read again)
+          tt += s_rowtop;
+          if (blc + tt + s_g[2] > (uint32_t)kBucket) {  // the skew launches know no timers: loud, the bucket's mail dropped
+            atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrTimerTile);
+            tt = 0u - blc - s_g[2];  // (cnt = 0 below)
+            s_rowtop = 0u;
+          }
+        }
         const uint32_t cnt = blc + tt + s_g[2];
         s_g[5] = cnt > (uint32_t)kBucket;
         if constexpr (kPrio)  // (as the multi-pass launch above)
@@ -4452,6 +4595,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           s_lo = (uint32_t)lo;
           s_hi = (uint32_t)lo + cnt;
           g.cntb[(size_t)a.slot * a.nb + b] = cnt;
+        }
+        if constexpr (kTm) {  // a pending timer at the entry of this tick: bit 31 of the row entry (the host's poll)
+          if (__hip_atomic_load(&P.timers[kTmBucketOff + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kTmNone)
+            g.cntb[(size_t)a.slot * a.nb + b] |= 0x80000000u;
+          if (g.cntb[(size_t)a.slot * a.nb + b]) atomicMax(&P.timers[kTmLastAct], P.timers[kTmBucketOff + 2u * a.nb + b] + 1u);
         }
       }
     }
@@ -4490,6 +4638,13 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           if (g.emc[wpar]) g.emc[wpar][b] = 0u;
       }
       __syncthreads();
+      if constexpr (kTm) {  // a tick without mail is still a tick: the clock, and the next tick's fires
+        const TimerDev TD = timer_dev(P, a.nb, a.bb);
+        if (kLateAlive) reinterpret_cast<uint32_t*>(s_alive)[tid] = alive4;
+        __syncthreads();
+        timer_tick_end<kGather>(a, TD, b, a0, na, TD.clock(b) + 1u, 0u, wpar, s_alive, scratch);
+        __syncthreads();
+      }
       continue;
     }
     // bypass: inbox item q < xblc is backlog item q (g.bl[rpar] at xblo + q), else sorted item xbst + q - xblc
@@ -4563,6 +4718,61 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           __syncthreads();
         }
       }
+      // kTm: the inbox's last np items are the tick's TimerMsgs, in (actor, key) order (the stable sort
+      // leaves them at the tail of each actor's segment, in key order), staged here from the slots; a
+      // periodic slot's next fire moves on by its period, a single slot's becomes none to come
+      if constexpr (kTm) {
+        const uint32_t np = s_rowtop;
+        uint32_t* const wk = reinterpret_cast<uint32_t*>(U);  // [3][kBucket] staged TimerMsgs
+        if (np) {  // (block-uniform)
+          const TimerDev TD = timer_dev(P, a.nb, a.bb);
+          const uint32_t now = TD.clock(b) + 1u;
+          uint32_t fm = 0, tot = 0;  // bit 4 * j + key: actor j's slot `key` fires
+          for (uint32_t key = 0; key < TD.nk; ++key) {
+            uint4 n4 = make_uint4(kTmNone, kTmNone, kTmNone, kTmNone);
+            if ((uint32_t)tid * kBAct < na) n4 = *reinterpret_cast<const uint4*>(TD.next + TD.at(key, a0 + tid * kBAct));
+            const uint32_t nx[kBAct] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+            for (int j = 0; j < kBAct; ++j) {
+              const uint32_t la = tid * kBAct + j, ab = (alive4 >> (8 * j)) & 0xFFu;
+              if (la < na && (ab & 1u) && nx[j] == now) {
+                fm |= 1u << (4 * j + key);
+                ++tot;
+              }
+            }
+          }
+          uint32_t t;
+          uint32_t ex = block_excl_sum<kBThreads>(tot, scratch, &t);
+          if (t < np) {
+            // fewer fires than the count the bucket's backlog count carries (never by the engine's own
+            // steps): loud, and the missing items defined
+            if (tid == 0) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
+            for (uint32_t i = t + tid; i < np; i += kBThreads) {
+              wk[i] = a0;
+              wk[kBucket + i] = AGX_NO_SENDER;
+              wk[2 * kBucket + i] = 0u;
+            }
+          }
+#pragma unroll 1
+          for (int j = 0; j < kBAct; ++j) {
+            for (uint32_t key = 0; key < TD.nk; ++key) {
+              if (!((fm >> (4 * j + key)) & 1u)) continue;
+              if (ex < np) {
+                const uint32_t l = a0 + tid * kBAct + j;
+                const size_t i = TD.at(key, l);
+                const uint32_t pr = TD.per[i] & ~kTmActive;
+                wk[ex] = l;
+                wk[kBucket + ex] = l;  // (single rank: the actor's own id)
+                wk[2 * kBucket + ex] = (AGX_TAG_TIMER << 24) | (key << 22) | (TD.gen[i] & kTmGenMask);
+                TD.next[i] = pr ? now + pr : kTmNone;
+              }
+              ++ex;
+            }
+          }
+          if (tid == 0) atomicAdd(TD.ctr(0), (unsigned long long)min(t, np));
+          __syncthreads();
+        }
+      }
       {  // locate every item first (LDS only), then issue all 3 x kBIpt loads back to back: selected
          // base pointers and no branches around the loads (per-item if/else made the compiler wait
          // for each item's loads before the next item's: 8 dependent round trips instead of 1)
@@ -4572,6 +4782,18 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           const uint32_t q = wbase + r * kWave + lane;
           sel[r] = 0;
           idx[r] = 0;
+          if constexpr (kTm) {  // (the last s_rowtop items are the TimerMsgs, filled in below)
+            if (q < cnt - s_rowtop) {
+              if (kGather) {
+                idx[r] = gv.locate(q, sel[r]);
+              } else if (q < xblc) {
+                idx[r] = xblo + q;
+              } else {
+                sel[r] = 1;
+                idx[r] = iv.at(xbst + q - xblc);
+              }
+            }
+          } else
           if constexpr (kStash) {  // (the first s_rowtop items are the windows, filled in below)
             const uint32_t np = s_rowtop;
             if (q < cnt && q >= np) {
@@ -4643,6 +4865,19 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
               k[r] = wk[q];
               sv[r] = wk[kBucket + q];
               pv[r] = wk[2 * kBucket + q];
+            }
+          }
+        }
+        if constexpr (kTm) {
+          const uint32_t nm = cnt - s_rowtop;
+          const uint32_t* const wk = reinterpret_cast<const uint32_t*>(U);
+#pragma unroll
+          for (int r = 0; r < kBIpt; ++r) {
+            const uint32_t q = wbase + r * kWave + lane;
+            if (q >= nm && q < cnt) {
+              k[r] = wk[q - nm];
+              sv[r] = wk[kBucket + q - nm];
+              pv[r] = wk[2 * kBucket + q - nm];
             }
           }
         }

@@ -219,6 +219,39 @@ class GpuEngine:
         check(self.lib.agx_read_kinds(self._h, first, count, _ptr(k, ctypes.c_uint8)))
         return k
 
+    def set_timers(self, n_keys: int) -> None:
+        """`n_keys` (1..4) timer slots for every actor (agx_set_timers): Behaviors.withTimers / TimerScheduler
+        (TY/internal/TimerSchedulerImpl.scala:61-172) in logical time -- one superstep is one tick.  Compiled
+        behaviours may start, cancel and test timers (typed.Behaviors.with_timers)."""
+        check(self.lib.agx_set_timers(self._h, n_keys))
+
+    def start_timers(self, first: int, count: int, key: int, delay: int = 1, *, periodic: bool = False, delays=None,
+                     payload: int = 0) -> None:
+        """agx_start_timers: start timer `key` of actors [first, first + count) at the current tick (a withTimers
+        setup block).  The first fire comes after `delay` ticks, or after `delays[i]` for actor first + i
+        (staggered phases); a periodic timer's period is `delay` either way."""
+        d = None
+        if delays is not None:
+            d = np.ascontiguousarray(delays, np.uint32)
+            if d.size != count:
+                raise ValueError("delays must hold one delay per actor of the range")
+        check(self.lib.agx_start_timers(self._h, first, count, key, 1 if periodic else 0, int(delay),
+                                        _ptr(d, ctypes.c_uint32) if d is not None else None, int(payload) & 0xFFFFFFFF))
+
+    def timer_info(self) -> dict:
+        """agx_timer_info: totals fired / discarded, the slots active / pending now, and the ticks that ran while
+        the engine was not quiescent."""
+        v = [ctypes.c_uint64() for _ in range(5)]
+        check(self.lib.agx_timer_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(("fired", "discarded", "active", "pending", "ticks"), (int(x.value) for x in v)))
+
+    def read_timers(self, actor_id: int) -> dict:
+        """agx_read_timers: one actor's four slots -- active, remaining (ticks to the next fire, 0xFFFFFFFF when
+        none is to come), period, payload, generation."""
+        a = [np.zeros(4, np.uint32) for _ in range(5)]
+        check(self.lib.agx_read_timers(self._h, actor_id, *(_ptr(x, ctypes.c_uint32) for x in a)))
+        return dict(zip(("active", "remaining", "period", "payload", "generation"), a))
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""
@@ -292,7 +325,8 @@ class GpuEngine:
         check(self.lib.agx_pump_cancel(self._h))
 
     def run(self, max_supersteps: int = 1 << 30, stats: bool = True) -> Stats | None:
-        """agx_run.  stats=False skips the counter read-back (read them with stats())."""
+        """agx_run.  stats=False skips the counter read-back (read them with stats()).  On an engine with timers
+        a superstep is a tick and a periodic timer never lets the engine go quiescent: always pass a budget."""
         if not stats:
             check(self.lib.agx_run(self._h, min(int(max_supersteps), 0xFFFFFFFF), None))
             return None

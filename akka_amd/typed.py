@@ -41,9 +41,13 @@ import numpy as np
 KIND_COMPILED = 16
 MAX_BEHAVIORS, MAX_CASES, MAX_ACTS = 64, 1024, 4096
 
-V_CONST, V_PAYLOAD, V_TAG, V_ARG, V_WORD, V_SENDER, V_SELF, V_STASH = range(8)
+V_CONST, V_PAYLOAD, V_TAG, V_ARG, V_WORD, V_SENDER, V_SELF, V_STASH, V_TIMER = range(9)
 CMP_ANY, CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(7)
 A_SET, A_ADD, A_MAX, A_MIN, A_TELL = 1, 2, 3, 4, 5
+A_TIMER_SINGLE, A_TIMER_PERIODIC, A_TIMER_CANCEL, A_TIMER_CANCEL_ALL = 6, 7, 8, 9
+TAG_TIMER = 0xFF     # the message tag of a TimerMsg: reserved when the tables use timers
+MAX_TIMER_KEYS = 4
+MAX_TIMER_DELAY = (1 << 31) - 1
 RES_SAME, RES_STOPPED, RES_UNHANDLED, RES_BECOME, RES_STASH, RES_UNSTASH_ALL = 0, 1, 2, 3, 4, 5
 NEXT_SAME = 0xFF  # agx_case.next of RES_UNSTASH_ALL: the behaviour stays
 MAX_STASH = 255
@@ -289,8 +293,65 @@ class StashBuffer:
         return self.size >= self.capacity
 
 
+class TimerScheduler:
+    """TimerScheduler[T] (TY/scaladsl/TimerScheduler.scala; TY/internal/TimerSchedulerImpl.scala:61-172) of the
+    actor running the behaviour, symbolic.  Time is logical: a delay is a count of ticks (supersteps), at least 1.
+    The scheduled task is only `self ! timerMsg`, so start_timer_with_fixed_delay and start_timer_at_fixed_rate
+    coincide (both fire at start + d, start + 2d, ...) and lower to one periodic action.  Keys are mapped to the
+    actor's timer slots 0..3 in the order they first appear.  A start used as an effect of a handler runs when
+    the message is handled; a start made in the with_timers block itself and not used as an effect is a setup
+    start: it is recorded (Tables.initial_timers) and needs a constant delay and message."""
+
+    def __init__(self):
+        self.keys: dict = {}
+        self._starts: list = []  # every start action created, in order
+
+    def _key(self, key) -> int:
+        if key not in self.keys:
+            if len(self.keys) >= MAX_TIMER_KEYS:
+                raise CompileError(f"an actor has at most {MAX_TIMER_KEYS} timer keys")
+            self.keys[key] = len(self.keys)
+        return self.keys[key]
+
+    def _start(self, op, key, msg, delay) -> "Action":
+        if isinstance(msg, Message):
+            val, mask = msg.arg, msg.or_mask
+        else:
+            val, mask = lift(msg), 0
+        d = lift(delay)
+        if d.src == V_CONST and d.k < 1:
+            raise CompileError(f"a timer delay is at least 1 tick, not {d.k}")
+        if d.src == V_CONST and d.k > MAX_TIMER_DELAY:
+            raise CompileError(f"a timer delay is at most {MAX_TIMER_DELAY} ticks")
+        a = Action(op, self._key(key), val, d, mask)
+        self._starts.append(a)
+        return a
+
+    def start_single_timer(self, key, msg, delay) -> "Action":
+        """startSingleTimer(key, msg, delay)."""
+        return self._start(A_TIMER_SINGLE, key, msg, delay)
+
+    def start_timer_with_fixed_delay(self, key, msg, delay) -> "Action":
+        """startTimerWithFixedDelay(key, msg, delay): periodic (the same op as start_timer_at_fixed_rate)."""
+        return self._start(A_TIMER_PERIODIC, key, msg, delay)
+
+    def start_timer_at_fixed_rate(self, key, msg, interval) -> "Action":
+        """startTimerAtFixedRate(key, msg, interval): periodic (the same op as start_timer_with_fixed_delay)."""
+        return self._start(A_TIMER_PERIODIC, key, msg, interval)
+
+    def cancel(self, key) -> "Action":
+        return Action(A_TIMER_CANCEL, self._key(key))
+
+    def cancel_all(self) -> "Action":
+        return Action(A_TIMER_CANCEL_ALL, 0)
+
+    def is_timer_active(self, key) -> Test:
+        """isTimerActive(key) as a test."""
+        return Operand(V_TIMER, self._key(key)) == 1
+
+
 class Behaviors:
-    """Behaviors.same / stopped / unhandled (TY/scaladsl/Behaviors.scala), receiveMessage and withStash."""
+    """Behaviors.same / stopped / unhandled (TY/scaladsl/Behaviors.scala), receiveMessage, withStash, withTimers."""
     same = _Result(RES_SAME, "same")
     stopped = _Result(RES_STOPPED, "stopped")
     unhandled = _Result(RES_UNHANDLED, "unhandled")
@@ -302,6 +363,30 @@ class Behaviors:
         b = factory(StashBuffer(capacity))
         if not isinstance(b, Behavior):
             raise CompileError("with_stash's factory must return a Behavior")
+        return b
+
+    @staticmethod
+    def with_timers(factory) -> "Behavior":
+        """Behaviors.withTimers(factory): `factory(timers)` builds the behaviour(s) around one TimerScheduler.
+        Starts made in the block that no handler uses as an effect are the setup starts of the actors that
+        begin in the returned behaviour (Tables.initial_timers; engine.start_timers applies them)."""
+        ts = TimerScheduler()
+        b = factory(ts)
+        if not isinstance(b, Behavior):
+            raise CompileError("with_timers' factory must return a Behavior")
+        used = {id(e) for x in _reachable([b]) for c in x.cases for e in c.effects}
+        initial = []
+        for a in ts._starts:
+            if id(a) in used:
+                continue
+            if a.val.src != V_CONST or a.dst.src != V_CONST:
+                raise CompileError("a timer started in the with_timers block needs a constant delay and message")
+            pay = ((a.val.k & 0xFFFFFF) | a.or_mask) if a.or_mask else (a.val.k & 0xFFFFFFFF)
+            initial.append((a.word, a.op == A_TIMER_PERIODIC, a.dst.k, pay))
+        for x in _reachable([b]):
+            if x.timers is None:
+                x.timers = ts
+        b.initial_timers = initial
         return b
 
     @staticmethod
@@ -326,6 +411,8 @@ class Behavior:
     name: str
     state: State
     cases: list = field(default_factory=list)
+    timers: object = None  # the TimerScheduler of the with_timers block the behaviour was built in
+    initial_timers: list = field(default_factory=list)  # with_timers' setup starts: (key, periodic, delay, payload)
 
 
 class ReceiveBuilder:
@@ -405,6 +492,7 @@ class Tables:
     cases: ctypes.Array
     acts: ctypes.Array
     first: np.ndarray
+    n_acts: int = 0
 
     @property
     def n_behaviors(self) -> int:
@@ -423,6 +511,21 @@ class Tables:
         actors' mailbox class needs (engine.set_stash)."""
         return max((c.result.buffer.capacity for b in self.behaviors for c in b.cases
                     if isinstance(c.result, (_StashEffect, _UnstashAll))), default=0)
+
+    @property
+    def timer_keys(self) -> int:
+        """The timer slots per actor these behaviours need (0: no timers): engine.set_timers(tables.timer_keys)."""
+        n = max((len(b.timers.keys) for b in self.behaviors if b.timers is not None), default=0)
+        for a in self.acts[:self.n_acts]:
+            if A_TIMER_SINGLE <= a.op <= A_TIMER_CANCEL_ALL:
+                n = max(n, 1 if a.op == A_TIMER_CANCEL_ALL else a.word + 1)
+        return n
+
+    @property
+    def initial_timers(self) -> list:
+        """with_timers' setup starts: (kind, key, periodic, delay, payload) -- actors registered with `kind`
+        start timer `key` when they start (engine.start_timers on their range, before the first run)."""
+        return [(KIND_COMPILED + i, *t) for i, b in enumerate(self.behaviors) for t in b.initial_timers]
 
     def kind_of(self, b: Behavior) -> int:
         """The actor kind that starts in behaviour `b`."""
@@ -483,7 +586,16 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
     if len(cases) > MAX_CASES or len(acts) > MAX_ACTS:
         raise CompileError("tables too large")
     t = Tables(behs, (AgxCase * max(len(cases), 1))(*cases), (AgxAct * max(len(acts), 1))(*acts),
-               np.asarray(first, dtype=np.uint32))
+               np.asarray(first, dtype=np.uint32), len(acts))
+    if t.timer_keys:  # tag 0xFF is the TimerMsg's: no message type of these behaviours may carry it
+        for a in acts:
+            if a.or_mask >> 24 == TAG_TIMER:
+                raise CompileError("message tag 0xFF is reserved for timer messages in behaviours that use timers")
+        for c in cases:
+            for s1, k1, cmp, s2, k2 in ((c.src1, c.k1, c.cmp1, c.src2, c.k2), (c.src3, c.k3, c.cmp2, c.src4, c.k4)):
+                if cmp == CMP_EQ and ((s1 == V_TAG and k1 == 0 and s2 == V_CONST and k2 == TAG_TIMER) or
+                                      (s2 == V_TAG and k2 == 0 and s1 == V_CONST and k1 == TAG_TIMER)):
+                    raise CompileError("message tag 0xFF is reserved for timer messages in behaviours that use timers")
     if max_emit is not None and t.max_tells > max(1, max_emit):
         raise CompileError(f"a case tells {t.max_tells} times per message but max_emit is {max_emit}")
     return t

@@ -49,6 +49,9 @@ class Workload:
     # class -> 256 priorities by message tag, bytes or a sequence (agx_set_mailbox_priority)
     mailbox_priorities: dict = field(default_factory=dict)
     stash: dict = field(default_factory=dict)  # class -> stash capacity (agx_set_stash: a deque-based mailbox)
+    # timers (agx_set_timers / agx_start_timers): {"n_keys": k, "starts": [(first, count, key, periodic, delay,
+    # delays or None, payload)]} -- empty: no timers
+    timers: dict = field(default_factory=dict)
 
     def engine_kwargs(self) -> dict:
         """Semantic parameters (shared by the GPU engine and the CPU oracles)."""
@@ -80,6 +83,10 @@ class Workload:
             target.set_delta_crdt(self.delta_crdt)
         if self.behaviors is not None:
             target.set_behaviors(self.behaviors)
+        if self.timers:  # (empty: targets without the calls are unaffected)
+            target.set_timers(self.timers["n_keys"])
+            for first, count, key, periodic, delay, delays, payload in self.timers.get("starts", ()):
+                target.start_timers(first, count, key, delay, periodic=periodic, delays=delays, payload=payload)
         if self.fanout is not None:
             target.set_fanout(*self.fanout)
         if self.graph is not None:
@@ -584,3 +591,69 @@ def stash_gate(n: int = 2048, seed: int = 1, throughput: int = 3, n_host: int = 
                     mailbox_classes={1: 0, 2: 4, 3: 8}, mailboxes=[(0, q, 1), (q, q, 2), (2 * q, q, 3)],
                     outbound=(n, n_host) if n_host else None, bucket_actors=128,
                     stash={0: 2, 1: 12, 2: 3})
+
+
+# ------------------------------------------------------------------ timers: a population of heartbeats
+HB_TICK, HB_PING, HB_CANCEL, HB_REPLACE, HB_ECHO, HB_STOP = 1, 2, 3, 4, 5, 6
+
+
+def heartbeater():
+    """A failure-detector style actor (Behaviors.withTimers): every Tick of its periodic timer "hb" it counts
+    the beat and pings its neighbour, which counts the ping.  Cancel cancels the timer, Replace(d) restarts it
+    with period d + 1 (a new generation: a Tick already in the mailbox is discarded), Echo answers the sender
+    with the beat count, Stop stops the actor (its timer with it)."""
+    from . import typed
+    st = typed.State("beats", "pings")
+    B = typed.Behaviors
+    tick = typed.MessageType("Tick", HB_TICK)
+    is_ = lambda t: (lambda m: m.tag == t)
+
+    def build(timers):
+        return (typed.ReceiveBuilder.create(st)
+                .on_any_message(lambda m, s: [s.beats.inc(), typed.self_ref(1).tell(s.beats, tag=HB_PING), B.same],
+                                test=is_(HB_TICK))
+                .on_any_message(lambda m, s: [s.pings.inc(), B.same], test=is_(HB_PING))
+                .on_any_message(lambda m, s: [timers.cancel("hb"), B.same], test=is_(HB_CANCEL))
+                .on_any_message(lambda m, s: [timers.start_timer_with_fixed_delay("hb", tick(m.arg), m.arg + 1), B.same],
+                                test=is_(HB_REPLACE))
+                .on_any_message(lambda m, s: [m.sender.tell(s.beats, tag=HB_ECHO), B.same], test=is_(HB_ECHO))
+                .on_any_message(lambda m, s: [B.stopped], test=is_(HB_STOP))
+                .on_any_message(lambda m, s: [B.unhandled])
+                .build("heartbeater"))
+    return B.with_timers(build)
+
+
+def heartbeat(n: int = 1 << 20, period: int = 16, seed: int = 1, throughput: int = 3, n_host: int = 8,
+              host_fraction: float = 0.05, bucket_actors: int = 0) -> Workload:
+    """Every actor starts a periodic timer of `period` ticks with a staggered phase (the first fire after
+    1..period ticks); each Tick it counts the beat and pings its neighbour.  A fraction of the actors get a host
+    message at the start: Cancel, Replace (another period), Stop, or Echo from a host-side sender (answered
+    through the outbox: the order observable).  A periodic timer never lets the engine go quiescent: run it
+    with a budget.  An engine with timers keeps a bucket's inbox within one 2048-message tile (agx_set_timers),
+    and every tick brings about 2 / period messages per actor (the Tick and the neighbour's ping), so choose
+    `bucket_actors` below 1024 x period: at period 1 the default 2048-actor bucket is refused with
+    AGX_ECAPACITY, 512-actor buckets run."""
+    from . import typed
+    rng = np.random.default_rng(seed)
+    b = heartbeater()
+    tb = typed.compile_behaviors([b], max_emit=1)
+    delays = (1 + rng.integers(0, max(period, 1), n)).astype(np.uint32)
+    m = int(n * host_fraction)
+    tells = None
+    if m:
+        dst = rng.integers(0, n, m).astype(np.uint32)
+        u = rng.random(m)
+        tag = np.full(m, HB_ECHO, np.uint32)
+        tag[u < 0.6] = HB_REPLACE
+        tag[u < 0.35] = HB_CANCEL
+        tag[u < 0.1] = HB_STOP
+        src = rng.integers(0, n, m).astype(np.uint32)
+        if n_host:
+            e = tag == HB_ECHO
+            src[e] = rng.integers(n, n + n_host, int(e.sum())).astype(np.uint32)
+        pay = (tag << np.uint32(24)) | rng.integers(0, 2 * max(period, 1), m).astype(np.uint32)
+        tells = (dst, src, pay)
+    return Workload("heartbeat", n, 2, 1, throughput, 0, [(0, n, tb.kind_of(b), None)], behaviors=tb, tells=tells,
+                    outbound=(n, n_host) if n_host else None, bucket_actors=bucket_actors,
+                    timers={"n_keys": tb.timer_keys,
+                            "starts": [(0, n, 0, True, period, delays, (HB_TICK << 24))]})

@@ -124,7 +124,9 @@ enum agx_behavior_kind {
 enum agx_operand { AGX_V_CONST = 0, AGX_V_PAYLOAD = 1, AGX_V_TAG = 2, AGX_V_ARG = 3, AGX_V_WORD = 4,
                    AGX_V_SENDER = 5, AGX_V_SELF = 6,
                    AGX_V_STASH = 7 /* the size of the actor's stash buffer (StashBuffer.size); 0 on an
-                                      engine without a deque-based mailbox class (agx_set_stash) */ };
+                                      engine without a deque-based mailbox class (agx_set_stash) */,
+                   AGX_V_TIMER = 8 /* 1 if the actor's timer slot `word` (the key) is active, else 0
+                                      (TimerScheduler.isTimerActive); engines with timers (agx_set_timers) */ };
 enum agx_cmp { AGX_CMP_ANY = 0, AGX_CMP_EQ = 1, AGX_CMP_NE = 2, AGX_CMP_LT = 3, AGX_CMP_LE = 4, AGX_CMP_GT = 5,
                AGX_CMP_GE = 6 };
 enum agx_action_op {
@@ -132,11 +134,21 @@ enum agx_action_op {
   AGX_A_ADD = 2,  /* word[w] += operand (wrapping)                              */
   AGX_A_MAX = 3,  /* word[w] = max(word[w], operand)                            */
   AGX_A_MIN = 4,
-  AGX_A_TELL = 5  /* tell(dst operand, payload): payload = (u32)operand, or with a message tag
+  AGX_A_TELL = 5, /* tell(dst operand, payload): payload = (u32)operand, or with a message tag
                      (or_mask != 0) (operand & 0xFFFFFF) | or_mask; a dst operand based on the
                      actor's own id is taken mod n_actors (ring neighbours); an unknown id is a
                      dead letter */
+  /* Timer actions (engines with timers, agx_set_timers; TimerScheduler, TY/internal/TimerSchedulerImpl.scala:
+   * 61-172).  `word` is the key (the slot index); the timer's message payload is the operand as a TELL's
+   * payload ((u32)operand, or (operand & 0xFFFFFF) | or_mask); the delay in ticks is the d-operand (dsrc,
+   * dword, dk), where a TELL has its destination: below 1 it counts as 1, above 2^31 - 1 it is clamped. */
+  AGX_A_TIMER_SINGLE = 6,     /* startSingleTimer(key, msg, delay)                                       */
+  AGX_A_TIMER_PERIODIC = 7,   /* startTimerWithFixedDelay / startTimerAtFixedRate (they coincide: 2.3) */
+  AGX_A_TIMER_CANCEL = 8,     /* cancel(key)                                                             */
+  AGX_A_TIMER_CANCEL_ALL = 9  /* cancelAll()                                                             */
 };
+#define AGX_TAG_TIMER 0xFFu     /* the message tag (payload >> 24) of a TimerMsg: reserved on an engine with timers */
+#define AGX_MAX_TIMER_KEYS 4u
 typedef struct agx_case {
   uint8_t src1, word1, cmp1, src2; /* test 1: operand(src1, word1, k1) cmp1 operand(src2, word2, k2) */
   uint8_t word2, src3, word3, cmp2; /* test 2: operand(src3, word3, k3) cmp2 operand(src4, word4, k4) */
@@ -349,7 +361,10 @@ agx_status agx_tell(agx_engine* eng, uint32_t dst, uint32_t src, uint32_t payloa
 agx_status agx_pump_idle(agx_engine* eng, int32_t* reschedule);
 agx_status agx_pump_cancel(agx_engine* eng);
 /* Run up to max_supersteps supersteps or until quiescent; stats are cumulative
- * over the engine's lifetime.  out may be NULL: the counters are then not read
+ * over the engine's lifetime.  On an engine with timers (agx_set_timers) a superstep is a tick, a
+ * tick without mail still counts against max_supersteps, and quiescent means no mail in flight and
+ * no timer pending: a periodic timer never lets the engine go quiescent, so agx_run on such an
+ * engine is always given a budget.  out may be NULL: the counters are then not read
  * back (agx_get_stats does it later, and reports AGX_ECAPACITY if an overflow
  * was recorded meanwhile).                                                    */
 agx_status agx_run(agx_engine* eng, uint32_t max_supersteps, agx_stats* out);
@@ -446,6 +461,58 @@ agx_status agx_read_kinds(agx_engine* eng, uint64_t first_id, uint64_t count, ui
  * case overflows and stops -- except in a bucket without any actor of a stash class whose inbox exceeds
  * one tile: that bucket takes the skew launch, which does not interpret the stash results (the message
  * is handled as Behaviors.same); keep such actors off behaviours that stash. */
+
+/* Timers (Behaviors.withTimers / TimerScheduler, TY/internal/TimerSchedulerImpl.scala:61-172; the classic
+ * dungeon/TimerSchedulerImpl.scala has the same rule; DESIGN.md 2.3 has the contract).
+ * Logical time: one superstep is one tick, a delay is a count of ticks >= 1 -- the reference's scheduler
+ * under manual time.  The scheduled task is only `self ! timerMsg`, so startTimerWithFixedDelay and
+ * startTimerAtFixedRate coincide (both fire at start + d, start + 2d, ...): one periodic op.
+ * agx_set_timers gives every actor n_keys (1..4) timer slots; the key is the slot index.  A slot is
+ * active or not and holds the tick of its next fire (or none to come), the period (0: single), a
+ * generation and the message payload; an actor's generation counter starts at 1 (timerGen).  Starting
+ * key k at tick s with delay d cancels the slot if active, gives it the actor's next generation and a
+ * next fire at s + d.  At tick s every alive actor's active slot whose next fire is s sends a TimerMsg
+ * to the actor's own mailbox: sender = the actor, payload = AGX_TAG_TIMER << 24 | key << 22 |
+ * (generation mod 2^22).  It comes last in that tick's inbox -- after the backlog, the arrivals and the
+ * host-staged tells, in key order -- and is admitted by position like any message (in a full bounded
+ * mailbox it is a dead letter; a single timer whose message died stays active and never fires again,
+ * as in the reference).  A periodic slot's next fire becomes s + period, a single slot's none to come.
+ * Receipt (interceptTimerMsg): a drained message with tag AGX_TAG_TIMER takes a drain slot and counts
+ * as delivered; if slot `key` is inactive or its generation differs (compared mod 2^22) it is discarded
+ * -- the behaviour does not run, `discarded` grows, it is not unhandled -- else a single slot becomes
+ * inactive and the behaviour runs on the slot's stored payload with sender = the actor itself.
+ * Cancelling leaves an already enqueued message in the mailbox (it is discarded at receipt); a stopping
+ * actor's slots all become inactive; a become leaves them alone.
+ * Tag AGX_TAG_TIMER is reserved: agx_stage_tells / agx_tell refuse it (AGX_EINVAL); a payload a
+ * behaviour computes that lands on it is taken for a TimerMsg (and normally discarded).
+ * Conservation: staged + emitted + fired = delivered + dead_letters + in_flight.
+ * Call before the first agx_run (AGX_ESTATE afterwards).  AGX_EINVAL: n_keys outside 1..4, n_ranks > 1,
+ * an engine with a CRDT kind, a priority table or a stash class (either call order), an engine whose
+ * bounded-mailbox ring pool exists, max_emit > 1 (a timer action must take effect once).  AGX_ENOMEM: the
+ * slots do not fit.  An engine with timers uses no wave, ring, dense or persistent launch, and a bucket
+ * (agx_cfg.bucket_actors actors) whose inbox -- backlog and the tick's TimerMsgs included -- exceeds one
+ * 2048-message tile makes agx_run return AGX_ECAPACITY (sticky).  Tables with a timer action or
+ * AGX_V_TIMER on an engine without timers (or with a key >= n_keys) make agx_run return AGX_EINVAL. */
+agx_status agx_set_timers(agx_engine* eng, uint32_t n_keys);
+/* withTimers' setup block: start timer `key` of actors [first_id, first_id + count) at the current tick
+ * (before the first run or between runs), single or periodic, with message payload `payload`.  The first
+ * fire comes after `delay` ticks -- or after delays[i] ticks for actor first_id + i when `delays` is not
+ * NULL (staggered phases); a periodic timer's period is `delay` either way.  A delay of 0 counts as 1, one
+ * above 2^31 - 1 is clamped.  Stopped actors are skipped.  AGX_EINVAL on an engine without timers (and the
+ * engine's agx_run then returns AGX_EINVAL too), or for a key >= n_keys. */
+agx_status agx_start_timers(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t key, int32_t periodic,
+                            uint32_t delay, const uint32_t* delays, uint32_t payload);
+/* Totals since agx_create: TimerMsgs sent (those that died at admission included), TimerMsgs discarded
+ * at receipt; right now: active slots, pending slots (active with a fire still to come: every active
+ * periodic slot, an active single slot that has not fired); and ticks: the supersteps that ran while
+ * the engine was not quiescent (agx_stats.supersteps still counts only those with mail).  Any pointer
+ * may be NULL. */
+agx_status agx_timer_info(agx_engine* eng, uint64_t* fired, uint64_t* discarded, uint64_t* active, uint64_t* pending,
+                          uint64_t* ticks);
+/* One actor's timer slots (for tests and tools): remaining = ticks to the next fire, 0xFFFFFFFF when
+ * none is to come.  Slots past n_keys read as zero (remaining 0xFFFFFFFF).  Any pointer may be NULL. */
+agx_status agx_read_timers(agx_engine* eng, uint64_t actor_id, uint32_t active[4], uint32_t remaining[4],
+                           uint32_t period[4], uint32_t payload[4], uint32_t generation[4]);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
