@@ -55,6 +55,9 @@ struct DevParams {
     // timers (agx_set_timers), read and written only by the timer k_bucket_apply instantiations: the
     // per-actor timer slots and their bookkeeping (TimerDev below)
     uint32_t* timers;
+    // death watch (agx_set_death_watch), read and written only by the watch k_bucket_apply instantiations: the
+    // per-actor watch slots, the death ticks and their bookkeeping (WatchDev below)
+    uint32_t* watch;
   };
   uint32_t* heap_top;       // [2] rows allocated in heap[parity]
   const uint32_t* step;     // superstep counter (bumped by the first kernel of a step)
@@ -231,6 +234,138 @@ __device__ __forceinline__ uint32_t tm_delay(uint64_t d) {
   return (int64_t)d < 1 ? 1u : d > (uint64_t)kTmMaxDelay ? kTmMaxDelay : (uint32_t)d;
 }
 
+// ---- death watch (agx_set_death_watch; AA/dungeon/DeathWatch.scala:19-113,147-162)
+// One superstep is one tick.  DevParams.watch, u32 units:
+//   [0]        n_slots: watch slots per actor (1..4)
+//   [2]        the last tick at whose entry the engine was active (atomicMax; the host's quiescence poll of the
+//              multi-pass pipeline and the `ticks` count read it)
+//   [4..13]    five u64 counters: watches, terminated, discarded, death_pacts, conflicts
+//   [14..15]   stopw[t & 1]: t once an actor stopped in tick t (writers of tick e write word e & 1, readers at
+//              the end of e and at the entry of e + 1 read a word of an earlier launch: no read races a write)
+//   [16..17]   anyw[t & 1]: t once a bucket ended tick t with a watching slot
+//   [18]       sticky: a watch found no free slot (the end of a tick raises kErrWatchSlots from it)
+//   [kWdBucketOff + b]           due: the bucket's due slots (counted into the bucket's backlog count, so the
+//                                next inbox has room for their Terminated envelopes; read at the bucket's entry)
+//   [kWdBucketOff + nb + b]      mark: a watch started in this bucket this tick (the end of the tick scans)
+//   [kWdBucketOff + 2 * nb + b]  clock: the ticks bucket b has run (every bucket runs every tick: all equal)
+//   [kWdBucketOff + 3 * nb + b]  nwatch: the bucket's watching slots
+//   then, 16-byte aligned and slot-major ([slot][actor], np = nb << bb actors):
+//     wee[slot][np]  the watchee id        st[slot][np]   state (free / watching / due / notified) | kWdHasMsg
+//     gen[slot][np]  the generation        pay[slot][np]  the custom message
+//   then died[np]: the actor's death tick, kWdNone while it is alive (written by the actor's own lane when it
+//   stops, with an agent-scope relaxed store; 0 for an id that was never registered).
+// Only a bucket's own block writes its actors' slots; died[] of other buckets is read at the end of a tick, and
+// only values below the tick count: those were written in earlier launches.
+constexpr uint32_t kWdBucketOff = 32;
+constexpr uint32_t kWdLastAct = 2, kWdCtr = 4, kWdStopW = 14, kWdAnyW = 16, kWdFull = 18;
+constexpr uint32_t kWdNone = 0xFFFFFFFFu, kWdGenMask = 0x3FFFFFu;
+constexpr uint32_t kWdFree = 0, kWdWatching = 1, kWdDue = 2, kWdNotified = 3, kWdStateMask = 3, kWdHasMsg = 4;
+constexpr uint32_t kWcWatches = 0, kWcTerminated = 1, kWcDiscarded = 2, kWcPacts = 3, kWcConflicts = 4;
+__host__ __device__ __forceinline__ size_t wd_slot_off(uint32_t nb) {
+  return ((size_t)kWdBucketOff + 4u * (size_t)nb + 3u) & ~(size_t)3;
+}
+struct WatchDev {
+  uint32_t* base;
+  uint32_t *wee, *st, *gen, *pay, *died;  // [slot * np + l]; died[l]
+  uint32_t ns, np, nb, n;                 // n: the population (ids at or above it count as dead)
+  __device__ __forceinline__ uint32_t* due(uint32_t b) const { return base + kWdBucketOff + b; }
+  __device__ __forceinline__ uint32_t* mark(uint32_t b) const { return base + kWdBucketOff + nb + b; }
+  __device__ __forceinline__ uint32_t& clock(uint32_t b) const { return base[kWdBucketOff + 2u * nb + b]; }
+  __device__ __forceinline__ uint32_t* nwatch(uint32_t b) const { return base + kWdBucketOff + 3u * nb + b; }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kWdCtr) + i;
+  }
+  __device__ __forceinline__ size_t at(uint32_t slot, uint32_t l) const { return (size_t)slot * np + l; }
+  __device__ __forceinline__ uint32_t ld(const uint32_t* p) const {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void sto(uint32_t* p, uint32_t v) const {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // watch(x) / watchWith(x, m) by actor l of bucket b (DeathWatch.scala:23-47, checkWatchingSame :113): 0 = done
+  // or a no-op, 1 = IllegalStateException; `slot_out`: the slot occupied now (ns: none)
+  __device__ __forceinline__ uint32_t watch(uint32_t l, uint32_t b, uint32_t x, bool with, uint32_t m,
+                                            uint32_t* slot_out = nullptr) const {
+    if (slot_out) *slot_out = ns;
+    if (x == l) return 0u;  // (single rank: the local id is the actor id)
+    uint32_t fr = ns;
+    for (uint32_t k = 0; k < ns; ++k) {
+      const size_t i = at(k, l);
+      const uint32_t s = st[i], state = s & kWdStateMask;
+      if (state == kWdFree) {
+        if (fr == ns) fr = k;
+      } else if (wee[i] == x) {
+        if (state == kWdNotified) return 0u;  // (the re-watch of a dead ref: its second Terminated would be dropped)
+        const bool has = (s & kWdHasMsg) != 0u;
+        return (has == with && (!with || pay[i] == m)) ? 0u : 1u;
+      }
+    }
+    if (fr == ns) {  // no free slot: loud, the watch is not recorded
+      sto(base + kWdFull, 1u);
+      return 0u;
+    }
+    const size_t i = at(fr, l);
+    wee[i] = x;
+    st[i] = kWdWatching | (with ? kWdHasMsg : 0u);
+    gen[i] = gen[i] + 1u;
+    pay[i] = with ? m : 0u;
+    atomicAdd(nwatch(b), 1u);
+    sto(mark(b), 1u);
+    atomicAdd(ctr(kWcWatches), 1ull);
+    if (slot_out) *slot_out = fr;
+    return 0u;
+  }
+  // unwatch(x): the slot holding x becomes free, in any state (DeathWatch.scala:49-60)
+  __device__ __forceinline__ void unwatch(uint32_t l, uint32_t b, uint32_t x) const {
+    for (uint32_t k = 0; k < ns; ++k) {
+      const size_t i = at(k, l);
+      const uint32_t state = st[i] & kWdStateMask;
+      if (state != kWdFree && wee[i] == x) {
+        if (state == kWdWatching) atomicSub(nwatch(b), 1u);
+        st[i] = kWdFree;
+      }
+    }
+  }
+  // the actor stops in tick `now`: its slots become free (unwatchWatchedActors, :147-162), its death tick is set
+  __device__ __forceinline__ void stop(uint32_t l, uint32_t b, uint32_t now) const {
+    for (uint32_t k = 0; k < ns; ++k) {
+      const size_t i = at(k, l);
+      const uint32_t state = st[i] & kWdStateMask;
+      if (state == kWdWatching) atomicSub(nwatch(b), 1u);
+      if (state != kWdFree) st[i] = kWdFree;
+    }
+    sto(died + l, now);
+    sto(base + kWdStopW + (now & 1u), now);
+  }
+  // is x dead before tick `now` (a death tick below it; an id outside the population always is)?
+  __device__ __forceinline__ bool dead_before(uint32_t x, uint32_t now) const {
+    if (x >= n) return true;
+    const uint32_t d = ld(died + x);
+    return d != kWdNone && d < now;
+  }
+};
+// the third rule of "active at the entry of tick t": an actor stopped in tick t - 1 while a slot of the engine
+// was watching at the end of t - 1 (both words were written in an earlier launch)
+__device__ __forceinline__ bool wd_stop_seen(const uint32_t* base, uint32_t t) {
+  const uint32_t p = t - 1u;
+  return __hip_atomic_load(base + kWdStopW + (p & 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p &&
+         __hip_atomic_load(base + kWdAnyW + (p & 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p;
+}
+__device__ __forceinline__ WatchDev watch_dev(uint32_t* base, uint32_t nb, uint32_t bb, uint32_t n) {
+  WatchDev t;
+  t.base = base;
+  t.ns = base[0];
+  t.nb = nb;
+  t.np = nb << bb;
+  t.n = n;
+  t.wee = base + wd_slot_off(nb);
+  t.st = t.wee + (size_t)t.ns * t.np;
+  t.gen = t.st + (size_t)t.ns * t.np;
+  t.pay = t.gen + (size_t)t.ns * t.np;
+  t.died = t.pay + (size_t)t.ns * t.np;
+  return t;
+}
+
 // A tell to a host-side actor (agx_set_outbound): appended to the outbox (when `write`); returns
 // false for any other id.  One thread's appends are ordered (same counter, program order), so each
 // sender's outbound tells keep their emission order.
@@ -393,6 +528,8 @@ constexpr uint32_t kDeltaKM = 1u << 31;
 constexpr uint32_t kStashKM = 1u << 30;
 // KM flag (not a kind): the variant knows timers (agx_set_timers).  A flag of KM for the same reason.
 constexpr uint32_t kTimersKM = 1u << 29;
+// KM flag (not a kind): the variant knows death watch (agx_set_death_watch).  A flag of KM for the same reason.
+constexpr uint32_t kWatchKM = 1u << 28;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -540,6 +677,69 @@ __device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const 
       return AGX_RES_SAME;
     }
     return C.result;
+  }
+  return AGX_RES_UNHANDLED;
+}
+
+// compiled_apply of the death-watch instantiations (agx_set_death_watch): the same rule, with
+// signal cases (AGX_CASE_SIGNAL in the result byte: an ordinary message skips them, a signal tries only them)
+// and the watch actions, run in order with the others, against the actor's slots.  A watch that conflicts
+// (checkWatchingSame) skips the rest of the case's actions and stops the actor: `conflict` is set and the
+// result is AGX_RES_STOPPED.  A signal no case matches returns AGX_RES_UNHANDLED: the caller's death pact.
+// A function of its own: every other instantiation compiles compiled_apply as before.
+template <typename Emit>
+__device__ __forceinline__ uint32_t compiled_apply_w(const DevParams& P, const WatchDev& WD, uint32_t l, uint32_t bkt,
+                                                     uint32_t& kind, uint32_t self, uint64_t* w, uint32_t src,
+                                                     uint32_t pay, bool signal, bool& conflict, Emit& emit) {
+  const uint32_t b = kind - AGX_KIND_COMPILED;
+  if (b >= P.n_beh) return AGX_RES_UNHANDLED;
+  const uint32_t c1 = P.bfirst[b + 1];
+  for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
+    const agx_case C = P.bcase[c];
+    if (((C.result & AGX_CASE_SIGNAL) != 0u) != signal) continue;
+    if (!cb_cmp(C.cmp1, cb_operand(C.src1, C.word1, C.k1, pay, w, src, self),
+                cb_operand(C.src2, C.word2, C.k2, pay, w, src, self)))
+      continue;
+    if (!cb_cmp(C.cmp2, cb_operand(C.src3, C.word3, C.k3, pay, w, src, self),
+                cb_operand(C.src4, C.word4, C.k4, pay, w, src, self)))
+      continue;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      const agx_act A = P.bact[i];
+      const uint64_t v = cb_operand(A.src, A.sword, A.k, pay, w, src, self);
+      uint64_t d = 0;
+      if (A.op == AGX_A_TELL || A.op >= AGX_A_WATCH) {  // a ref: (self + dk) mod n for ring neighbours
+        if (A.dsrc == AGX_V_SELF) {
+          int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+          d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+        } else {
+          d = cb_operand(A.dsrc, A.dword, A.dk, pay, w, src, self);
+        }
+      }
+      const uint32_t ref = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
+      const uint32_t msg = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;
+      switch (A.op) {
+        case AGX_A_SET: w[A.word & 1u] = v; break;
+        case AGX_A_ADD: w[A.word & 1u] += v; break;
+        case AGX_A_MAX: w[A.word & 1u] = v > w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_MIN: w[A.word & 1u] = v < w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_TELL: emit(ref, msg); break;
+        case AGX_A_WATCH:
+        case AGX_A_WATCH_WITH:
+          if (WD.watch(l, bkt, ref, A.op == AGX_A_WATCH_WITH, msg)) {
+            conflict = true;
+            return AGX_RES_STOPPED;
+          }
+          break;
+        case AGX_A_UNWATCH: WD.unwatch(l, bkt, ref); break;
+        default: break;
+      }
+    }
+    const uint32_t res = C.result & ~AGX_CASE_SIGNAL;
+    if (res == AGX_RES_BECOME) {
+      kind = AGX_KIND_COMPILED + C.next;
+      return AGX_RES_SAME;
+    }
+    return res;
   }
   return AGX_RES_UNHANDLED;
 }

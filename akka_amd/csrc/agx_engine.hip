@@ -150,6 +150,22 @@ struct agx_engine {
     std::vector<uint32_t> delays;
   };
   std::vector<TimerStart> tm_starts;  // agx_start_timers calls not yet applied on the device (prepare_run)
+  // death watch (agx_set_death_watch): n_slots watch slots per actor.  Such an engine launches the watch
+  // instantiation of the compiled catch-all variant and no wave / ring / dense / persistent launch
+  uint32_t wd_slots = 0;
+  uint32_t* d_watch = nullptr;  // DevParams.watch (agx_device.h WatchDev)
+  bool beh_watch = false;       // the compiled tables hold a watch action or a signal case
+  bool wd_bad_start = false;    // agx_start_watch was called on an engine without death watch: agx_run refuses
+  bool wd_died_init = false;    // the death ticks follow the registered actors (before the first run)
+  uint64_t wd_ticks = 0;        // supersteps that ran while the engine was active
+  uint32_t wd_clock = 0;        // the device clock after the last run (every bucket's tick count)
+  struct WatchStart {
+    uint64_t first, count;
+    int64_t offset;
+    uint32_t with, payload;
+    std::vector<uint32_t> watchees;
+  };
+  std::vector<WatchStart> wd_starts;  // agx_start_watch calls not yet applied on the device (prepare_run)
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -485,6 +501,7 @@ DevParams make_params(agx_engine* e) {
   if (e->prio_mask) P.ptab = e->d_ptab;  // (shares rx's slot: no CRDT kinds on an engine with priority tables)
   if (e->stash_on) P.stash = e->d_stash;  // (the same slot: neither CRDT kinds nor priority tables with a stash)
   if (e->tm_keys) P.timers = e->d_timers;  // (the same slot: none of the three on an engine with timers)
+  if (e->wd_slots) P.watch = e->d_watch;   // (the same slot: none of the four on an engine with death watch)
   P.heap_top = e->d_heap_top;
   P.step = e->d_step;
   P.heap_rows = (uint32_t)e->heap_rows;
@@ -652,6 +669,7 @@ uint32_t apply_variant(const agx_engine* e) {
     return (km & kb(AGX_KIND_COMPILED)) ? V_ALL_COMPILED : V_ALL;
   if (e->stash_on) return V_ALL_COMPILED;  // deque-based mailboxes: the compiled catch-all carries the stash (kStash)
   if (e->tm_keys) return V_ALL_COMPILED;   // timers: the compiled catch-all carries them (kTimers)
+  if (e->wd_slots) return V_ALL_COMPILED;  // death watch: the compiled catch-all carries it (kWatch)
   if (e->pw && e->delta_max) {  // delta-CRDT replication: the variants that carry the delta code
     if (km == kb(AGX_KIND_GCOUNTER)) return V_GC_DELTA;
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN_DELTA;
@@ -681,7 +699,7 @@ bool dense_on(const agx_engine* e, uint32_t vid) {
   // (k_dense_fused reads a fused bucket's table row one sender bucket per thread: nb <= 512, which
   // the fused superstep's <= 2^20 actors guarantee)
   if (e->fused && e->nb > (uint32_t)kDenseThreads) return false;
-  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask && !e->stash_on && !e->tm_keys &&
+  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots &&
          (e->dense_launch == 1 || (e->dense_launch < 0 && vid == V_RING));
 }
 
@@ -865,7 +883,7 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
     }
     // (priority mailboxes: the wave path drains in arrival order -- every bucket takes the block launch)
     const bool tl = mode == M_BYPASS && !kVariants[vid].wide && e->tiny_launch && e->tiny_max && !e->skew_only &&
-                    !e->prio_mask && !e->stash_on && !e->tm_keys;
+                    !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots;
     if (tl) {  // wave-per-bucket launch first; the block launch then takes the buckets it marked
       ba.blist = e->d_blist;
       ba.dense_first = dl ? 1u : 0u;
@@ -888,6 +906,9 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       } else if (e->tm_keys) {
         if (mode == M_OWNER) return set_err(AGX_ESTATE, "timers need a single-rank engine");
         HIP_TRY(agx_launch_apply_timers(vid, mode, g, e->stream, bf));
+      } else if (e->wd_slots) {
+        if (mode == M_OWNER) return set_err(AGX_ESTATE, "death watch needs a single-rank engine");
+        HIP_TRY(agx_launch_apply_watch(vid, mode, g, e->stream, bf));
       } else {
         HIP_TRY(agx_launch_apply(vid, mode, false, g, e->stream, bf));
       }
@@ -926,7 +947,7 @@ agx_status launch_staged_chunk(agx_engine* e) {
 // behaviours, every configured mailbox class bounded by <= kRingMaxC); from then on the classes
 // are fixed (agx_set_mailbox_class refuses a capacity the rings cannot hold).
 agx_status setup_rings(agx_engine* e) {
-  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask || e->stash_on || e->tm_keys) return AGX_OK;  // (a ring drains in arrival order)
+  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask || e->stash_on || e->tm_keys || e->wd_slots) return AGX_OK;  // (a ring drains in arrival order)
   uint32_t cmax = 0;
   for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) {
     if (!((e->mclass_set >> c) & 1u)) continue;
@@ -970,7 +991,7 @@ agx_status setup_rings(agx_engine* e) {
 constexpr uint32_t kRingAutoC = 256;  // ring apply by default from this mailbox capacity up (setup_ring_apply)
 agx_status setup_ring_apply(agx_engine* e) {
   if (e->started || e->rg_on || e->ring_live || e->ring_res) return AGX_OK;
-  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask || e->stash_on || e->tm_keys) return AGX_OK;
+  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask || e->stash_on || e->tm_keys || e->wd_slots) return AGX_OK;
   // AGX_RING_APPLY=1 / 0 forces rings on / off; unset: on when the largest bounded capacity is at
   // least kRingAutoC.  Deep queues are where re-copying the backlog every superstep costs most (C3,
   // BoundedMailbox(1000): 4.67e8 -> 6.7e8 msg/s with rings, the sparse buckets a wave each); at
@@ -1240,8 +1261,183 @@ agx_status timers_after_run(agx_engine* e) {
   return AGX_OK;
 }
 
+// ---- death watch (agx_set_death_watch)
+// the death ticks follow the actors' flags: an actor that is not alive and has no death tick yet was never
+// registered (before the first run: dead before tick 1) or was stopped from the host (dead in the current tick)
+static __global__ void __launch_bounds__(kThreads) k_watch_died(uint32_t* wd, const uint8_t* alive, uint32_t nb, uint32_t bb,
+                                                               uint32_t n_local, uint32_t started) {
+  const uint32_t l = blockIdx.x * kThreads + threadIdx.x, np = nb << bb;
+  if (l >= np) return;
+  uint32_t* const died = wd + wd_slot_off(nb) + 4ull * wd[0] * np;
+  if (l >= n_local || !(alive[l] & 1u)) {
+    if (died[l] == kWdNone) died[l] = started ? wd[kWdBucketOff + 2u * nb + (l >> bb)] : 0u;
+  }
+}
+// agx_start_watch on the device, first step: one thread per actor of the range records the watch by the rules of
+// a device watch.  A conflicting actor stops (in the current tick); `slot_of[i]` is the slot occupied, or none.
+static __global__ void __launch_bounds__(kThreads) k_watch_start(uint32_t* wd, uint8_t* alive, uint32_t nb, uint32_t bb,
+                                                                uint32_t n, uint32_t first, uint32_t count,
+                                                                const uint32_t* watchees, uint32_t offset, uint32_t with,
+                                                                uint32_t payload, uint32_t* slot_of) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= count) return;
+  const WatchDev WD = watch_dev(wd, nb, bb, n);
+  const uint32_t l = first + i, b = l >> bb;
+  slot_of[i] = WD.ns;
+  if (!(alive[l] & 1u) || WD.died[l] != kWdNone) return;  // (a stopped actor watches nothing)
+  const uint32_t x = watchees ? watchees[i] : (uint32_t)(((uint64_t)l + offset) % n);
+  uint32_t slot = WD.ns;
+  if (WD.watch(l, b, x, with != 0u, payload, &slot)) {  // checkWatchingSame: IllegalStateException
+    alive[l] &= 0xFEu;
+    WD.stop(l, b, WD.clock(b));
+    atomicAdd(WD.ctr(kWcConflicts), 1ull);
+  } else {
+    slot_of[i] = slot;
+  }
+}
+// second step: a slot occupied by this call whose watchee is dead by now is due at once; its count joins the
+// bucket's due count and backlog count, so the next tick's inbox has room for the Terminated envelope
+static __global__ void __launch_bounds__(kThreads) k_watch_start_due(uint32_t* wd, uint32_t nb, uint32_t bb, uint32_t n,
+                                                                    uint32_t first, uint32_t count, const uint32_t* slot_of,
+                                                                    uint32_t* blc) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= count) return;
+  const WatchDev WD = watch_dev(wd, nb, bb, n);
+  const uint32_t l = first + i, b = l >> bb, k = slot_of[i];
+  if (k >= WD.ns) return;
+  const size_t x = WD.at(k, l);
+  if ((WD.st[x] & kWdStateMask) != kWdWatching) return;  // (freed again: the actor was stopped by a conflict)
+  const uint32_t w = WD.wee[x];
+  if (w < n && WD.died[w] == kWdNone) return;
+  WD.st[x] = kWdDue | (WD.st[x] & kWdHasMsg);
+  atomicSub(WD.nwatch(b), 1u);
+  atomicAdd(WD.due(b), 1u);
+  atomicAdd(&blc[b], 1u);
+}
+// third step: a bucket with a watching slot marks the current tick's "a slot is watching" word (the stop rule of
+// the next tick's entry reads it)
+static __global__ void __launch_bounds__(kThreads) k_watch_start_any(uint32_t* wd, uint32_t nb) {
+  const uint32_t b = blockIdx.x * kThreads + threadIdx.x;
+  if (b >= nb) return;
+  if (wd[kWdBucketOff + 3u * nb + b]) {
+    const uint32_t clk = wd[kWdBucketOff + 2u * nb + b];
+    wd[kWdAnyW + (clk & 1u)] = clk;
+  }
+}
+
+size_t watch_words(const agx_engine* e) {
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  return wd_slot_off(e->nb) + (4ull * e->wd_slots + 1ull) * npad;
+}
+
+// The watch storage (agx_device.h WatchDev) -- allocated once, sized by n_local: everything zero (slots free),
+// the stop / watching words and every death tick "none"
+agx_status alloc_watch(agx_engine* e) {
+  if (e->d_watch) return AGX_OK;
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  const size_t total = watch_words(e);
+  if (hipMalloc((void**)&e->d_watch, total * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_watch = nullptr;
+    return set_err(AGX_ENOMEM, "the watch slots of %llu actors (%u slots each, %llu MB) do not fit on the device",
+                   (unsigned long long)npad, e->wd_slots, (unsigned long long)(total >> 18));
+  }
+  HIP_TRY(hipMemsetAsync(e->d_watch, 0, total * 4ull, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_watch + kWdStopW, 0xFF, 4ull * 4ull, e->stream));                     // stopw, anyw
+  HIP_TRY(hipMemsetAsync(e->d_watch + (total - npad), 0xFF, npad * 4ull, e->stream));               // died
+  const uint32_t ns = e->wd_slots;
+  HIP_TRY(hipMemcpyAsync(e->d_watch, &ns, 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->wd_died_init = false;
+  drop_graphs(e);  // (a kernel argument of the captured supersteps)
+  return AGX_OK;
+}
+
+// bring the death ticks up to date with the actors' flags (after registrations)
+agx_status watch_sync_died(agx_engine* e) {
+  if (e->wd_died_init) return AGX_OK;
+  if (e->actors_dirty)  // (a query before the run: the host's flags are the newer ones; prepare_run uploads the rest)
+    HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
+  const uint32_t np = e->nb << e->bb;
+  hipLaunchKernelGGL(k_watch_died, dim3((np + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, e->d_watch, e->d_alive,
+                     e->nb, e->bb, (uint32_t)e->n_local, e->started ? 1u : 0u);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->wd_died_init = !e->actors_dirty;
+  return AGX_OK;
+}
+
+// apply the recorded agx_start_watch calls (the actors' flags are on the device: prepare_run)
+agx_status flush_watch_starts(agx_engine* e) {
+  AGX_TRY(watch_sync_died(e));
+  if (e->wd_starts.empty()) return AGX_OK;
+  bool any = false;
+  for (const auto& ws : e->wd_starts) {
+    if (!ws.count) continue;
+    any = true;
+    uint32_t *d_w = nullptr, *d_slot = nullptr;
+    AGX_TRY(dalloc(&d_slot, ws.count));
+    if (!ws.watchees.empty()) {
+      AGX_TRY(dalloc(&d_w, ws.watchees.size()));
+      HIP_TRY(hipMemcpyAsync(d_w, ws.watchees.data(), ws.watchees.size() * 4ull, hipMemcpyHostToDevice, e->stream));
+    }
+    const int64_t n = (int64_t)e->n_global;
+    const uint32_t off = (uint32_t)(((ws.offset % n) + n) % n);
+    const dim3 g((uint32_t)((ws.count + kThreads - 1) / kThreads));
+    hipLaunchKernelGGL(k_watch_start, g, dim3(kThreads), 0, e->stream, e->d_watch, e->d_alive, e->nb, e->bb,
+                       (uint32_t)e->n_global, (uint32_t)ws.first, (uint32_t)ws.count, d_w, off, ws.with, ws.payload, d_slot);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_watch_start_due, g, dim3(kThreads), 0, e->stream, e->d_watch, e->nb, e->bb, (uint32_t)e->n_global,
+                       (uint32_t)ws.first, (uint32_t)ws.count, d_slot, next_backlog_counts(e));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_watch_start_any, dim3((e->nb + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, e->d_watch,
+                       e->nb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (d_w) hipFree(d_w);
+    hipFree(d_slot);
+  }
+  e->wd_starts.clear();
+  if (!any) return AGX_OK;
+  e->inflight_known = false;
+  // a conflicting actor was stopped on the device: the host's flags follow (they may be the newer ones otherwise)
+  std::vector<uint8_t> al(e->n_local);
+  AGX_TRY(copy_sync(e, al.data(), e->d_alive, e->n_local, hipMemcpyDeviceToHost));
+  for (uint64_t l = 0; l < e->n_local; ++l)
+    if (!(al[l] & 1u)) e->h_alive[l] &= 0xFEu;
+  uint32_t full = 0;
+  AGX_TRY(copy_sync(e, &full, e->d_watch + kWdFull, 4, hipMemcpyDeviceToHost));
+  if (full)
+    return set_err(AGX_ECAPACITY, "a watch found every one of its actor's %u watch slots taken: the watch is not recorded "
+                   "(agx_set_death_watch; at most %u watched refs per actor)", e->wd_slots, AGX_MAX_WATCH_SLOTS);
+  return AGX_OK;
+}
+
+// the bookkeeping words of the watch storage: [0, kWdBucketOff) then due / mark / clock / watching per bucket
+agx_status read_watch_head(agx_engine* e, std::vector<uint32_t>& h) {
+  h.assign(kWdBucketOff + 4ull * e->nb, 0u);
+  return copy_sync(e, h.data(), e->d_watch, h.size() * 4ull, hipMemcpyDeviceToHost);
+}
+
+// after a run: the ticks that passed while the engine was active (the device's last active tick against the
+// clock before the run), and the clock now
+agx_status watch_after_run(agx_engine* e) {
+  if (!e->d_watch) return AGX_OK;
+  uint32_t la = 0, clk = 0;
+  AGX_TRY(copy_sync(e, &la, e->d_watch + kWdLastAct, 4, hipMemcpyDeviceToHost));
+  AGX_TRY(copy_sync(e, &clk, e->d_watch + kWdBucketOff + 2ull * e->nb, 4, hipMemcpyDeviceToHost));
+  if (la > e->wd_clock) e->wd_ticks += la - e->wd_clock;
+  e->wd_clock = clk;
+  return AGX_OK;
+}
+
 // upload host mirrors / staged tells before a run
 agx_status prepare_run(agx_engine* e) {
+  if (e->wd_bad_start)
+    return set_err(AGX_EINVAL, "agx_start_watch was called on an engine without death watch (agx_set_death_watch)");
+  if (e->beh_watch && !e->wd_slots)  // (only the watch variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours watch, unwatch or hold a signal case, but the engine has no death "
+                   "watch (agx_set_death_watch)");
   if (e->tm_bad_start)
     return set_err(AGX_EINVAL, "agx_start_timers was called on an engine without timers (agx_set_timers)");
   if (e->beh_tm_keys > e->tm_keys)  // (only the timer variant interprets those: loud, never wrong)
@@ -1282,6 +1478,7 @@ agx_status prepare_run(agx_engine* e) {
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->actors_dirty = false;
+    e->wd_died_init = false;  // (actors registered since: their death ticks follow below)
     e->prio_dirty = e->prio_mask != 0;  // (mailboxes bound since: the per-bucket marks below)
     e->stash_dirty = e->stash_on;
   }
@@ -1289,6 +1486,10 @@ agx_status prepare_run(agx_engine* e) {
   if (e->tm_keys) {
     AGX_TRY(alloc_timers(e));
     AGX_TRY(flush_timer_starts(e));
+  }
+  if (e->wd_slots) {
+    AGX_TRY(alloc_watch(e));
+    AGX_TRY(flush_watch_starts(e));
   }
   if (e->prio_dirty) {  // priority tables and the buckets that hold an actor of a prioritised class
     std::vector<uint8_t> pb(e->prio_tab);  // tables, then the bucket marks (kPrioBucketOff)
@@ -1537,6 +1738,13 @@ agx_status error_status(const agx_engine* e, uint64_t err) {
     return set_err(AGX_ECAPACITY, "a bucket of %u actors of an engine with timers received more than one tile of %d "
                    "messages (backlog and the tick's timer messages included): the launches for larger inboxes know "
                    "no timers (smaller agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
+  if (err & kErrWatchTile)
+    return set_err(AGX_ECAPACITY, "a bucket of %u actors of an engine with death watch received more than one tile of %d "
+                   "messages (backlog and the tick's Terminated envelopes included): the launches for larger inboxes "
+                   "know no death watch (smaller agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
+  if (err & kErrWatchSlots)
+    return set_err(AGX_ECAPACITY, "a watch found every one of its actor's %u watch slots taken: the watch is not recorded "
+                   "(agx_set_death_watch; at most %u watched refs per actor)", e->wd_slots, AGX_MAX_WATCH_SLOTS);
   if (err & kErrCapacity)
     return set_err(AGX_ECAPACITY, "in-flight messages exceeded engine capacity (msg_capacity=%llu)",
                    (unsigned long long)e->cap);
@@ -1573,6 +1781,11 @@ agx_status collect_stats(agx_engine* e, agx_stats* out, bool check) {
     std::vector<uint32_t> h;
     AGX_TRY(read_timer_head(e, h));
     for (uint32_t b = 0; b < e->nb; ++b) st.in_flight -= std::min<uint64_t>(st.in_flight, h[kTmBucketOff + e->nb + b]);
+  }
+  if (e->d_watch) {  // the backlog counts carry the due slots: their envelopes are not sent yet, not in flight
+    std::vector<uint32_t> h;
+    AGX_TRY(read_watch_head(e, h));
+    for (uint32_t b = 0; b < e->nb; ++b) st.in_flight -= std::min<uint64_t>(st.in_flight, h[kWdBucketOff + b]);
   }
   // B = E_in + f_out*E_out + 2*S*(A/M); kind+alive bytes read per activation.
   // S = the state words a behaviour touches: words 0-1 (plain and compiled behaviours), a CRDT's
@@ -1619,7 +1832,7 @@ bool persist_ok(agx_engine* e) {
       e->persist = (uint64_t)e->nb <= (uint64_t)per_cu * (uint64_t)ncu ? 1 : 0;
     (void)hipGetLastError();
   }
-  return e->persist == 1 && !e->prio_mask && !e->stash_on && !e->tm_keys && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
+  return e->persist == 1 && !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
          !e->recover_dense;
 }
 
@@ -1745,7 +1958,7 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
       bool tpend = false;  // timers: bit 31 of an entry = the bucket had a pending timer at the tick's entry
       for (uint32_t b = 0; b < e->nb; ++b) {
         uint32_t v = h[(size_t)i * e->nb + b];
-        if (e->tm_keys) {
+        if (e->tm_keys || e->wd_slots) {  // (death watch: bit 31 = the stop rule held at the entry)
           tpend |= (v >> 31) != 0u;
           v &= 0x7FFFFFFFu;
         }
@@ -1848,7 +2061,7 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
           strict = true;
           e->strict_ok = true;
         }
-      } else if (e->tm_keys ? e->h_pin[8 + 2 * slot] != e->h_pin[9 + 2 * slot] : e->h_pin[slot] == 0) {
+      } else if ((e->tm_keys || e->wd_slots) ? e->h_pin[8 + 2 * slot] != e->h_pin[9 + 2 * slot] : e->h_pin[slot] == 0) {
         // (timers: the last tick with mail or a pending timer at its entry is not that replay's last tick)
         break;  // that replay ended on a superstep with no mail: quiescent
       }
@@ -1906,6 +2119,10 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
       if (e->tm_keys) {  // the last active tick and the clock after this replay
         hipMemcpyAsync(&e->h_pin[8 + 2 * slot], e->d_timers + kTmLastAct, 4, hipMemcpyDeviceToHost, e->stream);
         hipMemcpyAsync(&e->h_pin[9 + 2 * slot], e->d_timers + kTmBucketOff + 2ull * e->nb, 4, hipMemcpyDeviceToHost, e->stream);
+      }
+      if (e->wd_slots) {  // (death watch: the same two words of its storage)
+        hipMemcpyAsync(&e->h_pin[8 + 2 * slot], e->d_watch + kWdLastAct, 4, hipMemcpyDeviceToHost, e->stream);
+        hipMemcpyAsync(&e->h_pin[9 + 2 * slot], e->d_watch + kWdBucketOff + 2ull * e->nb, 4, hipMemcpyDeviceToHost, e->stream);
       }
     }
     launched_steps += cnt;
@@ -2360,6 +2577,8 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
                    "(agx_set_mailbox_priority): a state gossip's snapshot handle carries no message tag");
   if (e->tm_keys)
     return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with timers (agx_set_timers)");
+  if (e->wd_slots)
+    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with death watch (agx_set_death_watch)");
   if (e->stash_on)
     return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a deque-based mailbox "
                    "(agx_set_stash): a state gossip's snapshot row does not outlive its superstep in a stash");
@@ -2779,6 +2998,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_ptab);
   hipFree(e->d_stash);
   hipFree(e->d_timers);
+  hipFree(e->d_watch);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -2894,6 +3114,7 @@ agx_status agx_set_mailbox_priority(agx_engine* e, uint32_t cls, const uint8_t p
   if (e->stash_on)
     return set_err(AGX_EINVAL, "priority mailboxes need an engine without a deque-based mailbox class (agx_set_stash)");
   if (e->tm_keys) return set_err(AGX_EINVAL, "priority mailboxes need an engine without timers (agx_set_timers)");
+  if (e->wd_slots) return set_err(AGX_EINVAL, "priority mailboxes need an engine without death watch (agx_set_death_watch)");
   if (e->started) return set_err(AGX_ESTATE, "set mailbox priorities before the first agx_run");
   AGX_TRY(ensure_dev(e));
   if (prio) {
@@ -2919,6 +3140,7 @@ agx_status agx_set_stash(agx_engine* e, uint32_t cls, uint32_t capacity) {
   if (e->prio_mask)
     return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without priority tables (agx_set_mailbox_priority)");
   if (e->tm_keys) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without timers (agx_set_timers)");
+  if (e->wd_slots) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without death watch (agx_set_death_watch)");
   if (cls >= AGX_MAX_MAILBOX_CLASSES || !((e->mclass_set >> cls) & 1u))
     return set_err(AGX_EINVAL, "mailbox class %u is not configured (agx_set_mailbox_class; classes 0..%u)", cls,
                    AGX_MAX_MAILBOX_CLASSES - 1);
@@ -3006,6 +3228,7 @@ agx_status agx_set_timers(agx_engine* e, uint32_t n_keys) {
   if (e->pw) return set_err(AGX_EINVAL, "timers need an engine without CRDT kinds (one is registered)");
   if (e->prio_mask) return set_err(AGX_EINVAL, "timers need an engine without priority tables (agx_set_mailbox_priority)");
   if (e->stash_on) return set_err(AGX_EINVAL, "timers need an engine without a deque-based mailbox class (agx_set_stash)");
+  if (e->wd_slots) return set_err(AGX_EINVAL, "timers need an engine without death watch (agx_set_death_watch)");
   if (e->kmax != 1)
     return set_err(AGX_EINVAL, "timers need max_emit = 1 (it is %u): the drain for more evaluates a case more than once, "
                    "and a timer action must take effect once", e->kmax);
@@ -3106,6 +3329,113 @@ agx_status agx_read_timers(agx_engine* e, uint64_t actor_id, uint32_t active[4],
   return AGX_OK;
 }
 
+// AA/dungeon/DeathWatch.scala:19-113 (typed adapter: TY/internal/adapter/ActorAdapter.scala:84-91,134-138,200-205)
+agx_status agx_set_death_watch(agx_engine* e, uint32_t n_slots) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (n_slots < 1u || n_slots > AGX_MAX_WATCH_SLOTS)
+    return set_err(AGX_EINVAL, "death watch: %u slots per actor (1..%u)", n_slots, AGX_MAX_WATCH_SLOTS);
+  if (e->R > 1) return set_err(AGX_EINVAL, "death watch needs a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
+  if (e->pw) return set_err(AGX_EINVAL, "death watch needs an engine without CRDT kinds (one is registered)");
+  if (e->prio_mask) return set_err(AGX_EINVAL, "death watch needs an engine without priority tables (agx_set_mailbox_priority)");
+  if (e->stash_on) return set_err(AGX_EINVAL, "death watch needs an engine without a deque-based mailbox class (agx_set_stash)");
+  if (e->tm_keys) return set_err(AGX_EINVAL, "death watch needs an engine without timers (agx_set_timers)");
+  if (e->kmax != 1)
+    return set_err(AGX_EINVAL, "death watch needs max_emit = 1 (it is %u): the drain for more evaluates a case more than "
+                   "once, and a watch action must take effect once", e->kmax);
+  if (e->ring_live || e->rg_on)
+    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, which know no "
+                   "death watch: set death watch before the first run", e->ring_live ? e->ring_c : e->rg_c);
+  if (e->started) return set_err(AGX_ESTATE, "set death watch before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  if (e->d_watch && n_slots != e->wd_slots) {
+    hipFree(e->d_watch);
+    e->d_watch = nullptr;
+    e->wd_starts.clear();
+  }
+  e->wd_slots = n_slots;
+  e->wd_bad_start = false;  // (an agx_start_watch refused before this call no longer stands in the way of agx_run)
+  AGX_TRY(alloc_watch(e));  // (now: AGX_ENOMEM is this call's)
+  drop_graphs(e);  // the variant and the watch storage are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_start_watch(agx_engine* e, uint64_t first_id, uint64_t count, const uint32_t* watchees, int64_t offset,
+                           int32_t with_message, uint32_t payload) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->wd_slots) {
+    e->wd_bad_start = true;  // (agx_run refuses too: the rule for tables with watch actions)
+    return set_err(AGX_EINVAL, "agx_start_watch needs an engine with death watch (agx_set_death_watch)");
+  }
+  if (first_id + count > e->n_global || first_id + count < first_id) return set_err(AGX_EINVAL, "bad actor range");
+  agx_engine::WatchStart ws;
+  ws.first = first_id;
+  ws.count = count;
+  ws.offset = offset;
+  ws.with = with_message ? 1u : 0u;
+  ws.payload = payload;
+  if (watchees) ws.watchees.assign(watchees, watchees + count);
+  e->wd_starts.push_back(std::move(ws));
+  return AGX_OK;
+}
+
+agx_status agx_watch_info(agx_engine* e, uint64_t* watches, uint64_t* terminated, uint64_t* discarded, uint64_t* death_pacts,
+                          uint64_t* conflicts, uint64_t* watching, uint64_t* pending, uint64_t* ticks) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[5] = {0, 0, 0, 0, 0}, nw = 0, npd = 0;
+  if (e->d_watch) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(flush_watch_starts(e));  // (starts recorded since the last run: applied now, nothing else is uploaded)
+    AGX_TRY(copy_sync(e, c, e->d_watch + kWdCtr, sizeof(c), hipMemcpyDeviceToHost));
+    const uint64_t npad = (uint64_t)e->nb << e->bb;
+    std::vector<uint32_t> st((uint64_t)e->wd_slots * npad);
+    AGX_TRY(copy_sync(e, st.data(), e->d_watch + wd_slot_off(e->nb) + (uint64_t)e->wd_slots * npad, st.size() * 4ull,
+                      hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < e->wd_slots; ++k)
+      for (uint64_t l = 0; l < e->n_local; ++l) {
+        const uint32_t s = st[k * npad + l] & kWdStateMask;
+        nw += s == kWdWatching;
+        npd += s == kWdDue;
+      }
+  }
+  if (watches) *watches = c[kWcWatches];
+  if (terminated) *terminated = c[kWcTerminated];
+  if (discarded) *discarded = c[kWcDiscarded];
+  if (death_pacts) *death_pacts = c[kWcPacts];
+  if (conflicts) *conflicts = c[kWcConflicts];
+  if (watching) *watching = nw;
+  if (pending) *pending = npd;
+  if (ticks) *ticks = e->wd_ticks;
+  return AGX_OK;
+}
+
+agx_status agx_read_watch(agx_engine* e, uint64_t actor_id, uint32_t watchee[4], uint32_t state[4], uint32_t payload[4],
+                          uint32_t generation[4]) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (actor_id >= e->n_global) return set_err(AGX_EINVAL, "bad actor id");
+  for (uint32_t k = 0; k < AGX_MAX_WATCH_SLOTS; ++k) {
+    if (watchee) watchee[k] = 0;
+    if (state) state[k] = 0;
+    if (payload) payload[k] = 0;
+    if (generation) generation[k] = 0;
+  }
+  if (!e->d_watch) return AGX_OK;
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_watch_starts(e));  // (starts recorded since the last run: applied now, nothing else is uploaded)
+  const uint64_t npad = (uint64_t)e->nb << e->bb, l = actor_id;  // (single rank: local = global)
+  // the actor's column of the [field][slot][actor] arrays in one strided copy: row f * n_slots + k = field f of slot k
+  uint32_t col[4 * AGX_MAX_WATCH_SLOTS];
+  HIP_TRY(hipMemcpy2DAsync(col, 4, e->d_watch + wd_slot_off(e->nb) + l, npad * 4ull, 4, 4ull * e->wd_slots,
+                           hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t k = 0; k < e->wd_slots; ++k) {
+    if (watchee) watchee[k] = col[k];
+    if (state) state[k] = col[e->wd_slots + k];
+    if (generation) generation[k] = col[2 * e->wd_slots + k];
+    if (payload) payload[k] = col[3 * e->wd_slots + k];
+  }
+  return AGX_OK;
+}
+
 agx_status agx_set_outbound(agx_engine* e, uint32_t first_host_id, uint32_t n_host, uint64_t capacity) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (n_host && (first_host_id < e->n_global || (uint64_t)first_host_id + n_host > (1ull << 31)))
@@ -3178,7 +3508,11 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     return src == AGX_V_TIMER ? word < AGX_MAX_TIMER_KEYS : src <= AGX_V_STASH && word <= 1u;
   };
   for (uint32_t c = 0; c < n_cases; ++c) {
-    const agx_case& C = cases[c];
+    agx_case C = cases[c];
+    if (C.result & AGX_CASE_SIGNAL) {  // a signal case (death watch): same, stopped, unhandled or become
+      C.result &= (uint8_t)~AGX_CASE_SIGNAL;
+      if (C.result > AGX_RES_BECOME) return set_err(AGX_EINVAL, "compiled behaviours: signal case %u stashes or unstashes", c);
+    }
     if (!opnd_ok(C.src1, C.word1) || !opnd_ok(C.src2, C.word2) || !opnd_ok(C.src3, C.word3) ||
         !opnd_ok(C.src4, C.word4) || C.cmp1 > AGX_CMP_GE || C.cmp2 > AGX_CMP_GE || C.result > AGX_RES_UNSTASH_ALL ||
         (C.result == AGX_RES_BECOME && C.next >= n_beh) ||
@@ -3188,9 +3522,10 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   for (uint32_t i = 0; i < n_acts; ++i) {
     const agx_act& A = acts[i];
     const bool tmop = A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL;  // (`word` is the key)
-    if (A.op < AGX_A_SET || A.op > AGX_A_TIMER_CANCEL_ALL || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+    const bool wdop = A.op >= AGX_A_WATCH && A.op <= AGX_A_UNWATCH;  // (the ref is the d-operand)
+    if (A.op < AGX_A_SET || A.op > AGX_A_UNWATCH || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
         !opnd_ok(A.src, A.sword) ||
-        ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC) && !opnd_ok(A.dsrc, A.dword)))
+        ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop) && !opnd_ok(A.dsrc, A.dword)))
       return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (state words 0..1, timer keys 0..3)", i);
   }
   // the apply kernels reserve kmax tell slots per message (single pass: the tell overwrites the
@@ -3219,7 +3554,10 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   AGX_TRY(copy_sync(e, e->d_bfirst, first, (n_beh + 1) * 4ull, hipMemcpyHostToDevice));
   e->n_beh = n_beh;
   e->beh_stash = false;
-  for (uint32_t c = 0; c < n_cases; ++c) e->beh_stash |= cases[c].result >= AGX_RES_STASH;
+  for (uint32_t c = 0; c < n_cases; ++c) e->beh_stash |= (cases[c].result & ~AGX_CASE_SIGNAL) >= AGX_RES_STASH;
+  e->beh_watch = false;  // a watch action or a signal case (checked against agx_set_death_watch at agx_run)
+  for (uint32_t c = 0; c < n_cases; ++c) e->beh_watch |= (cases[c].result & AGX_CASE_SIGNAL) != 0;
+  for (uint32_t i = 0; i < n_acts; ++i) e->beh_watch |= acts[i].op >= AGX_A_WATCH && acts[i].op <= AGX_A_UNWATCH;
   e->beh_tm_keys = 0;  // the timer keys the tables use (checked against agx_set_timers at agx_run)
   auto tm_use = [&](uint32_t src, uint32_t word) {
     if (src == AGX_V_TIMER) e->beh_tm_keys = std::max(e->beh_tm_keys, word + 1u);
@@ -3234,7 +3572,7 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     tm_use(acts[i].src, acts[i].sword);
     tm_use(acts[i].dsrc, acts[i].dword);
     if (acts[i].op == AGX_A_TIMER_CANCEL_ALL) e->beh_tm_keys = std::max(e->beh_tm_keys, 1u);
-    else if (acts[i].op >= AGX_A_TIMER_SINGLE) e->beh_tm_keys = std::max<uint32_t>(e->beh_tm_keys, acts[i].word + 1u);
+    else if (acts[i].op >= AGX_A_TIMER_SINGLE && acts[i].op <= AGX_A_TIMER_CANCEL) e->beh_tm_keys = std::max<uint32_t>(e->beh_tm_keys, acts[i].word + 1u);
   }
   drop_graphs(e);  // the tables are kernel parameters captured in the superstep graphs
   return AGX_OK;
@@ -3384,6 +3722,8 @@ agx_status agx_stage_tells(agx_engine* e, const uint32_t* dst, const uint32_t* s
       return set_err(AGX_EINVAL, "tell %zu: sender %u is not an actor id (bit 31 tags CRDT state gossips)", i, sv);
     if (e->tm_keys && (payload[i] >> 24) == AGX_TAG_TIMER)
       return set_err(AGX_EINVAL, "tell %zu: message tag 0xFF is reserved for timer messages on an engine with timers", i);
+    if (e->wd_slots && (payload[i] >> 24) == AGX_TAG_WATCH)
+      return set_err(AGX_EINVAL, "tell %zu: message tag 0xFE is reserved for Terminated envelopes on an engine with death watch", i);
     ++take;
   }
   if (take) {
@@ -3464,6 +3804,8 @@ agx_status agx_tell(agx_engine* e, uint32_t dst, uint32_t src, uint32_t payload,
     return set_err(AGX_EINVAL, "tell: sender %u is not an actor id (bit 31 tags CRDT state gossips)", src);
   if (e->tm_keys && (payload >> 24) == AGX_TAG_TIMER)
     return set_err(AGX_EINVAL, "tell: message tag 0xFF is reserved for timer messages on an engine with timers");
+  if (e->wd_slots && (payload >> 24) == AGX_TAG_WATCH)
+    return set_err(AGX_EINVAL, "tell: message tag 0xFE is reserved for Terminated envelopes on an engine with death watch");
   const bool sched = e->tq.tell(dst, src, payload);
   if (schedule) *schedule = sched ? 1 : 0;
   return AGX_OK;
@@ -3486,6 +3828,14 @@ agx_status agx_pump_idle(agx_engine* e, int32_t* reschedule) {
       std::vector<uint32_t> h;
       AGX_TRY(read_timer_head(e, h));
       for (uint32_t b = 0; b < e->nb; ++b) again |= h[kTmBucketOff + b] != kTmNone;
+    }
+    if (!again && e->d_watch) {  // a due slot, or a stop that watching slots have yet to see, keeps the engine scheduled
+      AGX_TRY(flush_watch_starts(e));
+      std::vector<uint32_t> h;
+      AGX_TRY(read_watch_head(e, h));
+      const uint32_t clk = h[kWdBucketOff + 2ull * e->nb];
+      again = h[kWdStopW + (clk & 1u)] == clk && h[kWdAnyW + (clk & 1u)] == clk;
+      for (uint32_t b = 0; b < e->nb; ++b) again |= h[kWdBucketOff + b] != 0u;
     }
   }
   if (!again) again = e->tq.pump_idle();
@@ -3516,6 +3866,7 @@ agx_status agx_run(agx_engine* e, uint32_t max_supersteps, agx_stats* out) {
   } else {
     AGX_TRY(run_single(e, max_supersteps));
     AGX_TRY(timers_after_run(e));
+    AGX_TRY(watch_after_run(e));
   }
   prof_collect(e);
   if (e->ident_on && getenv("AGX_IDENT_DEBUG")) {  // diagnostic: the last superstep's slice summaries

@@ -56,6 +56,8 @@ constexpr uint64_t kErrBarrier = 4;  // a persistent superstep launch's grid bar
 constexpr uint64_t kErrPrioTile = 8;  // a bucket with a priority-mailbox actor exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrStashTile = 16;  // a bucket with an actor of a stash class exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrTimerTile = 32;  // a bucket of an engine with timers exceeded one LDS tile (AGX_ECAPACITY)
+constexpr uint64_t kErrWatchTile = 64;  // a bucket of an engine with death watch exceeded one LDS tile (AGX_ECAPACITY)
+constexpr uint64_t kErrWatchSlots = 128;  // a watch found every slot of its actor taken (AGX_ECAPACITY)
 // per-block counters of k_bucket_apply: delivered, dead, unhandled, emitted, active
 constexpr int kBStats = 5;
 constexpr uint32_t kMaxApplyGrid = 4096;
@@ -1383,6 +1385,59 @@ __device__ __forceinline__ void timer_tick_end(const BucketArgs& a, const TimerD
   }
 }
 
+// ---- death watch (agx_set_death_watch): the end of tick `now` in bucket b, by the bucket's own
+// block.  Unless an actor stopped in tick now - 1 or the bucket started a watch in this tick, no watching slot
+// of the bucket can have become answerable: the block then reads two words.  Else it gathers died[watchee] for
+// the bucket's watching slots (the one uncoalesced access; only death ticks below `now` count, and those were
+// written in earlier launches, so a value a block of this launch is writing reads as "not yet").  Such a
+// slot becomes due; the count joins the bucket's backlog count: the next inbox has room for the Terminated
+// envelopes.  A slot still due here could not send its envelope at the entry (the tile error): it becomes
+// notified all the same, so the state stays defined.
+__device__ __forceinline__ void watch_tick_end(const BucketArgs& a, const WatchDev& WD, uint32_t b, uint32_t a0,
+                                               uint32_t na, uint32_t now, uint32_t bltot, uint32_t w, bool gather,
+                                               uint32_t* scratch) {
+  const int tid = threadIdx.x;
+  const bool scan = WD.ld(WD.base + kWdStopW + ((now - 1u) & 1u)) == now - 1u || WD.ld(WD.mark(b)) != 0u;
+  __syncthreads();  // (every thread has read the clock, for `now`, and the mark)
+  uint32_t nd = 0;
+  if (scan) {  // (block-uniform: the stop word is an earlier launch's, the mark this block's own)
+    for (uint32_t k = 0; k < WD.ns; ++k) {
+      uint4 s4 = make_uint4(0u, 0u, 0u, 0u), x4 = s4;  // (16-byte loads: a0 is a multiple of 32)
+      if ((uint32_t)tid * kBAct < na) {
+        s4 = *reinterpret_cast<const uint4*>(WD.st + WD.at(k, a0 + tid * kBAct));
+        x4 = *reinterpret_cast<const uint4*>(WD.wee + WD.at(k, a0 + tid * kBAct));
+      }
+      const uint32_t sx[kBAct] = {s4.x, s4.y, s4.z, s4.w}, xx[kBAct] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll
+      for (int j = 0; j < kBAct; ++j) {
+        const uint32_t la = tid * kBAct + j, state = sx[j] & kWdStateMask;
+        if (la >= na) continue;
+        if (state == kWdWatching && WD.dead_before(xx[j], now)) {
+          WD.st[WD.at(k, a0 + la)] = kWdDue | (sx[j] & kWdHasMsg);
+          ++nd;
+        } else if (state == kWdDue) {
+          WD.st[WD.at(k, a0 + la)] = kWdNotified | (sx[j] & kWdHasMsg);
+        }
+      }
+    }
+    uint32_t tot;
+    block_excl_sum<kBThreads>(nd, scratch, &tot);
+    nd = tot;
+  }
+  if (tid == 0) {
+    if (scan) WD.sto(WD.mark(b), 0u);
+    if (nd) atomicSub(WD.nwatch(b), nd);
+    WD.sto(WD.due(b), nd);
+    if (nd) {
+      if (gather) a.g.blc[w][b] = bltot + nd;
+      else a.chunk_cnt[b] = bltot + nd;
+    }
+    WD.clock(b) = now;
+    if (WD.ld(WD.nwatch(b)) != 0u) WD.sto(WD.base + kWdAnyW + (now & 1u), now);
+    if (WD.ld(WD.base + kWdFull)) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrWatchSlots);
+  }
+}
+
 // kStash: deque-based mailboxes (agx_set_stash).  The inbox segment of an actor then
 // starts with its window: the buffered / parked messages this superstep processes instead of mailbox
 // mail (stash_window; k_bucket_apply put them there).  With a window every admitted mailbox message
@@ -1409,6 +1464,16 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
   if constexpr (kTm) {
     TD = timer_dev(P, a.nb, a.bb);
     tnow = TD.clock(b) + 1u;
+  }
+  // kWd: death watch (agx_set_death_watch).  The tick's Terminated envelopes are the inbox's
+  // last items (k_bucket_apply put them there); the drain intercepts them, compiled cases run the watch
+  // actions against the slots, and the end of the tick turns answerable watching slots due.
+  constexpr bool kWd = (KM & kWatchKM) != 0;
+  static_assert(!kWd || (kLds && !kWide && !kOwner && !kStash && !kTm), "death watch: single-rank fast launches, plain behaviours");
+  WatchDev WD{};
+  if constexpr (kWd) {
+    WD = watch_dev(P.watch, a.nb, a.bb, P.n_global);
+    tnow = WD.clock(b) + 1u;
   }
   uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
@@ -1962,6 +2027,49 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           }
         }
         if (ndisc) atomicAdd(TD.ctr(1), (unsigned long long)ndisc);
+      } else if constexpr (kWd) {
+        // the drain with receivedTerminated (DeathWatch.scala:62-77): a Terminated envelope takes a drain slot
+        // and counts as delivered; one whose slot is not notified, or of another generation, is discarded;
+        // else the slot becomes free and the custom message runs the ordinary cases, a plain Terminated the
+        // signal cases, with the watchee as the sender.  An unhandled signal is the death pact
+        // (ActorAdapter.scala:200-205); a conflicting watch stops the actor too (checkWatchingSame).
+        uint32_t ndisc = 0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          bool sig = false;
+          ++ndel;
+          if ((pv >> 24) == AGX_TAG_WATCH) {
+            const uint32_t k = (pv >> 22) & 3u;
+            const size_t i = WD.at(k < WD.ns ? k : 0u, l);
+            const uint32_t s = k < WD.ns ? WD.st[i] : 0u;
+            if ((s & kWdStateMask) != kWdNotified || ((WD.gen[i] ^ pv) & kWdGenMask)) {
+              ++ndisc;
+              continue;
+            }
+            WD.st[i] = kWdFree;
+            sv = WD.wee[i];
+            sig = !(s & kWdHasMsg);
+            pv = sig ? AGX_SIGNAL_TERMINATED : WD.pay[i];
+          }
+          bool conflict = false;
+          uint32_t r;
+          if (kcur >= AGX_KIND_COMPILED) r = compiled_apply_w(P, WD, l, b, kcur, self, wv, sv, pv, sig, conflict, em);
+          else r = sig ? AGX_RES_UNHANDLED : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          if (sig && r == AGX_RES_UNHANDLED) {  // the death pact
+            r = AGX_RES_STOPPED;
+            atomicAdd(WD.ctr(kWcPacts), 1ull);
+          }
+          if (conflict) atomicAdd(WD.ctr(kWcConflicts), 1ull);
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            WD.stop(l, b, tnow);
+            break;
+          }
+        }
+        if (ndisc) atomicAdd(WD.ctr(kWcDiscarded), (unsigned long long)ndisc);
       } else
       for (uint32_t q = 0; q < nd; ++q) {
         const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
@@ -2037,6 +2145,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       }
     }
     if constexpr (kTm) timer_tick_end<kGather>(a, TD, b, a0, na, tnow, bltot, w, L.alive, L.scratch);
+    if constexpr (kWd) watch_tick_end(a, WD, b, a0, na, tnow, bltot, w, kGather, L.scratch);
     AGX_STAMP(a, 5);
     {  // exclusive scan of tell counts in actor (= sender) order
       uint32_t ec[kBAct], run = 0;
@@ -4356,6 +4465,12 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
   // bucket runs every tick (its clock is the tick count), and a bucket never takes the skew launch.
   constexpr bool kTm = (KM & kTimersKM) != 0;  // (a flag of KM: agx_device.h)
   static_assert(!kTm || (!kWide && !kSkew && !kOwner && !kPrio && !kStash), "timers: single-rank fast launches, plain behaviours");
+  // kWd: death watch (agx_set_death_watch) -- the same launches of an engine with death watch.
+  // A bucket's inbox then ends with the tick's Terminated envelopes (written here from the due slots, in
+  // (actor, slot) order), its backlog count carries their number (watch_tick_end), every bucket runs every
+  // tick (its clock is the tick count), and a bucket never takes the skew launch.
+  constexpr bool kWd = (KM & kWatchKM) != 0;  // (a flag of KM: agx_device.h)
+  static_assert(!kWd || (!kWide && !kSkew && !kOwner && !kPrio && !kStash && !kTm), "death watch: single-rank fast launches, plain behaviours");
   if (kOwner && a.halt && a.halt[0]) return;  // (device-resident multi-rank replay stopped)
   // key/src/pay carved from one array: group_tells reuses key+src as a 16 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t s_ksp[3 * kBucket];
@@ -4447,6 +4562,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
     if (tid == 0) s_flags = 0;
     if constexpr (kTm)  // (a timer drain is not the dense rule: the flag that keeps a bucket off dense_finish)
       if (tid == 0) s_flags = 2u;
+    if constexpr (kWd)  // (nor is a watch drain)
+      if (tid == 0) s_flags = 2u;
     for (uint32_t d = tid; d < kRadix; d += kBThreads) s_nh[d] = 0;
     uint32_t* my_tc = nullptr;  // (fused) this thread's table entry, zeroed once the bucket is processed
     // fused fast path, plain behaviours: state words 0 / 1 of the bucket's actors are loaded here,
@@ -4490,6 +4607,17 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
                 s_rowtop = 0u;
               }
             }
+            if constexpr (kWd) {  // the backlog count carries the due slots: [backlog][mail][Terminated envelopes]
+              const uint32_t np = min(P.watch[kWdBucketOff + b], blc);
+              s_rowtop = np;
+              s_g[0] = blc - np;
+              if (s_hi - s_lo > (uint32_t)kBucket) {  // the skew launches know no death watch: loud, the bucket's mail dropped
+                atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrWatchTile);
+                s_lo = s_hi = 0u;
+                s_rowtop = 0u;
+                __hip_atomic_store(&P.watch[kWdBucketOff + a.nb + b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (the end of the tick moves the due slots on)
+              }
+            }
           }
           if ((uint64_t)s_hi > a.cap) {  // mail + backlog over the message capacity: report, drop
             atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
@@ -4507,6 +4635,10 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         if constexpr (kTm) {  // mail or a pending timer at the entry of this tick: the engine is not quiescent
           if (s_hi != s_lo || __hip_atomic_load(&P.timers[kTmBucketOff + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kTmNone)
             atomicMax(&P.timers[kTmLastAct], P.timers[kTmBucketOff + 2u * a.nb + b] + 1u);
+        }
+        if constexpr (kWd) {  // active at the entry of this tick: mail (the due slots count as such) or the stop rule
+          const uint32_t t = P.watch[kWdBucketOff + 2u * a.nb + b] + 1u;
+          if (s_hi != s_lo || wd_stop_seen(P.watch, t)) atomicMax(&P.watch[kWdLastAct], t);
         }
         if (kDefer && s_g[5]) a.skew_list[atomicAdd(skew_n, 1u)] = b;
       }
@@ -4544,6 +4676,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           s_rowtop = np;
           s_g[0] -= np;
         }
+        if constexpr (kWd) {  // (as the multi-pass launch above)
+          const uint32_t np = min(P.watch[kWdBucketOff + b], s_g[0]);
+          s_rowtop = np;
+          s_g[0] -= np;
+        }
         s_g[1] = g.blo[rpar][b];
         s_g[2] = g.stg_cnt[b];
         s_g[3] = g.stg_off[b];
@@ -4566,6 +4703,15 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
             atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrTimerTile);
             tt = 0u - blc - s_g[2];  // (cnt = 0 below)
             s_rowtop = 0u;
+          }
+        }
+        if constexpr (kWd) {  // (the tick's Terminated envelopes are part of the inbox; tt is not read again)
+          tt += s_rowtop;
+          if (blc + tt + s_g[2] > (uint32_t)kBucket) {  // the skew launches know no death watch: loud, the bucket's mail dropped
+            atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrWatchTile);
+            tt = 0u - blc - s_g[2];  // (cnt = 0 below)
+            s_rowtop = 0u;
+            __hip_atomic_store(&P.watch[kWdBucketOff + a.nb + b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (the end of the tick moves the due slots on)
           }
         }
         const uint32_t cnt = blc + tt + s_g[2];
@@ -4600,6 +4746,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           if (__hip_atomic_load(&P.timers[kTmBucketOff + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kTmNone)
             g.cntb[(size_t)a.slot * a.nb + b] |= 0x80000000u;
           if (g.cntb[(size_t)a.slot * a.nb + b]) atomicMax(&P.timers[kTmLastAct], P.timers[kTmBucketOff + 2u * a.nb + b] + 1u);
+        }
+        if constexpr (kWd) {  // the stop rule holds at the entry of this tick: bit 31 of the row entry (the host's poll)
+          const uint32_t t = P.watch[kWdBucketOff + 2u * a.nb + b] + 1u;
+          if (wd_stop_seen(P.watch, t)) g.cntb[(size_t)a.slot * a.nb + b] |= 0x80000000u;
+          if (g.cntb[(size_t)a.slot * a.nb + b]) atomicMax(&P.watch[kWdLastAct], t);
         }
       }
     }
@@ -4643,6 +4794,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         if (kLateAlive) reinterpret_cast<uint32_t*>(s_alive)[tid] = alive4;
         __syncthreads();
         timer_tick_end<kGather>(a, TD, b, a0, na, TD.clock(b) + 1u, 0u, wpar, s_alive, scratch);
+        __syncthreads();
+      }
+      if constexpr (kWd) {  // a tick without mail is still a tick: the clock, and the slots a death of the tick before answers
+        const WatchDev WD = watch_dev(P.watch, a.nb, a.bb, P.n_global);
+        watch_tick_end(a, WD, b, a0, na, WD.clock(b) + 1u, 0u, wpar, kGather, scratch);
         __syncthreads();
       }
       continue;
@@ -4773,6 +4929,62 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           __syncthreads();
         }
       }
+      // kWd: the inbox's last np items are the tick's Terminated envelopes, in (actor, slot) order (the stable
+      // sort leaves them at the tail of each actor's segment, in slot order), staged here from the due slots,
+      // which become notified: sender = the watchee, payload = tag | slot | generation
+      if constexpr (kWd) {
+        const uint32_t np = s_rowtop;
+        uint32_t* const wk = reinterpret_cast<uint32_t*>(U);  // [3][kBucket] staged envelopes
+        if (np) {  // (block-uniform)
+          const WatchDev WD = watch_dev(P.watch, a.nb, a.bb, P.n_global);
+          uint32_t fm = 0, tot = 0;  // bit 4 * j + slot: actor j's slot is due
+          for (uint32_t k = 0; k < WD.ns; ++k) {
+            uint4 s4 = make_uint4(0u, 0u, 0u, 0u);
+            if ((uint32_t)tid * kBAct < na) s4 = *reinterpret_cast<const uint4*>(WD.st + WD.at(k, a0 + tid * kBAct));
+            const uint32_t sx[kBAct] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+            for (int j = 0; j < kBAct; ++j) {
+              const uint32_t la = tid * kBAct + j;
+              if (la < na && (sx[j] & kWdStateMask) == kWdDue) {
+                fm |= 1u << (4 * j + k);
+                ++tot;
+              }
+            }
+          }
+          uint32_t t;
+          uint32_t ex = block_excl_sum<kBThreads>(tot, scratch, &t);
+          if (t != np) {
+            // another number of due slots than the bucket's backlog count carries (never by the engine's own
+            // steps): loud, the missing items defined, the slots left over moved on at the end of the tick
+            if (tid == 0) {
+              atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
+              __hip_atomic_store(WD.mark(b), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            for (uint32_t i = t + tid; i < np; i += kBThreads) {
+              wk[i] = a0;
+              wk[kBucket + i] = AGX_NO_SENDER;
+              wk[2 * kBucket + i] = 0u;
+            }
+          }
+#pragma unroll 1
+          for (int j = 0; j < kBAct; ++j) {
+            for (uint32_t k = 0; k < WD.ns; ++k) {
+              if (!((fm >> (4 * j + k)) & 1u)) continue;
+              if (ex < np) {
+                const uint32_t l = a0 + tid * kBAct + j;
+                const size_t i = WD.at(k, l);
+                wk[ex] = l;
+                wk[kBucket + ex] = WD.wee[i];
+                wk[2 * kBucket + ex] = (AGX_TAG_WATCH << 24) | (k << 22) | (WD.gen[i] & kWdGenMask);
+                WD.st[i] = kWdNotified | (WD.st[i] & kWdHasMsg);
+              }
+              ++ex;
+            }
+          }
+          if (tid == 0) atomicAdd(WD.ctr(kWcTerminated), (unsigned long long)min(t, np));
+          __syncthreads();
+        }
+      }
       {  // locate every item first (LDS only), then issue all 3 x kBIpt loads back to back: selected
          // base pointers and no branches around the loads (per-item if/else made the compiler wait
          // for each item's loads before the next item's: 8 dependent round trips instead of 1)
@@ -4782,7 +4994,7 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           const uint32_t q = wbase + r * kWave + lane;
           sel[r] = 0;
           idx[r] = 0;
-          if constexpr (kTm) {  // (the last s_rowtop items are the TimerMsgs, filled in below)
+          if constexpr (kTm || kWd) {  // (the last s_rowtop items are the TimerMsgs / Terminated envelopes, filled in below)
             if (q < cnt - s_rowtop) {
               if (kGather) {
                 idx[r] = gv.locate(q, sel[r]);
@@ -4868,7 +5080,7 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
             }
           }
         }
-        if constexpr (kTm) {
+        if constexpr (kTm || kWd) {
           const uint32_t nm = cnt - s_rowtop;
           const uint32_t* const wk = reinterpret_cast<const uint32_t*>(U);
 #pragma unroll

@@ -252,6 +252,40 @@ class GpuEngine:
         check(self.lib.agx_read_timers(self._h, actor_id, *(_ptr(x, ctypes.c_uint32) for x in a)))
         return dict(zip(("active", "remaining", "period", "payload", "generation"), a))
 
+    def set_death_watch(self, n_slots: int) -> None:
+        """`n_slots` (1..4) watch slots for every actor (agx_set_death_watch): context.watch / watchWith / unwatch
+        and the Terminated signal (AA/dungeon/DeathWatch.scala:19-113) in the timers' logical time.  Compiled
+        behaviours may watch, unwatch and handle the signal (typed.context, ReceiveBuilder.on_signal)."""
+        check(self.lib.agx_set_death_watch(self._h, n_slots))
+
+    def start_watch(self, first: int, count: int, watchees=None, *, offset: int = 0, message: int | None = None) -> None:
+        """agx_start_watch: actor first + i watches watchees[i], or (first + i + offset) mod n without the array (a
+        setup block, before the first run or between runs); `message`: watchWith's custom message payload."""
+        w = None
+        if watchees is not None:
+            w = np.ascontiguousarray(watchees, np.uint32)
+            if w.size != count:
+                raise ValueError("watchees must hold one id per actor of the range")
+        check(self.lib.agx_start_watch(self._h, first, count, _ptr(w, ctypes.c_uint32) if w is not None else None,
+                                       int(offset), 0 if message is None else 1,
+                                       0 if message is None else int(message) & 0xFFFFFFFF))
+
+    WATCH_INFO = ("watches", "terminated", "discarded", "death_pacts", "conflicts", "watching", "pending", "ticks")
+
+    def watch_info(self) -> dict:
+        """agx_watch_info: totals watches / terminated / discarded / death_pacts / conflicts, the slots watching /
+        pending (due) now, and the ticks that ran while the engine was active."""
+        v = [ctypes.c_uint64() for _ in range(8)]
+        check(self.lib.agx_watch_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(self.WATCH_INFO, (int(x.value) for x in v)))
+
+    def read_watch(self, actor_id: int) -> dict:
+        """agx_read_watch: one actor's four slots -- watchee, state (0 free, 1 watching, 2 due, 3 notified, | 4 with
+        a custom message), payload, generation."""
+        a = [np.zeros(4, np.uint32) for _ in range(4)]
+        check(self.lib.agx_read_watch(self._h, actor_id, *(_ptr(x, ctypes.c_uint32) for x in a)))
+        return dict(zip(("watchee", "state", "payload", "generation"), a))
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""

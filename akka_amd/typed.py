@@ -48,6 +48,11 @@ A_TIMER_SINGLE, A_TIMER_PERIODIC, A_TIMER_CANCEL, A_TIMER_CANCEL_ALL = 6, 7, 8, 
 TAG_TIMER = 0xFF     # the message tag of a TimerMsg: reserved when the tables use timers
 MAX_TIMER_KEYS = 4
 MAX_TIMER_DELAY = (1 << 31) - 1
+A_WATCH, A_WATCH_WITH, A_UNWATCH = 10, 11, 12
+TAG_WATCH = 0xFE     # the message tag of a Terminated envelope: reserved when the tables use death watch
+MAX_WATCH_SLOTS = 4
+CASE_SIGNAL = 0x80   # agx_case.result flag: a signal case (receiveSignal)
+SIGNAL_TERMINATED = 0xFE000001  # what the payload reads as inside a signal case
 RES_SAME, RES_STOPPED, RES_UNHANDLED, RES_BECOME, RES_STASH, RES_UNSTASH_ALL = 0, 1, 2, 3, 4, 5
 NEXT_SAME = 0xFF  # agx_case.next of RES_UNSTASH_ALL: the behaviour stays
 MAX_STASH = 255
@@ -350,6 +355,44 @@ class TimerScheduler:
         return Operand(V_TIMER, self._key(key)) == 1
 
 
+class ActorContext:
+    """ActorContext[T]'s death watch (TY/scaladsl/ActorContext.scala watch / watchWith / unwatch; classic
+    AA/dungeon/DeathWatch.scala:19-113) of the actor running the behaviour, symbolic: the calls return effects.
+    The actors need an engine with death watch (engine.set_death_watch); an actor watches at most
+    MAX_WATCH_SLOTS refs at a time, and host-side actors cannot be watched."""
+
+    @staticmethod
+    def _ref(ref) -> Operand:
+        if not isinstance(ref, Ref):
+            raise CompileError(f"not an ActorRef: {ref!r}")
+        return ref.dst
+
+    def watch(self, ref) -> "Action":
+        """context.watch(ref): Terminated(ref) arrives as a signal once `ref` has stopped (on_signal); a behaviour
+        without a matching signal case fails with the death pact."""
+        return Action(A_WATCH, 0, Operand(V_CONST), self._ref(ref), 0)
+
+    def watch_with(self, ref, msg) -> "Action":
+        """context.watchWith(ref, msg): `msg` arrives as an ordinary message, its sender the terminated ref."""
+        if isinstance(msg, Message):
+            val, mask = msg.arg, msg.or_mask
+        else:
+            val, mask = lift(msg), 0
+        return Action(A_WATCH_WITH, 0, val, self._ref(ref), mask)
+
+    def unwatch(self, ref) -> "Action":
+        """context.unwatch(ref): a Terminated of it that is already enqueued is dropped at receipt."""
+        return Action(A_UNWATCH, 0, Operand(V_CONST), self._ref(ref), 0)
+
+
+context = ActorContext()
+
+
+class Terminated:
+    """The Terminated signal (TY/MessageAndSignals.scala) as a handler sees it: `sig.ref` is the terminated ref."""
+    ref = Ref(Operand(V_SENDER))
+
+
 class Behaviors:
     """Behaviors.same / stopped / unhandled (TY/scaladsl/Behaviors.scala), receiveMessage, withStash, withTimers."""
     same = _Result(RES_SAME, "same")
@@ -390,6 +433,14 @@ class Behaviors:
         return b
 
     @staticmethod
+    def receive_signal(behavior: "Behavior", handler, when=None) -> "Behavior":
+        """behavior.receiveSignal { case (_, Terminated(ref)) => ... }: `handler(sig, state)` is appended to
+        `behavior` as a Terminated signal case (ReceiveBuilder.on_signal has the rules); returns `behavior`."""
+        rb = ReceiveBuilder.create(behavior.state).on_signal(Terminated, handler, when)
+        behavior.cases = list(behavior.cases) + rb.cases
+        return behavior
+
+    @staticmethod
     def receive_message(state: State, *handlers, name: str = "behavior") -> "Behavior":
         """Behaviors.receiveMessage with a partial function: `handlers` are
         (type or None, handler[, test[, when]]) tuples tried in order."""
@@ -404,6 +455,7 @@ class _Case:
     tests: list
     effects: list
     result: object  # _Result, Behavior, _StashEffect (stash, then same) or _UnstashAll
+    signal: bool = False  # a signal case (on_signal): ordinary messages skip it, signals try only these
 
 
 @dataclass(eq=False)
@@ -467,6 +519,23 @@ class ReceiveBuilder:
             tests.append(test(Incoming))
         return self._add(tests, handler, when)
 
+    def on_signal(self, signal, handler, when=None) -> "ReceiveBuilder":
+        """onSignal(Terminated.class, handler) (:104-122): `handler(sig, state)` sees `sig.ref`, the terminated
+        ref; `when` guards on the signal and the state.  Only Terminated is a signal of the compiled subset.  A
+        signal case neither stashes nor uses timers."""
+        if signal is not Terminated:
+            raise CompileError("the only signal of compiled behaviours is Terminated")
+        n = len(self.cases)
+        self._add([], lambda m, s: handler(Terminated, s), (lambda m, s: when(Terminated, s)) if when is not None else None)
+        c = self.cases[n]
+        if isinstance(c.result, (_StashEffect, _UnstashAll)):
+            raise CompileError("a signal case cannot stash or unstash_all (a signal is no message)")
+        if any(A_TIMER_SINGLE <= e.op <= A_TIMER_CANCEL_ALL for e in c.effects) or \
+                any(o.src == V_TIMER for t in c.tests for o in (t.lhs, t.rhs)):
+            raise CompileError("a signal case cannot use timers (death watch and timers do not share an engine)")
+        c.signal = True
+        return self
+
     def on_message_equals(self, payload: int, handler, when=None) -> "ReceiveBuilder":
         """onMessageEquals(msg, handler) (:83-90)."""
         return self._add([Incoming.payload == payload], lambda m, s: handler(m, s), when)
@@ -522,6 +591,12 @@ class Tables:
         return n
 
     @property
+    def uses_watch(self) -> bool:
+        """The behaviours watch, unwatch or hold a signal case: the engine needs engine.set_death_watch(n)."""
+        return any(c.signal for b in self.behaviors for c in b.cases) or \
+            any(A_WATCH <= a.op <= A_UNWATCH for a in self.acts[:self.n_acts])
+
+    @property
     def initial_timers(self) -> list:
         """with_timers' setup starts: (kind, key, periodic, delay, payload) -- actors registered with `kind`
         start timer `key` when they start (engine.start_timers on their range, before the first run)."""
@@ -571,6 +646,8 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
                 code, nxt = RES_UNSTASH_ALL, (index[id(res.target)] if isinstance(res.target, Behavior) else NEXT_SAME)
             else:
                 code, nxt = res.code, 0
+            if c.signal:
+                code |= CASE_SIGNAL
             if len(acts) + len(c.effects) > 0xFFFF:
                 raise CompileError("too many actions")
             cases.append(AgxCase(src1=t[0].lhs.src, word1=t[0].lhs.word, k1=t[0].lhs.k, cmp1=t[0].cmp,
@@ -596,6 +673,17 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
                 if cmp == CMP_EQ and ((s1 == V_TAG and k1 == 0 and s2 == V_CONST and k2 == TAG_TIMER) or
                                       (s2 == V_TAG and k2 == 0 and s1 == V_CONST and k1 == TAG_TIMER)):
                     raise CompileError("message tag 0xFF is reserved for timer messages in behaviours that use timers")
+    if t.uses_watch:  # tag 0xFE is the Terminated envelope's: no message type of these behaviours may carry it
+        if t.timer_keys:
+            raise CompileError("death watch and timers do not share an engine: behaviours use one or the other")
+        for a in acts:
+            if a.or_mask >> 24 == TAG_WATCH:
+                raise CompileError("message tag 0xFE is reserved for Terminated in behaviours that use death watch")
+        for c in cases:
+            for s1, k1, cmp, s2, k2 in ((c.src1, c.k1, c.cmp1, c.src2, c.k2), (c.src3, c.k3, c.cmp2, c.src4, c.k4)):
+                if cmp == CMP_EQ and ((s1 == V_TAG and k1 == 0 and s2 == V_CONST and k2 == TAG_WATCH) or
+                                      (s2 == V_TAG and k2 == 0 and s1 == V_CONST and k1 == TAG_WATCH)):
+                    raise CompileError("message tag 0xFE is reserved for Terminated in behaviours that use death watch")
     if max_emit is not None and t.max_tells > max(1, max_emit):
         raise CompileError(f"a case tells {t.max_tells} times per message but max_emit is {max_emit}")
     return t

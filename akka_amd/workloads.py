@@ -52,6 +52,9 @@ class Workload:
     # timers (agx_set_timers / agx_start_timers): {"n_keys": k, "starts": [(first, count, key, periodic, delay,
     # delays or None, payload)]} -- empty: no timers
     timers: dict = field(default_factory=dict)
+    # death watch (agx_set_death_watch / agx_start_watch): {"n_slots": k, "starts": [(first, count, watchees or
+    # None, offset, message or None)]} -- empty: no death watch
+    watch: dict = field(default_factory=dict)
 
     def engine_kwargs(self) -> dict:
         """Semantic parameters (shared by the GPU engine and the CPU oracles)."""
@@ -87,6 +90,10 @@ class Workload:
             target.set_timers(self.timers["n_keys"])
             for first, count, key, periodic, delay, delays, payload in self.timers.get("starts", ()):
                 target.start_timers(first, count, key, delay, periodic=periodic, delays=delays, payload=payload)
+        if self.watch:  # (empty: targets without the calls are unaffected)
+            target.set_death_watch(self.watch["n_slots"])
+            for first, count, watchees, offset, message in self.watch.get("starts", ()):
+                target.start_watch(first, count, watchees, offset=offset, message=message)
         if self.fanout is not None:
             target.set_fanout(*self.fanout)
         if self.graph is not None:
@@ -657,3 +664,53 @@ def heartbeat(n: int = 1 << 20, period: int = 16, seed: int = 1, throughput: int
                     outbound=(n, n_host) if n_host else None, bucket_actors=bucket_actors,
                     timers={"n_keys": tb.timer_keys,
                             "starts": [(0, n, 0, True, period, delays, (HB_TICK << 24))]})
+
+
+# ------------------------------------------------------------------ death watch: pacts and a self-healing ring
+DW_STOP, DW_DOWN = 1, 2
+
+
+def death_pact_chain(n: int = 1 << 20, throughput: int = 3, bucket_actors: int = 0) -> Workload:
+    """Actor i watches actor i - 1 and handles no Terminated signal (the death pact, ActorAdapter.scala:200-205):
+    a staged Stop to actor 0 takes the whole chain down, one actor every two ticks (a death at tick s reaches
+    its watcher's inbox at s + 2), so every actor is dead after 2 n - 1 ticks."""
+    from . import typed
+    st = typed.State("count", "unused")
+    B = typed.Behaviors
+    b = (typed.ReceiveBuilder.create(st)
+         .on_any_message(lambda m, s: [s.count.inc(), B.stopped], test=lambda m: m.tag == DW_STOP)
+         .on_any_message(lambda m, s: [B.unhandled])
+         .build("pact_link"))
+    tb =typed.compile_behaviors([b], max_emit=1)
+    tells = (np.asarray([0], np.uint32), np.asarray([NO_SENDER], np.uint32), np.asarray([DW_STOP << 24], np.uint32))
+    return Workload("death_pact_chain", n, 2, 1, throughput, 0, [(0, n, tb.kind_of(b), None)], behaviors=tb, tells=tells,
+                    bucket_actors=bucket_actors,
+                    watch={"n_slots": 1, "starts": [(1, n - 1, None, -1, None)] if n > 1 else []})
+
+
+def watch_ring(n: int = 1 << 20, kill=(0,), throughput: int = 3, bucket_actors: int = 0) -> Workload:
+    """A ring that heals itself: every actor watchWith(Down)es its successor, held in a state word; on Down it
+    counts the loss and watches the successor's successor -- a ref computed from state, possibly dead already
+    (adjacent kills: answered one tick later), in the slot the Terminated has just freed.  `kill`: the actors that
+    get a staged Stop."""
+    from . import typed
+    st = typed.State("succ", "downs")
+    B = typed.Behaviors
+    ctx = typed.context
+    down = typed.MessageType("Down", DW_DOWN)
+    b = (typed.ReceiveBuilder.create(st)
+         .on_any_message(lambda m, s: [B.stopped], test=lambda m: m.tag == DW_STOP)
+         .on_any_message(lambda m, s: [s.downs.inc(), s.succ.set(0), ctx.watch_with(s.succ.ref, down(0)), B.same],
+                         test=lambda m: m.tag == DW_DOWN, when=lambda m, s: s.succ >= n - 1)
+         .on_any_message(lambda m, s: [s.downs.inc(), s.succ.inc(), ctx.watch_with(s.succ.ref, down(0)), B.same],
+                         test=lambda m: m.tag == DW_DOWN)
+         .on_any_message(lambda m, s: [B.unhandled])
+         .build("ring_member"))
+    tb = typed.compile_behaviors([b], max_emit=1)
+    init = np.zeros((n, 2), np.uint64)
+    init[:, 0] = (np.arange(n, dtype=np.uint64) + 1) % n
+    k = np.asarray(sorted(set(int(x) % n for x in kill)), np.uint32)
+    tells = (k, np.full(k.size, NO_SENDER, np.uint32), np.full(k.size, DW_STOP << 24, np.uint32)) if k.size else None
+    return Workload("watch_ring", n, 2, 1, throughput, 0, [(0, n, tb.kind_of(b), init)], behaviors=tb, tells=tells,
+                    bucket_actors=bucket_actors,
+                    watch={"n_slots": 1, "starts": [(0, n, None, 1, down.payload(0))]})

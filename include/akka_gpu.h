@@ -145,10 +145,24 @@ enum agx_action_op {
   AGX_A_TIMER_SINGLE = 6,     /* startSingleTimer(key, msg, delay)                                       */
   AGX_A_TIMER_PERIODIC = 7,   /* startTimerWithFixedDelay / startTimerAtFixedRate (they coincide: 2.3) */
   AGX_A_TIMER_CANCEL = 8,     /* cancel(key)                                                             */
-  AGX_A_TIMER_CANCEL_ALL = 9  /* cancelAll()                                                             */
+  AGX_A_TIMER_CANCEL_ALL = 9, /* cancelAll()                                                             */
+  /* Death watch actions (engines with death watch, agx_set_death_watch; AA/dungeon/DeathWatch.scala:19-113).
+   * The ref is the d-operand (dsrc, dword, dk), where a TELL has its destination: a ref based on the actor's
+   * own id wraps mod n_actors, as a TELL's does.  WATCH_WITH's custom message is the operand as a TELL's
+   * payload ((u32)operand, or (operand & 0xFFFFFF) | or_mask). */
+  AGX_A_WATCH = 10,      /* context.watch(ref)          (DeathWatch.scala:23-34)  */
+  AGX_A_WATCH_WITH = 11, /* context.watchWith(ref, msg) (DeathWatch.scala:36-47)  */
+  AGX_A_UNWATCH = 12     /* context.unwatch(ref)        (DeathWatch.scala:49-60)  */
 };
 #define AGX_TAG_TIMER 0xFFu     /* the message tag (payload >> 24) of a TimerMsg: reserved on an engine with timers */
 #define AGX_MAX_TIMER_KEYS 4u
+#define AGX_TAG_WATCH 0xFEu     /* the message tag of a Terminated envelope: reserved on an engine with death watch */
+#define AGX_MAX_WATCH_SLOTS 4u
+/* agx_case.result flag: the case is a signal case (typed receiveSignal).  Ordinary messages skip signal cases,
+ * signals try only them.  Inside a signal case the payload reads as AGX_SIGNAL_TERMINATED and AGX_V_SENDER is
+ * the terminated ref (TY/internal/adapter/ActorAdapter.scala:84-91,134-138). */
+#define AGX_CASE_SIGNAL 0x80u
+#define AGX_SIGNAL_TERMINATED 0xFE000001u
 typedef struct agx_case {
   uint8_t src1, word1, cmp1, src2; /* test 1: operand(src1, word1, k1) cmp1 operand(src2, word2, k2) */
   uint8_t word2, src3, word3, cmp2; /* test 2: operand(src3, word3, k3) cmp2 operand(src4, word4, k4) */
@@ -513,6 +527,65 @@ agx_status agx_timer_info(agx_engine* eng, uint64_t* fired, uint64_t* discarded,
  * none is to come.  Slots past n_keys read as zero (remaining 0xFFFFFFFF).  Any pointer may be NULL. */
 agx_status agx_read_timers(agx_engine* eng, uint64_t actor_id, uint32_t active[4], uint32_t remaining[4],
                            uint32_t period[4], uint32_t payload[4], uint32_t generation[4]);
+
+/* Death watch (context.watch / watchWith / unwatch and the Terminated signal: AA/dungeon/DeathWatch.scala:19-113,
+ * :147-162; typed adapter TY/internal/adapter/ActorAdapter.scala:84-91,134-138,200-205; pinned by
+ * WatchSpec.scala:54-85,196-362; DESIGN.md 2.4 has the contract).
+ * agx_set_death_watch gives every actor n_slots (1..4) watch slots.  Time is the timers' logical time: one
+ * superstep is one tick.  Every actor has a death tick, "none" while alive, set to the tick in which it stops;
+ * an id that was never registered counts as dead before tick 1, and so does any id outside [0, n_actors)
+ * (host-side actors cannot be watched in this version).
+ * A slot is free, watching, due or notified and holds the watchee, an optional custom message, and a
+ * generation (+1 at every occupation).  watch(x) / watchWith(x, m) by actor a: x == a is a no-op; a slot that
+ * holds x and is watching or due makes the same kind with the same message a no-op and anything else an
+ * IllegalStateException (checkWatchingSame): the rest of the case's actions is skipped, the message counts as
+ * delivered, the actor stops, `conflicts` grows; a notified slot holding x makes it a no-op; otherwise the lowest
+ * free slot becomes watching; with no free slot AGX_ECAPACITY is raised (sticky) and the watch is not recorded
+ * (the one bounded difference: the reference's `watching` map is unbounded).  unwatch(x) frees the slot in any
+ * state; a Terminated already enqueued is discarded at receipt, by generation.  A stop frees all the actor's
+ * slots; a become leaves them alone.
+ * At the end of every tick e each watching slot whose watchee's death tick is <= e - 1 becomes due (a death in
+ * e itself is never seen at the end of e); at the entry of tick e + 1 each due slot becomes notified and a
+ * Terminated envelope enters the watcher's own inbox, after the backlog, the arrivals and the host-staged
+ * tells, in slot order: sender = the watchee, payload = AGX_TAG_WATCH << 24 | slot << 22 | (generation mod
+ * 2^22).  It is admitted by position like any message (a dead letter in a full bounded mailbox; its slot then
+ * stays notified until unwatch or stop).  So a death at tick s reaches its watchers' inboxes at s + 2, and a
+ * watch at tick s of an actor that died before s is answered at s + 1.
+ * Receipt: a drained message with tag AGX_TAG_WATCH takes a drain slot and counts as delivered; if the slot is
+ * not notified or its generation differs it is discarded (`discarded`, not unhandled); otherwise the slot
+ * becomes free and, with a custom message, the ordinary cases run on it with AGX_V_SENDER = the watchee, else
+ * the signal cases (AGX_CASE_SIGNAL) run; if none matches that is the death pact: the actor stops,
+ * `death_pacts` grows (DeathPactException, ActorAdapter.scala:200-205).
+ * Conservation: staged + emitted + terminated = delivered + dead_letters + in_flight.  The engine is active at
+ * the entry of tick t iff mail is in flight, or a slot is due, or some actor stopped in tick t - 1 while at
+ * least one slot of the engine was watching at the end of t - 1; a run ends at the first tick at whose entry the
+ * engine is not active, and agx_run(n) lets exactly min(n, ticks until then) ticks pass.
+ * Tag AGX_TAG_WATCH is reserved: agx_stage_tells / agx_tell refuse it (AGX_EINVAL).
+ * Call before the first agx_run (AGX_ESTATE afterwards).  AGX_EINVAL: n_slots outside 1..4, n_ranks > 1, an
+ * engine with a CRDT kind, a priority table, a stash class or timers (either call order), an engine whose
+ * bounded-mailbox ring pool exists, max_emit > 1.  AGX_ENOMEM: the slots do not fit.  Such an engine uses no
+ * wave, ring, dense or persistent launch, and a bucket whose inbox -- backlog and the tick's Terminated
+ * envelopes included -- exceeds one 2048-message tile makes agx_run return AGX_ECAPACITY (sticky).  Tables with
+ * a watch action or a signal case on an engine without death watch make agx_run return AGX_EINVAL. */
+agx_status agx_set_death_watch(agx_engine* eng, uint32_t n_slots);
+/* The setup block (before the first run or between runs): actor first_id + i watches watchees[i], or
+ * (first_id + i + offset) mod n_actors when watchees is NULL; with_message != 0: watchWith(.., payload).
+ * Stopped actors are skipped; the rules are those of a device watch, conflicts included (a conflicting actor is
+ * stopped and counted).  A host start happens between ticks: a watchee that is dead by then makes the slot due
+ * at once, and its Terminated arrives in the next tick.  AGX_EINVAL on an engine without death watch (and the
+ * engine's agx_run then returns AGX_EINVAL too). */
+agx_status agx_start_watch(agx_engine* eng, uint64_t first_id, uint64_t count, const uint32_t* watchees, int64_t offset,
+                           int32_t with_message, uint32_t payload);
+/* Totals since agx_create: slots occupied by a watch, Terminated envelopes sent (those that died at admission
+ * included), envelopes discarded at receipt, death pacts, conflicts; right now: watching slots, pending (due)
+ * slots; and ticks: the supersteps that ran while the engine was active.  Any pointer may be NULL. */
+agx_status agx_watch_info(agx_engine* eng, uint64_t* watches, uint64_t* terminated, uint64_t* discarded,
+                          uint64_t* death_pacts, uint64_t* conflicts, uint64_t* watching, uint64_t* pending,
+                          uint64_t* ticks);
+/* One actor's watch slots (for tests and tools): state 0 free, 1 watching, 2 due, 3 notified, | 4 with a custom
+ * message.  Slots past n_slots read as zero.  Any pointer may be NULL. */
+agx_status agx_read_watch(agx_engine* eng, uint64_t actor_id, uint32_t watchee[4], uint32_t state[4], uint32_t payload[4],
+                          uint32_t generation[4]);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
