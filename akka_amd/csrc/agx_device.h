@@ -58,6 +58,10 @@ struct DevParams {
     // death watch (agx_set_death_watch), read and written only by the watch k_bucket_apply instantiations: the
     // per-actor watch slots, the death ticks and their bookkeeping (WatchDev below)
     uint32_t* watch;
+    // supervision (agx_set_supervision), read and written only by the supervision k_bucket_apply instantiations,
+    // and only for a message that fails or stops: the strategy entries, the per-actor restart counts and
+    // deadlines, the initial kinds and the counters (SuperDev below)
+    uint32_t* super;
   };
   uint32_t* heap_top;       // [2] rows allocated in heap[parity]
   const uint32_t* step;     // superstep counter (bumped by the first kernel of a step)
@@ -530,6 +534,8 @@ constexpr uint32_t kStashKM = 1u << 30;
 constexpr uint32_t kTimersKM = 1u << 29;
 // KM flag (not a kind): the variant knows death watch (agx_set_death_watch).  A flag of KM for the same reason.
 constexpr uint32_t kWatchKM = 1u << 28;
+// KM flag (not a kind): the variant knows supervision (agx_set_supervision).  A flag of KM for the same reason.
+constexpr uint32_t kSuperKM = 1u << 27;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -742,6 +748,151 @@ __device__ __forceinline__ uint32_t compiled_apply_w(const DevParams& P, const W
     return res;
   }
   return AGX_RES_UNHANDLED;
+}
+
+// ---- supervision (agx_set_supervision; TY/internal/Supervision.scala:43-52,128-160,311-406)
+// DevParams.super, u32 units:
+//   [0]        n_levels: strategy entries per behaviour (1..4)
+//   [1]        the behaviours the entry table covers
+//   [2]        the clock's base: tick = clock + 1 - base (host-written after every run: a tick is a superstep
+//              with mail, and the launches of a replay after quiescence advance the clocks, not the time)
+//   [4..11]    four u64 counters: failures, resumes, restarts, stops
+//   [kSvBucketOff + b]  clock: the launches bucket b has seen (every bucket sees every launch: all equal)
+//   then, 16-byte aligned: the entries, AGX_MAX_SUPERVISORS per behaviour (agx_supervisor, 8 words each),
+//   then level-major count[level][np] and deadline[level][np] (np = nb << bb actors; deadline 0: none),
+//   then init_kind[np], one byte per actor: the kind the actor was registered with.
+// Only an actor's own lane reads or writes its counts and deadlines, and only in sv_failed: a message that
+// neither fails nor stops touches none of this.
+constexpr uint32_t kSvBucketOff = 16;
+constexpr uint32_t kSvLevels = 0, kSvBeh = 1, kSvBase = 2, kSvCtr = 4;
+constexpr uint32_t kScFailures = 0, kScResumes = 1, kScRestarts = 2, kScStops = 3;
+constexpr uint32_t kSvEntWords = AGX_MAX_BEHAVIORS * AGX_MAX_SUPERVISORS * 8u;
+__host__ __device__ __forceinline__ size_t sv_ent_off(uint32_t nb) {
+  return ((size_t)kSvBucketOff + (size_t)nb + 3u) & ~(size_t)3;
+}
+struct SuperDev {
+  uint32_t* base;
+  uint32_t nb, np;
+  __device__ __forceinline__ uint32_t& clock(uint32_t b) const { return base[kSvBucketOff + b]; }
+  __device__ __forceinline__ uint32_t tick(uint32_t b) const { return clock(b) + 1u - base[kSvBase]; }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kSvCtr) + i;
+  }
+  __device__ __forceinline__ const agx_supervisor* entries(uint32_t beh) const {
+    return reinterpret_cast<const agx_supervisor*>(base + sv_ent_off(nb)) + (size_t)beh * AGX_MAX_SUPERVISORS;
+  }
+  __device__ __forceinline__ uint32_t* count(uint32_t lev, uint32_t l) const {
+    return base + sv_ent_off(nb) + kSvEntWords + (size_t)lev * np + l;
+  }
+  __device__ __forceinline__ uint32_t* deadline(uint32_t lev, uint32_t l) const {
+    return count(base[kSvLevels] + lev, l);
+  }
+  __device__ __forceinline__ uint32_t init_kind(uint32_t l) const {
+    return reinterpret_cast<const uint8_t*>(count(2u * base[kSvLevels], 0u))[l];
+  }
+};
+__device__ __forceinline__ SuperDev super_dev(uint32_t* base, uint32_t nb, uint32_t bb) {
+  return SuperDev{base, nb, nb << bb};
+}
+
+// compiled_apply of the supervision instantiations (agx_set_supervision): the same rule, with
+// signal cases (an ordinary message skips them, a signal tries only them) and the result AGX_RES_FAIL, whose
+// exception class (agx_case.next) is returned in `cls`.  A function of its own: every other instantiation
+// compiles compiled_apply as before.
+template <typename Emit>
+__device__ __forceinline__ uint32_t compiled_apply_s(const DevParams& P, uint32_t& kind, uint32_t self, uint64_t* w,
+                                                     uint32_t src, uint32_t pay, bool signal, uint32_t& cls, Emit& emit) {
+  const uint32_t b = kind - AGX_KIND_COMPILED;
+  if (b >= P.n_beh) return AGX_RES_UNHANDLED;
+  const uint32_t c1 = P.bfirst[b + 1];
+  for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
+    const agx_case C = P.bcase[c];
+    if (((C.result & AGX_CASE_SIGNAL) != 0u) != signal) continue;
+    if (!cb_cmp(C.cmp1, cb_operand(C.src1, C.word1, C.k1, pay, w, src, self),
+                cb_operand(C.src2, C.word2, C.k2, pay, w, src, self)))
+      continue;
+    if (!cb_cmp(C.cmp2, cb_operand(C.src3, C.word3, C.k3, pay, w, src, self),
+                cb_operand(C.src4, C.word4, C.k4, pay, w, src, self)))
+      continue;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      const agx_act A = P.bact[i];
+      const uint64_t v = cb_operand(A.src, A.sword, A.k, pay, w, src, self);
+      switch (A.op) {
+        case AGX_A_SET: w[A.word & 1u] = v; break;
+        case AGX_A_ADD: w[A.word & 1u] += v; break;
+        case AGX_A_MAX: w[A.word & 1u] = v > w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_MIN: w[A.word & 1u] = v < w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_TELL: {
+          uint64_t d;
+          if (A.dsrc == AGX_V_SELF) {  // (self + dk) mod n: ring neighbours
+            int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+            d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+          } else {
+            d = cb_operand(A.dsrc, A.dword, A.dk, pay, w, src, self);
+          }
+          emit(d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d, A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v);
+          break;
+        }
+        default: break;
+      }
+    }
+    const uint32_t res = C.result & ~AGX_CASE_SIGNAL;
+    if (res == AGX_RES_BECOME) {
+      kind = AGX_KIND_COMPILED + C.next;
+      return AGX_RES_SAME;
+    }
+    if (res == AGX_RES_FAIL) cls = C.next;
+    return res;
+  }
+  return AGX_RES_UNHANDLED;
+}
+
+// The cold path of the supervision drain: message handling of actor l (bucket b) ended in `res`, AGX_RES_FAIL of
+// exception class `cls` or AGX_RES_STOPPED.  Returns AGX_RES_SAME (resumed or restarted: the drain goes on, `kind`
+// and `w` are the actor's behaviour and state from here) or AGX_RES_STOPPED (PostStop has run).  Not inlined:
+// the common drain's register use must not grow by this.
+template <typename Emit>
+__device__ __noinline__ uint32_t sv_failed(const DevParams& P, uint32_t nb, uint32_t bb, uint32_t l, uint32_t b,
+                                           uint32_t& kind, uint32_t self, uint64_t* w, uint32_t res, uint32_t cls,
+                                           Emit& emit) {
+  const SuperDev SV = super_dev(P.super, nb, bb);
+  uint32_t none = 0;
+  if (res == AGX_RES_FAIL) {
+    atomicAdd(SV.ctr(kScFailures), 1ull);
+    const uint32_t ik = SV.init_kind(l), ib = ik - AGX_KIND_COMPILED, nl = SV.base[kSvLevels];
+    if (ik >= AGX_KIND_COMPILED && ib < SV.base[kSvBeh]) {
+      const agx_supervisor* const E = SV.entries(ib);
+      const uint32_t t = SV.tick(b);
+      for (uint32_t lev = 0; lev < nl; ++lev) {  // inner first
+        if (!((E[lev].class_mask >> (cls & 31u)) & 1u)) continue;
+        const uint32_t strat = E[lev].strategy;
+        if (strat == AGX_SUP_RESUME) {
+          atomicAdd(SV.ctr(kScResumes), 1ull);
+          return AGX_RES_SAME;
+        }
+        if (strat != AGX_SUP_RESTART) break;  // STOP
+        const uint32_t c = *SV.count(lev, l), d = *SV.deadline(lev, l);
+        const bool left = d == 0u || t <= d;
+        const int32_t mx = E[lev].max_restarts;
+        if (mx != -1 && c >= (uint32_t)mx && left) continue;  // rethrown: the next outer entry that catches it
+        if (kind >= AGX_KIND_COMPILED) compiled_apply_s(P, kind, self, w, self, AGX_SIGNAL_PRERESTART, true, none, emit);
+        *SV.count(lev, l) = left ? c + 1u : 1u;
+        *SV.deadline(lev, l) = (d != 0u && left) ? d : t + E[lev].within;
+        for (uint32_t in = 0; in < lev; ++in) {  // a restart re-creates the inner interceptors
+          *SV.count(in, l) = 0u;
+          *SV.deadline(in, l) = 0u;
+        }
+        kind = ik;
+        if (E[lev].reset_mask & 1u) w[0] = E[lev].reset[0];
+        if (E[lev].reset_mask & 2u) w[1] = E[lev].reset[1];
+        atomicAdd(SV.ctr(kScRestarts), 1ull);
+        return AGX_RES_SAME;
+      }
+    }
+  }
+  if (kind >= AGX_KIND_COMPILED) compiled_apply_s(P, kind, self, w, self, AGX_SIGNAL_POSTSTOP, true, none, emit);
+  atomicAdd(SV.ctr(kScStops), 1ull);
+  return AGX_RES_STOPPED;
 }
 
 // `kind` is the actor's current behaviour: a compiled behaviour's become updates it (the caller

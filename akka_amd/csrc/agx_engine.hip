@@ -166,6 +166,20 @@ struct agx_engine {
     std::vector<uint32_t> watchees;
   };
   std::vector<WatchStart> wd_starts;  // agx_start_watch calls not yet applied on the device (prepare_run)
+  // supervision (agx_set_supervision): strategy entries per compiled behaviour.  Such an engine launches the
+  // supervision instantiation of the compiled catch-all variant and no wave / ring / dense / persistent launch
+  bool sv_on = false;
+  uint32_t sv_levels = 0, sv_beh = 0;
+  uint32_t* d_super = nullptr;         // DevParams.super (agx_device.h SuperDev)
+  std::vector<agx_supervisor> sv_tab;  // [behaviour][AGX_MAX_SUPERVISORS], as on the device
+  std::vector<uint8_t> h_init;         // the kind every actor was registered with (empty without supervision)
+  bool sv_init_dirty = false;          // h_init is newer than the device's copy
+  bool beh_fail = false;               // the compiled tables hold an AGX_RES_FAIL case
+  bool beh_svsig = false;              // ... a PreRestart / PostStop signal case
+  bool beh_vstash = false;             // ... an AGX_V_STASH operand
+  uint32_t beh_sv_tells = 0;           // the most tells a failing or stopping case and a supervision signal case of one behaviour make together
+  uint64_t sv_ticks = 0;               // supersteps with mail so far (= agx_stats.supersteps)
+  uint32_t sv_clock = 0;               // the device clock after the last run (every bucket's launch count)
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -502,6 +516,7 @@ DevParams make_params(agx_engine* e) {
   if (e->stash_on) P.stash = e->d_stash;  // (the same slot: neither CRDT kinds nor priority tables with a stash)
   if (e->tm_keys) P.timers = e->d_timers;  // (the same slot: none of the three on an engine with timers)
   if (e->wd_slots) P.watch = e->d_watch;   // (the same slot: none of the four on an engine with death watch)
+  if (e->sv_on) P.super = e->d_super;      // (the same slot: none of the five on an engine with supervision)
   P.heap_top = e->d_heap_top;
   P.step = e->d_step;
   P.heap_rows = (uint32_t)e->heap_rows;
@@ -670,6 +685,7 @@ uint32_t apply_variant(const agx_engine* e) {
   if (e->stash_on) return V_ALL_COMPILED;  // deque-based mailboxes: the compiled catch-all carries the stash (kStash)
   if (e->tm_keys) return V_ALL_COMPILED;   // timers: the compiled catch-all carries them (kTimers)
   if (e->wd_slots) return V_ALL_COMPILED;  // death watch: the compiled catch-all carries it (kWatch)
+  if (e->sv_on) return V_ALL_COMPILED;     // supervision: the compiled catch-all carries it (kSuper)
   if (e->pw && e->delta_max) {  // delta-CRDT replication: the variants that carry the delta code
     if (km == kb(AGX_KIND_GCOUNTER)) return V_GC_DELTA;
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN_DELTA;
@@ -699,7 +715,7 @@ bool dense_on(const agx_engine* e, uint32_t vid) {
   // (k_dense_fused reads a fused bucket's table row one sender bucket per thread: nb <= 512, which
   // the fused superstep's <= 2^20 actors guarantee)
   if (e->fused && e->nb > (uint32_t)kDenseThreads) return false;
-  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots &&
+  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots && !e->sv_on &&
          (e->dense_launch == 1 || (e->dense_launch < 0 && vid == V_RING));
 }
 
@@ -883,7 +899,7 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
     }
     // (priority mailboxes: the wave path drains in arrival order -- every bucket takes the block launch)
     const bool tl = mode == M_BYPASS && !kVariants[vid].wide && e->tiny_launch && e->tiny_max && !e->skew_only &&
-                    !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots;
+                    !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots && !e->sv_on;
     if (tl) {  // wave-per-bucket launch first; the block launch then takes the buckets it marked
       ba.blist = e->d_blist;
       ba.dense_first = dl ? 1u : 0u;
@@ -909,6 +925,9 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       } else if (e->wd_slots) {
         if (mode == M_OWNER) return set_err(AGX_ESTATE, "death watch needs a single-rank engine");
         HIP_TRY(agx_launch_apply_watch(vid, mode, g, e->stream, bf));
+      } else if (e->sv_on) {
+        if (mode == M_OWNER) return set_err(AGX_ESTATE, "supervision needs a single-rank engine");
+        HIP_TRY(agx_launch_apply_super(vid, mode, g, e->stream, bf));
       } else {
         HIP_TRY(agx_launch_apply(vid, mode, false, g, e->stream, bf));
       }
@@ -947,7 +966,7 @@ agx_status launch_staged_chunk(agx_engine* e) {
 // behaviours, every configured mailbox class bounded by <= kRingMaxC); from then on the classes
 // are fixed (agx_set_mailbox_class refuses a capacity the rings cannot hold).
 agx_status setup_rings(agx_engine* e) {
-  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask || e->stash_on || e->tm_keys || e->wd_slots) return AGX_OK;  // (a ring drains in arrival order)
+  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask || e->stash_on || e->tm_keys || e->wd_slots || e->sv_on) return AGX_OK;  // (a ring drains in arrival order)
   uint32_t cmax = 0;
   for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) {
     if (!((e->mclass_set >> c) & 1u)) continue;
@@ -991,7 +1010,7 @@ agx_status setup_rings(agx_engine* e) {
 constexpr uint32_t kRingAutoC = 256;  // ring apply by default from this mailbox capacity up (setup_ring_apply)
 agx_status setup_ring_apply(agx_engine* e) {
   if (e->started || e->rg_on || e->ring_live || e->ring_res) return AGX_OK;
-  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask || e->stash_on || e->tm_keys || e->wd_slots) return AGX_OK;
+  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask || e->stash_on || e->tm_keys || e->wd_slots || e->sv_on) return AGX_OK;
   // AGX_RING_APPLY=1 / 0 forces rings on / off; unset: on when the largest bounded capacity is at
   // least kRingAutoC.  Deep queues are where re-copying the backlog every superstep costs most (C3,
   // BoundedMailbox(1000): 4.67e8 -> 6.7e8 msg/s with rings, the sparse buckets a wave each); at
@@ -1431,8 +1450,71 @@ agx_status watch_after_run(agx_engine* e) {
   return AGX_OK;
 }
 
+// ---- supervision (agx_set_supervision)
+agx_status read_counters(agx_engine* e, uint64_t* s);
+size_t super_words(const agx_engine* e) {
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  return sv_ent_off(e->nb) + kSvEntWords + 2ull * e->sv_levels * npad + (npad + 3ull) / 4ull;
+}
+
+// The supervision storage (agx_device.h SuperDev) -- sized by n_local: everything zero (no restart counted, no
+// deadline), then the levels and the entries
+agx_status alloc_super(agx_engine* e) {
+  if (!e->d_super) {
+    const size_t total = super_words(e);
+    if (hipMalloc((void**)&e->d_super, total * 4ull) != hipSuccess) {
+      (void)hipGetLastError();
+      e->d_super = nullptr;
+      return set_err(AGX_ENOMEM, "the supervision state of %llu actors (%u levels, %llu MB) does not fit on the device",
+                     (unsigned long long)((uint64_t)e->nb << e->bb), e->sv_levels, (unsigned long long)(total >> 18));
+    }
+    HIP_TRY(hipMemsetAsync(e->d_super, 0, total * 4ull, e->stream));
+    e->sv_init_dirty = true;
+    drop_graphs(e);  // (a kernel argument of the captured supersteps)
+  }
+  const uint32_t head[2] = {e->sv_levels, e->sv_beh};
+  HIP_TRY(hipMemcpyAsync(e->d_super, head, sizeof(head), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_super + sv_ent_off(e->nb), e->sv_tab.data(), e->sv_tab.size() * sizeof(agx_supervisor),
+                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return AGX_OK;
+}
+
+// the kinds the actors were registered with (before a run: registrations since the last upload)
+agx_status upload_super_init(agx_engine* e) {
+  if (!e->sv_init_dirty) return AGX_OK;
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  uint32_t* const at = e->d_super + sv_ent_off(e->nb) + kSvEntWords + 2ull * e->sv_levels * npad;
+  AGX_TRY(copy_sync(e, at, e->h_init.data(), e->n_local, hipMemcpyHostToDevice));
+  e->sv_init_dirty = false;
+  return AGX_OK;
+}
+
+// after a run: the ticks so far are the supersteps with mail; the launches of a replay after quiescence advanced
+// the clocks and not the time, so the clock's base follows (tick = clock + 1 - base)
+agx_status super_after_run(agx_engine* e) {
+  if (!e->d_super) return AGX_OK;
+  uint64_t s[kStatBlk];
+  AGX_TRY(read_counters(e, s));
+  e->sv_ticks = s[ST_STEPS] + e->host_steps;
+  AGX_TRY(copy_sync(e, &e->sv_clock, e->d_super + kSvBucketOff, 4, hipMemcpyDeviceToHost));
+  const uint32_t base = e->sv_clock - (uint32_t)e->sv_ticks;
+  return copy_sync(e, e->d_super + kSvBase, &base, 4, hipMemcpyHostToDevice);
+}
+
 // upload host mirrors / staged tells before a run
 agx_status prepare_run(agx_engine* e) {
+  if ((e->beh_fail || e->beh_svsig) && !e->sv_on)  // (only the supervision variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours fail (AGX_RES_FAIL) or hold a PreRestart / PostStop signal case, but "
+                   "the engine has no supervision (agx_set_supervision)");
+  if (e->sv_on && (e->beh_watch || e->beh_tm_keys || e->beh_stash || e->beh_vstash))
+    return set_err(AGX_EINVAL, "the compiled behaviours of an engine with supervision (agx_set_supervision) %s",
+                   e->beh_watch ? "watch, unwatch or hold a Terminated signal case: death watch needs an engine of its own"
+                   : e->beh_tm_keys ? "use timers: timers need an engine of their own"
+                                    : "stash, unstash_all or read the stash size: a stash needs an engine of its own");
+  if (e->sv_on && e->beh_sv_tells > e->kmax)
+    return set_err(AGX_EINVAL, "supervision: within one behaviour a case that fails or stops and the largest PreRestart / "
+                   "PostStop case tell %u times together, max_emit is %u", e->beh_sv_tells, e->kmax);
   if (e->wd_bad_start)
     return set_err(AGX_EINVAL, "agx_start_watch was called on an engine without death watch (agx_set_death_watch)");
   if (e->beh_watch && !e->wd_slots)  // (only the watch variant interprets those: loud, never wrong)
@@ -1479,6 +1561,7 @@ agx_status prepare_run(agx_engine* e) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->actors_dirty = false;
     e->wd_died_init = false;  // (actors registered since: their death ticks follow below)
+    e->sv_init_dirty = e->sv_on;  // (... their initial kinds)
     e->prio_dirty = e->prio_mask != 0;  // (mailboxes bound since: the per-bucket marks below)
     e->stash_dirty = e->stash_on;
   }
@@ -1490,6 +1573,10 @@ agx_status prepare_run(agx_engine* e) {
   if (e->wd_slots) {
     AGX_TRY(alloc_watch(e));
     AGX_TRY(flush_watch_starts(e));
+  }
+  if (e->sv_on) {
+    AGX_TRY(alloc_super(e));
+    AGX_TRY(upload_super_init(e));
   }
   if (e->prio_dirty) {  // priority tables and the buckets that hold an actor of a prioritised class
     std::vector<uint8_t> pb(e->prio_tab);  // tables, then the bucket marks (kPrioBucketOff)
@@ -1742,6 +1829,10 @@ agx_status error_status(const agx_engine* e, uint64_t err) {
     return set_err(AGX_ECAPACITY, "a bucket of %u actors of an engine with death watch received more than one tile of %d "
                    "messages (backlog and the tick's Terminated envelopes included): the launches for larger inboxes "
                    "know no death watch (smaller agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
+  if (err & kErrSuperTile)
+    return set_err(AGX_ECAPACITY, "a bucket of %u actors of an engine with supervision received more than one tile of %d "
+                   "messages (backlog included): the launches for larger inboxes know no supervision (smaller "
+                   "agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
   if (err & kErrWatchSlots)
     return set_err(AGX_ECAPACITY, "a watch found every one of its actor's %u watch slots taken: the watch is not recorded "
                    "(agx_set_death_watch; at most %u watched refs per actor)", e->wd_slots, AGX_MAX_WATCH_SLOTS);
@@ -1832,7 +1923,7 @@ bool persist_ok(agx_engine* e) {
       e->persist = (uint64_t)e->nb <= (uint64_t)per_cu * (uint64_t)ncu ? 1 : 0;
     (void)hipGetLastError();
   }
-  return e->persist == 1 && !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
+  return e->persist == 1 && !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots && !e->sv_on && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
          !e->recover_dense;
 }
 
@@ -2579,6 +2670,8 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
     return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with timers (agx_set_timers)");
   if (e->wd_slots)
     return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with death watch (agx_set_death_watch)");
+  if (e->sv_on)
+    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with supervision (agx_set_supervision)");
   if (e->stash_on)
     return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a deque-based mailbox "
                    "(agx_set_stash): a state gossip's snapshot row does not outlive its superstep in a stash");
@@ -2999,6 +3092,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_stash);
   hipFree(e->d_timers);
   hipFree(e->d_watch);
+  hipFree(e->d_super);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -3045,6 +3139,7 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
       l = id;
     }
     e->h_kind[l] = (uint8_t)kind;
+    if (!e->h_init.empty()) e->h_init[l] = (uint8_t)kind;  // (supervision: the kind a restart returns to)
     e->h_alive[l] = (uint8_t)((e->h_alive[l] & 0xFEu) | (kind != AGX_KIND_NONE ? 1u : 0u));  // (bits 1..3: mailbox class)
     for (uint32_t w = 0; w < e->W; ++w) {
       uint64_t v = 0;
@@ -3115,6 +3210,7 @@ agx_status agx_set_mailbox_priority(agx_engine* e, uint32_t cls, const uint8_t p
     return set_err(AGX_EINVAL, "priority mailboxes need an engine without a deque-based mailbox class (agx_set_stash)");
   if (e->tm_keys) return set_err(AGX_EINVAL, "priority mailboxes need an engine without timers (agx_set_timers)");
   if (e->wd_slots) return set_err(AGX_EINVAL, "priority mailboxes need an engine without death watch (agx_set_death_watch)");
+  if (e->sv_on) return set_err(AGX_EINVAL, "priority mailboxes need an engine without supervision (agx_set_supervision)");
   if (e->started) return set_err(AGX_ESTATE, "set mailbox priorities before the first agx_run");
   AGX_TRY(ensure_dev(e));
   if (prio) {
@@ -3141,6 +3237,7 @@ agx_status agx_set_stash(agx_engine* e, uint32_t cls, uint32_t capacity) {
     return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without priority tables (agx_set_mailbox_priority)");
   if (e->tm_keys) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without timers (agx_set_timers)");
   if (e->wd_slots) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without death watch (agx_set_death_watch)");
+  if (e->sv_on) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without supervision (agx_set_supervision)");
   if (cls >= AGX_MAX_MAILBOX_CLASSES || !((e->mclass_set >> cls) & 1u))
     return set_err(AGX_EINVAL, "mailbox class %u is not configured (agx_set_mailbox_class; classes 0..%u)", cls,
                    AGX_MAX_MAILBOX_CLASSES - 1);
@@ -3229,6 +3326,7 @@ agx_status agx_set_timers(agx_engine* e, uint32_t n_keys) {
   if (e->prio_mask) return set_err(AGX_EINVAL, "timers need an engine without priority tables (agx_set_mailbox_priority)");
   if (e->stash_on) return set_err(AGX_EINVAL, "timers need an engine without a deque-based mailbox class (agx_set_stash)");
   if (e->wd_slots) return set_err(AGX_EINVAL, "timers need an engine without death watch (agx_set_death_watch)");
+  if (e->sv_on) return set_err(AGX_EINVAL, "timers need an engine without supervision (agx_set_supervision)");
   if (e->kmax != 1)
     return set_err(AGX_EINVAL, "timers need max_emit = 1 (it is %u): the drain for more evaluates a case more than once, "
                    "and a timer action must take effect once", e->kmax);
@@ -3339,6 +3437,7 @@ agx_status agx_set_death_watch(agx_engine* e, uint32_t n_slots) {
   if (e->prio_mask) return set_err(AGX_EINVAL, "death watch needs an engine without priority tables (agx_set_mailbox_priority)");
   if (e->stash_on) return set_err(AGX_EINVAL, "death watch needs an engine without a deque-based mailbox class (agx_set_stash)");
   if (e->tm_keys) return set_err(AGX_EINVAL, "death watch needs an engine without timers (agx_set_timers)");
+  if (e->sv_on) return set_err(AGX_EINVAL, "death watch needs an engine without supervision (agx_set_supervision)");
   if (e->kmax != 1)
     return set_err(AGX_EINVAL, "death watch needs max_emit = 1 (it is %u): the drain for more evaluates a case more than "
                    "once, and a watch action must take effect once", e->kmax);
@@ -3436,6 +3535,92 @@ agx_status agx_read_watch(agx_engine* e, uint64_t actor_id, uint32_t watchee[4],
   return AGX_OK;
 }
 
+// TY/internal/Supervision.scala:43-52,128-160,311-406
+agx_status agx_set_supervision(agx_engine* e, const agx_supervisor* table, uint32_t n_behaviors, uint32_t n_levels) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!table || n_levels < 1u || n_levels > AGX_MAX_SUPERVISORS || n_behaviors < 1u || n_behaviors > AGX_MAX_BEHAVIORS)
+    return set_err(AGX_EINVAL, "supervision: %u levels (1..%u) for %u behaviours (1..%u)", n_levels, AGX_MAX_SUPERVISORS,
+                   n_behaviors, AGX_MAX_BEHAVIORS);
+  for (uint32_t i = 0; i < n_behaviors * n_levels; ++i) {
+    const agx_supervisor& S = table[i];
+    if (!S.class_mask) continue;  // (an unused entry)
+    if (S.strategy < AGX_SUP_RESUME || S.strategy > AGX_SUP_STOP || S.reset_mask > 3u ||
+        (S.strategy == AGX_SUP_RESTART && (S.max_restarts < -1 || S.within < 1u)))
+      return set_err(AGX_EINVAL, "supervision: bad entry %u of behaviour %u (a strategy, reset words 0..1, max_restarts >= -1, "
+                     "within >= 1 tick)", i % n_levels, i / n_levels);
+  }
+  if (e->R > 1) return set_err(AGX_EINVAL, "supervision needs a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
+  if (e->pw) return set_err(AGX_EINVAL, "supervision needs an engine without CRDT kinds (one is registered)");
+  if (e->prio_mask) return set_err(AGX_EINVAL, "supervision needs an engine without priority tables (agx_set_mailbox_priority)");
+  if (e->stash_on) return set_err(AGX_EINVAL, "supervision needs an engine without a deque-based mailbox class (agx_set_stash)");
+  if (e->tm_keys) return set_err(AGX_EINVAL, "supervision needs an engine without timers (agx_set_timers)");
+  if (e->wd_slots) return set_err(AGX_EINVAL, "supervision needs an engine without death watch (agx_set_death_watch)");
+  if (e->kmax != 1)
+    return set_err(AGX_EINVAL, "supervision needs max_emit = 1 (it is %u): the drain for more evaluates a case more than "
+                   "once, and a failure must take effect once", e->kmax);
+  if (e->ring_live || e->rg_on)
+    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, which know no "
+                   "supervision: set supervision before the first run", e->ring_live ? e->ring_c : e->rg_c);
+  if (e->started) return set_err(AGX_ESTATE, "set supervision before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  if (e->d_super && n_levels != e->sv_levels) {
+    hipFree(e->d_super);
+    e->d_super = nullptr;
+  }
+  e->sv_on = true;
+  e->sv_levels = n_levels;
+  e->sv_beh = n_behaviors;
+  e->sv_tab.assign((size_t)AGX_MAX_BEHAVIORS * AGX_MAX_SUPERVISORS, agx_supervisor{});
+  for (uint32_t b = 0; b < n_behaviors; ++b)
+    for (uint32_t k = 0; k < n_levels; ++k) e->sv_tab[(size_t)b * AGX_MAX_SUPERVISORS + k] = table[(size_t)b * n_levels + k];
+  e->h_init = e->h_kind;  // (before the first run the mirror holds the kinds the actors were registered with)
+  e->sv_init_dirty = true;
+  AGX_TRY(alloc_super(e));  // (now: AGX_ENOMEM is this call's)
+  drop_graphs(e);  // the variant and the supervision storage are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_supervision_info(agx_engine* e, uint64_t* failures, uint64_t* resumes, uint64_t* restarts, uint64_t* stops,
+                                uint64_t* ticks) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[4] = {0, 0, 0, 0};
+  if (e->d_super) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(copy_sync(e, c, e->d_super + kSvCtr, sizeof(c), hipMemcpyDeviceToHost));
+  }
+  if (failures) *failures = c[kScFailures];
+  if (resumes) *resumes = c[kScResumes];
+  if (restarts) *restarts = c[kScRestarts];
+  if (stops) *stops = c[kScStops];
+  if (ticks) *ticks = e->sv_ticks;
+  return AGX_OK;
+}
+
+agx_status agx_read_supervision(agx_engine* e, uint64_t actor_id, uint32_t* initial_kind, uint32_t count[4],
+                                uint32_t remaining[4]) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (actor_id >= e->n_global) return set_err(AGX_EINVAL, "bad actor id");
+  for (uint32_t k = 0; k < AGX_MAX_SUPERVISORS; ++k) {
+    if (count) count[k] = 0;
+    if (remaining) remaining[k] = 0xFFFFFFFFu;
+  }
+  if (initial_kind) *initial_kind = e->h_init.empty() ? 0u : e->h_init[actor_id];  // (single rank: local = global)
+  if (!e->d_super) return AGX_OK;
+  AGX_TRY(ensure_dev(e));
+  const uint64_t npad = (uint64_t)e->nb << e->bb, l = actor_id;
+  // the actor's column of count[level][actor], deadline[level][actor] in one strided copy
+  uint32_t col[2 * AGX_MAX_SUPERVISORS];
+  HIP_TRY(hipMemcpy2DAsync(col, 4, e->d_super + sv_ent_off(e->nb) + kSvEntWords + l, npad * 4ull, 4, 2ull * e->sv_levels,
+                           hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t k = 0; k < e->sv_levels; ++k) {
+    const uint32_t d = col[e->sv_levels + k];
+    if (count) count[k] = col[k];
+    if (remaining) remaining[k] = d == 0u ? 0xFFFFFFFFu : (uint64_t)d > e->sv_ticks ? (uint32_t)(d - e->sv_ticks) : 0u;
+  }
+  return AGX_OK;
+}
+
 agx_status agx_set_outbound(agx_engine* e, uint32_t first_host_id, uint32_t n_host, uint64_t capacity) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (n_host && (first_host_id < e->n_global || (uint64_t)first_host_id + n_host > (1ull << 31)))
@@ -3507,14 +3692,23 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   auto opnd_ok = [](uint32_t src, uint32_t word) {
     return src == AGX_V_TIMER ? word < AGX_MAX_TIMER_KEYS : src <= AGX_V_STASH && word <= 1u;
   };
+  // a supervision signal case (include/akka_gpu.h AGX_SIGNAL_PRERESTART): a signal case whose first test is
+  // payload == PreRestart / PostStop; every other signal case is death watch's
+  auto sv_signal = [](const agx_case& C) {
+    return (C.result & AGX_CASE_SIGNAL) && C.src1 == AGX_V_PAYLOAD && C.k1 == 0 && C.cmp1 == AGX_CMP_EQ &&
+           C.src2 == AGX_V_CONST && (C.k2 == (int64_t)AGX_SIGNAL_PRERESTART || C.k2 == (int64_t)AGX_SIGNAL_POSTSTOP);
+  };
   for (uint32_t c = 0; c < n_cases; ++c) {
     agx_case C = cases[c];
     if (C.result & AGX_CASE_SIGNAL) {  // a signal case (death watch): same, stopped, unhandled or become
       C.result &= (uint8_t)~AGX_CASE_SIGNAL;
-      if (C.result > AGX_RES_BECOME) return set_err(AGX_EINVAL, "compiled behaviours: signal case %u stashes or unstashes", c);
+      if (sv_signal(cases[c]) && C.result != AGX_RES_SAME)
+        return set_err(AGX_EINVAL, "compiled behaviours: PreRestart / PostStop signal case %u must end in same", c);
+      if (C.result > AGX_RES_BECOME) return set_err(AGX_EINVAL, "compiled behaviours: signal case %u stashes, unstashes or fails", c);
     }
     if (!opnd_ok(C.src1, C.word1) || !opnd_ok(C.src2, C.word2) || !opnd_ok(C.src3, C.word3) ||
-        !opnd_ok(C.src4, C.word4) || C.cmp1 > AGX_CMP_GE || C.cmp2 > AGX_CMP_GE || C.result > AGX_RES_UNSTASH_ALL ||
+        !opnd_ok(C.src4, C.word4) || C.cmp1 > AGX_CMP_GE || C.cmp2 > AGX_CMP_GE || C.result > AGX_RES_FAIL ||
+        (C.result == AGX_RES_FAIL && C.next >= AGX_MAX_EXCEPTION_CLASSES) ||
         (C.result == AGX_RES_BECOME && C.next >= n_beh) ||
         (C.result == AGX_RES_UNSTASH_ALL && C.next >= n_beh && C.next != AGX_NEXT_SAME) || (uint32_t)C.act_first + C.act_count > n_acts)
       return set_err(AGX_EINVAL, "compiled behaviours: bad case %u", c);
@@ -3554,9 +3748,32 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   AGX_TRY(copy_sync(e, e->d_bfirst, first, (n_beh + 1) * 4ull, hipMemcpyHostToDevice));
   e->n_beh = n_beh;
   e->beh_stash = false;
-  for (uint32_t c = 0; c < n_cases; ++c) e->beh_stash |= (cases[c].result & ~AGX_CASE_SIGNAL) >= AGX_RES_STASH;
+  e->beh_fail = e->beh_svsig = e->beh_vstash = false;  // (checked against agx_set_supervision at agx_run)
+  for (uint32_t c = 0; c < n_cases; ++c) {
+    const uint32_t r = cases[c].result & ~AGX_CASE_SIGNAL;
+    e->beh_stash |= r == AGX_RES_STASH || r == AGX_RES_UNSTASH_ALL;
+    e->beh_fail |= r == AGX_RES_FAIL;
+    e->beh_svsig |= sv_signal(cases[c]);
+    e->beh_vstash |= cases[c].src1 == AGX_V_STASH || cases[c].src2 == AGX_V_STASH || cases[c].src3 == AGX_V_STASH ||
+                     cases[c].src4 == AGX_V_STASH;
+  }
+  for (uint32_t i = 0; i < n_acts; ++i) e->beh_vstash |= acts[i].src == AGX_V_STASH || acts[i].dsrc == AGX_V_STASH;
+  // supervision: a failing or stopping case's tells and a PreRestart / PostStop case's tells share the message's slots
+  e->beh_sv_tells = 0;
+  for (uint32_t b = 0; b < n_beh; ++b) {
+    uint32_t fs = 0, sg = 0;
+    for (uint32_t c = first[b]; c < first[b + 1]; ++c) {
+      uint32_t tells = 0;
+      for (uint32_t i = cases[c].act_first; i < (uint32_t)cases[c].act_first + cases[c].act_count; ++i)
+        tells += acts[i].op == AGX_A_TELL;
+      const uint32_t r = cases[c].result & ~AGX_CASE_SIGNAL;
+      if (sv_signal(cases[c])) sg = std::max(sg, tells);
+      else if (r == AGX_RES_FAIL || r == AGX_RES_STOPPED) fs = std::max(fs, tells);
+    }
+    e->beh_sv_tells = std::max(e->beh_sv_tells, fs + sg);
+  }
   e->beh_watch = false;  // a watch action or a signal case (checked against agx_set_death_watch at agx_run)
-  for (uint32_t c = 0; c < n_cases; ++c) e->beh_watch |= (cases[c].result & AGX_CASE_SIGNAL) != 0;
+  for (uint32_t c = 0; c < n_cases; ++c) e->beh_watch |= (cases[c].result & AGX_CASE_SIGNAL) != 0 && !sv_signal(cases[c]);
   for (uint32_t i = 0; i < n_acts; ++i) e->beh_watch |= acts[i].op >= AGX_A_WATCH && acts[i].op <= AGX_A_UNWATCH;
   e->beh_tm_keys = 0;  // the timer keys the tables use (checked against agx_set_timers at agx_run)
   auto tm_use = [&](uint32_t src, uint32_t word) {
@@ -3867,6 +4084,7 @@ agx_status agx_run(agx_engine* e, uint32_t max_supersteps, agx_stats* out) {
     AGX_TRY(run_single(e, max_supersteps));
     AGX_TRY(timers_after_run(e));
     AGX_TRY(watch_after_run(e));
+    AGX_TRY(super_after_run(e));
   }
   prof_collect(e);
   if (e->ident_on && getenv("AGX_IDENT_DEBUG")) {  // diagnostic: the last superstep's slice summaries

@@ -58,6 +58,7 @@ constexpr uint64_t kErrStashTile = 16;  // a bucket with an actor of a stash cla
 constexpr uint64_t kErrTimerTile = 32;  // a bucket of an engine with timers exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrWatchTile = 64;  // a bucket of an engine with death watch exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrWatchSlots = 128;  // a watch found every slot of its actor taken (AGX_ECAPACITY)
+constexpr uint64_t kErrSuperTile = 256;  // a bucket of an engine with supervision exceeded one LDS tile (AGX_ECAPACITY)
 // per-block counters of k_bucket_apply: delivered, dead, unhandled, emitted, active
 constexpr int kBStats = 5;
 constexpr uint32_t kMaxApplyGrid = 4096;
@@ -1475,6 +1476,10 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     WD = watch_dev(P.watch, a.nb, a.bb, P.n_global);
     tnow = WD.clock(b) + 1u;
   }
+  // kSv: supervision (agx_set_supervision).  The drain knows AGX_RES_FAIL and the PreRestart /
+  // PostStop signals; a message that neither fails nor stops touches none of the supervision storage.
+  constexpr bool kSv = (KM & kSuperKM) != 0;
+  static_assert(!kSv || (kLds && !kWide && !kOwner && !kStash && !kTm && !kWd), "supervision: single-rank fast launches, plain behaviours");
   uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
   auto ikey = [&](uint32_t q) -> uint32_t { return kLds ? L.key[q] : a.scr.key[lo + q]; };
@@ -2070,6 +2075,38 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           }
         }
         if (ndisc) atomicAdd(WD.ctr(kWcDiscarded), (unsigned long long)ndisc);
+      } else if constexpr (kSv) {
+        // the drain under the supervisor (Supervision.scala:122-126): a failure or a stop takes the cold path,
+        // which resumes, restarts (the drain goes on under the restarted behaviour: the mailbox survives) or
+        // stops the actor after PostStop
+        for (uint32_t q = 0; q < nd; ++q) {
+          const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          uint32_t cls = 0;
+          uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_s(P, kcur, self, wv, sv, pv, false, cls, em)
+                                                 : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          ++ndel;
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (__builtin_expect(r == AGX_RES_FAIL || r == AGX_RES_STOPPED, 0)) {
+            // (copies: what the call takes by address lives in memory, and the drain's own state must stay in registers)
+            DevParams Pl = P;  // (the kernel's own arguments included: their copy is made here, on the cold path only)
+            EmitterLds em2 = em;
+            em2.P = &Pl;
+            uint64_t w2[2] = {wv[0], wv[1]};
+            uint32_t k2 = kcur;
+            r = sv_failed(Pl, a.nb, a.bb, l, b, k2, self, w2, r, cls, em2);
+            em = em2;
+            em.P = &P;
+            wv[0] = w2[0];
+            wv[1] = w2[1];
+            kcur = k2;
+          }
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            break;
+          }
+        }
       } else
       for (uint32_t q = 0; q < nd; ++q) {
         const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
@@ -2146,6 +2183,8 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     }
     if constexpr (kTm) timer_tick_end<kGather>(a, TD, b, a0, na, tnow, bltot, w, L.alive, L.scratch);
     if constexpr (kWd) watch_tick_end(a, WD, b, a0, na, tnow, bltot, w, kGather, L.scratch);
+    if constexpr (kSv)  // (after the barrier: every drain of the bucket has read this launch's clock)
+      if (tid == 0) P.super[kSvBucketOff + b] += 1u;
     AGX_STAMP(a, 5);
     {  // exclusive scan of tell counts in actor (= sender) order
       uint32_t ec[kBAct], run = 0;
@@ -4471,6 +4510,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
   // tick (its clock is the tick count), and a bucket never takes the skew launch.
   constexpr bool kWd = (KM & kWatchKM) != 0;  // (a flag of KM: agx_device.h)
   static_assert(!kWd || (!kWide && !kSkew && !kOwner && !kPrio && !kStash && !kTm), "death watch: single-rank fast launches, plain behaviours");
+  // kSv: supervision (agx_set_supervision) -- the same launches of an engine with supervision.
+  // The inbox is the plain one; every bucket counts every launch (its clock), and a bucket never takes the
+  // skew launch.
+  constexpr bool kSv = (KM & kSuperKM) != 0;  // (a flag of KM: agx_device.h)
+  static_assert(!kSv || (!kWide && !kSkew && !kOwner && !kPrio && !kStash && !kTm && !kWd), "supervision: single-rank fast launches, plain behaviours");
   if (kOwner && a.halt && a.halt[0]) return;  // (device-resident multi-rank replay stopped)
   // key/src/pay carved from one array: group_tells reuses key+src as a 16 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t s_ksp[3 * kBucket];
@@ -4564,6 +4608,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
       if (tid == 0) s_flags = 2u;
     if constexpr (kWd)  // (nor is a watch drain)
       if (tid == 0) s_flags = 2u;
+    if constexpr (kSv)  // (nor is a supervised drain)
+      if (tid == 0) s_flags = 2u;
     for (uint32_t d = tid; d < kRadix; d += kBThreads) s_nh[d] = 0;
     uint32_t* my_tc = nullptr;  // (fused) this thread's table entry, zeroed once the bucket is processed
     // fused fast path, plain behaviours: state words 0 / 1 of the bucket's actors are loaded here,
@@ -4616,6 +4662,12 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
                 s_lo = s_hi = 0u;
                 s_rowtop = 0u;
                 __hip_atomic_store(&P.watch[kWdBucketOff + a.nb + b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (the end of the tick moves the due slots on)
+              }
+            }
+            if constexpr (kSv) {
+              if (s_hi - s_lo > (uint32_t)kBucket) {  // the skew launches know no supervision: loud, the bucket's mail dropped
+                atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrSuperTile);
+                s_lo = s_hi = 0u;
               }
             }
           }
@@ -4714,6 +4766,12 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
             __hip_atomic_store(&P.watch[kWdBucketOff + a.nb + b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (the end of the tick moves the due slots on)
           }
         }
+        if constexpr (kSv) {
+          if (blc + tt + s_g[2] > (uint32_t)kBucket) {  // the skew launches know no supervision: loud, the bucket's mail dropped
+            atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrSuperTile);
+            tt = 0u - blc - s_g[2];  // (cnt = 0 below)
+          }
+        }
         const uint32_t cnt = blc + tt + s_g[2];
         s_g[5] = cnt > (uint32_t)kBucket;
         if constexpr (kPrio)  // (as the multi-pass launch above)
@@ -4801,6 +4859,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         watch_tick_end(a, WD, b, a0, na, WD.clock(b) + 1u, 0u, wpar, kGather, scratch);
         __syncthreads();
       }
+      if constexpr (kSv)  // (a launch without mail for this bucket: the clock all the same)
+        if (tid == 0) P.super[kSvBucketOff + b] += 1u;
       continue;
     }
     // bypass: inbox item q < xblc is backlog item q (g.bl[rpar] at xblo + q), else sorted item xbst + q - xblc

@@ -286,6 +286,36 @@ class GpuEngine:
         check(self.lib.agx_read_watch(self._h, actor_id, *(_ptr(x, ctypes.c_uint32) for x in a)))
         return dict(zip(("watchee", "state", "payload", "generation"), a))
 
+    def set_supervision(self, rows) -> None:
+        """agx_set_supervision: `rows[b]` are compiled behaviour b's supervisor entries (typed.AgxSupervisor, inner
+        first, at most 4; typed.Tables.supervisors has them): Behaviors.supervise(..).onFailure(strategy)
+        (TY/internal/Supervision.scala:43-52,311-406).  Compiled cases may then end in Behaviors.throw(exc), and
+        PreRestart / PostStop signal cases run."""
+        from .typed import AgxSupervisor
+        rows = [list(r) for r in rows]
+        n_levels = max([len(r) for r in rows] + [1])  # (a row without entries: no supervisor, every failure stops)
+        arr = (AgxSupervisor * max(len(rows) * n_levels, 1))()
+        for b, r in enumerate(rows):
+            for k, s in enumerate(r):
+                arr[b * n_levels + k] = s
+        check(self.lib.agx_set_supervision(self._h, ctypes.cast(arr, ctypes.c_void_p), len(rows), n_levels))
+
+    SUPERVISION_INFO = ("failures", "resumes", "restarts", "stops", "ticks")
+
+    def supervision_info(self) -> dict:
+        """agx_supervision_info: totals failures / resumes / restarts / stops, and the ticks (supersteps with mail)."""
+        v = [ctypes.c_uint64() for _ in range(5)]
+        check(self.lib.agx_supervision_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(self.SUPERVISION_INFO, (int(x.value) for x in v)))
+
+    def read_supervision(self, actor_id: int) -> dict:
+        """agx_read_supervision: one actor's initial kind and, per level, the restart count and the ticks left of
+        the window (0xFFFFFFFF: no deadline)."""
+        kind = ctypes.c_uint32()
+        a = [np.zeros(4, np.uint32) for _ in range(2)]
+        check(self.lib.agx_read_supervision(self._h, actor_id, ctypes.byref(kind), *(_ptr(x, ctypes.c_uint32) for x in a)))
+        return dict(initial_kind=int(kind.value), count=a[0], remaining=a[1])
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""

@@ -20,6 +20,11 @@ What lowers:
     ``buffer.unstash_all(behavior)`` as its result releases the buffered messages into `behavior`,
     ``buffer.size`` / ``is_empty`` / ``is_full`` are usable in tests and values; the actors' mailbox class
     carries the capacity (``Tables.stash_capacity`` -> engine.set_stash);
+  * ``Behaviors.supervise(behavior, reset={field: value}).on_failure(strategy, exc=...)`` (TY/internal/
+    Supervision.scala:43-52,311-406), nestable, with ``SupervisorStrategy.resume / stop / restart /
+    restart.with_limit(n, within)``; a case may end in ``Behaviors.throw(exc)``, ``ExceptionType(name, parent)``
+    declares the classes, and ``on_signal(PreRestart | PostStop, ...)`` handles the two signals
+    (``Tables.supervisors`` -> engine.set_supervision);
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -56,6 +61,11 @@ SIGNAL_TERMINATED = 0xFE000001  # what the payload reads as inside a signal case
 RES_SAME, RES_STOPPED, RES_UNHANDLED, RES_BECOME, RES_STASH, RES_UNSTASH_ALL = 0, 1, 2, 3, 4, 5
 NEXT_SAME = 0xFF  # agx_case.next of RES_UNSTASH_ALL: the behaviour stays
 MAX_STASH = 255
+RES_FAIL = 6         # the handler throws; agx_case.next is the exception class (engines with supervision)
+MAX_EXCEPTION_CLASSES = 32
+MAX_SUPERVISORS = 4
+SIGNAL_PRERESTART, SIGNAL_POSTSTOP = 0xFE000002, 0xFE000003
+SUP_RESUME, SUP_RESTART, SUP_STOP = 1, 2, 3
 
 
 class AgxCase(ctypes.Structure):
@@ -74,7 +84,14 @@ class AgxAct(ctypes.Structure):
                 ("or_mask", ctypes.c_uint32), ("k", ctypes.c_int64), ("dk", ctypes.c_int64)]
 
 
-assert ctypes.sizeof(AgxCase) == 48 and ctypes.sizeof(AgxAct) == 32
+class AgxSupervisor(ctypes.Structure):
+    """include/akka_gpu.h agx_supervisor (32 B)."""
+    _fields_ = [("class_mask", ctypes.c_uint32), ("strategy", ctypes.c_uint8), ("reset_mask", ctypes.c_uint8),
+                ("pad0", ctypes.c_uint8), ("pad1", ctypes.c_uint8), ("max_restarts", ctypes.c_int32),
+                ("within", ctypes.c_uint32), ("reset", ctypes.c_uint64 * 2)]
+
+
+assert ctypes.sizeof(AgxCase) == 48 and ctypes.sizeof(AgxAct) == 32 and ctypes.sizeof(AgxSupervisor) == 32
 
 
 class CompileError(ValueError):
@@ -393,11 +410,132 @@ class Terminated:
     ref = Ref(Operand(V_SENDER))
 
 
+class PreRestart:
+    """The PreRestart signal (TY/MessageAndSignals.scala): it runs on the failing behaviour before a restart."""
+    code = SIGNAL_PRERESTART
+
+
+class PostStop:
+    """The PostStop signal: it runs on the current behaviour at every stop of the actor."""
+    code = SIGNAL_POSTSTOP
+
+
+class ExceptionType:
+    """An exception class a handler may throw (Behaviors.throw) and a supervisor may catch (on_failure).  `parent`
+    defaults to Throwable, the root; a supervisor of a class catches it and its descendants, so the root catches
+    all.  The lowering numbers the classes used (at most 32) and flattens the hierarchy into masks."""
+
+    def __init__(self, name: str, parent: "ExceptionType | None" = None):
+        if parent is not None and not isinstance(parent, ExceptionType):
+            raise CompileError(f"not an ExceptionType: {parent!r}")
+        self.name = name
+        self.parent = parent if parent is not None else getattr(ExceptionType, "root", None)
+
+    def is_a(self, other: "ExceptionType") -> bool:
+        x = self
+        while x is not None:
+            if x is other:
+                return True
+            x = x.parent
+        return False
+
+    def __repr__(self):
+        return f"ExceptionType({self.name})"
+
+
+ExceptionType.root = Throwable = ExceptionType("Throwable")
+
+
+@dataclass(frozen=True, eq=False)
+class _Throw:
+    """Behaviors.throw(exc) as a case's result."""
+    exc: ExceptionType
+
+
+@dataclass(frozen=True)
+class _Strategy:
+    """A SupervisorStrategy value (TY/SupervisorStrategy.scala): resume, stop, restart [with a limit]."""
+    kind: int
+    max_restarts: int = -1
+    within: int = 1
+
+
+class _Restart(_Strategy):
+    def with_limit(self, max_restarts: int, within: int) -> _Strategy:
+        """restart.withLimit(maxNrOfRetries, withinTimeRange): `within` in ticks (supersteps with mail), >= 1."""
+        if not isinstance(max_restarts, int) or max_restarts < 0:
+            raise CompileError(f"with_limit: max_restarts is an integer >= 0, not {max_restarts!r}")
+        if not isinstance(within, int) or not 1 <= within <= MAX_TIMER_DELAY:
+            raise CompileError(f"with_limit: within is a number of ticks >= 1, not {within!r}")
+        return _Strategy(SUP_RESTART, max_restarts, within)
+
+
+class SupervisorStrategy:
+    """SupervisorStrategy.resume / stop / restart / restart.with_limit(n, within).  restartWithBackoff is left out
+    (it needs a stash and a timer), and so are children (stopChildren) and logging."""
+    resume = _Strategy(SUP_RESUME)
+    stop = _Strategy(SUP_STOP)
+    restart = _Restart(SUP_RESTART)
+
+
+@dataclass(eq=False)
+class _Supervisor:
+    strategy: _Strategy
+    exc: ExceptionType
+    reset: dict  # state word -> value
+
+
+class _Supervise:
+    """Behaviors.supervise(behavior): the wrapper waiting for on_failure."""
+
+    def __init__(self, behavior: "Behavior", reset: dict):
+        self.behavior, self.reset = behavior, reset
+
+    def on_failure(self, strategy, exc: ExceptionType | None = None) -> "Behavior":
+        """onFailure[exc](strategy): returns the behaviour, supervised; supervise it again for an outer supervisor."""
+        if not isinstance(strategy, _Strategy):
+            raise CompileError(f"not a SupervisorStrategy: {strategy!r}")
+        exc = Throwable if exc is None else exc
+        if not isinstance(exc, ExceptionType):
+            raise CompileError(f"not an ExceptionType: {exc!r}")
+        if len(self.behavior.supervisors) >= MAX_SUPERVISORS:
+            raise CompileError(f"a behaviour has at most {MAX_SUPERVISORS} nested supervisors")
+        self.behavior.supervisors.append(_Supervisor(strategy, exc, self.reset))
+        return self.behavior
+
+
 class Behaviors:
-    """Behaviors.same / stopped / unhandled (TY/scaladsl/Behaviors.scala), receiveMessage, withStash, withTimers."""
+    """Behaviors.same / stopped / unhandled (TY/scaladsl/Behaviors.scala), receiveMessage, withStash, withTimers,
+    supervise and throw."""
     same = _Result(RES_SAME, "same")
     stopped = _Result(RES_STOPPED, "stopped")
     unhandled = _Result(RES_UNHANDLED, "unhandled")
+
+    @staticmethod
+    def throw(exc: ExceptionType) -> _Throw:
+        """`throw new Exc` as a case's result: the case's effects are those before the throw; the actors need an
+        engine with supervision (engine.set_supervision(tables.supervisors))."""
+        if not isinstance(exc, ExceptionType):
+            raise CompileError(f"not an ExceptionType: {exc!r}")
+        return _Throw(exc)
+
+    @staticmethod
+    def supervise(behavior: "Behavior", reset: dict | None = None) -> _Supervise:
+        """Behaviors.supervise(behavior).on_failure(strategy, exc=...) (TY/internal/Supervision.scala:43-52),
+        nestable (the first is the innermost).  `reset`: {field: value} -- the state a restart re-creates; the
+        other fields model constructor arguments and stay.  Only an actor's initial behaviour can be supervised."""
+        if not isinstance(behavior, Behavior):
+            raise CompileError("supervise takes a Behavior")
+        words = {}
+        for f, v in (reset or {}).items():
+            if isinstance(f, str):
+                f = getattr(behavior.state, f, None)
+            if not isinstance(f, Field):
+                raise CompileError("reset maps state fields to values")
+            if not isinstance(v, (int, np.integer)) or not 0 <= int(v) < (1 << 64):
+                raise CompileError(f"a reset value is a u64 constant, not {v!r}")
+            words[f.word] = int(v)
+        return _Supervise(behavior, words)
 
     @staticmethod
     def with_stash(capacity: int, factory) -> "Behavior":
@@ -433,10 +571,11 @@ class Behaviors:
         return b
 
     @staticmethod
-    def receive_signal(behavior: "Behavior", handler, when=None) -> "Behavior":
+    def receive_signal(behavior: "Behavior", handler, when=None, signal=None) -> "Behavior":
         """behavior.receiveSignal { case (_, Terminated(ref)) => ... }: `handler(sig, state)` is appended to
-        `behavior` as a Terminated signal case (ReceiveBuilder.on_signal has the rules); returns `behavior`."""
-        rb = ReceiveBuilder.create(behavior.state).on_signal(Terminated, handler, when)
+        `behavior` as a signal case of `signal` (Terminated unless given; PreRestart, PostStop) -- the rules are
+        ReceiveBuilder.on_signal's; returns `behavior`."""
+        rb = ReceiveBuilder.create(behavior.state).on_signal(Terminated if signal is None else signal, handler, when)
         behavior.cases = list(behavior.cases) + rb.cases
         return behavior
 
@@ -456,6 +595,7 @@ class _Case:
     effects: list
     result: object  # _Result, Behavior, _StashEffect (stash, then same) or _UnstashAll
     signal: bool = False  # a signal case (on_signal): ordinary messages skip it, signals try only these
+    sig_code: int = 0     # SIGNAL_PRERESTART / SIGNAL_POSTSTOP: a supervision signal case (0: Terminated)
 
 
 @dataclass(eq=False)
@@ -465,6 +605,7 @@ class Behavior:
     cases: list = field(default_factory=list)
     timers: object = None  # the TimerScheduler of the with_timers block the behaviour was built in
     initial_timers: list = field(default_factory=list)  # with_timers' setup starts: (key, periodic, delay, payload)
+    supervisors: list = field(default_factory=list)     # Behaviors.supervise(..).on_failure(..), inner first
 
 
 class ReceiveBuilder:
@@ -488,9 +629,9 @@ class ReceiveBuilder:
         effects, result = list(out[:-1]), out[-1]
         if isinstance(result, _StashEffect):
             raise CompileError("buffer.stash() is an effect: end the case with Behaviors.same")
-        if not isinstance(result, (_Result, Behavior, _UnstashAll)):
-            raise CompileError("a handler's last element must be Behaviors.same/stopped/unhandled, a Behavior "
-                               "or buffer.unstash_all(...)")
+        if not isinstance(result, (_Result, Behavior, _UnstashAll, _Throw)):
+            raise CompileError("a handler's last element must be Behaviors.same/stopped/unhandled, a Behavior, "
+                               "buffer.unstash_all(...) or Behaviors.throw(...)")
         if effects and isinstance(effects[-1], _StashEffect):  # the message is kept: the behaviour stays
             if isinstance(result, _UnstashAll):
                 raise CompileError("a case cannot stash its message and unstash_all")
@@ -523,8 +664,22 @@ class ReceiveBuilder:
         """onSignal(Terminated.class, handler) (:104-122): `handler(sig, state)` sees `sig.ref`, the terminated
         ref; `when` guards on the signal and the state.  Only Terminated is a signal of the compiled subset.  A
         signal case neither stashes nor uses timers."""
+        if signal is PreRestart or signal is PostStop:
+            # a supervision signal: the first test is payload == the signal (how the engine tells it from Terminated)
+            n = len(self.cases)
+            self._add([Incoming.payload == signal.code], lambda m, s: handler(signal, s),
+                      (lambda m, s: when(signal, s)) if when is not None else None)
+            c = self.cases[n]
+            if c.result is not Behaviors.same:
+                raise CompileError("a PreRestart / PostStop case ends with Behaviors.same (the restart or the stop follows)")
+            if any(e.op > A_TELL for e in c.effects) or \
+                    any(o.src in (V_TIMER, V_STASH) for t in c.tests for o in (t.lhs, t.rhs)):
+                raise CompileError("a PreRestart / PostStop case cannot use timers, death watch or the stash "
+                                   "(supervision shares an engine with none of them)")
+            c.signal, c.sig_code = True, signal.code
+            return self
         if signal is not Terminated:
-            raise CompileError("the only signal of compiled behaviours is Terminated")
+            raise CompileError("the signals of compiled behaviours are Terminated, PreRestart and PostStop")
         n = len(self.cases)
         self._add([], lambda m, s: handler(Terminated, s), (lambda m, s: when(Terminated, s)) if when is not None else None)
         c = self.cases[n]
@@ -562,6 +717,14 @@ class Tables:
     acts: ctypes.Array
     first: np.ndarray
     n_acts: int = 0
+    supervisors: list = field(default_factory=list)  # per behaviour: its AgxSupervisor entries, inner first
+    exception_classes: list = field(default_factory=list)  # the ExceptionTypes in use; the index is the class number
+
+    @property
+    def uses_supervision(self) -> bool:
+        """A behaviour is supervised, throws or holds a PreRestart / PostStop case: the engine needs
+        engine.set_supervision(tables.supervisors)."""
+        return any(self.supervisors) or any(c.sig_code or isinstance(c.result, _Throw) for b in self.behaviors for c in b.cases)
 
     @property
     def n_behaviors(self) -> int:
@@ -593,7 +756,7 @@ class Tables:
     @property
     def uses_watch(self) -> bool:
         """The behaviours watch, unwatch or hold a signal case: the engine needs engine.set_death_watch(n)."""
-        return any(c.signal for b in self.behaviors for c in b.cases) or \
+        return any(c.signal and not c.sig_code for b in self.behaviors for c in b.cases) or \
             any(A_WATCH <= a.op <= A_UNWATCH for a in self.acts[:self.n_acts])
 
     @property
@@ -633,6 +796,15 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
     if len(behs) > MAX_BEHAVIORS:
         raise CompileError(f"more than {MAX_BEHAVIORS} behaviours")
     index = {id(b): i for i, b in enumerate(behs)}
+    # the exception classes in use, numbered in order of appearance: thrown ones first, then the supervisors'
+    excs = []
+    for x in [c.result.exc for b in behs for c in b.cases if isinstance(c.result, _Throw)] + \
+            [sv.exc for b in behs for sv in b.supervisors if sv.exc is not Throwable]:  # (the root: every bit)
+        if not any(x is y for y in excs):
+            excs.append(x)
+    if len(excs) > MAX_EXCEPTION_CLASSES:
+        raise CompileError(f"more than {MAX_EXCEPTION_CLASSES} exception classes")
+    exc_id = {id(x): i for i, x in enumerate(excs)}
     cases, acts, first = [], [], [0]
     for b in behs:
         for c in b.cases:
@@ -644,6 +816,8 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
                 code, nxt = RES_STASH, 0
             elif isinstance(res, _UnstashAll):
                 code, nxt = RES_UNSTASH_ALL, (index[id(res.target)] if isinstance(res.target, Behavior) else NEXT_SAME)
+            elif isinstance(res, _Throw):
+                code, nxt = RES_FAIL, exc_id[id(res.exc)]
             else:
                 code, nxt = res.code, 0
             if c.signal:
@@ -664,6 +838,39 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
         raise CompileError("tables too large")
     t = Tables(behs, (AgxCase * max(len(cases), 1))(*cases), (AgxAct * max(len(acts), 1))(*acts),
                np.asarray(first, dtype=np.uint32), len(acts))
+    t.exception_classes = excs
+    for b in behs:  # a supervisor of a class catches it and its descendants: the hierarchy as masks
+        row = []
+        for sv in b.supervisors:
+            mask = 0xFFFFFFFF if sv.exc is Throwable else sum(1 << i for i, x in enumerate(excs) if x.is_a(sv.exc))
+            e = AgxSupervisor(class_mask=mask, strategy=sv.strategy.kind, max_restarts=sv.strategy.max_restarts,
+                              within=sv.strategy.within)
+            if sv.strategy.kind == SUP_RESTART:
+                for w, v in sv.reset.items():
+                    e.reset_mask |= 1 << w
+                    e.reset[w] = v
+            row.append(e)
+        t.supervisors.append(row)
+    if t.uses_supervision:
+        if t.uses_watch or t.timer_keys or t.stash_capacity or \
+                any(V_STASH in (a.src, a.dsrc) for a in acts) or \
+                any(V_STASH in (c.src1, c.src2, c.src3, c.src4) for c in cases):
+            raise CompileError("supervision shares an engine with neither death watch, timers nor a stash: the behaviours "
+                               "use supervision and one of them")
+        if max_emit is not None and max_emit > 1:
+            raise CompileError(f"supervision needs max_emit = 1, not {max_emit}")
+        for b in behs:
+            if b.supervisors and any(c.result is b for x in behs if x is not b for c in x.cases):
+                raise CompileError(f"behaviour {b.name!r} is supervised and reached by become: only an actor's initial "
+                                   "behaviour can be supervised")
+        for i, b in enumerate(behs):  # a failing or stopping case and a signal case share the message's tell slot
+            tells = lambda c: sum(1 for j in range(c.act_first, c.act_first + c.act_count) if acts[j].op == A_TELL)
+            fs = max((tells(cases[first[i] + j]) for j, c in enumerate(b.cases)
+                      if not c.sig_code and (isinstance(c.result, _Throw) or c.result is Behaviors.stopped)), default=0)
+            sg = max((tells(cases[first[i] + j]) for j, c in enumerate(b.cases) if c.sig_code), default=0)
+            if fs + sg > 1:
+                raise CompileError(f"behaviour {b.name!r}: a case that fails or stops and the largest PreRestart / PostStop "
+                                   f"case tell {fs + sg} times together; an engine with supervision has max_emit 1")
     if t.timer_keys:  # tag 0xFF is the TimerMsg's: no message type of these behaviours may carry it
         for a in acts:
             if a.or_mask >> 24 == TAG_TIMER:

@@ -55,6 +55,9 @@ class Workload:
     # death watch (agx_set_death_watch / agx_start_watch): {"n_slots": k, "starts": [(first, count, watchees or
     # None, offset, message or None)]} -- empty: no death watch
     watch: dict = field(default_factory=dict)
+    # supervision (agx_set_supervision): {"rows": per compiled behaviour its supervisor entries, inner first
+    # (typed.Tables.supervisors)} -- empty: no supervision
+    supervision: dict = field(default_factory=dict)
 
     def engine_kwargs(self) -> dict:
         """Semantic parameters (shared by the GPU engine and the CPU oracles)."""
@@ -94,6 +97,8 @@ class Workload:
             target.set_death_watch(self.watch["n_slots"])
             for first, count, watchees, offset, message in self.watch.get("starts", ()):
                 target.start_watch(first, count, watchees, offset=offset, message=message)
+        if self.supervision:  # (empty: targets without the call are unaffected)
+            target.set_supervision(self.supervision["rows"])
         if self.fanout is not None:
             target.set_fanout(*self.fanout)
         if self.graph is not None:
@@ -714,3 +719,44 @@ def watch_ring(n: int = 1 << 20, kill=(0,), throughput: int = 3, bucket_actors: 
     return Workload("watch_ring", n, 2, 1, throughput, 0, [(0, n, tb.kind_of(b), init)], behaviors=tb, tells=tells,
                     bucket_actors=bucket_actors,
                     watch={"n_slots": 1, "starts": [(0, n, None, 1, down.payload(0))]})
+
+
+# ------------------------------------------------------------------ supervision: workers that fail and restart
+FW_JOB, FW_POISON, FW_RESTARTED, FW_STOPPED = 1, 2, 3, 4
+
+
+def flaky_workers(n: int = 1 << 20, hops: int = 8, poison_every: int = 16, max_poison: int = 5, max_restarts: int = 3,
+                  within: int = 4, n_host: int = 4, seed: int = 1, throughput: int = 3, bucket_actors: int = 1024) -> Workload:
+    """Workers under restart.with_limit(max_restarts, within) (TY/internal/Supervision.scala:311-406).  Every
+    worker gets a Job(hops), counts it and passes it on with one hop less; one worker in `poison_every` also gets
+    1..max_poison poison jobs, on each of which it throws.  A restart resets the jobs done since the last one
+    (word 0) and keeps the worker's monitor (word 1, a host-side actor: a constructor argument); PreRestart reports
+    the lost count to the monitor, and PostStop reports a worker that ran out of restarts and stopped -- the
+    jobs that reach it afterwards are dead letters.  (Buckets of 1024 actors: the first tick's inbox of a bucket,
+    a job per worker and the poison, stays within the one tile an engine with supervision handles.)"""
+    from . import typed
+    st = typed.State("since", "monitor")
+    B = typed.Behaviors
+    job = typed.MessageType("Job", FW_JOB)
+    poisoned = typed.ExceptionType("PoisonedJob")
+    b = (typed.ReceiveBuilder.create(st)
+         .on_message(job, lambda m, s: [s.since.inc(), typed.self_ref(1).tell(job(m.arg - 1)), B.same], test=lambda m: m.arg > 0)
+         .on_message(job, lambda m, s: [s.since.inc(), B.same])
+         .on_any_message(lambda m, s: [B.throw(poisoned)], test=lambda m: m.tag == FW_POISON)
+         .on_any_message(lambda m, s: [B.unhandled])
+         .on_signal(typed.PreRestart, lambda sig, s: [s.monitor.ref.tell(s.since, tag=FW_RESTARTED), B.same])
+         .on_signal(typed.PostStop, lambda sig, s: [s.monitor.ref.tell(s.since, tag=FW_STOPPED), B.same])
+         .build("flaky_worker"))
+    b = B.supervise(b, reset={st.since: 0}).on_failure(typed.SupervisorStrategy.restart.with_limit(max_restarts, within),
+                                                       exc=poisoned)
+    tb = typed.compile_behaviors([b], max_emit=1)
+    rng = np.random.default_rng(seed)
+    init = np.zeros((n, 2), np.uint64)
+    init[:, 1] = n + np.arange(n, dtype=np.uint64) % max(n_host, 1)
+    sick = np.flatnonzero(rng.random(n) < 1.0 / poison_every).astype(np.uint32)
+    doses = rng.integers(1, max_poison + 1, sick.size)
+    dst = np.concatenate([np.arange(n, dtype=np.uint32), np.repeat(sick, doses)])
+    pay = np.concatenate([np.full(n, job.payload(hops), np.uint32), np.full(int(doses.sum()), FW_POISON << 24, np.uint32)])
+    return Workload("flaky_workers", n, 2, 1, throughput, 0, [(0, n, tb.kind_of(b), init)], behaviors=tb,
+                    tells=(dst, np.full(dst.size, NO_SENDER, np.uint32), pay), outbound=(n, max(n_host, 1)),
+                    bucket_actors=bucket_actors, supervision={"rows": tb.supervisors})

@@ -104,6 +104,11 @@ enum agx_behavior_kind {
 #define AGX_RES_STASH 4u
 #define AGX_RES_UNSTASH_ALL 5u
 #define AGX_NEXT_SAME 0xFFu /* agx_case.next of AGX_RES_UNSTASH_ALL: Behaviors.same */
+/* compiled behaviours of an engine with supervision (agx_set_supervision): the handler throws.  The case's
+ * actions run first (the effects before the throw), the message counts as delivered, and agx_case.next is the
+ * exception class, 0..AGX_MAX_EXCEPTION_CLASSES - 1. */
+#define AGX_RES_FAIL 6u
+#define AGX_MAX_EXCEPTION_CLASSES 32u
 
 /* --- compiled behaviours ------------------------------------------------------
  * A typed Behaviors.receiveMessage / javadsl ReceiveBuilder subset lowered to tables
@@ -163,6 +168,11 @@ enum agx_action_op {
  * the terminated ref (TY/internal/adapter/ActorAdapter.scala:84-91,134-138). */
 #define AGX_CASE_SIGNAL 0x80u
 #define AGX_SIGNAL_TERMINATED 0xFE000001u
+/* The signals of an engine with supervision (agx_set_supervision).  A signal case of these tests the payload:
+ * its first test is AGX_V_PAYLOAD (k 0) AGX_CMP_EQ AGX_V_CONST (k = the signal).  Such a case is a supervision
+ * signal case; every other signal case belongs to death watch.  AGX_V_SENDER is the actor itself. */
+#define AGX_SIGNAL_PRERESTART 0xFE000002u
+#define AGX_SIGNAL_POSTSTOP 0xFE000003u
 typedef struct agx_case {
   uint8_t src1, word1, cmp1, src2; /* test 1: operand(src1, word1, k1) cmp1 operand(src2, word2, k2) */
   uint8_t word2, src3, word3, cmp2; /* test 2: operand(src3, word3, k3) cmp2 operand(src4, word4, k4) */
@@ -586,6 +596,60 @@ agx_status agx_watch_info(agx_engine* eng, uint64_t* watches, uint64_t* terminat
  * message.  Slots past n_slots read as zero.  Any pointer may be NULL. */
 agx_status agx_read_watch(agx_engine* eng, uint64_t actor_id, uint32_t watchee[4], uint32_t state[4], uint32_t payload[4],
                           uint32_t generation[4]);
+
+/* Supervision (Behaviors.supervise(..).onFailure(strategy), the PreRestart and PostStop signals:
+ * TY/internal/Supervision.scala:43-52,128-160,311-406, pinned by SupervisionSpec.scala:100-245; DESIGN.md 2.5 has
+ * the contract).
+ * A compiled case may end in AGX_RES_FAIL: its actions run, the message counts as delivered, `failures` grows
+ * and agx_case.next is the exception class.  agx_set_supervision gives compiled behaviour b the entries
+ * table[b * n_levels .. + n_levels), inner first; an entry with class_mask 0 catches nothing.  The entries
+ * that count for an actor are those of the kind it was registered with; they stay in force across become.
+ * A failure goes to the first entry whose mask has the class.  No such entry, or AGX_SUP_STOP: the actor
+ * stops.  AGX_SUP_RESUME: behaviour and state stay as the case left them.  AGX_SUP_RESTART at tick t with the
+ * entry's count c and deadline d (none at first; time is left iff there is none or t <= d): if max_restarts
+ * != -1, c >= max_restarts and time is left, the failure passes to the next outer entry whose mask matches
+ * (none: the actor stops).  Otherwise the PreRestart signal runs on the current behaviour, c becomes c + 1
+ * (1 if no time was left), d stays if it exists and time is left and else becomes t + within, every inner
+ * entry's count and deadline are cleared, the kind becomes the initial kind, the state words of reset_mask take
+ * their reset values, and the drain goes on with the next message under the restarted behaviour.
+ * AGX_SIGNAL_PRERESTART / AGX_SIGNAL_POSTSTOP run the matching supervision signal cases of the behaviour current at
+ * that moment, inside the drain (no envelope, no tag reserved); PostStop runs at every stop of an actor (a
+ * `stopped` result, a failure that stops).  A supervision signal case's actions apply, its result must be
+ * AGX_RES_SAME (AGX_EINVAL at agx_set_behaviors otherwise); no matching case is not unhandled.  Its tells
+ * count as emitted.  Within one behaviour the tells of a case that fails or stops plus the tells of the
+ * largest supervision signal case may not exceed max_emit (1): agx_run refuses such tables (AGX_EINVAL).
+ * A tick is a superstep with mail: ticks == agx_stats.supersteps; time does not pass between runs.
+ * Call before the first agx_run (AGX_ESTATE afterwards).  AGX_EINVAL: n_levels outside 1..4, n_behaviors
+ * outside 1..64, a bad entry, n_ranks > 1, an engine with a CRDT kind, a priority table, a stash class, timers
+ * or death watch (either call order), an engine whose bounded-mailbox ring pool exists, max_emit > 1.  Such an
+ * engine uses no wave, ring, dense or persistent launch, and a bucket whose inbox exceeds one 2048-message
+ * tile makes agx_run return AGX_ECAPACITY (sticky).  Tables with AGX_RES_FAIL or a supervision signal case on
+ * an engine without supervision, and tables with watch, timer or stash content on an engine with it, make
+ * agx_run return AGX_EINVAL.  Left out: restartWithBackoff, children, supervise around a behaviour reached by
+ * become, logging. */
+#define AGX_MAX_SUPERVISORS 4u
+#define AGX_SUP_RESUME 1u
+#define AGX_SUP_RESTART 2u
+#define AGX_SUP_STOP 3u
+typedef struct agx_supervisor {
+  uint32_t class_mask;  /* bit c: the entry catches exception class c; 0: the entry is unused            */
+  uint8_t strategy;     /* AGX_SUP_RESUME / _RESTART / _STOP                                              */
+  uint8_t reset_mask;   /* RESTART: bit w = state word w (0, 1) takes reset[w]; the others stay           */
+  uint8_t pad[2];
+  int32_t max_restarts; /* RESTART: -1 = unlimited                                                        */
+  uint32_t within;      /* RESTART: the window of max_restarts in ticks, >= 1                             */
+  uint64_t reset[2];
+} agx_supervisor; /* 32 bytes */
+agx_status agx_set_supervision(agx_engine* eng, const agx_supervisor* table, uint32_t n_behaviors, uint32_t n_levels);
+/* Totals since agx_create: failures (AGX_RES_FAIL results), resumes, restarts, stops (every stop of an actor
+ * inside a drain), and ticks: the supersteps with mail so far.  Any pointer may be NULL. */
+agx_status agx_supervision_info(agx_engine* eng, uint64_t* failures, uint64_t* resumes, uint64_t* restarts,
+                                uint64_t* stops, uint64_t* ticks);
+/* One actor (for tests and tools): the kind it was registered with, and per level the restart count and the
+ * ticks left of its window (deadline - ticks so far, 0 once it has passed; 0xFFFFFFFF when there is no
+ * deadline).  Levels past n_levels read as 0 / 0xFFFFFFFF.  Any pointer may be NULL. */
+agx_status agx_read_supervision(agx_engine* eng, uint64_t actor_id, uint32_t* initial_kind, uint32_t count[4],
+                                uint32_t remaining[4]);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
