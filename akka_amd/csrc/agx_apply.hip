@@ -34,6 +34,7 @@ hipError_t agx_launch_apply_prio_g7(uint32_t, uint32_t, dim3, hipStream_t, const
 hipError_t agx_launch_apply_stash_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_apply_timers_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_apply_watch_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
+hipError_t agx_launch_apply_child_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_apply_super_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_tiny_g0(uint32_t, dim3, hipStream_t, const BucketArgs&);
 hipError_t agx_launch_tiny_g1(uint32_t, dim3, hipStream_t, const BucketArgs&);
@@ -241,6 +242,18 @@ hipError_t agx_launch_apply_super_g(uint32_t vid, uint32_t mode, dim3 g, hipStre
     return hipErrorInvalidValue;
   return hipGetLastError();
 }
+// the children fast launch (k_bucket_apply<.., kWatch | kChild>) of the compiled catch-all variant, in the same group
+hipError_t agx_launch_apply_child_g(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
+  if (vid != V_ALL_COMPILED) return hipErrorInvalidValue;
+  constexpr uint32_t M = kVariants[V_ALL_COMPILED].km | kWatchKM | kChildKM;
+  if (mode == M_FUSED)
+    hipLaunchKernelGGL((k_bucket_apply<false, M, true, false, false, false>), g, dim3(kBThreads), 0, s, ba);
+  else if (mode == M_BYPASS)
+    hipLaunchKernelGGL((k_bucket_apply<false, M, false, false, false, false>), g, dim3(kBThreads), 0, s, ba);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
 #endif
 
 hipError_t AGX_CAT(agx_launch_ring_g, AGX_VGROUP)(uint32_t vid, bool tiny, dim3 g, hipStream_t s, const BucketArgs& ba,
@@ -303,6 +316,9 @@ hipError_t agx_launch_apply_timers(uint32_t vid, uint32_t mode, dim3 g, hipStrea
 }
 hipError_t agx_launch_apply_watch(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
   return agx_launch_apply_watch_g(vid, mode, g, s, ba);
+}
+hipError_t agx_launch_apply_child(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
+  return agx_launch_apply_child_g(vid, mode, g, s, ba);
 }
 hipError_t agx_launch_apply_super(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
   return agx_launch_apply_super_g(vid, mode, g, s, ba);

@@ -370,6 +370,93 @@ __device__ __forceinline__ WatchDev watch_dev(uint32_t* base, uint32_t nb, uint3
   return t;
 }
 
+// ---- children (agx_set_children; AA/dungeon/Children.scala, TY/internal/adapter/
+// ActorContextAdapter.scala:79-106).  An engine with death watch only.  The child storage is an allocation of its
+// own; the watch storage's header words [kWdChildPtr, +2) hold its device address (0: no children).  u32 units:
+//   [0] n_regions   [1] n_sites
+//   [4..19]   eight u64 counters: spawned, refused, created, child_stops, cascade_stops, illegal_stops, discarded
+//   [kCdRegionOff + 4 * r]  region r: first_parent, n_parents, first_child, max_children
+//   [kCdSiteOff + 8 * s]    site s: kind, flags (kCdSiteParent: word 1 = the parent's id), word-0 base (lo, hi),
+//                           word-1 constant (lo, hi)
+//   [kCdBucketOff + b]      nlive: the bucket's live created children
+//   then sc[np]: the actor's spawn count | kCdCreated once the actor was created by a Create envelope
+// Only a bucket's own block writes its actors' words.  The k-th spawn of parent p creates id first_child +
+// (p - first_parent) * max_children + k; the parent of an id is computed from the same formula.
+constexpr uint32_t kWdChildPtr = 20;
+constexpr uint32_t kCdCtr = 4, kCdRegionOff = 32, kCdSiteOff = 64, kCdBucketOff = kCdSiteOff + 8u * AGX_MAX_SPAWN_SITES;
+constexpr uint32_t kCdCreated = 0x80000000u, kCdSiteParent = 1u;
+constexpr uint32_t kCcSpawned = 0, kCcRefused = 1, kCcCreated = 2, kCcChildStops = 3, kCcCascade = 4, kCcIllegal = 5,
+                   kCcDiscarded = 6;
+__host__ __device__ __forceinline__ size_t cd_count_off(uint32_t nb) {
+  return ((size_t)kCdBucketOff + (size_t)nb + 3u) & ~(size_t)3;
+}
+struct ChildDev {
+  uint32_t* base;
+  uint32_t* sc;  // [np]
+  uint32_t nr, nsites;
+  __device__ __forceinline__ uint32_t* nlive(uint32_t b) const { return base + kCdBucketOff + b; }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kCdCtr) + i;
+  }
+  __device__ __forceinline__ const uint32_t* site(uint32_t s) const { return base + kCdSiteOff + 8u * s; }
+  // the computed parent of id x (kWdNone: x lies in no child block)
+  __device__ __forceinline__ uint32_t parent_of(uint32_t x) const {
+    for (uint32_t r = 0; r < nr; ++r) {
+      const uint32_t* R = base + kCdRegionOff + 4u * r;
+      const uint32_t off = x - R[2];
+      if (x >= R[2] && off < R[1] * R[3]) return R[0] + off / R[3];
+    }
+    return kWdNone;
+  }
+  // the child block of parent p: its first id and its size (false: p lies in no parent range)
+  __device__ __forceinline__ bool block_of(uint32_t p, uint32_t& first, uint32_t& cap) const {
+    for (uint32_t r = 0; r < nr; ++r) {
+      const uint32_t* R = base + kCdRegionOff + 4u * r;
+      const uint32_t off = p - R[0];
+      if (p >= R[0] && off < R[1]) {
+        first = R[2] + off * R[3];
+        cap = R[3];
+        return true;
+      }
+    }
+    return false;
+  }
+  __device__ __forceinline__ uint32_t spawned(uint32_t l) const { return sc[l] & ~kCdCreated; }
+  // context.spawn by actor l: the new child's id, or kWdNone when the spawn is refused
+  __device__ __forceinline__ uint32_t spawn(uint32_t l) const {
+    uint32_t first = 0, cap = 0;
+    const uint32_t c = sc[l], n = c & ~kCdCreated;
+    if (!block_of(l, first, cap) || n >= cap) {
+      atomicAdd(ctr(kCcRefused), 1ull);
+      return kWdNone;
+    }
+    sc[l] = c + 1u;
+    atomicAdd(ctr(kCcSpawned), 1ull);
+    return first + n;
+  }
+  // is x one of actor l's children already spawned?
+  __device__ __forceinline__ bool own_child(uint32_t l, uint32_t x) const {
+    uint32_t first = 0, cap = 0;
+    if (!block_of(l, first, cap)) return false;
+    return x >= first && x - first < spawned(l);
+  }
+  // child number i mod spawn count of actor l (kWdNone without children)
+  __device__ __forceinline__ uint32_t child_at(uint32_t l, uint64_t i) const {
+    uint32_t first = 0, cap = 0;
+    const uint32_t n = spawned(l);
+    if (!n || !block_of(l, first, cap)) return kWdNone;
+    return first + (uint32_t)(i % n);
+  }
+};
+__device__ __forceinline__ ChildDev child_dev(const uint32_t* watch_base, uint32_t nb) {
+  ChildDev c;
+  c.base = reinterpret_cast<uint32_t*>(*reinterpret_cast<const unsigned long long*>(watch_base + kWdChildPtr));
+  c.nr = c.base[0];
+  c.nsites = c.base[1];
+  c.sc = c.base + cd_count_off(nb);
+  return c;
+}
+
 // A tell to a host-side actor (agx_set_outbound): appended to the outbox (when `write`); returns
 // false for any other id.  One thread's appends are ordered (same counter, program order), so each
 // sender's outbound tells keep their emission order.
@@ -536,6 +623,8 @@ constexpr uint32_t kTimersKM = 1u << 29;
 constexpr uint32_t kWatchKM = 1u << 28;
 // KM flag (not a kind): the variant knows supervision (agx_set_supervision).  A flag of KM for the same reason.
 constexpr uint32_t kSuperKM = 1u << 27;
+// KM flag (not a kind): the variant knows children (agx_set_children); only ever combined with kWatchKM.
+constexpr uint32_t kChildKM = 1u << 26;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -793,6 +882,89 @@ struct SuperDev {
 };
 __device__ __forceinline__ SuperDev super_dev(uint32_t* base, uint32_t nb, uint32_t bb) {
   return SuperDev{base, nb, nb << bb};
+}
+
+// compiled_apply of the children instantiations (agx_set_children): compiled_apply_w plus the
+// operands AGX_V_SPAWNED / AGX_V_CHILD and the actions AGX_A_SPAWN / AGX_A_STOP_CHILD.  A spawn takes the next id
+// of the actor's child block and tells it a Create envelope (the case's tell slot: max_emit is 1); a refused
+// spawn sends nothing.  context.stop of a ref that is not one of the actor's spawned children is the reference's
+// IllegalArgumentException: `illegal` is set, the rest of the case is skipped and the result is AGX_RES_STOPPED.
+__device__ __forceinline__ uint64_t cc_operand(const ChildDev& CD, uint32_t l, uint32_t src, uint32_t word, int64_t k,
+                                               uint32_t pay, const uint64_t* w, uint32_t sender, uint32_t self) {
+  if (src == AGX_V_SPAWNED) return (uint64_t)CD.spawned(l) + (uint64_t)k;
+  if (src == AGX_V_CHILD) return CD.child_at(l, (word <= 1u ? w[word] : 0ull) + (uint64_t)k);
+  return cb_operand(src, word, k, pay, w, sender, self);
+}
+template <typename Emit>
+__device__ __forceinline__ uint32_t compiled_apply_c(const DevParams& P, const WatchDev& WD, const ChildDev& CD, uint32_t l,
+                                                     uint32_t bkt, uint32_t& kind, uint32_t self, uint64_t* w, uint32_t src,
+                                                     uint32_t pay, bool signal, bool& conflict, bool& illegal, Emit& emit) {
+  const uint32_t b = kind - AGX_KIND_COMPILED;
+  if (b >= P.n_beh) return AGX_RES_UNHANDLED;
+  const uint32_t c1 = P.bfirst[b + 1];
+  for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
+    const agx_case C = P.bcase[c];
+    if (((C.result & AGX_CASE_SIGNAL) != 0u) != signal) continue;
+    if (!cb_cmp(C.cmp1, cc_operand(CD, l, C.src1, C.word1, C.k1, pay, w, src, self),
+                cc_operand(CD, l, C.src2, C.word2, C.k2, pay, w, src, self)))
+      continue;
+    if (!cb_cmp(C.cmp2, cc_operand(CD, l, C.src3, C.word3, C.k3, pay, w, src, self),
+                cc_operand(CD, l, C.src4, C.word4, C.k4, pay, w, src, self)))
+      continue;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      const agx_act A = P.bact[i];
+      const uint64_t v = cc_operand(CD, l, A.src, A.sword, A.k, pay, w, src, self);
+      uint64_t d = 0;
+      if (A.op == AGX_A_TELL || (A.op >= AGX_A_WATCH && A.op != AGX_A_SPAWN)) {  // a ref
+        if (A.dsrc == AGX_V_SELF) {
+          int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+          d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+        } else {
+          d = cc_operand(CD, l, A.dsrc, A.dword, A.dk, pay, w, src, self);
+        }
+      }
+      const uint32_t ref = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
+      const uint32_t msg = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;
+      switch (A.op) {
+        case AGX_A_SET: w[A.word & 1u] = v; break;
+        case AGX_A_ADD: w[A.word & 1u] += v; break;
+        case AGX_A_MAX: w[A.word & 1u] = v > w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_MIN: w[A.word & 1u] = v < w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_TELL: emit(ref, msg); break;
+        case AGX_A_WATCH:
+        case AGX_A_WATCH_WITH:
+          if (WD.watch(l, bkt, ref, A.op == AGX_A_WATCH_WITH, msg)) {
+            conflict = true;
+            return AGX_RES_STOPPED;
+          }
+          break;
+        case AGX_A_UNWATCH: WD.unwatch(l, bkt, ref); break;
+        case AGX_A_SPAWN: {  // dword: the site; pad0 & 1: state word `word` receives the child's id
+          const uint32_t ch = CD.spawn(l);
+          if (A.pad0 & 1u) w[A.word & 1u] = ch;
+          if (ch != kWdNone)
+            emit(ch, (AGX_TAG_CREATE << 24) | (((uint32_t)A.dword & (AGX_MAX_SPAWN_SITES - 1u)) << AGX_SPAWN_ARG_BITS) |
+                         ((uint32_t)v & AGX_SPAWN_ARG_MASK));
+          break;
+        }
+        case AGX_A_STOP_CHILD:
+          if (!CD.own_child(l, ref)) {
+            illegal = true;
+            return AGX_RES_STOPPED;
+          }
+          emit(ref, AGX_TAG_STOP << 24);
+          break;
+        default: break;
+      }
+    }
+    const uint32_t res = C.result & ~AGX_CASE_SIGNAL;
+    if (res == AGX_RES_BECOME) {
+      kind = AGX_KIND_COMPILED + C.next;
+      return AGX_RES_SAME;
+    }
+    return res;
+  }
+  return AGX_RES_UNHANDLED;
 }
 
 // compiled_apply of the supervision instantiations (agx_set_supervision): the same rule, with

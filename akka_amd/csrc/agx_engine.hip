@@ -166,6 +166,19 @@ struct agx_engine {
     std::vector<uint32_t> watchees;
   };
   std::vector<WatchStart> wd_starts;  // agx_start_watch calls not yet applied on the device (prepare_run)
+  // children (agx_set_children): regions and spawn sites on an engine with death watch.  Such an engine launches
+  // the children instantiation of the compiled catch-all variant (kWatch | kChild)
+  std::vector<agx_child_region> ch_regions;
+  std::vector<agx_spawn_site> ch_sites;
+  uint32_t* d_child = nullptr;  // the child storage (agx_device.h ChildDev); its address stands in the watch storage
+  bool beh_child = false;       // the compiled tables spawn, stop a child or read AGX_V_SPAWNED / AGX_V_CHILD
+  bool beh_ctl_tags = false;    // the compiled tables name tag 0xFD or 0xFC (an or_mask or a tag test)
+  bool ch_bad_spawn = false;    // agx_spawn_children was called on an engine without children: agx_run refuses
+  struct ChildSpawn {
+    uint64_t first, count;
+    uint32_t site, arg;
+  };
+  std::vector<ChildSpawn> ch_spawns;  // agx_spawn_children calls not yet applied on the device (prepare_run)
   // supervision (agx_set_supervision): strategy entries per compiled behaviour.  Such an engine launches the
   // supervision instantiation of the compiled catch-all variant and no wave / ring / dense / persistent launch
   bool sv_on = false;
@@ -924,7 +937,8 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
         HIP_TRY(agx_launch_apply_timers(vid, mode, g, e->stream, bf));
       } else if (e->wd_slots) {
         if (mode == M_OWNER) return set_err(AGX_ESTATE, "death watch needs a single-rank engine");
-        HIP_TRY(agx_launch_apply_watch(vid, mode, g, e->stream, bf));
+        if (e->d_child) HIP_TRY(agx_launch_apply_child(vid, mode, g, e->stream, bf));
+        else HIP_TRY(agx_launch_apply_watch(vid, mode, g, e->stream, bf));
       } else if (e->sv_on) {
         if (mode == M_OWNER) return set_err(AGX_ESTATE, "supervision needs a single-rank engine");
         HIP_TRY(agx_launch_apply_super(vid, mode, g, e->stream, bf));
@@ -1283,11 +1297,13 @@ agx_status timers_after_run(agx_engine* e) {
 // ---- death watch (agx_set_death_watch)
 // the death ticks follow the actors' flags: an actor that is not alive and has no death tick yet was never
 // registered (before the first run: dead before tick 1) or was stopped from the host (dead in the current tick)
+// (children: an id of a child block keeps "none" until it was created and stopped on the device)
 static __global__ void __launch_bounds__(kThreads) k_watch_died(uint32_t* wd, const uint8_t* alive, uint32_t nb, uint32_t bb,
-                                                               uint32_t n_local, uint32_t started) {
+                                                               uint32_t n_local, uint32_t started, uint32_t children) {
   const uint32_t l = blockIdx.x * kThreads + threadIdx.x, np = nb << bb;
   if (l >= np) return;
   uint32_t* const died = wd + wd_slot_off(nb) + 4ull * wd[0] * np;
+  if (children && child_dev(wd, nb).parent_of(l) != kWdNone) return;
   if (l >= n_local || !(alive[l] & 1u)) {
     if (died[l] == kWdNone) died[l] = started ? wd[kWdBucketOff + 2u * nb + (l >> bb)] : 0u;
   }
@@ -1379,7 +1395,7 @@ agx_status watch_sync_died(agx_engine* e) {
     HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
   const uint32_t np = e->nb << e->bb;
   hipLaunchKernelGGL(k_watch_died, dim3((np + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, e->d_watch, e->d_alive,
-                     e->nb, e->bb, (uint32_t)e->n_local, e->started ? 1u : 0u);
+                     e->nb, e->bb, (uint32_t)e->n_local, e->started ? 1u : 0u, e->d_child ? 1u : 0u);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->wd_died_init = !e->actors_dirty;
@@ -1502,8 +1518,80 @@ agx_status super_after_run(agx_engine* e) {
   return copy_sync(e, e->d_super + kSvBase, &base, 4, hipMemcpyHostToDevice);
 }
 
+// ---- children (agx_set_children)
+// the death ticks of the child blocks start as "none" (written once, at agx_set_children)
+static __global__ void __launch_bounds__(kThreads) k_child_init(uint32_t* wd, uint32_t nb, uint32_t bb, uint32_t first,
+                                                               uint32_t count) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= count) return;
+  uint32_t* const died = wd + wd_slot_off(nb) + 4ull * wd[0] * (nb << bb);
+  died[first + i] = kWdNone;
+}
+// agx_spawn_children on the device: one thread per actor of the range spawns by the rules of a device spawn;
+// `child[i]` is the new child's id, or none (the host stages the Create envelopes)
+static __global__ void __launch_bounds__(kThreads) k_child_spawn(uint32_t* wd, const uint8_t* alive, uint32_t nb, uint32_t bb,
+                                                                uint32_t n, uint32_t first, uint32_t count, uint32_t* child) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= count) return;
+  const WatchDev WD = watch_dev(wd, nb, bb, n);
+  const ChildDev CD = child_dev(wd, nb);
+  const uint32_t l = first + i;
+  child[i] = kWdNone;
+  if (!(alive[l] & 1u) || WD.died[l] != kWdNone) return;  // (a stopped actor spawns nothing)
+  child[i] = CD.spawn(l);
+}
+
+size_t child_words(const agx_engine* e) { return cd_count_off(e->nb) + ((size_t)e->nb << e->bb); }
+
+// apply the recorded agx_spawn_children calls (the actors' flags and death ticks are on the device: after
+// flush_watch_starts); the Create envelopes join the host-staged tells
+agx_status flush_child_spawns(agx_engine* e) {
+  if (e->ch_spawns.empty()) return AGX_OK;
+  for (const auto& cs : e->ch_spawns) {
+    if (!cs.count) continue;
+    uint32_t* d_ch = nullptr;
+    AGX_TRY(dalloc(&d_ch, cs.count));
+    hipLaunchKernelGGL(k_child_spawn, dim3((uint32_t)((cs.count + kThreads - 1) / kThreads)), dim3(kThreads), 0, e->stream,
+                       e->d_watch, e->d_alive, e->nb, e->bb, (uint32_t)e->n_global, (uint32_t)cs.first, (uint32_t)cs.count, d_ch);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> ch(cs.count);
+    const agx_status st = copy_sync(e, ch.data(), d_ch, cs.count * 4ull, hipMemcpyDeviceToHost);
+    hipFree(d_ch);
+    AGX_TRY(st);
+    for (uint64_t i = 0; i < cs.count; ++i) {
+      if (ch[i] == kWdNone) continue;
+      e->staged_total++;
+      e->hs_key.push_back(ch[i]);
+      e->hs_src.push_back((uint32_t)(cs.first + i));
+      e->hs_pay.push_back((AGX_TAG_CREATE << 24) | (cs.site << AGX_SPAWN_ARG_BITS) | (cs.arg & AGX_SPAWN_ARG_MASK));
+    }
+  }
+  e->ch_spawns.clear();
+  e->inflight_known = false;
+  return AGX_OK;
+}
+
 // upload host mirrors / staged tells before a run
 agx_status prepare_run(agx_engine* e) {
+  if (e->ch_bad_spawn)
+    return set_err(AGX_EINVAL, "agx_spawn_children was called on an engine without children (agx_set_children)");
+  if (e->beh_child && !e->d_child)  // (only the children variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours spawn, stop a child or read the spawn count, but the engine has no "
+                   "children (agx_set_children)");
+  if (e->d_child) {
+    if (e->beh_ctl_tags)
+      return set_err(AGX_EINVAL, "the compiled behaviours name message tag 0xFD or 0xFC, reserved for Create and Stop "
+                     "envelopes on an engine with children");
+    for (const auto& st : e->ch_sites)
+      if (st.kind - AGX_KIND_COMPILED >= e->n_beh)
+        return set_err(AGX_EINVAL, "children: a spawn site's kind %u is no compiled behaviour of the tables (%u behaviours)",
+                       st.kind, e->n_beh);
+    if (!e->started)
+      for (const auto& r : e->ch_regions)
+        for (uint64_t x = r.first_child; x < (uint64_t)r.first_child + (uint64_t)r.n_parents * r.max_children; ++x)
+          if (e->h_alive[x] & 1u)
+            return set_err(AGX_EINVAL, "children: id %llu of a child block is registered", (unsigned long long)x);
+  }
   if ((e->beh_fail || e->beh_svsig) && !e->sv_on)  // (only the supervision variant interprets those: loud, never wrong)
     return set_err(AGX_EINVAL, "the compiled behaviours fail (AGX_RES_FAIL) or hold a PreRestart / PostStop signal case, but "
                    "the engine has no supervision (agx_set_supervision)");
@@ -1573,6 +1661,7 @@ agx_status prepare_run(agx_engine* e) {
   if (e->wd_slots) {
     AGX_TRY(alloc_watch(e));
     AGX_TRY(flush_watch_starts(e));
+    if (e->d_child) AGX_TRY(flush_child_spawns(e));
   }
   if (e->sv_on) {
     AGX_TRY(alloc_super(e));
@@ -3092,6 +3181,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_stash);
   hipFree(e->d_timers);
   hipFree(e->d_watch);
+  hipFree(e->d_child);
   hipFree(e->d_super);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
@@ -3123,6 +3213,13 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
   if ((kind == AGX_KIND_FORWARD_RR || kind == AGX_KIND_STOP_AFTER) && e->W < 2)
     return set_err(AGX_EINVAL, "behaviour kind %u needs n_words >= 2", kind);
   if (init && stride < e->W * 8ull) return set_err(AGX_EINVAL, "state_stride smaller than n_words*8");
+  for (const auto& r : e->ch_regions) {  // (children: the ids of a child block belong to the engine)
+    const uint64_t c0 = r.first_child, c1 = c0 + (uint64_t)r.n_parents * r.max_children;
+    if (count && first_id < c1 && c0 < first_id + count)
+      return set_err(AGX_EINVAL, "register_range [%llu, %llu) overlaps the child block [%llu, %llu) (agx_set_children): "
+                     "its actors are created by their parents", (unsigned long long)first_id,
+                     (unsigned long long)(first_id + count), (unsigned long long)c0, (unsigned long long)c1);
+  }
   if (kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET) AGX_TRY(enable_crdt(e, kind));
   if (count && !(e->kinds_mask & kb(kind))) {  // the apply variant is captured in the superstep graphs
     e->kinds_mask |= kb(kind);
@@ -3446,6 +3543,8 @@ agx_status agx_set_death_watch(agx_engine* e, uint32_t n_slots) {
                    "death watch: set death watch before the first run", e->ring_live ? e->ring_c : e->rg_c);
   if (e->started) return set_err(AGX_ESTATE, "set death watch before the first agx_run");
   AGX_TRY(ensure_dev(e));
+  if (e->d_child && n_slots != e->wd_slots)
+    return set_err(AGX_EINVAL, "death watch: the slot count cannot change once children are set (agx_set_children)");
   if (e->d_watch && n_slots != e->wd_slots) {
     hipFree(e->d_watch);
     e->d_watch = nullptr;
@@ -3621,6 +3720,149 @@ agx_status agx_read_supervision(agx_engine* e, uint64_t actor_id, uint32_t* init
   return AGX_OK;
 }
 
+// AA/dungeon/Children.scala; TY/internal/adapter/ActorContextAdapter.scala:79-106
+agx_status agx_set_children(agx_engine* e, const agx_child_region* regions, uint32_t n_regions, const agx_spawn_site* sites,
+                            uint32_t n_sites) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->wd_slots) return set_err(AGX_EINVAL, "children need an engine with death watch (agx_set_death_watch first)");
+  if (e->started) return set_err(AGX_ESTATE, "set children before the first agx_run");
+  if (n_regions < 1u || n_regions > AGX_MAX_CHILD_REGIONS || !regions)
+    return set_err(AGX_EINVAL, "children: %u regions (1..%u)", n_regions, AGX_MAX_CHILD_REGIONS);
+  if (n_sites > AGX_MAX_SPAWN_SITES || (n_sites && !sites))
+    return set_err(AGX_EINVAL, "children: %u spawn sites (0..%u)", n_sites, AGX_MAX_SPAWN_SITES);
+  if (e->beh_ctl_tags)
+    return set_err(AGX_EINVAL, "children: the compiled behaviours name message tag 0xFD or 0xFC, reserved for Create and Stop "
+                   "envelopes");
+  const uint64_t n = e->n_global;
+  for (uint32_t i = 0; i < n_regions; ++i) {
+    const agx_child_region& r = regions[i];
+    const uint64_t p0 = r.first_parent, p1 = p0 + r.n_parents, c0 = r.first_child, c1 = c0 + (uint64_t)r.n_parents * r.max_children;
+    if (!r.n_parents || !r.max_children || p1 > n || c1 > n)
+      return set_err(AGX_EINVAL, "children: region %u is empty or leaves [0, n_actors)", i);
+    if (p0 < c1 && c0 < p1) return set_err(AGX_EINVAL, "children: region %u's child block overlaps its own parent range", i);
+    for (uint32_t j = 0; j < i; ++j) {
+      const agx_child_region& q = regions[j];
+      const uint64_t q0 = q.first_parent, q1 = q0 + q.n_parents, d0 = q.first_child, d1 = d0 + (uint64_t)q.n_parents * q.max_children;
+      if (p0 < q1 && q0 < p1) return set_err(AGX_EINVAL, "children: the parent ranges of regions %u and %u overlap", j, i);
+      if (c0 < d1 && d0 < c1) return set_err(AGX_EINVAL, "children: the child blocks of regions %u and %u overlap", j, i);
+    }
+    for (uint64_t x = c0; x < c1; ++x)
+      if (e->h_alive[x] & 1u)
+        return set_err(AGX_EINVAL, "children: id %llu of region %u's child block is registered", (unsigned long long)x, i);
+  }
+  for (uint32_t i = 0; i < n_sites; ++i)
+    if (sites[i].kind < AGX_KIND_COMPILED || sites[i].kind >= AGX_KIND_COMPILED + AGX_MAX_BEHAVIORS || (sites[i].flags & ~AGX_SITE_WORD1_PARENT))
+      return set_err(AGX_EINVAL, "children: spawn site %u: kind %u is no compiled behaviour kind, or unknown flags", i, sites[i].kind);
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(sync_mirrors(e));
+  AGX_TRY(alloc_watch(e));
+  const size_t total = child_words(e);
+  if (!e->d_child && hipMalloc((void**)&e->d_child, total * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_child = nullptr;
+    return set_err(AGX_ENOMEM, "the child storage of %llu actors does not fit on the device", (unsigned long long)n);
+  }
+  std::vector<uint32_t> h(kCdBucketOff, 0u);
+  h[0] = n_regions;
+  h[1] = n_sites;
+  for (uint32_t i = 0; i < n_regions; ++i) {
+    h[kCdRegionOff + 4 * i] = regions[i].first_parent;
+    h[kCdRegionOff + 4 * i + 1] = regions[i].n_parents;
+    h[kCdRegionOff + 4 * i + 2] = regions[i].first_child;
+    h[kCdRegionOff + 4 * i + 3] = regions[i].max_children;
+  }
+  for (uint32_t i = 0; i < n_sites; ++i) {
+    uint32_t* S = &h[kCdSiteOff + 8 * i];
+    S[0] = sites[i].kind;
+    S[1] = sites[i].flags;
+    S[2] = (uint32_t)sites[i].base0;
+    S[3] = (uint32_t)(sites[i].base0 >> 32);
+    S[4] = (uint32_t)sites[i].word1;
+    S[5] = (uint32_t)(sites[i].word1 >> 32);
+  }
+  HIP_TRY(hipMemsetAsync(e->d_child, 0, total * 4ull, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_child, h.data(), h.size() * 4ull, hipMemcpyHostToDevice, e->stream));
+  const unsigned long long addr = (unsigned long long)(uintptr_t)e->d_child;
+  HIP_TRY(hipMemcpyAsync(e->d_watch + kWdChildPtr, &addr, 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t i = 0; i < n_regions; ++i) {  // death tick "none" for the child blocks, once
+    const uint32_t cnt = regions[i].n_parents * regions[i].max_children;
+    hipLaunchKernelGGL(k_child_init, dim3((cnt + kThreads - 1) / kThreads), dim3(kThreads), 0, e->stream, e->d_watch, e->nb, e->bb,
+                       regions[i].first_child, cnt);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->ch_regions.assign(regions, regions + n_regions);
+  e->ch_sites.assign(sites, sites + n_sites);
+  e->ch_spawns.clear();
+  e->ch_bad_spawn = false;
+  if (!(e->kinds_mask & kb(AGX_KIND_COMPILED))) e->kinds_mask |= kb(AGX_KIND_COMPILED);  // (the children's kinds)
+  drop_graphs(e);  // the variant is captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_spawn_children(agx_engine* e, uint64_t first_parent, uint64_t count, uint32_t site, uint32_t arg) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_child) {
+    e->ch_bad_spawn = true;  // (agx_run refuses too: the rule of agx_start_watch)
+    return set_err(AGX_EINVAL, "agx_spawn_children needs an engine with children (agx_set_children)");
+  }
+  if (first_parent + count > e->n_global || first_parent + count < first_parent) return set_err(AGX_EINVAL, "bad actor range");
+  if (site >= e->ch_sites.size()) return set_err(AGX_EINVAL, "spawn site %u of %zu", site, e->ch_sites.size());
+  if (arg > AGX_SPAWN_ARG_MASK) return set_err(AGX_EINVAL, "a spawn argument has %u bits", AGX_SPAWN_ARG_BITS);
+  e->ch_spawns.push_back({first_parent, count, site, arg});
+  return AGX_OK;
+}
+
+// the recorded host spawns take effect now (the actors' flags reach the device first when they are the newer ones)
+static agx_status child_flush_now(agx_engine* e) {
+  if (e->ch_spawns.empty()) return AGX_OK;
+  AGX_TRY(flush_watch_starts(e));
+  return flush_child_spawns(e);
+}
+
+agx_status agx_children_info(agx_engine* e, uint64_t* spawned, uint64_t* refused, uint64_t* created, uint64_t* child_stops,
+                             uint64_t* cascade_stops, uint64_t* illegal_stops, uint64_t* discarded, uint64_t* live) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nl = 0;
+  if (e->d_child) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(child_flush_now(e));
+    AGX_TRY(copy_sync(e, c, e->d_child + kCdCtr, sizeof(c), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> lv(e->nb);
+    AGX_TRY(copy_sync(e, lv.data(), e->d_child + kCdBucketOff, e->nb * 4ull, hipMemcpyDeviceToHost));
+    for (uint32_t b = 0; b < e->nb; ++b) nl += lv[b];
+  }
+  if (spawned) *spawned = c[kCcSpawned];
+  if (refused) *refused = c[kCcRefused];
+  if (created) *created = c[kCcCreated];
+  if (child_stops) *child_stops = c[kCcChildStops];
+  if (cascade_stops) *cascade_stops = c[kCcCascade];
+  if (illegal_stops) *illegal_stops = c[kCcIllegal];
+  if (discarded) *discarded = c[kCcDiscarded];
+  if (live) *live = nl;
+  return AGX_OK;
+}
+
+agx_status agx_read_children(agx_engine* e, uint64_t actor_id, uint32_t* parent, uint32_t* spawn_count, uint32_t* created) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (actor_id >= e->n_global) return set_err(AGX_EINVAL, "bad actor id");
+  uint32_t par = kWdNone, w = 0;
+  for (const auto& r : e->ch_regions) {
+    const uint64_t c0 = r.first_child, c1 = c0 + (uint64_t)r.n_parents * r.max_children;
+    if (actor_id >= c0 && actor_id < c1) par = r.first_parent + (uint32_t)((actor_id - c0) / r.max_children);
+  }
+  if (e->d_child) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(child_flush_now(e));
+    AGX_TRY(copy_sync(e, &w, e->d_child + cd_count_off(e->nb) + actor_id, 4, hipMemcpyDeviceToHost));
+  }
+  if (parent) *parent = par;
+  if (spawn_count) *spawn_count = w & ~kCdCreated;
+  if (created) *created = (w & kCdCreated) ? 1u : 0u;
+  return AGX_OK;
+}
+
 agx_status agx_set_outbound(agx_engine* e, uint32_t first_host_id, uint32_t n_host, uint64_t capacity) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (n_host && (first_host_id < e->n_global || (uint64_t)first_host_id + n_host > (1ull << 31)))
@@ -3690,6 +3932,8 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   for (uint32_t b = 0; b < n_beh; ++b)
     if (first[b] > first[b + 1]) return set_err(AGX_EINVAL, "first[] must be non-decreasing");
   auto opnd_ok = [](uint32_t src, uint32_t word) {
+    if (src == AGX_V_SPAWNED) return word <= 1u;
+    if (src == AGX_V_CHILD) return word <= AGX_CHILD_NO_WORD;
     return src == AGX_V_TIMER ? word < AGX_MAX_TIMER_KEYS : src <= AGX_V_STASH && word <= 1u;
   };
   // a supervision signal case (include/akka_gpu.h AGX_SIGNAL_PRERESTART): a signal case whose first test is
@@ -3717,11 +3961,46 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     const agx_act& A = acts[i];
     const bool tmop = A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL;  // (`word` is the key)
     const bool wdop = A.op >= AGX_A_WATCH && A.op <= AGX_A_UNWATCH;  // (the ref is the d-operand)
-    if (A.op < AGX_A_SET || A.op > AGX_A_UNWATCH || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+    if (A.op < AGX_A_SET || A.op > AGX_A_STOP_CHILD || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
         !opnd_ok(A.src, A.sword) ||
-        ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop) && !opnd_ok(A.dsrc, A.dword)))
-      return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (state words 0..1, timer keys 0..3)", i);
+        ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop || A.op == AGX_A_STOP_CHILD) &&
+         !opnd_ok(A.dsrc, A.dword)) ||
+        (A.op == AGX_A_SPAWN && A.dword >= AGX_MAX_SPAWN_SITES))
+      return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (state words 0..1, timer keys 0..3, spawn sites 0..63)", i);
   }
+  // children: a spawn and a stop of a child each send one envelope through the case's tell slot
+  bool uses_child = false, ctl_tags = false;
+  auto ch_use = [&](uint32_t src) { uses_child |= src == AGX_V_SPAWNED || src == AGX_V_CHILD; };
+  auto tag_named = [&](uint32_t s1, int64_t k1, uint32_t cmp, uint32_t s2, int64_t k2) {
+    if (cmp == AGX_CMP_ANY) return;
+    ctl_tags |= s1 == AGX_V_TAG && k1 == 0 && s2 == AGX_V_CONST && (k2 == (int64_t)AGX_TAG_CREATE || k2 == (int64_t)AGX_TAG_STOP);
+    ctl_tags |= s2 == AGX_V_TAG && k2 == 0 && s1 == AGX_V_CONST && (k1 == (int64_t)AGX_TAG_CREATE || k1 == (int64_t)AGX_TAG_STOP);
+  };
+  for (uint32_t c = 0; c < n_cases; ++c) {
+    const agx_case& C = cases[c];
+    ch_use(C.src1); ch_use(C.src2); ch_use(C.src3); ch_use(C.src4);
+    tag_named(C.src1, C.k1, C.cmp1, C.src2, C.k2);
+    tag_named(C.src3, C.k3, C.cmp2, C.src4, C.k4);
+    uint32_t sends = 0;
+    bool child_op = false;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      sends += acts[i].op == AGX_A_TELL || acts[i].op == AGX_A_SPAWN || acts[i].op == AGX_A_STOP_CHILD;
+      child_op |= acts[i].op == AGX_A_SPAWN || acts[i].op == AGX_A_STOP_CHILD;
+    }
+    if (child_op && sends > 1u)
+      return set_err(AGX_EINVAL, "compiled behaviours: case %u holds %u of tell, spawn and stop-child; an engine with children "
+                     "has max_emit 1", c, sends);
+  }
+  for (uint32_t i = 0; i < n_acts; ++i) {
+    ch_use(acts[i].src);
+    ch_use(acts[i].dsrc);
+    uses_child |= acts[i].op == AGX_A_SPAWN || acts[i].op == AGX_A_STOP_CHILD;
+    const uint32_t t = acts[i].or_mask >> 24;
+    ctl_tags |= t == AGX_TAG_CREATE || t == AGX_TAG_STOP;
+  }
+  if (e->d_child && ctl_tags)
+    return set_err(AGX_EINVAL, "compiled behaviours: message tags 0xFD and 0xFC are reserved for Create and Stop envelopes on "
+                   "an engine with children");
   // the apply kernels reserve kmax tell slots per message (single pass: the tell overwrites the
   // message's own consumed LDS slot; otherwise a bucket's tells live in [lo*kmax, (lo+cnt)*kmax)):
   // a case that tells more often would overwrite unprocessed mail or the next bucket's tells
@@ -3772,6 +4051,8 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     }
     e->beh_sv_tells = std::max(e->beh_sv_tells, fs + sg);
   }
+  e->beh_child = uses_child;  // (checked against agx_set_children at agx_run)
+  e->beh_ctl_tags = ctl_tags;
   e->beh_watch = false;  // a watch action or a signal case (checked against agx_set_death_watch at agx_run)
   for (uint32_t c = 0; c < n_cases; ++c) e->beh_watch |= (cases[c].result & AGX_CASE_SIGNAL) != 0 && !sv_signal(cases[c]);
   for (uint32_t i = 0; i < n_acts; ++i) e->beh_watch |= acts[i].op >= AGX_A_WATCH && acts[i].op <= AGX_A_UNWATCH;
@@ -3941,6 +4222,9 @@ agx_status agx_stage_tells(agx_engine* e, const uint32_t* dst, const uint32_t* s
       return set_err(AGX_EINVAL, "tell %zu: message tag 0xFF is reserved for timer messages on an engine with timers", i);
     if (e->wd_slots && (payload[i] >> 24) == AGX_TAG_WATCH)
       return set_err(AGX_EINVAL, "tell %zu: message tag 0xFE is reserved for Terminated envelopes on an engine with death watch", i);
+    if (e->d_child && ((payload[i] >> 24) == AGX_TAG_CREATE || (payload[i] >> 24) == AGX_TAG_STOP))
+      return set_err(AGX_EINVAL, "tell %zu: message tags 0xFD and 0xFC are reserved for Create and Stop envelopes on an engine "
+                     "with children", i);
     ++take;
   }
   if (take) {
@@ -4023,6 +4307,9 @@ agx_status agx_tell(agx_engine* e, uint32_t dst, uint32_t src, uint32_t payload,
     return set_err(AGX_EINVAL, "tell: message tag 0xFF is reserved for timer messages on an engine with timers");
   if (e->wd_slots && (payload >> 24) == AGX_TAG_WATCH)
     return set_err(AGX_EINVAL, "tell: message tag 0xFE is reserved for Terminated envelopes on an engine with death watch");
+  if (e->d_child && ((payload >> 24) == AGX_TAG_CREATE || (payload >> 24) == AGX_TAG_STOP))
+    return set_err(AGX_EINVAL, "tell: message tags 0xFD and 0xFC are reserved for Create and Stop envelopes on an engine with "
+                   "children");
   const bool sched = e->tq.tell(dst, src, payload);
   if (schedule) *schedule = sched ? 1 : 0;
   return AGX_OK;

@@ -1439,6 +1439,163 @@ __device__ __forceinline__ void watch_tick_end(const BucketArgs& a, const WatchD
   }
 }
 
+// ---- children (agx_set_children): the control envelopes of tick `now` in bucket b, before
+// admission (Mailbox.run drains system messages first).  Message-parallel: every thread looks at four inbox
+// items; without a Create or Stop among the bucket's items (one scan) nothing else happens.  Else each control
+// item whose sender is its destination's computed parent lowers the actor's LDS word to its inbox position
+// (ds_min: the first such Create / Stop in inbox order is the one that counts); an actor-parallel step then
+// decides birth (alive, kind and state words as the site says: written to memory, the prefetch below reads
+// them after the barrier) and stop; last the control items leave the inbox: the rest keeps its order, the
+// segment starts move, `cnt` shrinks.  Every control item counts as delivered.
+template <bool kGather>
+__device__ __forceinline__ void child_classify(const BucketArgs& a, const BucketLds& L, const ChildDev& CD,
+                                               const WatchDev& WD, uint32_t b, uint32_t a0, uint32_t na, uint32_t now,
+                                               uint32_t& cnt, uint32_t& ndel) {
+  const DevParams& P = a.P;
+  const int tid = threadIdx.x;
+  constexpr uint32_t kNone = 0xFFFFFFFFu;
+  const uint4 k4 = reinterpret_cast<const uint4*>(L.key)[tid], s4 = reinterpret_cast<const uint4*>(L.src)[tid],
+              p4 = reinterpret_cast<const uint4*>(L.pay)[tid];
+  const uint32_t kk[kBIpt] = {k4.x, k4.y, k4.z, k4.w}, ss[kBIpt] = {s4.x, s4.y, s4.z, s4.w},
+                 pp[kBIpt] = {p4.x, p4.y, p4.z, p4.w};
+  uint32_t ctl = 0, nctl = 0;  // bit r: item tid * 4 + r is a control envelope
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) {
+    const uint32_t q = tid * kBIpt + r, tag = pp[r] >> 24;
+    if (q < cnt && (tag == AGX_TAG_CREATE || tag == AGX_TAG_STOP)) {
+      ctl |= 1u << r;
+      ++nctl;
+    }
+  }
+  uint32_t tot;
+  const uint32_t cex = block_excl_sum<kBThreads>(nctl, L.scratch, &tot);
+  if (!tot) return;  // (block-uniform)
+  uint32_t* const cmin = reinterpret_cast<uint32_t*>(L.U);  // [kBucket] the first Create from the parent
+  uint32_t* const smin = cmin + kBucket;                    // [kBucket] the first Stop from the parent
+  uint32_t* const pre = smin + kBucket;                     // [kBucket + 1] the items that stay, before item q
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) {
+    cmin[tid * kBAct + j] = kNone;
+    smin[tid * kBAct + j] = kNone;
+  }
+  {
+    uint32_t run = tid * kBIpt - cex;  // (the items before this thread's that stay)
+#pragma unroll
+    for (int r = 0; r < kBIpt; ++r) {
+      pre[tid * kBIpt + r] = run;
+      run += ((ctl >> r) & 1u) ? 0u : 1u;
+    }
+    if (tid == kBThreads - 1) pre[kBucket] = run;
+  }
+  __syncthreads();
+  const uint32_t amask = (1u << a.bb) - 1u;
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) {
+    if (!((ctl >> r) & 1u)) continue;
+    const uint32_t q = tid * kBIpt + r, la = kk[r] & amask;
+    if (la >= na || ss[r] != CD.parent_of(a0 + la)) continue;  // (parent_of: none for an id outside every child block)
+    if ((pp[r] >> 24) == AGX_TAG_CREATE) {
+      if (((pp[r] >> AGX_SPAWN_ARG_BITS) & (AGX_MAX_SPAWN_SITES - 1u)) < CD.nsites) atomicMin(&cmin[la], q);
+    } else {
+      atomicMin(&smin[la], q);
+    }
+  }
+  __syncthreads();
+  uint32_t nborn = 0, nstop = 0;
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) {
+    const uint32_t la = tid * kBAct + j, l = a0 + la;
+    if (la >= na) continue;
+    const uint32_t c = cmin[la], s = smin[la];
+    if (c == kNone && s == kNone) continue;
+    uint32_t cw = CD.sc[l];
+    if (c != kNone && !(cw & kCdCreated)) {  // born: before admission
+      const uint32_t pv = L.pay[c];
+      const uint32_t* S = CD.site((pv >> AGX_SPAWN_ARG_BITS) & (AGX_MAX_SPAWN_SITES - 1u));
+      const uint64_t w0 = (((uint64_t)S[3] << 32) | S[2]) + (pv & AGX_SPAWN_ARG_MASK);
+      const uint64_t w1 = (S[1] & kCdSiteParent) ? (uint64_t)L.src[c] : (((uint64_t)S[5] << 32) | S[4]);
+      const uint8_t ab = L.alive[la] | 1u;
+      L.alive[la] = ab;
+      P.alive[l] = ab;
+      P.kind[l] = (uint8_t)S[0];
+      stg64(P.state, sidx(P, l, 0), w0);
+      if (P.W > 1) stg64(P.state, sidx(P, l, 1), w1);
+      cw |= kCdCreated;
+      CD.sc[l] = cw;
+      ++nborn;
+    }
+    if (s != kNone && (cw & kCdCreated) && (L.alive[la] & 1u)) {  // context.stop by the parent: as Behaviors.stopped
+      const uint8_t ab = L.alive[la] & 0xFEu;
+      L.alive[la] = ab;
+      if constexpr (kGather) P.alive[l] = ab;
+      else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+      WD.stop(l, b, now);
+      ++nstop;
+    }
+  }
+  uint32_t tb, ts;
+  block_excl_sum2<kBThreads>(nborn, nstop, L.scratch, &tb, &ts);  // (syncs: L.pay / L.src [c] are read)
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) {
+    const uint32_t q = tid * kBIpt + r;
+    if (q < cnt && !((ctl >> r) & 1u)) {
+      const uint32_t to = pre[q];  // (<= q: only items already in registers are overwritten)
+      L.key[to] = kk[r];
+      L.src[to] = ss[r];
+      L.pay[to] = pp[r];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) L.seg[tid * kBAct + j] = pre[L.seg[tid * kBAct + j]];
+  if (tid == 0) {
+    L.seg[kBucket] = pre[L.seg[kBucket]];
+    if (tb) atomicAdd(CD.ctr(kCcCreated), (unsigned long long)tb);
+    if (ts) atomicAdd(CD.ctr(kCcChildStops), (unsigned long long)ts);
+    if (tot - tb - ts) atomicAdd(CD.ctr(kCcDiscarded), (unsigned long long)(tot - tb - ts));
+    if (tb != ts) atomicAdd(CD.nlive(b), tb - ts);  // (wraps for a negative difference: the sum is what counts)
+  }
+  ndel += nctl;
+  cnt -= tot;
+  __syncthreads();
+}
+
+// the end of tick `now` in bucket b: a parent's stop takes its children.  The skip rule is
+// watch_tick_end's: unless an actor stopped in tick now - 1 and the bucket holds a live created child the block
+// reads two words.  Else it gathers died[parent] for the bucket's live children (uncoalesced, one load per
+// child; children of one parent are neighbours and share it); only death ticks below `now` count, written in
+// earlier launches.  A bucket with a live child keeps the engine's "watching" word of the tick up to date: the
+// stop rule of the next tick's entry reads it.
+template <bool kGather>
+__device__ __forceinline__ void child_tick_end(const BucketArgs& a, const BucketLds& L, const ChildDev& CD,
+                                               const WatchDev& WD, uint32_t b, uint32_t a0, uint32_t na, uint32_t now) {
+  const DevParams& P = a.P;
+  const int tid = threadIdx.x;
+  __syncthreads();  // (watch_tick_end's last stores; the drains' death ticks)
+  const bool scan = WD.ld(WD.base + kWdStopW + ((now - 1u) & 1u)) == now - 1u && WD.ld(CD.nlive(b)) != 0u;
+  uint32_t ns = 0, tot = 0;
+  if (scan) {  // (block-uniform)
+#pragma unroll
+    for (int j = 0; j < kBAct; ++j) {
+      const uint32_t la = tid * kBAct + j, l = a0 + la;
+      if (la >= na || !(CD.sc[l] & kCdCreated) || WD.ld(WD.died + l) != kWdNone) continue;
+      const uint32_t p = CD.parent_of(l);
+      if (p == kWdNone || !WD.dead_before(p, now)) continue;
+      if constexpr (kGather) P.alive[l] &= 0xFEu;  // (a byte of this lane's own actor; bits 1..3: mailbox class)
+      else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+      WD.stop(l, b, now);
+      ++ns;
+    }
+    block_excl_sum<kBThreads>(ns, L.scratch, &tot);
+  }
+  if (tid == 0) {
+    if (tot) {
+      atomicSub(CD.nlive(b), tot);
+      atomicAdd(CD.ctr(kCcCascade), (unsigned long long)tot);
+    }
+    if (WD.ld(CD.nlive(b)) != 0u) WD.sto(WD.base + kWdAnyW + (now & 1u), now);
+  }
+}
+
 // kStash: deque-based mailboxes (agx_set_stash).  The inbox segment of an actor then
 // starts with its window: the buffered / parked messages this superstep processes instead of mailbox
 // mail (stash_window; k_bucket_apply put them there).  With a window every admitted mailbox message
@@ -1480,6 +1637,18 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
   // PostStop signals; a message that neither fails nor stops touches none of the supervision storage.
   constexpr bool kSv = (KM & kSuperKM) != 0;
   static_assert(!kSv || (kLds && !kWide && !kOwner && !kStash && !kTm && !kWd), "supervision: single-rank fast launches, plain behaviours");
+  // kCh: children (agx_set_children), on top of death watch.  The tick's Create and Stop envelopes
+  // are consumed here, before admission: the classification below sees the inbox without them and the actors
+  // they gave birth to or stopped; compiled cases spawn and stop children; the end of the tick stops the
+  // children of stopped parents.
+  constexpr bool kCh = (KM & kChildKM) != 0;
+  static_assert(!kCh || kWd, "children: on the death-watch instantiations only");
+  ChildDev CD{};
+  if constexpr (kCh) {
+    CD = child_dev(P.watch, a.nb);
+    pre0 = pre1 = nullptr;  // (a born actor's state words are written to memory: the prefetch reads them there)
+    child_classify<kGather>(a, L, CD, WD, b, a0, na, tnow, cnt, acc[0]);
+  }
   uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
   auto ikey = [&](uint32_t q) -> uint32_t { return kLds ? L.key[q] : a.scr.key[lo + q]; };
@@ -2032,6 +2201,49 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           }
         }
         if (ndisc) atomicAdd(TD.ctr(1), (unsigned long long)ndisc);
+      } else if constexpr (kCh) {
+        // the death-watch drain below with compiled_apply_c: a case may spawn or stop a child; context.stop of a
+        // ref that is no child of the actor stops the actor (IllegalArgumentException); a created child that
+        // stops leaves the bucket's live-child count
+        uint32_t ndisc = 0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          bool sig = false;
+          ++ndel;
+          if ((pv >> 24) == AGX_TAG_WATCH) {
+            const uint32_t k = (pv >> 22) & 3u;
+            const size_t i = WD.at(k < WD.ns ? k : 0u, l);
+            const uint32_t s = k < WD.ns ? WD.st[i] : 0u;
+            if ((s & kWdStateMask) != kWdNotified || ((WD.gen[i] ^ pv) & kWdGenMask)) {
+              ++ndisc;
+              continue;
+            }
+            WD.st[i] = kWdFree;
+            sv = WD.wee[i];
+            sig = !(s & kWdHasMsg);
+            pv = sig ? AGX_SIGNAL_TERMINATED : WD.pay[i];
+          }
+          bool conflict = false, illegal = false;
+          uint32_t r;
+          if (kcur >= AGX_KIND_COMPILED) r = compiled_apply_c(P, WD, CD, l, b, kcur, self, wv, sv, pv, sig, conflict, illegal, em);
+          else r = sig ? AGX_RES_UNHANDLED : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          if (sig && r == AGX_RES_UNHANDLED) {  // the death pact
+            r = AGX_RES_STOPPED;
+            atomicAdd(WD.ctr(kWcPacts), 1ull);
+          }
+          if (conflict) atomicAdd(WD.ctr(kWcConflicts), 1ull);
+          if (illegal) atomicAdd(CD.ctr(kCcIllegal), 1ull);
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            WD.stop(l, b, tnow);
+            if (CD.sc[l] & kCdCreated) atomicSub(CD.nlive(b), 1u);
+            break;
+          }
+        }
+        if (ndisc) atomicAdd(WD.ctr(kWcDiscarded), (unsigned long long)ndisc);
       } else if constexpr (kWd) {
         // the drain with receivedTerminated (DeathWatch.scala:62-77): a Terminated envelope takes a drain slot
         // and counts as delivered; one whose slot is not notified, or of another generation, is discarded;
@@ -2182,6 +2394,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       }
     }
     if constexpr (kTm) timer_tick_end<kGather>(a, TD, b, a0, na, tnow, bltot, w, L.alive, L.scratch);
+    if constexpr (kCh) child_tick_end<kGather>(a, L, CD, WD, b, a0, na, tnow);  // (before the watch scan: the slots a cascade frees)
     if constexpr (kWd) watch_tick_end(a, WD, b, a0, na, tnow, bltot, w, kGather, L.scratch);
     if constexpr (kSv)  // (after the barrier: every drain of the bucket has read this launch's clock)
       if (tid == 0) P.super[kSvBucketOff + b] += 1u;
@@ -4853,6 +5066,10 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         __syncthreads();
         timer_tick_end<kGather>(a, TD, b, a0, na, TD.clock(b) + 1u, 0u, wpar, s_alive, scratch);
         __syncthreads();
+      }
+      if constexpr ((KM & kChildKM) != 0) {  // (and the children of a parent that stopped in the tick before)
+        const WatchDev WD = watch_dev(P.watch, a.nb, a.bb, P.n_global);
+        child_tick_end<kGather>(a, L, child_dev(P.watch, a.nb), WD, b, a0, na, WD.clock(b) + 1u);
       }
       if constexpr (kWd) {  // a tick without mail is still a tick: the clock, and the slots a death of the tick before answers
         const WatchDev WD = watch_dev(P.watch, a.nb, a.bb, P.n_global);

@@ -60,6 +60,9 @@ hipError_t agx_launch_apply_timers(uint32_t vid, uint32_t mode, dim3 grid, hipSt
 // launch the death-watch fast launch k_bucket_apply<V_ALL_COMPILED, mode, no skew, kWatch> (agx_set_death_watch): only
 // V_ALL_COMPILED in the modes M_FUSED / M_BYPASS is instantiated (hipErrorInvalidValue otherwise)
 hipError_t agx_launch_apply_watch(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
+// launch the children fast launch k_bucket_apply<V_ALL_COMPILED, mode, no skew, kWatch | kChild> (agx_set_children):
+// only V_ALL_COMPILED in the modes M_FUSED / M_BYPASS is instantiated (hipErrorInvalidValue otherwise)
+hipError_t agx_launch_apply_child(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
 // launch the supervision fast launch k_bucket_apply<V_ALL_COMPILED, mode, no skew, kSuper> (agx_set_supervision): only
 // V_ALL_COMPILED in the modes M_FUSED / M_BYPASS is instantiated (hipErrorInvalidValue otherwise)
 hipError_t agx_launch_apply_super(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);

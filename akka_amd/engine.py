@@ -316,6 +316,39 @@ class GpuEngine:
         check(self.lib.agx_read_supervision(self._h, actor_id, ctypes.byref(kind), *(_ptr(x, ctypes.c_uint32) for x in a)))
         return dict(initial_kind=int(kind.value), count=a[0], remaining=a[1])
 
+    def set_children(self, regions, sites) -> None:
+        """agx_set_children (an engine with death watch, before the first run): `regions` are (first_parent,
+        n_parents, first_child, max_children) -- the k-th spawn of parent p creates id first_child + (p -
+        first_parent) * max_children + k; `sites` are (kind, word-0 base, word-1 constant or None for the parent's
+        id), typed.Tables.spawn_sites has them.  Compiled behaviours may then context.spawn / context.stop."""
+        r = np.ascontiguousarray(np.asarray(list(regions), np.uint32).reshape(-1, 4))
+        st = np.zeros(max(len(sites), 1), np.dtype([("kind", "<u4"), ("flags", "<u4"), ("base0", "<u8"), ("word1", "<u8")]))
+        for i, (kind, base, w1) in enumerate(sites):
+            st[i] = (int(kind), 1 if w1 is None else 0, int(base), 0 if w1 is None else int(w1))
+        check(self.lib.agx_set_children(self._h, r.ctypes.data_as(ctypes.c_void_p), r.shape[0],
+                                        st.ctypes.data_as(ctypes.c_void_p), len(sites)))
+
+    def spawn_children(self, first: int, count: int, site: int, arg: int = 0) -> None:
+        """agx_spawn_children: every live actor of the range spawns once from `site` (the setup block,
+        Behaviors.setup { ctx => ctx.spawn(..) }); the Create arrives in the next tick."""
+        check(self.lib.agx_spawn_children(self._h, first, count, site, arg))
+
+    CHILDREN_INFO = ("spawned", "refused", "created", "child_stops", "cascade_stops", "illegal_stops", "discarded", "live")
+
+    def children_info(self) -> dict:
+        """agx_children_info: totals spawned / refused / created / child_stops / cascade_stops / illegal_stops /
+        discarded, and the created children alive now."""
+        v = [ctypes.c_uint64() for _ in range(8)]
+        check(self.lib.agx_children_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(self.CHILDREN_INFO, (int(x.value) for x in v)))
+
+    def read_children(self, actor_id: int) -> dict:
+        """agx_read_children: the actor's computed parent (0xFFFFFFFF: none), its spawn count, whether it was ever
+        created."""
+        v = [ctypes.c_uint32() for _ in range(3)]
+        check(self.lib.agx_read_children(self._h, actor_id, *(ctypes.byref(x) for x in v)))
+        return dict(zip(("parent", "spawn_count", "created"), (int(x.value) for x in v)))
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""

@@ -25,6 +25,10 @@ What lowers:
     restart.with_limit(n, within)``; a case may end in ``Behaviors.throw(exc)``, ``ExceptionType(name, parent)``
     declares the classes, and ``on_signal(PreRestart | PostStop, ...)`` handles the two signals
     (``Tables.supervisors`` -> engine.set_supervision);
+  * ``context.spawn(behavior, arg, word1=<const> | context.PARENT, into=field)``, ``context.stop(child)``,
+    ``context.child_at(x)`` and ``context.spawned`` (children on the death-watch engine): the
+    spawned behaviours are lowered with their parents, ``Tables.spawn_sites`` goes to engine.set_children, and a
+    case holds at most one of tell, spawn and stop;
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -66,6 +70,12 @@ MAX_EXCEPTION_CLASSES = 32
 MAX_SUPERVISORS = 4
 SIGNAL_PRERESTART, SIGNAL_POSTSTOP = 0xFE000002, 0xFE000003
 SUP_RESUME, SUP_RESTART, SUP_STOP = 1, 2, 3
+V_SPAWNED, V_CHILD = 9, 10   # engines with children: the spawn count; child number (value + k) mod the spawn count
+CHILD_NO_WORD = 2            # V_CHILD's `word` when the index is a constant (no state word)
+A_SPAWN, A_STOP_CHILD = 13, 14
+TAG_CREATE, TAG_STOP = 0xFD, 0xFC  # the tags of Create / Stop envelopes: reserved when the tables use children
+MAX_CHILD_REGIONS, MAX_SPAWN_SITES = 8, 64
+SPAWN_ARG_BITS = 18          # a spawn's argument: its low 18 bits are added to the site's word-0 base
 
 
 class AgxCase(ctypes.Structure):
@@ -163,6 +173,8 @@ class Action:
     val: Operand = Operand(V_CONST)
     dst: Operand | None = None
     or_mask: int = 0
+    site: object = None   # A_SPAWN: the _SpawnSite
+    into: bool = False    # A_SPAWN: state word `word` receives the child's id
 
 
 class Field(Operand):
@@ -372,6 +384,21 @@ class TimerScheduler:
         return Operand(V_TIMER, self._key(key)) == 1
 
 
+class _Parent:
+    """context.PARENT: a spawned child's state word 1 starts as its parent's id."""
+
+    def __repr__(self):
+        return "context.PARENT"
+
+
+@dataclass(frozen=True, eq=False)
+class _SpawnSite:
+    """What a child starts as: its behaviour, the base of state word 0, state word 1 (None: the parent's id)."""
+    behavior: "Behavior"
+    base: int
+    word1: int | None
+
+
 class ActorContext:
     """ActorContext[T]'s death watch (TY/scaladsl/ActorContext.scala watch / watchWith / unwatch; classic
     AA/dungeon/DeathWatch.scala:19-113) of the actor running the behaviour, symbolic: the calls return effects.
@@ -400,6 +427,48 @@ class ActorContext:
     def unwatch(self, ref) -> "Action":
         """context.unwatch(ref): a Terminated of it that is already enqueued is dropped at receipt."""
         return Action(A_UNWATCH, 0, Operand(V_CONST), self._ref(ref), 0)
+
+    # children (engine.set_children(regions, tables.spawn_sites); TY/scaladsl/ActorContext.scala spawnAnonymous / stop)
+    PARENT = _Parent()
+
+    def spawn(self, behavior, arg=0, word1=0, into=None, base: int = 0) -> "Action":
+        """context.spawn(behavior): the actor's next child starts in `behavior` with state word 0 = base + arg (the
+        low 18 bits of `arg`, an operand) and state word 1 = `word1` (a constant, or context.PARENT: the parent's
+        id).  `into`: a state field of the parent that receives the child's id (0xFFFFFFFF when the spawn is
+        refused: the actor lies in no parent range or its child block is full).  The child's id is fixed by the
+        engine's regions.  A case holds at most one of tell, spawn and stop."""
+        if not isinstance(behavior, Behavior):
+            raise CompileError(f"spawn takes a Behavior, not {behavior!r}")
+        if word1 is not self.PARENT and (not isinstance(word1, (int, np.integer)) or not 0 <= int(word1) < (1 << 64)):
+            raise CompileError(f"a child's word 1 is a u64 constant or context.PARENT, not {word1!r}")
+        if not isinstance(base, (int, np.integer)) or not 0 <= int(base) < (1 << 64):
+            raise CompileError(f"a spawn site's base is a u64 constant, not {base!r}")
+        if into is not None and not isinstance(into, Field):
+            raise CompileError(f"into= names a state field of the parent, not {into!r}")
+        a = lift(arg)
+        if a.src == V_CONST and not 0 <= a.k < (1 << SPAWN_ARG_BITS):
+            raise CompileError(f"a spawn argument has {SPAWN_ARG_BITS} bits: {a.k} does not fit")
+        return Action(A_SPAWN, into.word if into is not None else 0, a, None, 0,
+                      _SpawnSite(behavior, int(base), None if word1 is self.PARENT else int(word1)), into is not None)
+
+    def stop(self, ref) -> "Action":
+        """context.stop(child): the child stops at the start of the next tick.  A ref that is not one of the actor's
+        spawned children (the actor itself included) is the reference's IllegalArgumentException: the actor stops."""
+        return Action(A_STOP_CHILD, 0, Operand(V_CONST), self._ref(ref), 0)
+
+    def child_at(self, x) -> Ref:
+        """The actor's child number x mod its spawn count (x: a state field, + a constant, or a constant) -- the
+        routee of a round-robin pool; 0xFFFFFFFF (a dead letter) without children."""
+        if isinstance(x, Operand) and x.src == V_WORD:
+            return Ref(Operand(V_CHILD, x.word, x.k))
+        if isinstance(x, (int, np.integer)):
+            return Ref(Operand(V_CHILD, CHILD_NO_WORD, int(x)))
+        raise CompileError(f"child_at takes a state field or a constant, not {x!r}")
+
+    @property
+    def spawned(self) -> Operand:
+        """The number of children the actor has spawned so far."""
+        return Operand(V_SPAWNED)
 
 
 context = ActorContext()
@@ -719,6 +788,7 @@ class Tables:
     n_acts: int = 0
     supervisors: list = field(default_factory=list)  # per behaviour: its AgxSupervisor entries, inner first
     exception_classes: list = field(default_factory=list)  # the ExceptionTypes in use; the index is the class number
+    spawn_sites: list = field(default_factory=list)  # (kind, word-0 base, word 1 or None: the parent's id) -> engine.set_children
 
     @property
     def uses_supervision(self) -> bool:
@@ -760,6 +830,14 @@ class Tables:
             any(A_WATCH <= a.op <= A_UNWATCH for a in self.acts[:self.n_acts])
 
     @property
+    def uses_children(self) -> bool:
+        """The behaviours spawn, stop a child or read the spawn count: the engine needs engine.set_children(regions,
+        tables.spawn_sites) on top of engine.set_death_watch(n)."""
+        return any(a.op in (A_SPAWN, A_STOP_CHILD) or V_SPAWNED in (a.src, a.dsrc) or V_CHILD in (a.src, a.dsrc)
+                   for a in self.acts[:self.n_acts]) or \
+            any(s in (V_SPAWNED, V_CHILD) for c in self.cases[:int(self.first[-1])] for s in (c.src1, c.src2, c.src3, c.src4))
+
+    @property
     def initial_timers(self) -> list:
         """with_timers' setup starts: (kind, key, periodic, delay, payload) -- actors registered with `kind`
         start timer `key` when they start (engine.start_timers on their range, before the first run)."""
@@ -785,6 +863,7 @@ def _reachable(roots) -> list:
         todo.extend(c.result for c in b.cases if isinstance(c.result, Behavior))
         todo.extend(c.result.target for c in b.cases
                     if isinstance(c.result, _UnstashAll) and isinstance(c.result.target, Behavior))
+        todo.extend(e.site.behavior for c in b.cases for e in c.effects if isinstance(e, Action) and e.site is not None)
     return order
 
 
@@ -806,6 +885,7 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
         raise CompileError(f"more than {MAX_EXCEPTION_CLASSES} exception classes")
     exc_id = {id(x): i for i, x in enumerate(excs)}
     cases, acts, first = [], [], [0]
+    sites = []  # the spawn sites in use, in order of appearance: (behaviour index, base, word 1)
     for b in behs:
         for c in b.cases:
             t = c.tests + [ALWAYS] * (2 - len(c.tests))
@@ -831,6 +911,15 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
                                  result=code, next=nxt, act_first=len(acts), act_count=len(c.effects)))
             for e in c.effects:
                 d = e.dst or Operand(V_CONST)
+                if e.op == A_SPAWN:  # dword: the site; pad0: the word `word` receives the child's id
+                    key = (index[id(e.site.behavior)], e.site.base, e.site.word1)
+                    if key not in sites:
+                        if len(sites) >= MAX_SPAWN_SITES:
+                            raise CompileError(f"more than {MAX_SPAWN_SITES} spawn sites")
+                        sites.append(key)
+                    acts.append(AgxAct(op=e.op, word=e.word, src=e.val.src, sword=e.val.word, k=e.val.k,
+                                       dsrc=V_CONST, dword=sites.index(key), dk=0, pad0=1 if e.into else 0))
+                    continue
                 acts.append(AgxAct(op=e.op, word=e.word, src=e.val.src, sword=e.val.word, k=e.val.k,
                                    dsrc=d.src, dword=d.word, dk=d.k, or_mask=e.or_mask))
         first.append(len(cases))
@@ -839,6 +928,7 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
     t = Tables(behs, (AgxCase * max(len(cases), 1))(*cases), (AgxAct * max(len(acts), 1))(*acts),
                np.asarray(first, dtype=np.uint32), len(acts))
     t.exception_classes = excs
+    t.spawn_sites = [(KIND_COMPILED + bi, base, w1) for bi, base, w1 in sites]
     for b in behs:  # a supervisor of a class catches it and its descendants: the hierarchy as masks
         row = []
         for sv in b.supervisors:
@@ -891,6 +981,26 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
                 if cmp == CMP_EQ and ((s1 == V_TAG and k1 == 0 and s2 == V_CONST and k2 == TAG_WATCH) or
                                       (s2 == V_TAG and k2 == 0 and s1 == V_CONST and k1 == TAG_WATCH)):
                     raise CompileError("message tag 0xFE is reserved for Terminated in behaviours that use death watch")
+    if t.uses_children:  # on the death-watch engine: max_emit 1, tags 0xFD / 0xFC are the Create / Stop envelopes
+        if t.timer_keys or t.stash_capacity or t.uses_supervision:
+            raise CompileError("children live on the death-watch engine, which shares an engine with neither timers, a "
+                               "stash nor supervision: the behaviours use children and one of them")
+        if max_emit is not None and max_emit > 1:
+            raise CompileError(f"children need max_emit = 1, not {max_emit}")
+        for c in cases:
+            n = sum(1 for j in range(c.act_first, c.act_first + c.act_count) if acts[j].op in (A_TELL, A_SPAWN, A_STOP_CHILD))
+            if n > 1:
+                raise CompileError(f"a case holds {n} of tell, spawn and stop: each sends one envelope, and an engine "
+                                   "with children has max_emit 1")
+        for a in acts:
+            if a.or_mask >> 24 in (TAG_CREATE, TAG_STOP):
+                raise CompileError("message tags 0xFD and 0xFC are reserved for Create and Stop in behaviours that use children")
+        for c in cases:
+            for s1, k1, cmp, s2, k2 in ((c.src1, c.k1, c.cmp1, c.src2, c.k2), (c.src3, c.k3, c.cmp2, c.src4, c.k4)):
+                if cmp != CMP_ANY and ((s1 == V_TAG and k1 == 0 and s2 == V_CONST and k2 in (TAG_CREATE, TAG_STOP)) or
+                                       (s2 == V_TAG and k2 == 0 and s1 == V_CONST and k1 in (TAG_CREATE, TAG_STOP))):
+                    raise CompileError("message tags 0xFD and 0xFC are reserved for Create and Stop in behaviours that use "
+                                       "children")
     if max_emit is not None and t.max_tells > max(1, max_emit):
         raise CompileError(f"a case tells {t.max_tells} times per message but max_emit is {max_emit}")
     return t

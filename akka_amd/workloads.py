@@ -58,6 +58,10 @@ class Workload:
     # supervision (agx_set_supervision): {"rows": per compiled behaviour its supervisor entries, inner first
     # (typed.Tables.supervisors)} -- empty: no supervision
     supervision: dict = field(default_factory=dict)
+    # children (agx_set_children / agx_spawn_children, on top of `watch`): {"regions": [(first_parent, n_parents,
+    # first_child, max_children)], "sites": typed.Tables.spawn_sites, "spawns": [(first, count, site, arg)]} --
+    # empty: no children
+    children: dict = field(default_factory=dict)
 
     def engine_kwargs(self) -> dict:
         """Semantic parameters (shared by the GPU engine and the CPU oracles)."""
@@ -95,10 +99,15 @@ class Workload:
                 target.start_timers(first, count, key, delay, periodic=periodic, delays=delays, payload=payload)
         if self.watch:  # (empty: targets without the calls are unaffected)
             target.set_death_watch(self.watch["n_slots"])
+            if self.children:  # (before the setup watches: a child block's ids are "not created yet", not "dead")
+                target.set_children(self.children["regions"], self.children["sites"])
             for first, count, watchees, offset, message in self.watch.get("starts", ()):
                 target.start_watch(first, count, watchees, offset=offset, message=message)
         if self.supervision:  # (empty: targets without the call are unaffected)
             target.set_supervision(self.supervision["rows"])
+        if self.children:  # (empty: targets without the calls are unaffected; set_children: with the watch above)
+            for first, count, site, arg in self.children.get("spawns", ()):
+                target.spawn_children(first, count, site, arg)
         if self.fanout is not None:
             target.set_fanout(*self.fanout)
         if self.graph is not None:
@@ -760,3 +769,103 @@ def flaky_workers(n: int = 1 << 20, hops: int = 8, poison_every: int = 16, max_p
     return Workload("flaky_workers", n, 2, 1, throughput, 0, [(0, n, tb.kind_of(b), init)], behaviors=tb,
                     tells=(dst, np.full(dst.size, NO_SENDER, np.uint32), pay), outbound=(n, max(n_host, 1)),
                     bucket_actors=bucket_actors, supervision={"rows": tb.supervisors})
+
+
+# ------------------------------------------------------------------ children
+CH_SPAWN, CH_STOP, CH_WORK = 1, 2, 3
+
+
+def spawn_tree_levels(depth: int, fanout: int) -> list:
+    """(first id, count) of every level of spawn_tree(depth, fanout), the root first."""
+    out, first = [], 0
+    for lv in range(depth + 1):
+        out.append((first, fanout ** lv))
+        first += fanout ** lv
+    return out
+
+
+def spawn_tree(depth: int = 4, fanout: int = 32, throughput: int = 3, bucket_actors: int = 0) -> Workload:
+    """A tree that grows on the device, level by level (at most 8 levels below the root: one region each).  Only
+    the root is registered.  A node holds its remaining depth in state word 0 and its parent in word 1; on Spawn
+    it spawns one child with depth - 1 while its depth is above 0 (a leaf leaves Spawn unhandled), on Stop it stops.
+    With max_emit = 1 a message has one envelope to send and the Create takes it, so the host tells every node of
+    a level `fanout` Spawn messages (grow_tree) instead of the nodes telling each other.  Stopping the root then
+    takes the tree down one level per tick."""
+    from . import typed
+    if not 1 <= depth <= 8:
+        raise ValueError("spawn_tree: depth 1..8 (one region per level)")
+    st = typed.State("depth", "parent")
+    B, ctx = typed.Behaviors, typed.context
+    node = typed.Behavior("tree_node", st)
+    (typed.ReceiveBuilder.create(st)
+     .on_any_message(lambda m, s: [ctx.spawn(node, arg=s.depth - 1, word1=ctx.PARENT), B.same],
+                     test=lambda m: m.tag == CH_SPAWN, when=lambda m, s: s.depth > 0)
+     .on_any_message(lambda m, s: [B.stopped], test=lambda m: m.tag == CH_STOP)
+     .on_any_message(lambda m, s: [B.unhandled])
+     .build(into=node))
+    tb = typed.compile_behaviors([node], max_emit=1)
+    lv = spawn_tree_levels(depth, fanout)
+    regions = [(lv[i][0], lv[i][1], lv[i + 1][0], fanout) for i in range(depth)]
+    n = lv[-1][0] + lv[-1][1]
+    return Workload("spawn_tree", n, 2, 1, throughput, 0,
+                    [(0, 1, tb.kind_of(node), np.asarray([[depth, 0xFFFFFFFF]], np.uint64))], behaviors=tb,
+                    bucket_actors=bucket_actors, watch={"n_slots": 1},
+                    children={"regions": regions, "sites": tb.spawn_sites})
+
+
+def grow_tree(target, depth: int, fanout: int, run=None):
+    """Grow spawn_tree(depth, fanout) on `target`: per level, `fanout` Spawn messages to each of its nodes, then a
+    run to quiescence; -> the stats of every run (`run(target)` replaces target.run())."""
+    out = []
+    for first, count in spawn_tree_levels(depth, fanout)[:-1]:
+        dst = np.repeat(np.arange(first, first + count, dtype=np.uint32), fanout)
+        target.tell(dst, np.full(dst.size, CH_SPAWN << 24, np.uint32), np.full(dst.size, NO_SENDER, np.uint32))
+        out.append(target.run() if run is None else run(target))
+    return out
+
+
+def pool_router(n_routers: int = 1 << 14, pool_size: int = 16, throughput: int = 3, bucket_actors: int = 0,
+                host_id: int | None = None) -> Workload:
+    """Routers.pool(pool_size) with round-robin logic (PoolRouterImpl.scala:60-64, RoutingLogic.scala:42-53):
+    router r (ids 0..n_routers - 1) spawns its routees in the setup block (ids n_routers + r * pool_size + k),
+    watches them and forwards every Work message to child number `next`, then next += 1.  It stops when its last
+    routee has (RoutersSpec.scala:104): it counts the Terminated signals.  An actor has at most four watch slots,
+    so a router watches its first four routees (pool_watch_starts) and, at every Terminated, the next one not yet
+    watched; one that is dead already answers a tick later.  A routee counts its Work, keeps the last payload
+    (and echoes it to `host_id` when given) and stops on Stop."""
+    from . import typed
+    B, ctx = typed.Behaviors, typed.context
+    rs = typed.State("count", "last")
+    echo = (lambda m: [typed.actor_ref(host_id).tell(m.payload)]) if host_id is not None else (lambda m: [])
+    routee = (typed.ReceiveBuilder.create(rs)
+              .on_any_message(lambda m, s: [B.stopped], test=lambda m: m.tag == CH_STOP)
+              .on_any_message(lambda m, s: [s.count.inc(), s.last.set(m.payload)] + echo(m) + [B.same],
+                              test=lambda m: m.tag == CH_WORK)
+              .on_any_message(lambda m, s: [B.unhandled])
+              .build("routee"))
+    st = typed.State("next", "dead")
+    slots = min(pool_size, typed.MAX_WATCH_SLOTS)
+    router = typed.Behavior("pool_router", st)
+    setup = ctx.spawn(routee, word1=ctx.PARENT)  # the setup block's spawn: its site is site 0 (agx_spawn_children)
+    (typed.ReceiveBuilder.create(st)
+     .on_any_message(lambda m, s: [ctx.child_at(s.next).tell(m.payload), s.next.inc(), B.same], test=lambda m: m.tag == CH_WORK)
+     .on_any_message(lambda m, s: [setup, B.same], test=lambda m: m.tag == CH_SPAWN)
+     .on_any_message(lambda m, s: [B.unhandled])
+     .on_signal(typed.Terminated, lambda sig, s: [s.dead.inc(), B.stopped], when=lambda sig, s: s.dead + 1 >= pool_size)
+     .on_signal(typed.Terminated, lambda sig, s: [s.dead.inc(), ctx.watch(ctx.child_at(s.dead + (slots - 1))), B.same],
+                when=lambda sig, s: s.dead + slots < pool_size)
+     .on_signal(typed.Terminated, lambda sig, s: [s.dead.inc(), B.same])
+     .build(into=router))
+    tb = typed.compile_behaviors([router], max_emit=1)
+    n = n_routers * (1 + pool_size)
+    return Workload("pool_router", n, 2, 1, throughput, 0, [(0, n_routers, tb.kind_of(router), None)], behaviors=tb,
+                    bucket_actors=bucket_actors, outbound=(host_id, 1) if host_id is not None else None,
+                    watch={"n_slots": slots, "starts": pool_watch_starts(n_routers, pool_size)},
+                    children={"regions": [(0, n_routers, n_routers, pool_size)], "sites": tb.spawn_sites,
+                              "spawns": [(0, n_routers, 0, 0)] * pool_size})
+
+
+def pool_watch_starts(n_routers: int, pool_size: int) -> list:
+    """pool_router's setup watches: router r watches its routees 0 .. min(pool_size, 4) - 1."""
+    r = np.arange(n_routers, dtype=np.uint32)
+    return [(0, n_routers, n_routers + r * pool_size + k, 0, None) for k in range(min(pool_size, 4))]

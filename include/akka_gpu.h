@@ -131,7 +131,13 @@ enum agx_operand { AGX_V_CONST = 0, AGX_V_PAYLOAD = 1, AGX_V_TAG = 2, AGX_V_ARG 
                    AGX_V_STASH = 7 /* the size of the actor's stash buffer (StashBuffer.size); 0 on an
                                       engine without a deque-based mailbox class (agx_set_stash) */,
                    AGX_V_TIMER = 8 /* 1 if the actor's timer slot `word` (the key) is active, else 0
-                                      (TimerScheduler.isTimerActive); engines with timers (agx_set_timers) */ };
+                                      (TimerScheduler.isTimerActive); engines with timers (agx_set_timers) */,
+                   /* engines with children (agx_set_children): */
+                   AGX_V_SPAWNED = 9 /* the actor's spawn count */,
+                   AGX_V_CHILD = 10 /* the id of child number (value + k) mod spawn count of the actor; value =
+                                       state word `word` (0, 1) or 0 (word = AGX_CHILD_NO_WORD); 0xFFFFFFFF with no
+                                       children */ };
+#define AGX_CHILD_NO_WORD 2u
 enum agx_cmp { AGX_CMP_ANY = 0, AGX_CMP_EQ = 1, AGX_CMP_NE = 2, AGX_CMP_LT = 3, AGX_CMP_LE = 4, AGX_CMP_GT = 5,
                AGX_CMP_GE = 6 };
 enum agx_action_op {
@@ -157,8 +163,21 @@ enum agx_action_op {
    * payload ((u32)operand, or (operand & 0xFFFFFF) | or_mask). */
   AGX_A_WATCH = 10,      /* context.watch(ref)          (DeathWatch.scala:23-34)  */
   AGX_A_WATCH_WITH = 11, /* context.watchWith(ref, msg) (DeathWatch.scala:36-47)  */
-  AGX_A_UNWATCH = 12     /* context.unwatch(ref)        (DeathWatch.scala:49-60)  */
+  AGX_A_UNWATCH = 12,    /* context.unwatch(ref)        (DeathWatch.scala:49-60)  */
+  /* Children (engines with children, agx_set_children).  SPAWN: `dword` is the spawn site, the operand (src, sword,
+   * k) is the argument, whose low AGX_SPAWN_ARG_BITS bits are added to the site's word-0 base; with pad0 & 1 the
+   * state word `word` receives the child's id, 0xFFFFFFFF when the spawn is refused.  STOP_CHILD: the ref is the
+   * d-operand, as a WATCH's.  Each sends one envelope through the case's tell slot: with max_emit = 1 a case
+   * holds at most one of TELL, SPAWN and STOP_CHILD. */
+  AGX_A_SPAWN = 13,      /* context.spawn(site behaviour) (TY/scaladsl/ActorContext.scala spawnAnonymous) */
+  AGX_A_STOP_CHILD = 14  /* context.stop(ref)           (ActorContextAdapter.scala:79-106) */
 };
+#define AGX_TAG_CREATE 0xFDu    /* the message tag of a Create envelope: reserved on an engine with children */
+#define AGX_TAG_STOP 0xFCu      /* the message tag of a Stop envelope: reserved on an engine with children */
+#define AGX_MAX_CHILD_REGIONS 8u
+#define AGX_MAX_SPAWN_SITES 64u
+#define AGX_SPAWN_ARG_BITS 18u  /* a Create's payload: AGX_TAG_CREATE << 24 | site << 18 | argument */
+#define AGX_SPAWN_ARG_MASK 0x3FFFFu
 #define AGX_TAG_TIMER 0xFFu     /* the message tag (payload >> 24) of a TimerMsg: reserved on an engine with timers */
 #define AGX_MAX_TIMER_KEYS 4u
 #define AGX_TAG_WATCH 0xFEu     /* the message tag of a Terminated envelope: reserved on an engine with death watch */
@@ -650,6 +669,67 @@ agx_status agx_supervision_info(agx_engine* eng, uint64_t* failures, uint64_t* r
  * deadline).  Levels past n_levels read as 0 / 0xFFFFFFFF.  Any pointer may be NULL. */
 agx_status agx_read_supervision(agx_engine* eng, uint64_t actor_id, uint32_t* initial_kind, uint32_t count[4],
                                 uint32_t remaining[4]);
+
+/* Child actors (context.spawn / context.stop(child) and the parent's stop taking its children: AA/dungeon/
+ * Children.scala, TY/internal/adapter/ActorContextAdapter.scala:79-106, pinned by ActorContextSpec.scala:214-240,
+ * 336-428,656-, GracefulStopSpec.scala:20-48, RoutersSpec.scala:40-104; DESIGN.md 2.6 has the contract).
+ * Children live on an engine with death watch: agx_set_children is AGX_EINVAL before agx_set_death_watch, and
+ * the slot count cannot change afterwards.  They inherit that engine's refusals (n_ranks > 1, max_emit > 1,
+ * timers, a stash, priority tables, supervision, CRDT kinds, the one-tile limit of a bucket's inbox).
+ * Ids are laid out by regions: the k-th spawn (k = 0, 1, ...) of parent p of a region creates id first_child +
+ * (p - first_parent) * max_children + k; ids are never reused and the parent of an id is computed from this
+ * formula.  Parent ranges are pairwise disjoint; child blocks (n_parents * max_children ids from first_child) are
+ * pairwise disjoint and lie in [0, n_actors); a region's child block may lie inside another region's parent range
+ * (grandchildren) but not overlap its own; child-block ids must be unregistered when the first run starts, and
+ * agx_register_range into a child block is refused (either call order).  Their death tick starts as "none" (not
+ * "dead before tick 1"): a watch on an id that is never created never fires (the one bounded difference).
+ * A spawn site says what a child starts as: its kind (a compiled behaviour), state word 0 = base0 + the spawn's
+ * argument (low AGX_SPAWN_ARG_BITS bits), state word 1 = word1 or, with AGX_SITE_WORD1_PARENT, the parent's id.
+ * AGX_A_SPAWN by actor p at tick s: p in no parent range or p's block full -> refused (`refused`, the receiving
+ * word reads 0xFFFFFFFF, nothing is sent, the run goes on); else the spawn count and `spawned` grow, the word takes
+ * the child id and a Create envelope (sender p, payload AGX_TAG_CREATE << 24 | site << 18 | argument) goes to the
+ * child through the case's tell slot and counts as emitted.  AGX_A_STOP_CHILD(ref): ref one of the actor's spawned
+ * children -> a Stop envelope (AGX_TAG_STOP << 24) the same way; any other value, the actor itself included, is
+ * the IllegalArgumentException: the rest of the case's actions is skipped, the message counts as delivered, the
+ * actor stops, `illegal_stops` grows.
+ * Receipt: Create and Stop envelopes are system messages.  One arriving in tick t is consumed at the start of
+ * the tick, wherever it stands in the inbox; it takes no mailbox capacity and no drain slot, is never queued, a
+ * dead letter or unhandled, and counts as delivered.  All Creates of an actor are looked at before its Stops, each
+ * in inbox order.  A Create from the id's computed parent, for an id never created, with a valid site, is
+ * effective: the actor is alive from this tick on with the site's kind and state (`created`), and the tick's other
+ * mail is admitted as for any live actor.  A Stop from the computed parent to a live created child is effective:
+ * the child stops at the start of the tick as by Behaviors.stopped (death tick t, watch slots freed,
+ * `child_stops`), and all its mail of the tick is dead letters.  Every other Create or Stop: `discarded`.
+ * At the end of tick e every live created child whose computed parent has a death tick <= e - 1 stops (death tick
+ * e, slots freed, `cascade_stops`): a subtree dies one level per tick, and a parent's watchers may hear of its
+ * death before its deep descendants are gone (the reference's parent terminates after its children: the second
+ * bounded difference).  The scan runs only in a tick after one in which an actor stopped in the engine.
+ * The engine is active at the entry of tick t also if an actor stopped in t - 1 while a created child was alive at
+ * the end of t - 1.  Conservation keeps its form.  Tags 0xFD and 0xFC are reserved like 0xFE.
+ * Call before the first agx_run (AGX_ESTATE afterwards).  AGX_EINVAL: no death watch, more than
+ * AGX_MAX_CHILD_REGIONS regions or AGX_MAX_SPAWN_SITES sites, a layout rule broken, a registered id in a child
+ * block, a site whose kind is no compiled behaviour kind. */
+typedef struct agx_child_region {
+  uint32_t first_parent, n_parents, first_child, max_children;
+} agx_child_region;
+#define AGX_SITE_WORD1_PARENT 1u
+typedef struct agx_spawn_site {
+  uint32_t kind, flags;
+  uint64_t base0, word1;
+} agx_spawn_site;
+agx_status agx_set_children(agx_engine* eng, const agx_child_region* regions, uint32_t n_regions,
+                            const agx_spawn_site* sites, uint32_t n_sites);
+/* The setup block (Behaviors.setup { ctx => ctx.spawn(..) }), before the first run or between runs: every live
+ * actor of [first_parent, first_parent + count) spawns once by the rules of AGX_A_SPAWN; its Create arrives in the
+ * next tick.  Such a Create travels with the host-staged tells and counts as staged, not emitted. */
+agx_status agx_spawn_children(agx_engine* eng, uint64_t first_parent, uint64_t count, uint32_t site, uint32_t arg);
+/* Totals since agx_create (see above) and the created children alive right now.  Any pointer may be NULL. */
+agx_status agx_children_info(agx_engine* eng, uint64_t* spawned, uint64_t* refused, uint64_t* created,
+                             uint64_t* child_stops, uint64_t* cascade_stops, uint64_t* illegal_stops,
+                             uint64_t* discarded, uint64_t* live);
+/* One actor: its computed parent (0xFFFFFFFF: none), its spawn count, whether it was ever created. */
+agx_status agx_read_children(agx_engine* eng, uint64_t actor_id, uint32_t* parent, uint32_t* spawn_count,
+                             uint32_t* created);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
