@@ -1,6 +1,7 @@
 // agx_apply.hip — k_bucket_apply instantiations of one variant group (agx_variants.h).
-// Built once per group with -DAGX_VGROUP=g; the unit with AGX_VGROUP_DISPATCH also holds the
-// dispatcher agx_launch_apply() that routes a variant id to its group.
+// Built once per group with -DAGX_VGROUP=g; every unit exports its group's launches as one GroupLaunch
+// (agx_group_<g>(), a host function: a const object would be emitted for the device too), and the unit of
+// group 0 also holds the public launchers, which route a variant id to its group.
 #include <hip/hip_runtime.h>
 
 #include "agx_variants.h"
@@ -11,64 +12,22 @@
 
 #define AGX_CAT2(a, b) a##b
 #define AGX_CAT(a, b) AGX_CAT2(a, b)
-#define AGX_GROUP_FN AGX_CAT(agx_launch_apply_g, AGX_VGROUP)
 
 namespace agx {
 
-hipError_t agx_launch_apply_g0(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_g1(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_g2(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_g3(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_g4(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_g5(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_g6(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_g7(uint32_t, uint32_t, bool, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_prio_g0(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_prio_g1(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_prio_g2(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_prio_g3(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_prio_g4(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_prio_g5(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_prio_g6(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_prio_g7(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_stash_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_timers_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_watch_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_child_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_apply_super_g(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_tiny_g0(uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_tiny_g1(uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_tiny_g2(uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_tiny_g3(uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_tiny_g4(uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_tiny_g5(uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_tiny_g6(uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_tiny_g7(uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_dense_g0(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_dense_g1(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_dense_g2(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_dense_g3(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_dense_g4(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_dense_g5(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_dense_g6(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_dense_g7(uint32_t, uint32_t, dim3, hipStream_t, const BucketArgs&);
-hipError_t agx_launch_ring_g0(uint32_t, bool, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
-hipError_t agx_launch_ring_g1(uint32_t, bool, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
-hipError_t agx_launch_ring_g2(uint32_t, bool, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
-hipError_t agx_launch_ring_g3(uint32_t, bool, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
-hipError_t agx_launch_ring_g4(uint32_t, bool, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
-hipError_t agx_launch_ring_g5(uint32_t, bool, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
-hipError_t agx_launch_ring_g6(uint32_t, bool, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
-hipError_t agx_launch_ring_g7(uint32_t, bool, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
-hipError_t agx_dense_persist_occupancy_g0(uint32_t, int*);
-hipError_t agx_dense_persist_occupancy_g1(uint32_t, int*);
-hipError_t agx_dense_persist_occupancy_g2(uint32_t, int*);
-hipError_t agx_dense_persist_occupancy_g3(uint32_t, int*);
-hipError_t agx_dense_persist_occupancy_g4(uint32_t, int*);
-hipError_t agx_dense_persist_occupancy_g5(uint32_t, int*);
-hipError_t agx_dense_persist_occupancy_g6(uint32_t, int*);
-hipError_t agx_dense_persist_occupancy_g7(uint32_t, int*);
-static_assert(kVGroups == 8, "one declaration per group");
+// the launches of one group's variants (hipErrorInvalidValue for a variant of another group)
+struct GroupLaunch {
+  hipError_t (*apply)(uint32_t vid, uint32_t mode, bool skew, dim3, hipStream_t, const BucketArgs&);
+  hipError_t (*feature)(uint32_t vid, uint32_t mode, uint32_t km_flags, bool prio, dim3, hipStream_t, const BucketArgs&);
+  hipError_t (*tiny)(uint32_t vid, dim3, hipStream_t, const BucketArgs&);
+  hipError_t (*dense)(uint32_t vid, uint32_t mode, dim3, hipStream_t, const BucketArgs&);
+  hipError_t (*ring)(uint32_t vid, bool tiny, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
+  hipError_t (*persist_occupancy)(uint32_t vid, int*);
+};
+#define AGX_GROUPS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
+static_assert(kVGroups == 8, "AGX_GROUPS names every group");
+#define AGX_GROUP_DECL(g) const GroupLaunch& agx_group_##g();
+AGX_GROUPS(AGX_GROUP_DECL)
 
 namespace {
 
@@ -101,25 +60,41 @@ hipError_t group_dispatch(uint32_t vid, uint32_t mode, bool skew, dim3 g, hipStr
   }
 }
 
-// the prioritised fast launch (k_bucket_apply<.., kPrio>) of the catch-all plain variants of this group
-template <uint32_t V>
-hipError_t prio_dispatch(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  if constexpr (V >= V_N) {
+// a feature's fast launch of the plain variant V: k_bucket_apply<.., KM | F, .., kPrio> in the single-rank modes
+template <uint32_t V, uint32_t F, bool kPrio>
+hipError_t launch_feature(uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
+  constexpr uint32_t M = kVariants[V].km | F;
+  if (mode == M_FUSED)
+    hipLaunchKernelGGL((k_bucket_apply<false, M, true, false, false, kPrio>), g, dim3(kBThreads), 0, s, ba);
+  else if (mode == M_BYPASS)
+    hipLaunchKernelGGL((k_bucket_apply<false, M, false, false, false, kPrio>), g, dim3(kBThreads), 0, s, ba);
+  else
     return hipErrorInvalidValue;
-  } else {
-    if constexpr (kVariantGroup[V] == AGX_VGROUP && (V == V_ALL || V == V_ALL_COMPILED))
-      if (vid == V) {
-        constexpr uint32_t M = kVariants[V].km;
-        if (mode == M_FUSED)
-          hipLaunchKernelGGL((k_bucket_apply<false, M, true, false, false, true>), g, dim3(kBThreads), 0, s, ba);
-        else if (mode == M_BYPASS)
-          hipLaunchKernelGGL((k_bucket_apply<false, M, false, false, false, true>), g, dim3(kBThreads), 0, s, ba);
-        else
-          return hipErrorInvalidValue;
-        return hipGetLastError();
+  return hipGetLastError();
+}
+
+// the feature launches of group G: kPrio of the catch-all plain variants, the KM flag combinations of the
+// compiled catch-all variant (agx_launch_apply_feature)
+template <uint32_t G>
+hipError_t feature_dispatch(uint32_t vid, uint32_t mode, uint32_t km_flags, bool prio, dim3 g, hipStream_t s,
+                            const BucketArgs& ba) {
+  if (prio && km_flags) return hipErrorInvalidValue;
+  if constexpr (kVariantGroup[V_ALL] == G)
+    if (vid == V_ALL && prio) return launch_feature<V_ALL, 0, true>(mode, g, s, ba);
+  if constexpr (kVariantGroup[V_ALL_COMPILED] == G) {
+    static_assert(kVariantGroup[V_ALL_COMPILED] == G, "the flag combinations live in V_ALL_COMPILED's group");
+    if (vid == V_ALL_COMPILED) {
+      if (prio) return launch_feature<V_ALL_COMPILED, 0, true>(mode, g, s, ba);
+      switch (km_flags) {
+        case kStashKM: return launch_feature<V_ALL_COMPILED, kStashKM, false>(mode, g, s, ba);
+        case kTimersKM: return launch_feature<V_ALL_COMPILED, kTimersKM, false>(mode, g, s, ba);
+        case kWatchKM: return launch_feature<V_ALL_COMPILED, kWatchKM, false>(mode, g, s, ba);
+        case kWatchKM | kChildKM: return launch_feature<V_ALL_COMPILED, kWatchKM | kChildKM, false>(mode, g, s, ba);
+        case kSuperKM: return launch_feature<V_ALL_COMPILED, kSuperKM, false>(mode, g, s, ba);
       }
-    return prio_dispatch<V + 1>(vid, mode, g, s, ba);
+    }
   }
+  return hipErrorInvalidValue;
 }
 
 // k_tiny_apply of the plain / compiled variants of this group
@@ -137,7 +112,7 @@ hipError_t tiny_dispatch(uint32_t vid, dim3 g, hipStream_t s, const BucketArgs& 
   }
 }
 
-// k_ring_apply (tiny: k_ring_tiny) of the plain / compiled variants of this group
+// k_dense_apply / k_dense_fused of the plain / compiled variants of this group
 template <uint32_t V>
 hipError_t dense_dispatch(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
   if constexpr (V >= V_N) {
@@ -172,6 +147,7 @@ hipError_t persist_occ(uint32_t vid, int* n) {
   }
 }
 
+// k_ring_apply (tiny: k_ring_tiny) of the plain / compiled variants of this group
 template <uint32_t V>
 hipError_t ring_dispatch(uint32_t vid, bool tiny, dim3 g, hipStream_t s, const BucketArgs& ba, const RingArgs& ra) {
   if constexpr (V >= V_N) {
@@ -191,193 +167,49 @@ hipError_t ring_dispatch(uint32_t vid, bool tiny, dim3 g, hipStream_t s, const B
 
 }  // namespace
 
-// the stash fast launch (k_bucket_apply<.., kStash>) of the compiled catch-all variant, in its group
-#define AGX_STASH_GROUP 6  // = kVariantGroup[V_ALL_COMPILED] (asserted below)
-#if AGX_VGROUP == AGX_STASH_GROUP
-static_assert(kVariantGroup[V_ALL_COMPILED] == AGX_STASH_GROUP, "the stash launch lives in V_ALL_COMPILED's group");
-hipError_t agx_launch_apply_stash_g(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  if (vid != V_ALL_COMPILED) return hipErrorInvalidValue;
-  constexpr uint32_t M = kVariants[V_ALL_COMPILED].km;
-  if (mode == M_FUSED)
-    hipLaunchKernelGGL((k_bucket_apply<false, M | kStashKM, true, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else if (mode == M_BYPASS)
-    hipLaunchKernelGGL((k_bucket_apply<false, M | kStashKM, false, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-// the timer fast launch (k_bucket_apply<.., kTimers>) of the compiled catch-all variant, in the same group
-hipError_t agx_launch_apply_timers_g(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  if (vid != V_ALL_COMPILED) return hipErrorInvalidValue;
-  constexpr uint32_t M = kVariants[V_ALL_COMPILED].km;
-  if (mode == M_FUSED)
-    hipLaunchKernelGGL((k_bucket_apply<false, M | kTimersKM, true, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else if (mode == M_BYPASS)
-    hipLaunchKernelGGL((k_bucket_apply<false, M | kTimersKM, false, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-// the death-watch fast launch (k_bucket_apply<.., kWatch>) of the compiled catch-all variant, in the same group
-hipError_t agx_launch_apply_watch_g(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  if (vid != V_ALL_COMPILED) return hipErrorInvalidValue;
-  constexpr uint32_t M = kVariants[V_ALL_COMPILED].km;
-  if (mode == M_FUSED)
-    hipLaunchKernelGGL((k_bucket_apply<false, M | kWatchKM, true, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else if (mode == M_BYPASS)
-    hipLaunchKernelGGL((k_bucket_apply<false, M | kWatchKM, false, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-// the supervision fast launch (k_bucket_apply<.., kSuper>) of the compiled catch-all variant, in the same group
-hipError_t agx_launch_apply_super_g(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  if (vid != V_ALL_COMPILED) return hipErrorInvalidValue;
-  constexpr uint32_t M = kVariants[V_ALL_COMPILED].km;
-  if (mode == M_FUSED)
-    hipLaunchKernelGGL((k_bucket_apply<false, M | kSuperKM, true, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else if (mode == M_BYPASS)
-    hipLaunchKernelGGL((k_bucket_apply<false, M | kSuperKM, false, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-// the children fast launch (k_bucket_apply<.., kWatch | kChild>) of the compiled catch-all variant, in the same group
-hipError_t agx_launch_apply_child_g(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  if (vid != V_ALL_COMPILED) return hipErrorInvalidValue;
-  constexpr uint32_t M = kVariants[V_ALL_COMPILED].km | kWatchKM | kChildKM;
-  if (mode == M_FUSED)
-    hipLaunchKernelGGL((k_bucket_apply<false, M, true, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else if (mode == M_BYPASS)
-    hipLaunchKernelGGL((k_bucket_apply<false, M, false, false, false, false>), g, dim3(kBThreads), 0, s, ba);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-#endif
-
-hipError_t AGX_CAT(agx_launch_ring_g, AGX_VGROUP)(uint32_t vid, bool tiny, dim3 g, hipStream_t s, const BucketArgs& ba,
-                                                  const RingArgs& ra) {
-  return ring_dispatch<0>(vid, tiny, g, s, ba, ra);
-}
-
-hipError_t AGX_CAT(agx_dense_persist_occupancy_g, AGX_VGROUP)(uint32_t vid, int* n) { return persist_occ<0>(vid, n); }
-
-hipError_t AGX_CAT(agx_launch_tiny_g, AGX_VGROUP)(uint32_t vid, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  return tiny_dispatch<0>(vid, g, s, ba);
-}
-
-hipError_t AGX_CAT(agx_launch_dense_g, AGX_VGROUP)(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s,
-                                                   const BucketArgs& ba) {
-  return dense_dispatch<0>(vid, mode, g, s, ba);
-}
-
-hipError_t AGX_GROUP_FN(uint32_t vid, uint32_t mode, bool skew, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  return group_dispatch<0>(vid, mode, skew, g, s, ba);
-}
-
-hipError_t AGX_CAT(agx_launch_apply_prio_g, AGX_VGROUP)(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s,
-                                                        const BucketArgs& ba) {
-  return prio_dispatch<0>(vid, mode, g, s, ba);
+const GroupLaunch& AGX_CAT(agx_group_, AGX_VGROUP)() {
+  static const GroupLaunch launch = {group_dispatch<0>, feature_dispatch<AGX_VGROUP>, tiny_dispatch<0>,
+                                     dense_dispatch<0>, ring_dispatch<0>, persist_occ<0>};
+  return launch;
 }
 
 #if AGX_VGROUP == 0
+namespace {
+#define AGX_GROUP_REF(g) agx_group_##g,
+const GroupLaunch& (*const kGroups[kVGroups])() = {AGX_GROUPS(AGX_GROUP_REF)};
+const GroupLaunch& group_of(uint32_t vid) { return kGroups[kVariantGroup[vid]](); }
+}  // namespace
+
 hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 g, hipStream_t s, const BucketArgs& ba) {
   if (vid >= V_N) return hipErrorInvalidValue;
-  switch (kVariantGroup[vid]) {
-    case 0: return agx_launch_apply_g0(vid, mode, skew, g, s, ba);
-    case 1: return agx_launch_apply_g1(vid, mode, skew, g, s, ba);
-    case 2: return agx_launch_apply_g2(vid, mode, skew, g, s, ba);
-    case 3: return agx_launch_apply_g3(vid, mode, skew, g, s, ba);
-    case 4: return agx_launch_apply_g4(vid, mode, skew, g, s, ba);
-    case 5: return agx_launch_apply_g5(vid, mode, skew, g, s, ba);
-    case 6: return agx_launch_apply_g6(vid, mode, skew, g, s, ba);
-    default: return agx_launch_apply_g7(vid, mode, skew, g, s, ba);
-  }
+  return group_of(vid).apply(vid, mode, skew, g, s, ba);
 }
-hipError_t agx_launch_apply_prio(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  if (vid != V_ALL && vid != V_ALL_COMPILED) return hipErrorInvalidValue;
-  switch (kVariantGroup[vid]) {
-    case 0: return agx_launch_apply_prio_g0(vid, mode, g, s, ba);
-    case 1: return agx_launch_apply_prio_g1(vid, mode, g, s, ba);
-    case 2: return agx_launch_apply_prio_g2(vid, mode, g, s, ba);
-    case 3: return agx_launch_apply_prio_g3(vid, mode, g, s, ba);
-    case 4: return agx_launch_apply_prio_g4(vid, mode, g, s, ba);
-    case 5: return agx_launch_apply_prio_g5(vid, mode, g, s, ba);
-    case 6: return agx_launch_apply_prio_g6(vid, mode, g, s, ba);
-    default: return agx_launch_apply_prio_g7(vid, mode, g, s, ba);
-  }
+
+hipError_t agx_launch_apply_feature(uint32_t vid, uint32_t mode, uint32_t km_flags, bool prio, dim3 g, hipStream_t s,
+                                    const BucketArgs& ba) {
+  if (vid >= V_N) return hipErrorInvalidValue;
+  return group_of(vid).feature(vid, mode, km_flags, prio, g, s, ba);
 }
-hipError_t agx_launch_apply_stash(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  return agx_launch_apply_stash_g(vid, mode, g, s, ba);
-}
-hipError_t agx_launch_apply_timers(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  return agx_launch_apply_timers_g(vid, mode, g, s, ba);
-}
-hipError_t agx_launch_apply_watch(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  return agx_launch_apply_watch_g(vid, mode, g, s, ba);
-}
-hipError_t agx_launch_apply_child(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  return agx_launch_apply_child_g(vid, mode, g, s, ba);
-}
-hipError_t agx_launch_apply_super(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
-  return agx_launch_apply_super_g(vid, mode, g, s, ba);
-}
+
 hipError_t agx_launch_ring(uint32_t vid, bool tiny, dim3 g, hipStream_t s, const BucketArgs& ba, const RingArgs& ra) {
   if (vid >= V_N || kVariants[vid].wide) return hipErrorInvalidValue;
-  switch (kVariantGroup[vid]) {
-    case 0: return agx_launch_ring_g0(vid, tiny, g, s, ba, ra);
-    case 1: return agx_launch_ring_g1(vid, tiny, g, s, ba, ra);
-    case 2: return agx_launch_ring_g2(vid, tiny, g, s, ba, ra);
-    case 3: return agx_launch_ring_g3(vid, tiny, g, s, ba, ra);
-    case 4: return agx_launch_ring_g4(vid, tiny, g, s, ba, ra);
-    case 5: return agx_launch_ring_g5(vid, tiny, g, s, ba, ra);
-    case 6: return agx_launch_ring_g6(vid, tiny, g, s, ba, ra);
-    default: return agx_launch_ring_g7(vid, tiny, g, s, ba, ra);
-  }
+  return group_of(vid).ring(vid, tiny, g, s, ba, ra);
 }
 
 hipError_t agx_launch_dense(uint32_t vid, uint32_t mode, dim3 g, hipStream_t s, const BucketArgs& ba) {
   if (vid >= V_N || kVariants[vid].wide) return hipErrorInvalidValue;
-  switch (kVariantGroup[vid]) {
-    case 0: return agx_launch_dense_g0(vid, mode, g, s, ba);
-    case 1: return agx_launch_dense_g1(vid, mode, g, s, ba);
-    case 2: return agx_launch_dense_g2(vid, mode, g, s, ba);
-    case 3: return agx_launch_dense_g3(vid, mode, g, s, ba);
-    case 4: return agx_launch_dense_g4(vid, mode, g, s, ba);
-    case 5: return agx_launch_dense_g5(vid, mode, g, s, ba);
-    case 6: return agx_launch_dense_g6(vid, mode, g, s, ba);
-    default: return agx_launch_dense_g7(vid, mode, g, s, ba);
-  }
+  return group_of(vid).dense(vid, mode, g, s, ba);
 }
 
 hipError_t agx_dense_persist_occupancy(uint32_t vid, int* n) {
   *n = 0;
   if (vid >= V_N || kVariants[vid].wide) return hipErrorInvalidValue;
-  switch (kVariantGroup[vid]) {
-    case 0: return agx_dense_persist_occupancy_g0(vid, n);
-    case 1: return agx_dense_persist_occupancy_g1(vid, n);
-    case 2: return agx_dense_persist_occupancy_g2(vid, n);
-    case 3: return agx_dense_persist_occupancy_g3(vid, n);
-    case 4: return agx_dense_persist_occupancy_g4(vid, n);
-    case 5: return agx_dense_persist_occupancy_g5(vid, n);
-    case 6: return agx_dense_persist_occupancy_g6(vid, n);
-    default: return agx_dense_persist_occupancy_g7(vid, n);
-  }
+  return group_of(vid).persist_occupancy(vid, n);
 }
 
 hipError_t agx_launch_tiny(uint32_t vid, dim3 g, hipStream_t s, const BucketArgs& ba) {
   if (vid >= V_N || kVariants[vid].wide) return hipErrorInvalidValue;
-  switch (kVariantGroup[vid]) {
-    case 0: return agx_launch_tiny_g0(vid, g, s, ba);
-    case 1: return agx_launch_tiny_g1(vid, g, s, ba);
-    case 2: return agx_launch_tiny_g2(vid, g, s, ba);
-    case 3: return agx_launch_tiny_g3(vid, g, s, ba);
-    case 4: return agx_launch_tiny_g4(vid, g, s, ba);
-    case 5: return agx_launch_tiny_g5(vid, g, s, ba);
-    case 6: return agx_launch_tiny_g6(vid, g, s, ba);
-    default: return agx_launch_tiny_g7(vid, g, s, ba);
-  }
+  return group_of(vid).tiny(vid, g, s, ba);
 }
 #endif
 

@@ -416,6 +416,88 @@ struct agx_engine {
 
 namespace {
 
+// The actor features, host side: one row per feature.  The top-level ones exclude one another, a multi-rank engine,
+// CRDT kinds and a ring pool, and are set before the first run; such an engine launches the feature's instantiation
+// of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
+// the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
+// apply_variant, launch_apply and make_params.
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_N, F_NONE = F_N };
+
+struct FeatureRow {
+  bool (*on)(const agx_engine*);
+  const void* (*storage)(const agx_engine*);  // what stands in DevParams' shared slot (rx's)
+  const char* needs;       // its refusals' subject and verb
+  const char* named;       // as the other party of another feature's refusal
+  const char* crdt_named;  // as the other party of enable_crdt's refusal
+  const char* crdt_why;    // the reason tail of both CRDT refusals
+  const char* emit_why;    // the reason tail of the max_emit refusal (null: any max_emit)
+  const char* ring_why;    // the ring-pool refusal, between "rings of %u slots, " and " before the first run"
+  const char* set_what;    // "set <set_what> before the first agx_run"
+  uint32_t km;             // the launch: its KM flag bits ...
+  bool prio;               // ... or kPrio
+  Feature on_top_of;       // the feature it is set on top of (F_NONE: a top-level feature)
+};
+
+#define AGX_ONCE "the drain for more evaluates a case more than once, and "
+const FeatureRow kFeatures[F_N] = {
+    {[](const agx_engine* e) { return e->prio_mask != 0; }, [](const agx_engine* e) -> const void* { return e->d_ptab; },
+     "priority mailboxes need", "priority tables (agx_set_mailbox_priority)", "a priority mailbox (agx_set_mailbox_priority)",
+     ": a state gossip's snapshot handle carries no message tag", nullptr,
+     "drained in arrival order: set priority tables", "mailbox priorities", 0, true, F_NONE},
+    {[](const agx_engine* e) { return e->stash_on; }, [](const agx_engine* e) -> const void* { return e->d_stash; },
+     "deque-based mailboxes need", "a deque-based mailbox class (agx_set_stash)", "a deque-based mailbox (agx_set_stash)",
+     ": a state gossip's snapshot row does not outlive its superstep in a stash",
+     "a stash drain stages at most one tell per message", "which know no stash: set stash capacities", "stash capacities",
+     kStashKM, false, F_NONE},
+    {[](const agx_engine* e) { return e->tm_keys != 0; }, [](const agx_engine* e) -> const void* { return e->d_timers; },
+     "timers need", "timers (agx_set_timers)", "timers (agx_set_timers)", "", AGX_ONCE "a timer action must take effect once",
+     "which know no timers: set timers", "timers", kTimersKM, false, F_NONE},
+    {[](const agx_engine* e) { return e->wd_slots != 0; }, [](const agx_engine* e) -> const void* { return e->d_watch; },
+     "death watch needs", "death watch (agx_set_death_watch)", "death watch (agx_set_death_watch)", "",
+     AGX_ONCE "a watch action must take effect once", "which know no death watch: set death watch", "death watch", kWatchKM,
+     false, F_NONE},
+    {[](const agx_engine* e) { return e->sv_on; }, [](const agx_engine* e) -> const void* { return e->d_super; },
+     "supervision needs", "supervision (agx_set_supervision)", "supervision (agx_set_supervision)", "",
+     AGX_ONCE "a failure must take effect once", "which know no supervision: set supervision", "supervision", kSuperKM, false,
+     F_NONE},
+    // children (agx_set_children) come on top of death watch, whose storage holds theirs and whose refusals are
+    // theirs: the row only selects the launch
+    {[](const agx_engine* e) { return e->d_child != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+     nullptr, kWatchKM | kChildKM, false, F_WATCH},
+};
+#undef AGX_ONCE
+
+// the engine's top-level feature (at most one is on: refuse_feature), F_NONE without one
+Feature active_feature(const agx_engine* e) {
+  for (uint32_t f = 0; f < F_N; ++f)
+    if (kFeatures[f].on_top_of == F_NONE && kFeatures[f].on(e)) return (Feature)f;
+  return F_NONE;
+}
+
+// the feature whose instantiation the engine launches: `a`, or the one set on top of it
+Feature launched_feature(const agx_engine* e, Feature a) {
+  for (uint32_t f = 0; f < F_N; ++f)
+    if (a != F_NONE && kFeatures[f].on_top_of == a && kFeatures[f].on(e)) return (Feature)f;
+  return a;
+}
+
+// What every setter of a top-level feature refuses, after its own argument checks: more than one rank, CRDT kinds,
+// another feature, max_emit, a ring pool (all AGX_EINVAL), and only then a started engine (AGX_ESTATE).
+agx_status refuse_feature(const agx_engine* e, Feature f) {
+  const FeatureRow& F = kFeatures[f];
+  if (e->R > 1) return set_err(AGX_EINVAL, "%s a single-rank engine (n_ranks is %u; the limit is 1)", F.needs, e->R);
+  if (e->pw) return set_err(AGX_EINVAL, "%s an engine without CRDT kinds (one is registered)%s", F.needs, F.crdt_why);
+  const Feature a = active_feature(e);
+  if (a != F_NONE && a != f) return set_err(AGX_EINVAL, "%s an engine without %s", F.needs, kFeatures[a].named);
+  if (F.emit_why && e->kmax != 1)
+    return set_err(AGX_EINVAL, "%s max_emit = 1 (it is %u): %s", F.needs, e->kmax, F.emit_why);
+  if (e->ring_live || e->rg_on)
+    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, %s before the "
+                   "first run", e->ring_live ? e->ring_c : e->rg_c, F.ring_why);
+  if (e->started) return set_err(AGX_ESTATE, "set %s before the first agx_run", F.set_what);
+  return AGX_OK;
+}
+
 agx_status ensure_dev(agx_engine* e) {
   HIP_TRY(hipSetDevice((int)e->cfg.device));
   return AGX_OK;
@@ -525,11 +607,8 @@ DevParams make_params(agx_engine* e) {
   P.nstop = e->d_nstop;
   P.heap = e->d_heap;
   P.rx = e->d_rx;
-  if (e->prio_mask) P.ptab = e->d_ptab;  // (shares rx's slot: no CRDT kinds on an engine with priority tables)
-  if (e->stash_on) P.stash = e->d_stash;  // (the same slot: neither CRDT kinds nor priority tables with a stash)
-  if (e->tm_keys) P.timers = e->d_timers;  // (the same slot: none of the three on an engine with timers)
-  if (e->wd_slots) P.watch = e->d_watch;   // (the same slot: none of the four on an engine with death watch)
-  if (e->sv_on) P.super = e->d_super;      // (the same slot: none of the five on an engine with supervision)
+  // (a feature's storage shares rx's slot -- ptab, stash, timers, watch, super: no CRDT kinds on such an engine)
+  if (const Feature f = active_feature(e); f != F_NONE) P.rx = static_cast<const uint32_t*>(kFeatures[f].storage(e));
   P.heap_top = e->d_heap_top;
   P.step = e->d_step;
   P.heap_rows = (uint32_t)e->heap_rows;
@@ -693,12 +772,9 @@ void skew_prepass(agx_engine* e, const BucketArgs& ba, const SkewArgs& ska) {
 // the k_bucket_apply variant for the registered behaviour kinds (agx_variants.h)
 uint32_t apply_variant(const agx_engine* e) {
   const uint32_t km = e->kinds_mask & ~kb(AGX_KIND_NONE);
-  if (e->prio_mask)  // priority mailboxes: the catch-all plain variants carry the order step (kPrio)
-    return (km & kb(AGX_KIND_COMPILED)) ? V_ALL_COMPILED : V_ALL;
-  if (e->stash_on) return V_ALL_COMPILED;  // deque-based mailboxes: the compiled catch-all carries the stash (kStash)
-  if (e->tm_keys) return V_ALL_COMPILED;   // timers: the compiled catch-all carries them (kTimers)
-  if (e->wd_slots) return V_ALL_COMPILED;  // death watch: the compiled catch-all carries it (kWatch)
-  if (e->sv_on) return V_ALL_COMPILED;     // supervision: the compiled catch-all carries it (kSuper)
+  // a feature: the compiled catch-all carries its code (its KM flags); both plain catch-alls carry the order step (kPrio)
+  if (const Feature f = active_feature(e); f != F_NONE)
+    return kFeatures[f].prio && !(km & kb(AGX_KIND_COMPILED)) ? V_ALL : V_ALL_COMPILED;
   if (e->pw && e->delta_max) {  // delta-CRDT replication: the variants that carry the delta code
     if (km == kb(AGX_KIND_GCOUNTER)) return V_GC_DELTA;
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN_DELTA;
@@ -728,7 +804,7 @@ bool dense_on(const agx_engine* e, uint32_t vid) {
   // (k_dense_fused reads a fused bucket's table row one sender bucket per thread: nb <= 512, which
   // the fused superstep's <= 2^20 actors guarantee)
   if (e->fused && e->nb > (uint32_t)kDenseThreads) return false;
-  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots && !e->sv_on &&
+  return mode_ok && !kVariants[vid].wide && e->kmax == 1 && !e->ring_live && active_feature(e) == F_NONE &&
          (e->dense_launch == 1 || (e->dense_launch < 0 && vid == V_RING));
 }
 
@@ -912,7 +988,7 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
     }
     // (priority mailboxes: the wave path drains in arrival order -- every bucket takes the block launch)
     const bool tl = mode == M_BYPASS && !kVariants[vid].wide && e->tiny_launch && e->tiny_max && !e->skew_only &&
-                    !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots && !e->sv_on;
+                    active_feature(e) == F_NONE;
     if (tl) {  // wave-per-bucket launch first; the block launch then takes the buckets it marked
       ba.blist = e->d_blist;
       ba.dense_first = dl ? 1u : 0u;
@@ -926,22 +1002,10 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       Scope s(e, K_APPLY);
       BucketArgs bf = ba;
       if (e->stamps_skew) bf.dbg = nullptr;  // (diagnostic: stamps of the skew launch only)
-      if (e->prio_mask) {
-        if (mode == M_OWNER) return set_err(AGX_ESTATE, "priority mailboxes need a single-rank engine");
-        HIP_TRY(agx_launch_apply_prio(vid, mode, g, e->stream, bf));
-      } else if (e->stash_on) {
-        if (mode == M_OWNER) return set_err(AGX_ESTATE, "deque-based mailboxes need a single-rank engine");
-        HIP_TRY(agx_launch_apply_stash(vid, mode, g, e->stream, bf));
-      } else if (e->tm_keys) {
-        if (mode == M_OWNER) return set_err(AGX_ESTATE, "timers need a single-rank engine");
-        HIP_TRY(agx_launch_apply_timers(vid, mode, g, e->stream, bf));
-      } else if (e->wd_slots) {
-        if (mode == M_OWNER) return set_err(AGX_ESTATE, "death watch needs a single-rank engine");
-        if (e->d_child) HIP_TRY(agx_launch_apply_child(vid, mode, g, e->stream, bf));
-        else HIP_TRY(agx_launch_apply_watch(vid, mode, g, e->stream, bf));
-      } else if (e->sv_on) {
-        if (mode == M_OWNER) return set_err(AGX_ESTATE, "supervision needs a single-rank engine");
-        HIP_TRY(agx_launch_apply_super(vid, mode, g, e->stream, bf));
+      if (const Feature a = active_feature(e); a != F_NONE) {
+        if (mode == M_OWNER) return set_err(AGX_ESTATE, "%s a single-rank engine", kFeatures[a].needs);
+        const FeatureRow& F = kFeatures[launched_feature(e, a)];
+        HIP_TRY(agx_launch_apply_feature(vid, mode, F.km, F.prio, g, e->stream, bf));
       } else {
         HIP_TRY(agx_launch_apply(vid, mode, false, g, e->stream, bf));
       }
@@ -980,7 +1044,7 @@ agx_status launch_staged_chunk(agx_engine* e) {
 // behaviours, every configured mailbox class bounded by <= kRingMaxC); from then on the classes
 // are fixed (agx_set_mailbox_class refuses a capacity the rings cannot hold).
 agx_status setup_rings(agx_engine* e) {
-  if (e->ring_live || !e->ring_res || e->pw || e->prio_mask || e->stash_on || e->tm_keys || e->wd_slots || e->sv_on) return AGX_OK;  // (a ring drains in arrival order)
+  if (e->ring_live || !e->ring_res || e->pw || active_feature(e) != F_NONE) return AGX_OK;  // (a ring drains in arrival order)
   uint32_t cmax = 0;
   for (uint32_t c = 0; c < AGX_MAX_MAILBOX_CLASSES; ++c) {
     if (!((e->mclass_set >> c) & 1u)) continue;
@@ -1024,7 +1088,7 @@ agx_status setup_rings(agx_engine* e) {
 constexpr uint32_t kRingAutoC = 256;  // ring apply by default from this mailbox capacity up (setup_ring_apply)
 agx_status setup_ring_apply(agx_engine* e) {
   if (e->started || e->rg_on || e->ring_live || e->ring_res) return AGX_OK;
-  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || e->prio_mask || e->stash_on || e->tm_keys || e->wd_slots || e->sv_on) return AGX_OK;
+  if (e->fused || e->R != 1 || e->pw || e->kmax != 1 || e->n_local == 0 || active_feature(e) != F_NONE) return AGX_OK;
   // AGX_RING_APPLY=1 / 0 forces rings on / off; unset: on when the largest bounded capacity is at
   // least kRingAutoC.  Deep queues are where re-copying the backlog every superstep costs most (C3,
   // BoundedMailbox(1000): 4.67e8 -> 6.7e8 msg/s with rings, the sparse buckets a wave each); at
@@ -2012,7 +2076,7 @@ bool persist_ok(agx_engine* e) {
       e->persist = (uint64_t)e->nb <= (uint64_t)per_cu * (uint64_t)ncu ? 1 : 0;
     (void)hipGetLastError();
   }
-  return e->persist == 1 && !e->prio_mask && !e->stash_on && !e->tm_keys && !e->wd_slots && !e->sv_on && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
+  return e->persist == 1 && active_feature(e) == F_NONE && e->fused && e->strict_cap && e->dense_alone && dense_on(e, vid) && !e->skew_only &&
          !e->recover_dense;
 }
 
@@ -2752,18 +2816,9 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
   const uint32_t pw = ru > kRowAlign ? (ru + kRowAlign - 1) / kRowAlign * kRowAlign : ru;
   if (pw <= e->pw) return AGX_OK;
   if (e->started) return set_err(AGX_ESTATE, "register CRDT kinds before the first agx_run");
-  if (e->prio_mask)
-    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a priority mailbox "
-                   "(agx_set_mailbox_priority): a state gossip's snapshot handle carries no message tag");
-  if (e->tm_keys)
-    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with timers (agx_set_timers)");
-  if (e->wd_slots)
-    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with death watch (agx_set_death_watch)");
-  if (e->sv_on)
-    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with supervision (agx_set_supervision)");
-  if (e->stash_on)
-    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with a deque-based mailbox "
-                   "(agx_set_stash): a state gossip's snapshot row does not outlive its superstep in a stash");
+  if (const Feature f = active_feature(e); f != F_NONE)
+    return set_err(AGX_EINVAL, "CRDT kinds cannot be registered on an engine with %s%s", kFeatures[f].crdt_named,
+                   kFeatures[f].crdt_why);
   const uint64_t rows = ((uint64_t)e->nb << e->bb) + e->cap;
   if (rows + e->cap > kHandleMask) return set_err(AGX_EINVAL, "CRDT kinds need msg_capacity < 2^28 - n_actors");
   hipFree(e->d_heap);
@@ -3292,23 +3347,10 @@ agx_status agx_set_mailbox(agx_engine* e, uint64_t first_id, uint64_t count, uin
 // Mailbox.scala:726-816 (priority / stable priority), :867-1025 (control-aware)
 agx_status agx_set_mailbox_priority(agx_engine* e, uint32_t cls, const uint8_t prio[256]) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
-  if (e->R > 1)
-    return set_err(AGX_EINVAL, "priority mailboxes need a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
-  if (e->pw)
-    return set_err(AGX_EINVAL, "priority mailboxes need an engine without CRDT kinds (one is registered): a state "
-                   "gossip's snapshot handle carries no message tag");
   if (cls >= AGX_MAX_MAILBOX_CLASSES || !((e->mclass_set >> cls) & 1u))
     return set_err(AGX_EINVAL, "mailbox class %u is not configured (agx_set_mailbox_class; classes 0..%u)", cls,
                    AGX_MAX_MAILBOX_CLASSES - 1);
-  if (e->ring_live || e->rg_on)
-    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, drained in "
-                   "arrival order: set priority tables before the first run", e->ring_live ? e->ring_c : e->rg_c);
-  if (e->stash_on)
-    return set_err(AGX_EINVAL, "priority mailboxes need an engine without a deque-based mailbox class (agx_set_stash)");
-  if (e->tm_keys) return set_err(AGX_EINVAL, "priority mailboxes need an engine without timers (agx_set_timers)");
-  if (e->wd_slots) return set_err(AGX_EINVAL, "priority mailboxes need an engine without death watch (agx_set_death_watch)");
-  if (e->sv_on) return set_err(AGX_EINVAL, "priority mailboxes need an engine without supervision (agx_set_supervision)");
-  if (e->started) return set_err(AGX_ESTATE, "set mailbox priorities before the first agx_run");
+  AGX_TRY(refuse_feature(e, F_PRIO));
   AGX_TRY(ensure_dev(e));
   if (prio) {
     memcpy(e->prio_tab.data() + cls * 256u, prio, 256);
@@ -3325,29 +3367,13 @@ agx_status agx_set_mailbox_priority(agx_engine* e, uint32_t cls, const uint8_t p
 // Stash.scala (classic `stash-capacity`, *DequeBasedMailbox); TY/internal/StashBufferImpl.scala:61-79,131-218
 agx_status agx_set_stash(agx_engine* e, uint32_t cls, uint32_t capacity) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
-  if (e->R > 1)
-    return set_err(AGX_EINVAL, "deque-based mailboxes need a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
-  if (e->pw)
-    return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without CRDT kinds (one is registered): a state "
-                   "gossip's snapshot row does not outlive its superstep in a stash");
-  if (e->prio_mask)
-    return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without priority tables (agx_set_mailbox_priority)");
-  if (e->tm_keys) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without timers (agx_set_timers)");
-  if (e->wd_slots) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without death watch (agx_set_death_watch)");
-  if (e->sv_on) return set_err(AGX_EINVAL, "deque-based mailboxes need an engine without supervision (agx_set_supervision)");
   if (cls >= AGX_MAX_MAILBOX_CLASSES || !((e->mclass_set >> cls) & 1u))
     return set_err(AGX_EINVAL, "mailbox class %u is not configured (agx_set_mailbox_class; classes 0..%u)", cls,
                    AGX_MAX_MAILBOX_CLASSES - 1);
   if (capacity == 0 || capacity > 255u)
     return set_err(AGX_EINVAL, "stash capacity %u: a stash holds 1..255 messages (there is no unbounded stash: "
                    "stash-capacity = -1 is not supported)", capacity);
-  if (e->kmax != 1)
-    return set_err(AGX_EINVAL, "deque-based mailboxes need max_emit = 1 (it is %u): a stash drain stages at most one "
-                   "tell per message", e->kmax);
-  if (e->ring_live || e->rg_on)
-    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, which know no "
-                   "stash: set stash capacities before the first run", e->ring_live ? e->ring_c : e->rg_c);
-  if (e->started) return set_err(AGX_ESTATE, "set stash capacities before the first agx_run");
+  AGX_TRY(refuse_feature(e, F_STASH));
   AGX_TRY(ensure_dev(e));
   e->stash_cap[cls] = capacity;
   e->stash_on = true;
@@ -3418,19 +3444,7 @@ agx_status agx_set_timers(agx_engine* e, uint32_t n_keys) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (n_keys < 1u || n_keys > AGX_MAX_TIMER_KEYS)
     return set_err(AGX_EINVAL, "timers: %u keys per actor (1..%u)", n_keys, AGX_MAX_TIMER_KEYS);
-  if (e->R > 1) return set_err(AGX_EINVAL, "timers need a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
-  if (e->pw) return set_err(AGX_EINVAL, "timers need an engine without CRDT kinds (one is registered)");
-  if (e->prio_mask) return set_err(AGX_EINVAL, "timers need an engine without priority tables (agx_set_mailbox_priority)");
-  if (e->stash_on) return set_err(AGX_EINVAL, "timers need an engine without a deque-based mailbox class (agx_set_stash)");
-  if (e->wd_slots) return set_err(AGX_EINVAL, "timers need an engine without death watch (agx_set_death_watch)");
-  if (e->sv_on) return set_err(AGX_EINVAL, "timers need an engine without supervision (agx_set_supervision)");
-  if (e->kmax != 1)
-    return set_err(AGX_EINVAL, "timers need max_emit = 1 (it is %u): the drain for more evaluates a case more than once, "
-                   "and a timer action must take effect once", e->kmax);
-  if (e->ring_live || e->rg_on)
-    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, which know no "
-                   "timers: set timers before the first run", e->ring_live ? e->ring_c : e->rg_c);
-  if (e->started) return set_err(AGX_ESTATE, "set timers before the first agx_run");
+  AGX_TRY(refuse_feature(e, F_TIMERS));
   AGX_TRY(ensure_dev(e));
   if (e->d_timers && n_keys != e->tm_keys) {
     hipFree(e->d_timers);
@@ -3529,19 +3543,7 @@ agx_status agx_set_death_watch(agx_engine* e, uint32_t n_slots) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (n_slots < 1u || n_slots > AGX_MAX_WATCH_SLOTS)
     return set_err(AGX_EINVAL, "death watch: %u slots per actor (1..%u)", n_slots, AGX_MAX_WATCH_SLOTS);
-  if (e->R > 1) return set_err(AGX_EINVAL, "death watch needs a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
-  if (e->pw) return set_err(AGX_EINVAL, "death watch needs an engine without CRDT kinds (one is registered)");
-  if (e->prio_mask) return set_err(AGX_EINVAL, "death watch needs an engine without priority tables (agx_set_mailbox_priority)");
-  if (e->stash_on) return set_err(AGX_EINVAL, "death watch needs an engine without a deque-based mailbox class (agx_set_stash)");
-  if (e->tm_keys) return set_err(AGX_EINVAL, "death watch needs an engine without timers (agx_set_timers)");
-  if (e->sv_on) return set_err(AGX_EINVAL, "death watch needs an engine without supervision (agx_set_supervision)");
-  if (e->kmax != 1)
-    return set_err(AGX_EINVAL, "death watch needs max_emit = 1 (it is %u): the drain for more evaluates a case more than "
-                   "once, and a watch action must take effect once", e->kmax);
-  if (e->ring_live || e->rg_on)
-    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, which know no "
-                   "death watch: set death watch before the first run", e->ring_live ? e->ring_c : e->rg_c);
-  if (e->started) return set_err(AGX_ESTATE, "set death watch before the first agx_run");
+  AGX_TRY(refuse_feature(e, F_WATCH));
   AGX_TRY(ensure_dev(e));
   if (e->d_child && n_slots != e->wd_slots)
     return set_err(AGX_EINVAL, "death watch: the slot count cannot change once children are set (agx_set_children)");
@@ -3648,19 +3650,7 @@ agx_status agx_set_supervision(agx_engine* e, const agx_supervisor* table, uint3
       return set_err(AGX_EINVAL, "supervision: bad entry %u of behaviour %u (a strategy, reset words 0..1, max_restarts >= -1, "
                      "within >= 1 tick)", i % n_levels, i / n_levels);
   }
-  if (e->R > 1) return set_err(AGX_EINVAL, "supervision needs a single-rank engine (n_ranks is %u; the limit is 1)", e->R);
-  if (e->pw) return set_err(AGX_EINVAL, "supervision needs an engine without CRDT kinds (one is registered)");
-  if (e->prio_mask) return set_err(AGX_EINVAL, "supervision needs an engine without priority tables (agx_set_mailbox_priority)");
-  if (e->stash_on) return set_err(AGX_EINVAL, "supervision needs an engine without a deque-based mailbox class (agx_set_stash)");
-  if (e->tm_keys) return set_err(AGX_EINVAL, "supervision needs an engine without timers (agx_set_timers)");
-  if (e->wd_slots) return set_err(AGX_EINVAL, "supervision needs an engine without death watch (agx_set_death_watch)");
-  if (e->kmax != 1)
-    return set_err(AGX_EINVAL, "supervision needs max_emit = 1 (it is %u): the drain for more evaluates a case more than "
-                   "once, and a failure must take effect once", e->kmax);
-  if (e->ring_live || e->rg_on)
-    return set_err(AGX_EINVAL, "this engine keeps queued messages in bounded-mailbox rings of %u slots, which know no "
-                   "supervision: set supervision before the first run", e->ring_live ? e->ring_c : e->rg_c);
-  if (e->started) return set_err(AGX_ESTATE, "set supervision before the first agx_run");
+  AGX_TRY(refuse_feature(e, F_SUPER));
   AGX_TRY(ensure_dev(e));
   if (e->d_super && n_levels != e->sv_levels) {
     hipFree(e->d_super);

@@ -47,25 +47,12 @@ constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 
 // launch k_bucket_apply<variant vid, mode, skew> with `grid` x kBThreads threads on `s`
 // (defined in agx_apply.hip; returns hipErrorInvalidValue for an unknown combination)
 hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 grid, hipStream_t s, const BucketArgs& ba);
-// launch the prioritised fast launch k_bucket_apply<variant vid, mode, no skew, kPrio> (priority mailboxes,
-// agx_set_mailbox_priority): only the catch-all plain variants V_ALL / V_ALL_COMPILED in the modes M_FUSED /
-// M_BYPASS are instantiated (hipErrorInvalidValue otherwise)
-hipError_t agx_launch_apply_prio(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
-// launch the stash fast launch k_bucket_apply<V_ALL_COMPILED, mode, no skew, kStash> (deque-based mailboxes,
-// agx_set_stash): only V_ALL_COMPILED in the modes M_FUSED / M_BYPASS is instantiated (hipErrorInvalidValue otherwise)
-hipError_t agx_launch_apply_stash(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
-// launch the timer fast launch k_bucket_apply<V_ALL_COMPILED, mode, no skew, kTimers> (agx_set_timers): only
-// V_ALL_COMPILED in the modes M_FUSED / M_BYPASS is instantiated (hipErrorInvalidValue otherwise)
-hipError_t agx_launch_apply_timers(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
-// launch the death-watch fast launch k_bucket_apply<V_ALL_COMPILED, mode, no skew, kWatch> (agx_set_death_watch): only
-// V_ALL_COMPILED in the modes M_FUSED / M_BYPASS is instantiated (hipErrorInvalidValue otherwise)
-hipError_t agx_launch_apply_watch(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
-// launch the children fast launch k_bucket_apply<V_ALL_COMPILED, mode, no skew, kWatch | kChild> (agx_set_children):
-// only V_ALL_COMPILED in the modes M_FUSED / M_BYPASS is instantiated (hipErrorInvalidValue otherwise)
-hipError_t agx_launch_apply_child(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
-// launch the supervision fast launch k_bucket_apply<V_ALL_COMPILED, mode, no skew, kSuper> (agx_set_supervision): only
-// V_ALL_COMPILED in the modes M_FUSED / M_BYPASS is instantiated (hipErrorInvalidValue otherwise)
-hipError_t agx_launch_apply_super(uint32_t vid, uint32_t mode, dim3 grid, hipStream_t s, const BucketArgs& ba);
+// launch a feature's fast launch k_bucket_apply<variant vid, mode, no skew, KM | km_flags, kPrio = prio> (agx_engine.hip
+// kFeatures: km_flags = the feature's KM flag bits, or none and `prio` for priority mailboxes).  Instantiated in the
+// modes M_FUSED / M_BYPASS: kPrio for the catch-all plain variants V_ALL / V_ALL_COMPILED, the flag combinations
+// kStashKM, kTimersKM, kWatchKM, kWatchKM | kChildKM, kSuperKM for V_ALL_COMPILED (hipErrorInvalidValue otherwise)
+hipError_t agx_launch_apply_feature(uint32_t vid, uint32_t mode, uint32_t km_flags, bool prio, dim3 grid, hipStream_t s,
+                                    const BucketArgs& ba);
 // launch k_tiny_apply<variant vid's kinds> (plain / compiled variants only: hipErrorInvalidValue otherwise)
 hipError_t agx_launch_tiny(uint32_t vid, dim3 grid, hipStream_t s, const BucketArgs& ba);
 // launch k_dense_apply<variant vid's kinds> (mode M_FUSED / M_OWNER: k_dense_fused) (plain / compiled variants only)
