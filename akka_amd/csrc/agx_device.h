@@ -238,6 +238,51 @@ __device__ __forceinline__ uint32_t tm_delay(uint64_t d) {
   return (int64_t)d < 1 ? 1u : d > (uint64_t)kTmMaxDelay ? kTmMaxDelay : (uint32_t)d;
 }
 
+// ---- receive timeouts (agx_set_receive_timeout; AA/dungeon/ReceiveTimeout.scala:18-74), on top
+// of the timers: the same logical time, clocks, due counts and backlog trick.  The timer storage of such an engine
+// is longer: after agen[np] come three [actor]-indexed rows
+//     rt_next[np]   the tick of the actor's next receive-timeout fire, kTmNone when none is to come
+//     rt_delay[np]  the timeout in ticks, 0: none set        rt_pay[np]  the message the behaviour receives
+// and the 8 words of the transparent-tag mask (bit t: messages of tag t are NotInfluenceReceiveTimeout).
+// Header words [8..11]: two u64 counters, fired and discarded.  On such an engine the bucket's `earliest` word is
+// a lower bound of the idle row's fires, not their exact minimum: an influencing receipt pushes a fire later
+// without touching it, and the rescan at the end of the tick the bound names re-establishes the exact value.
+constexpr uint32_t kRtCtr = 8;
+struct IdleDev {
+  uint32_t *next, *delay, *pay;
+  const uint32_t* mask;
+  unsigned long long* ctrs;
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const { return ctrs + i; }
+};
+__device__ __forceinline__ IdleDev idle_dev(const TimerDev& TD) {
+  IdleDev d;
+  d.next = TD.agen + TD.np;
+  d.delay = d.next + TD.np;
+  d.pay = d.delay + TD.np;
+  d.mask = d.pay + TD.np;
+  d.ctrs = reinterpret_cast<unsigned long long*>(TD.base + kRtCtr);
+  return d;
+}
+// an actor's timeout across its drained window, in registers: the delay, the message, and what the window's
+// cases did (kRtChanged: the case set or cancelled -- receiveTimeoutChanged; kRtWasOff: it turned a set timeout off)
+constexpr uint32_t kRtChanged = 1u, kRtWasOff = 2u;
+struct RtRegs {
+  uint32_t delay, pay, flags;
+};
+// is a message of this tag NotInfluenceReceiveTimeout?  The mask's words live in registers: a select chain, no load
+__device__ __forceinline__ bool rt_transparent(const uint32_t (&m)[8], uint32_t tag) {
+  const uint32_t i = tag >> 5;
+  uint32_t x = m[0];
+  x = i == 1u ? m[1] : x;
+  x = i == 2u ? m[2] : x;
+  x = i == 3u ? m[3] : x;
+  x = i == 4u ? m[4] : x;
+  x = i == 5u ? m[5] : x;
+  x = i == 6u ? m[6] : x;
+  x = i == 7u ? m[7] : x;
+  return (x >> (tag & 31u)) & 1u;
+}
+
 // ---- death watch (agx_set_death_watch; AA/dungeon/DeathWatch.scala:19-113,147-162)
 // One superstep is one tick.  DevParams.watch, u32 units:
 //   [0]        n_slots: watch slots per actor (1..4)
@@ -625,6 +670,8 @@ constexpr uint32_t kWatchKM = 1u << 28;
 constexpr uint32_t kSuperKM = 1u << 27;
 // KM flag (not a kind): the variant knows children (agx_set_children); only ever combined with kWatchKM.
 constexpr uint32_t kChildKM = 1u << 26;
+// KM flag (not a kind): the variant knows receive timeouts (agx_set_receive_timeout); only ever combined with kTimersKM.
+constexpr uint32_t kIdleKM = 1u << 25;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -716,10 +763,12 @@ __device__ __forceinline__ uint64_t tm_operand(const TimerDev& TD, uint32_t l, u
     return (uint64_t)((word < TD.nk && (TD.per[TD.at(word, l)] & kTmActive)) ? 1u : 0u) + (uint64_t)k;
   return cb_operand(src, word, k, pay, w, sender, self);
 }
-template <typename Emit>
+// (kIdle: the receive-timeout instantiations, DESIGN.md §2.7 -- AGX_A_SET_RECEIVE_TIMEOUT / _CANCEL_ act on the
+// actor's timeout in the caller's registers, `rt`; every other instantiation compiles as before)
+template <bool kIdle = false, typename Emit>
 __device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const TimerDev& TD, uint32_t l, uint32_t bkt,
                                                       uint32_t now, uint32_t& kind, uint32_t self, uint64_t* w,
-                                                      uint32_t src, uint32_t pay, Emit& emit) {
+                                                      uint32_t src, uint32_t pay, Emit& emit, RtRegs* rt = nullptr) {
   const uint32_t b = kind - AGX_KIND_COMPILED;
   if (b >= P.n_beh) return AGX_RES_UNHANDLED;
   const uint32_t c1 = P.bfirst[b + 1];
@@ -764,7 +813,18 @@ __device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const 
         case AGX_A_TIMER_CANCEL_ALL:
           for (uint32_t k = 0; k < TD.nk; ++k) TD.cancel(k, l, bkt);
           break;
-        default: break;
+        default:
+          if constexpr (kIdle) {
+            if (A.op == AGX_A_SET_RECEIVE_TIMEOUT) {
+              rt->delay = tm_delay(tm_operand(TD, l, A.dsrc, A.dword, A.dk, pay, w, src, self));
+              rt->pay = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;
+              rt->flags |= kRtChanged;
+            } else if (A.op == AGX_A_CANCEL_RECEIVE_TIMEOUT) {
+              rt->flags |= kRtChanged | (rt->delay ? kRtWasOff : 0u);
+              rt->delay = 0u;
+            }
+          }
+          break;
       }
     }
     if (C.result == AGX_RES_BECOME) {

@@ -150,6 +150,18 @@ struct agx_engine {
     std::vector<uint32_t> delays;
   };
   std::vector<TimerStart> tm_starts;  // agx_start_timers calls not yet applied on the device (prepare_run)
+  // receive timeouts (agx_set_receive_timeout), on top of the timers: three [actor] rows and the transparent-tag
+  // mask appended to the timer storage.  Such an engine launches the kTimers | kIdle instantiation
+  bool rt_on = false;
+  uint32_t rt_mask[8] = {0};   // bit t: messages of tag t are NotInfluenceReceiveTimeout
+  bool beh_rt = false;         // the compiled tables set or cancel a receive timeout
+  bool beh_rt_tag = false;     // the compiled tables name tag 0xFB (an or_mask or a tag test)
+  bool rt_bad_start = false;   // agx_start_receive_timeout was called on an engine without the feature: agx_run refuses
+  struct RtStart {
+    uint64_t first, count;
+    uint32_t delay, payload;
+  };
+  std::vector<RtStart> rt_starts;  // agx_start_receive_timeout calls not yet applied on the device (prepare_run)
   // death watch (agx_set_death_watch): n_slots watch slots per actor.  Such an engine launches the watch
   // instantiation of the compiled catch-all variant and no wave / ring / dense / persistent launch
   uint32_t wd_slots = 0;
@@ -421,7 +433,7 @@ namespace {
 // of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
 // the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
 // apply_variant, launch_apply and make_params.
-enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_N, F_NONE = F_N };
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_N, F_NONE = F_N };
 
 struct FeatureRow {
   bool (*on)(const agx_engine*);
@@ -464,6 +476,9 @@ const FeatureRow kFeatures[F_N] = {
     // theirs: the row only selects the launch
     {[](const agx_engine* e) { return e->d_child != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      nullptr, kWatchKM | kChildKM, false, F_WATCH},
+    // receive timeouts (agx_set_receive_timeout) come on top of the timers in the same way
+    {[](const agx_engine* e) { return e->rt_on; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+     kTimersKM | kIdleKM, false, F_TIMERS},
 };
 #undef AGX_ONCE
 
@@ -1282,9 +1297,61 @@ static __global__ void __launch_bounds__(kThreads) k_timer_sync(uint32_t* tm, co
   }
 }
 
+// ---- receive timeouts (agx_set_receive_timeout): the rows after the timers' (agx_device.h IdleDev)
+// agx_start_receive_timeout on the device: one thread per actor of the range sets (delay, payload) at its bucket's
+// clock; delay 0 cancels
+static __global__ void __launch_bounds__(kThreads) k_rt_start(uint32_t* tm, const uint8_t* alive, uint32_t nb, uint32_t bb,
+                                                             uint32_t first, uint32_t count, uint32_t delay, uint32_t payload) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t l = first + i, np = nb << bb;
+  if (!(alive[l] & 1u)) return;  // (a stopped actor has no timeout)
+  uint32_t* const rnext = tm + tm_slot_off(nb) + (4ull * tm[0] + 1ull) * np;
+  const uint32_t d = delay > kTmMaxDelay ? kTmMaxDelay : delay;
+  rnext[l] = d ? tm[kTmBucketOff + 2u * nb + (l >> bb)] + d : kTmNone;
+  rnext[(size_t)np + l] = d;
+  if (d) rnext[2ull * np + l] = payload;
+}
+// k_timer_sync of an engine with receive timeouts: the idle row counts as one more key
+static __global__ void __launch_bounds__(kThreads) k_rt_sync(uint32_t* tm, const uint8_t* alive, uint32_t nb, uint32_t bb,
+                                                            uint32_t n_local, uint32_t* blc) {
+  __shared__ uint32_t s_min, s_due;
+  const uint32_t b = blockIdx.x, np = nb << bb, nk = tm[0];
+  if (threadIdx.x == 0) {
+    s_min = kTmNone;
+    s_due = 0u;
+  }
+  __syncthreads();
+  const uint32_t* next = tm + tm_slot_off(nb);
+  const uint32_t* rnext = next + (4ull * nk + 1ull) * np;
+  const uint32_t now = tm[kTmBucketOff + 2u * nb + b];
+  const uint32_t a0 = b << bb, na = min(1u << bb, n_local - a0);
+  uint32_t mn = kTmNone, nd = 0;
+  for (uint32_t k = 0; k <= nk; ++k)
+    for (uint32_t la = threadIdx.x; la < na; la += kThreads) {
+      const uint32_t n = k < nk ? next[(size_t)k * np + a0 + la] : rnext[a0 + la];
+      if (n != kTmNone && (alive[a0 + la] & 1u)) {
+        mn = min(mn, n);
+        nd += n == now + 1u ? 1u : 0u;
+      }
+    }
+  if (mn != kTmNone) atomicMin(&s_min, mn);
+  if (nd) atomicAdd(&s_due, nd);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    tm[kTmBucketOff + b] = s_min;
+    blc[b] = blc[b] - min(tm[kTmBucketOff + nb + b], blc[b]) + s_due;
+    tm[kTmBucketOff + nb + b] = s_due;
+  }
+}
+
 size_t timers_words(const agx_engine* e) {
   const uint64_t npad = (uint64_t)e->nb << e->bb;
-  return tm_slot_off(e->nb) + (4ull * e->tm_keys + 1ull) * npad;
+  return tm_slot_off(e->nb) + (4ull * e->tm_keys + 1ull) * npad + (e->rt_on ? 3ull * npad + 8ull : 0ull);
+}
+// the receive-timeout rows of the timer storage: rt_next, then rt_delay, rt_pay and the mask (agx_device.h IdleDev)
+size_t rt_row_off(const agx_engine* e) {
+  return tm_slot_off(e->nb) + (4ull * e->tm_keys + 1ull) * ((uint64_t)e->nb << e->bb);
 }
 
 // The timer storage (agx_device.h TimerDev) -- allocated once, sized by n_local: counters, clocks and due counts
@@ -1302,6 +1369,11 @@ agx_status alloc_timers(agx_engine* e) {
   HIP_TRY(hipMemsetAsync(e->d_timers, 0, total * 4ull, e->stream));
   HIP_TRY(hipMemsetAsync(e->d_timers + kTmBucketOff, 0xFF, (size_t)e->nb * 4ull, e->stream));       // earliest
   HIP_TRY(hipMemsetAsync(e->d_timers + soff, 0xFF, (size_t)e->tm_keys * npad * 4ull, e->stream));  // next
+  if (e->rt_on) {
+    HIP_TRY(hipMemsetAsync(e->d_timers + rt_row_off(e), 0xFF, npad * 4ull, e->stream));  // rt_next
+    HIP_TRY(hipMemcpyAsync(e->d_timers + rt_row_off(e) + 3ull * npad, e->rt_mask, sizeof(e->rt_mask), hipMemcpyHostToDevice,
+                           e->stream));
+  }
   const uint32_t nk = e->tm_keys;
   HIP_TRY(hipMemcpyAsync(e->d_timers, &nk, 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1314,7 +1386,7 @@ uint32_t* next_backlog_counts(agx_engine* e) { return e->fused ? e->d_blc[e->par
 
 // apply the recorded agx_start_timers calls (the actors' flags are on the device: prepare_run)
 agx_status flush_timer_starts(agx_engine* e) {
-  if (e->tm_starts.empty()) return AGX_OK;
+  if (e->tm_starts.empty() && e->rt_starts.empty()) return AGX_OK;
   if (e->actors_dirty)  // (a query before the run: the host's flags are the newer ones; prepare_run uploads the rest)
     HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
   for (const auto& ts : e->tm_starts) {
@@ -1332,6 +1404,17 @@ agx_status flush_timer_starts(agx_engine* e) {
     if (d_del) hipFree(d_del);
   }
   e->tm_starts.clear();
+  for (const auto& rs : e->rt_starts) {  // (after the timer starts: a call order between the two kinds does not matter)
+    if (rs.count)
+      hipLaunchKernelGGL(k_rt_start, dim3((uint32_t)((rs.count + kThreads - 1) / kThreads)), dim3(kThreads), 0, e->stream,
+                         e->d_timers, e->d_alive, e->nb, e->bb, (uint32_t)rs.first, (uint32_t)rs.count, rs.delay, rs.payload);
+    HIP_TRY(hipGetLastError());
+  }
+  e->rt_starts.clear();
+  if (e->rt_on)
+    hipLaunchKernelGGL(k_rt_sync, dim3(e->nb), dim3(kThreads), 0, e->stream, e->d_timers, e->d_alive, e->nb, e->bb,
+                       (uint32_t)e->n_local, next_backlog_counts(e));
+  else
   hipLaunchKernelGGL(k_timer_sync, dim3(e->nb), dim3(kThreads), 0, e->stream, e->d_timers, e->d_alive, e->nb, e->bb,
                      (uint32_t)e->n_local, next_backlog_counts(e));
   HIP_TRY(hipGetLastError());
@@ -1672,6 +1755,15 @@ agx_status prepare_run(agx_engine* e) {
   if (e->beh_watch && !e->wd_slots)  // (only the watch variant interprets those: loud, never wrong)
     return set_err(AGX_EINVAL, "the compiled behaviours watch, unwatch or hold a signal case, but the engine has no death "
                    "watch (agx_set_death_watch)");
+  if (e->rt_bad_start)
+    return set_err(AGX_EINVAL, "agx_start_receive_timeout was called on an engine without receive timeouts "
+                   "(agx_set_receive_timeout)");
+  if (e->beh_rt && !e->rt_on)  // (only the receive-timeout variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours set or cancel a receive timeout, but the engine has no receive "
+                   "timeouts (agx_set_receive_timeout)");
+  if (e->rt_on && e->beh_rt_tag)
+    return set_err(AGX_EINVAL, "the compiled behaviours name message tag 0xFB, reserved for receive-timeout envelopes on an "
+                   "engine with receive timeouts");
   if (e->tm_bad_start)
     return set_err(AGX_EINVAL, "agx_start_timers was called on an engine without timers (agx_set_timers)");
   if (e->beh_tm_keys > e->tm_keys)  // (only the timer variant interprets those: loud, never wrong)
@@ -3445,6 +3537,8 @@ agx_status agx_set_timers(agx_engine* e, uint32_t n_keys) {
   if (n_keys < 1u || n_keys > AGX_MAX_TIMER_KEYS)
     return set_err(AGX_EINVAL, "timers: %u keys per actor (1..%u)", n_keys, AGX_MAX_TIMER_KEYS);
   AGX_TRY(refuse_feature(e, F_TIMERS));
+  if (e->rt_on && n_keys != e->tm_keys)
+    return set_err(AGX_EINVAL, "timers: the key count cannot change once receive timeouts are set (agx_set_receive_timeout)");
   AGX_TRY(ensure_dev(e));
   if (e->d_timers && n_keys != e->tm_keys) {
     hipFree(e->d_timers);
@@ -3467,6 +3561,9 @@ agx_status agx_start_timers(agx_engine* e, uint64_t first_id, uint64_t count, ui
   }
   if (key >= e->tm_keys) return set_err(AGX_EINVAL, "timer key %u: the engine has %u slots per actor", key, e->tm_keys);
   if (first_id + count > e->n_global || first_id + count < first_id) return set_err(AGX_EINVAL, "bad actor range");
+  if (e->rt_on && (payload >> 24) == AGX_TAG_RECEIVE_TIMEOUT)
+    return set_err(AGX_EINVAL, "agx_start_timers: message tag 0xFB is reserved for receive-timeout envelopes on an engine "
+                   "with receive timeouts");
   agx_engine::TimerStart ts;
   ts.first = first_id;
   ts.count = count;
@@ -3535,6 +3632,100 @@ agx_status agx_read_timers(agx_engine* e, uint64_t actor_id, uint32_t active[4],
     if (payload) payload[k] = v[3];
     if (generation) generation[k] = v[2];
   }
+  return AGX_OK;
+}
+
+// AA/dungeon/ReceiveTimeout.scala:18-74 (typed: TY/internal/adapter/ActorContextAdapter.scala:120-131)
+agx_status agx_set_receive_timeout(agx_engine* e, const uint32_t transparent_tags[8]) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->tm_keys) return set_err(AGX_EINVAL, "receive timeouts need an engine with timers (agx_set_timers first)");
+  if (e->started) return set_err(AGX_ESTATE, "set receive timeouts before the first agx_run");
+  if (e->rt_on) return set_err(AGX_EINVAL, "receive timeouts are set already (agx_set_receive_timeout is called once)");
+  if (e->beh_rt_tag)
+    return set_err(AGX_EINVAL, "receive timeouts: the compiled behaviours name message tag 0xFB, reserved for receive-timeout "
+                   "envelopes");
+  for (const auto& ts : e->tm_starts)
+    if ((ts.payload >> 24) == AGX_TAG_RECEIVE_TIMEOUT)
+      return set_err(AGX_EINVAL, "receive timeouts: a recorded agx_start_timers payload carries message tag 0xFB, reserved for "
+                     "receive-timeout envelopes");
+  if (e->hs_pay.end() != std::find_if(e->hs_pay.begin(), e->hs_pay.end(),
+                                      [](uint32_t p) { return (p >> 24) == AGX_TAG_RECEIVE_TIMEOUT; }))
+    return set_err(AGX_EINVAL, "receive timeouts: a staged tell carries message tag 0xFB, reserved for receive-timeout "
+                   "envelopes");
+  AGX_TRY(ensure_dev(e));
+  for (uint32_t i = 0; i < 8; ++i) e->rt_mask[i] = transparent_tags ? transparent_tags[i] : 0u;
+  // the storage grows by the three rows and the mask: allocated anew (no timer has run; recorded starts are kept)
+  hipFree(e->d_timers);
+  e->d_timers = nullptr;
+  e->rt_on = true;
+  e->rt_bad_start = false;  // (an agx_start_receive_timeout refused before this call no longer stands in the way of agx_run)
+  const agx_status r = alloc_timers(e);  // (now: AGX_ENOMEM is this call's)
+  if (r != AGX_OK) {
+    e->rt_on = false;
+    (void)alloc_timers(e);
+    return r;
+  }
+  drop_graphs(e);  // the variant and the timer storage are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_start_receive_timeout(agx_engine* e, uint64_t first_id, uint64_t count, uint32_t delay, uint32_t payload) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->rt_on) {
+    e->rt_bad_start = true;  // (agx_run refuses too: the rule for tables that set a receive timeout)
+    return set_err(AGX_EINVAL, "agx_start_receive_timeout needs an engine with receive timeouts (agx_set_receive_timeout)");
+  }
+  if (first_id + count > e->n_global || first_id + count < first_id) return set_err(AGX_EINVAL, "bad actor range");
+  if (delay && (payload >> 24) == AGX_TAG_RECEIVE_TIMEOUT)
+    return set_err(AGX_EINVAL, "agx_start_receive_timeout: message tag 0xFB is reserved for receive-timeout envelopes");
+  e->rt_starts.push_back({first_id, count, delay, payload});
+  return AGX_OK;
+}
+
+agx_status agx_receive_timeout_info(agx_engine* e, uint64_t* fired, uint64_t* discarded, uint64_t* set, uint64_t* pending) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[2] = {0, 0}, ns = 0, npd = 0;
+  if (e->rt_on && e->d_timers) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(flush_timer_starts(e));  // (starts recorded since the last run: applied now, nothing else is uploaded)
+    AGX_TRY(copy_sync(e, c, e->d_timers + kRtCtr, sizeof(c), hipMemcpyDeviceToHost));
+    const uint64_t npad = (uint64_t)e->nb << e->bb;
+    std::vector<uint32_t> rows(2ull * npad);  // rt_next, rt_delay
+    AGX_TRY(copy_sync(e, rows.data(), e->d_timers + rt_row_off(e), rows.size() * 4ull, hipMemcpyDeviceToHost));
+    for (uint64_t l = 0; l < e->n_local; ++l) {
+      if (!rows[npad + l]) continue;
+      ++ns;
+      npd += rows[l] != kTmNone;
+    }
+  }
+  if (fired) *fired = c[0];
+  if (discarded) *discarded = c[1];
+  if (set) *set = ns;
+  if (pending) *pending = npd;
+  return AGX_OK;
+}
+
+agx_status agx_read_receive_timeout(agx_engine* e, uint64_t first_id, uint64_t count, uint32_t* delay, uint32_t* remaining,
+                                    uint32_t* payload) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (first_id + count > e->n_global || first_id + count < first_id) return set_err(AGX_EINVAL, "bad actor range");
+  for (uint64_t i = 0; i < count; ++i) {
+    if (delay) delay[i] = 0;
+    if (remaining) remaining[i] = 0xFFFFFFFFu;
+    if (payload) payload[i] = 0;
+  }
+  if (!e->rt_on || !e->d_timers || !count) return AGX_OK;
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_timer_starts(e));  // (starts recorded since the last run: applied now, nothing else is uploaded)
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  uint32_t clk = 0;  // (every bucket's clock holds the tick count)
+  AGX_TRY(copy_sync(e, &clk, e->d_timers + kTmBucketOff + 2ull * e->nb, 4, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> nx(count);
+  AGX_TRY(copy_sync(e, nx.data(), e->d_timers + rt_row_off(e) + first_id, count * 4ull, hipMemcpyDeviceToHost));
+  if (delay) AGX_TRY(copy_sync(e, delay, e->d_timers + rt_row_off(e) + npad + first_id, count * 4ull, hipMemcpyDeviceToHost));
+  if (payload) AGX_TRY(copy_sync(e, payload, e->d_timers + rt_row_off(e) + 2ull * npad + first_id, count * 4ull, hipMemcpyDeviceToHost));
+  if (remaining)
+    for (uint64_t i = 0; i < count; ++i) remaining[i] = nx[i] == kTmNone ? 0xFFFFFFFFu : nx[i] - clk;
   return AGX_OK;
 }
 
@@ -3951,13 +4142,33 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     const agx_act& A = acts[i];
     const bool tmop = A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL;  // (`word` is the key)
     const bool wdop = A.op >= AGX_A_WATCH && A.op <= AGX_A_UNWATCH;  // (the ref is the d-operand)
-    if (A.op < AGX_A_SET || A.op > AGX_A_STOP_CHILD || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+    if (A.op < AGX_A_SET || A.op > AGX_A_CANCEL_RECEIVE_TIMEOUT || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
         !opnd_ok(A.src, A.sword) ||
-        ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop || A.op == AGX_A_STOP_CHILD) &&
+        ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop || A.op == AGX_A_STOP_CHILD ||
+          A.op == AGX_A_SET_RECEIVE_TIMEOUT) &&
          !opnd_ok(A.dsrc, A.dword)) ||
         (A.op == AGX_A_SPAWN && A.dword >= AGX_MAX_SPAWN_SITES))
       return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (state words 0..1, timer keys 0..3, spawn sites 0..63)", i);
   }
+  for (uint32_t i = 0; i < n_acts; ++i)
+    if (acts[i].op == AGX_A_SET_RECEIVE_TIMEOUT && acts[i].dsrc == AGX_V_CONST && acts[i].dk < 1)
+      return set_err(AGX_EINVAL, "compiled behaviours: action %u sets a receive timeout of %lld ticks (a constant delay is at "
+                     "least 1)", i, (long long)acts[i].dk);
+  // receive timeouts: tag 0xFB named by a tag test or a message tag (refused on an engine with receive timeouts)
+  bool rt_tag = false;
+  auto rt_named = [&](uint32_t s1, int64_t k1, uint32_t cmp, uint32_t s2, int64_t k2) {
+    if (cmp == AGX_CMP_ANY) return;
+    rt_tag |= s1 == AGX_V_TAG && k1 == 0 && s2 == AGX_V_CONST && k2 == (int64_t)AGX_TAG_RECEIVE_TIMEOUT;
+    rt_tag |= s2 == AGX_V_TAG && k2 == 0 && s1 == AGX_V_CONST && k1 == (int64_t)AGX_TAG_RECEIVE_TIMEOUT;
+  };
+  for (uint32_t c = 0; c < n_cases; ++c) {
+    rt_named(cases[c].src1, cases[c].k1, cases[c].cmp1, cases[c].src2, cases[c].k2);
+    rt_named(cases[c].src3, cases[c].k3, cases[c].cmp2, cases[c].src4, cases[c].k4);
+  }
+  for (uint32_t i = 0; i < n_acts; ++i) rt_tag |= (acts[i].or_mask >> 24) == AGX_TAG_RECEIVE_TIMEOUT;
+  if (e->rt_on && rt_tag)
+    return set_err(AGX_EINVAL, "compiled behaviours: message tag 0xFB is reserved for receive-timeout envelopes on an engine "
+                   "with receive timeouts");
   // children: a spawn and a stop of a child each send one envelope through the case's tell slot
   bool uses_child = false, ctl_tags = false;
   auto ch_use = [&](uint32_t src) { uses_child |= src == AGX_V_SPAWNED || src == AGX_V_CHILD; };
@@ -4041,6 +4252,10 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     }
     e->beh_sv_tells = std::max(e->beh_sv_tells, fs + sg);
   }
+  e->beh_rt = false;  // (checked against agx_set_receive_timeout at agx_run)
+  for (uint32_t i = 0; i < n_acts; ++i)
+    e->beh_rt |= acts[i].op == AGX_A_SET_RECEIVE_TIMEOUT || acts[i].op == AGX_A_CANCEL_RECEIVE_TIMEOUT;
+  e->beh_rt_tag = rt_tag;
   e->beh_child = uses_child;  // (checked against agx_set_children at agx_run)
   e->beh_ctl_tags = ctl_tags;
   e->beh_watch = false;  // a watch action or a signal case (checked against agx_set_death_watch at agx_run)
@@ -4210,6 +4425,9 @@ agx_status agx_stage_tells(agx_engine* e, const uint32_t* dst, const uint32_t* s
       return set_err(AGX_EINVAL, "tell %zu: sender %u is not an actor id (bit 31 tags CRDT state gossips)", i, sv);
     if (e->tm_keys && (payload[i] >> 24) == AGX_TAG_TIMER)
       return set_err(AGX_EINVAL, "tell %zu: message tag 0xFF is reserved for timer messages on an engine with timers", i);
+    if (e->rt_on && (payload[i] >> 24) == AGX_TAG_RECEIVE_TIMEOUT)
+      return set_err(AGX_EINVAL, "tell %zu: message tag 0xFB is reserved for receive-timeout envelopes on an engine with "
+                     "receive timeouts", i);
     if (e->wd_slots && (payload[i] >> 24) == AGX_TAG_WATCH)
       return set_err(AGX_EINVAL, "tell %zu: message tag 0xFE is reserved for Terminated envelopes on an engine with death watch", i);
     if (e->d_child && ((payload[i] >> 24) == AGX_TAG_CREATE || (payload[i] >> 24) == AGX_TAG_STOP))
@@ -4295,6 +4513,9 @@ agx_status agx_tell(agx_engine* e, uint32_t dst, uint32_t src, uint32_t payload,
     return set_err(AGX_EINVAL, "tell: sender %u is not an actor id (bit 31 tags CRDT state gossips)", src);
   if (e->tm_keys && (payload >> 24) == AGX_TAG_TIMER)
     return set_err(AGX_EINVAL, "tell: message tag 0xFF is reserved for timer messages on an engine with timers");
+  if (e->rt_on && (payload >> 24) == AGX_TAG_RECEIVE_TIMEOUT)
+    return set_err(AGX_EINVAL, "tell: message tag 0xFB is reserved for receive-timeout envelopes on an engine with receive "
+                   "timeouts");
   if (e->wd_slots && (payload >> 24) == AGX_TAG_WATCH)
     return set_err(AGX_EINVAL, "tell: message tag 0xFE is reserved for Terminated envelopes on an engine with death watch");
   if (e->d_child && ((payload >> 24) == AGX_TAG_CREATE || (payload >> 24) == AGX_TAG_STOP))

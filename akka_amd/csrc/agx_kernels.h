@@ -1333,7 +1333,9 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
   for (int d = kWave / 2; d > 0; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d, kWave));
   return v;
 }
-template <bool kGather>
+// kIdle (receive timeouts): the earliest word is then a lower bound for the idle row, the scan
+// takes that row as one more key, and it leaves the exact value behind.
+template <bool kGather, bool kIdle = false>
 __device__ __forceinline__ void timer_tick_end(const BucketArgs& a, const TimerDev& TD, uint32_t b, uint32_t a0,
                                                uint32_t na, uint32_t now, uint32_t bltot, uint32_t w,
                                                const uint8_t* alive, uint32_t* scratch) {
@@ -1366,6 +1368,24 @@ __device__ __forceinline__ void timer_tick_end(const BucketArgs& a, const TimerD
           if (nv != kTmNone) {
             nd += nv == now + 1u ? 1u : 0u;
             mn = min(mn, nv);
+          }
+        }
+      }
+    }
+    if constexpr (kIdle) {  // the idle row: one more key
+      const IdleDev ID = idle_dev(TD);
+      uint4 n4 = make_uint4(kTmNone, kTmNone, kTmNone, kTmNone);
+      if ((uint32_t)tid * kBAct < na) n4 = *reinterpret_cast<const uint4*>(ID.next + a0 + tid * kBAct);
+      const uint32_t nx[kBAct] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+      for (int j = 0; j < kBAct; ++j) {
+        const uint32_t la = tid * kBAct + j;
+        if (la < na && (alive[la] & 1u) && nx[j] != kTmNone) {
+          if (nx[j] <= now) {  // (a fire of this tick that was not sent: the task is one-shot, none is to come)
+            ID.next[a0 + la] = kTmNone;
+          } else {
+            nd += nx[j] == now + 1u ? 1u : 0u;
+            mn = min(mn, nx[j]);
           }
         }
       }
@@ -1622,6 +1642,19 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
   if constexpr (kTm) {
     TD = timer_dev(P, a.nb, a.bb);
     tnow = TD.clock(b) + 1u;
+  }
+  // kIdle: receive timeouts (agx_set_receive_timeout), on top of the timers.  The tick's
+  // receive-timeout envelopes follow the TimerMsgs in the inbox; the drain keeps an actor's timeout in registers
+  // across its window and writes the next fire once, after it; the transparent-tag mask lives in registers.
+  constexpr bool kIdle = (KM & kIdleKM) != 0;
+  static_assert(!kIdle || kTm, "receive timeouts: on the timer instantiations only");
+  IdleDev ID{};
+  uint32_t rtmask[8] = {};
+  uint32_t rtmin = kTmNone;  // kIdle: the lowest next fire this thread wrote (0: a timeout was turned off)
+  if constexpr (kIdle) {
+    ID = idle_dev(TD);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) rtmask[i] = ID.mask[i];
   }
   // kWd: death watch (agx_set_death_watch).  The tick's Terminated envelopes are the inbox's
   // last items (k_bucket_apply put them there); the drain intercepts them, compiled cases run the watch
@@ -2035,6 +2068,17 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       __syncthreads();
       ppar = L.scratch[0] == 0u;
     }
+    // kIdle: the delays of this thread's actors with mail, fetched beside their state (striped as the drain is:
+    // a wave's 64 lanes read 64 consecutive words), so the drain starts with them in registers
+    uint32_t rtd[kBAct] = {};
+    if constexpr (kIdle) {
+#pragma unroll
+      for (int j = 0; j < kBAct; ++j) {
+        const uint32_t la = j * kBThreads + tid;
+        const bool has = la < na && (L.alive[la] & 1u) && L.seg[la + 1] != L.seg[la];
+        rtd[j] = has ? ID.delay[a0 + la] : 0u;
+      }
+    }
     auto sp_actor = [&](int j) {
       const uint32_t la = act_of(j);
       ecl[j] = 0;
@@ -2169,6 +2213,82 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         if (nst) atomicAdd(SD.ctr(0), (unsigned long long)nst);
         if (nun) atomicAdd(SD.ctr(1), (unsigned long long)nun);
         if (nov) atomicAdd(SD.ctr(2), (unsigned long long)nov);
+      } else if constexpr (kIdle) {
+        // the timer drain below with the receive timeout (dungeon/ReceiveTimeout.scala:33-74): the actor's delay
+        // (prefetched with its state) and message stay in registers across the window.  An envelope (tag 0xFB)
+        // takes a drain slot and counts as delivered; with no timeout set at that point it is discarded, else the
+        // behaviour runs on the message stored now, with the actor itself as the sender.  A message that is not
+        // transparent, the envelope's, or one whose case set or cancelled, moves the next fire to now + delay:
+        // one store after the window, and no atomic per message (the bucket's bound: rtmin, folded per wave)
+        uint32_t rd = j == 0 ? rtd[0] : j == 1 ? rtd[1] : j == 2 ? rtd[2] : rtd[3];  // (j is wave-uniform)
+        const uint32_t rd0 = rd;
+        uint32_t rp = 0u, rn = kTmNone;
+        bool rp_known = false, rp_set = false, touched = false, was_off = false;
+        uint32_t ndisc = 0, nrdisc = 0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          bool envelope = false;
+          ++ndel;
+          if ((pv >> 24) == AGX_TAG_TIMER) {
+            const uint32_t key = (pv >> 22) & 3u;
+            const size_t i = TD.at(key < TD.nk ? key : 0u, l);
+            const uint32_t pr = key < TD.nk ? TD.per[i] : 0u;
+            if (!(pr & kTmActive) || ((TD.gen[i] ^ pv) & kTmGenMask)) {
+              ++ndisc;  // (a discarded TimerMsg does not influence: the bounded difference of §2.7)
+              continue;
+            }
+            if (!(pr & ~kTmActive)) TD.per[i] = 0u;  // a single timer: inactive now (nothing of it is to come)
+            sv = self;
+            pv = TD.pay[i];
+          } else if ((pv >> 24) == AGX_TAG_RECEIVE_TIMEOUT) {
+            if (!rd) {
+              ++nrdisc;
+              continue;
+            }
+            if (!rp_known) {
+              rp = ID.pay[l];
+              rp_known = true;
+            }
+            envelope = true;
+            sv = self;
+            pv = rp;
+          }
+          RtRegs rt{rd, rp, 0u};
+          const uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_tm<true>(P, TD, l, b, tnow, kcur, self, wv, sv, pv, em, &rt)
+                                                       : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          if (rt.flags & kRtChanged) {
+            if (rt.delay) {
+              rp = rt.pay;
+              rp_known = rp_set = true;
+            }
+            rd = rt.delay;
+            was_off |= (rt.flags & kRtWasOff) != 0u;
+          }
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            for (uint32_t k = 0; k < TD.nk; ++k) TD.cancel(k, l, b);  // cancelAll on PostStop
+            was_off |= rd != 0u;  // any stop turns the timeout off
+            rd = 0u;
+            rn = kTmNone;
+            touched = true;
+            break;
+          }
+          if ((rt.flags & kRtChanged) || (rd && (envelope || !rt_transparent(rtmask, pv >> 24)))) {
+            rn = rd ? tnow + rd : kTmNone;
+            touched = true;
+          }
+        }
+        if (touched) ID.next[l] = rn;
+        if (rd != rd0) ID.delay[l] = rd;
+        if (rp_set) ID.pay[l] = rp;
+        // the bucket's bound: a fire written here may be the earliest; a timeout turned off may have been (0: rescan)
+        if (was_off) rtmin = 0u;
+        else if (touched && rn != kTmNone) rtmin = min(rtmin, rn);
+        if (ndisc) atomicAdd(TD.ctr(1), (unsigned long long)ndisc);
+        if (nrdisc) atomicAdd(ID.ctr(1), (unsigned long long)nrdisc);
       } else if constexpr (kTm) {
         // the drain with interceptTimerMsg (TimerSchedulerImpl.scala:145-172): a TimerMsg takes a drain
         // slot and counts as delivered; a stale one is discarded, else the behaviour runs on the slot's
@@ -2380,6 +2500,10 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
 #pragma unroll 1
       for (int j = 0; j < kBAct; ++j) sp_actor(j);
     }
+    if constexpr (kIdle) {  // at most one atomic per wave per tick keeps the bucket's bound below every fire written
+      const uint32_t m = wave_min_u32(rtmin);
+      if (lane_id() == 0 && m != kTmNone) atomicMin(&TD.earliest(b), m);
+    }
     __syncthreads();
     if constexpr (kStash) {
       // the bucket's pending count (read at its entry next superstep) joins its backlog count: the
@@ -2393,7 +2517,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         else a.chunk_cnt[b] = bltot + nptot;
       }
     }
-    if constexpr (kTm) timer_tick_end<kGather>(a, TD, b, a0, na, tnow, bltot, w, L.alive, L.scratch);
+    if constexpr (kTm) timer_tick_end<kGather, kIdle>(a, TD, b, a0, na, tnow, bltot, w, L.alive, L.scratch);
     if constexpr (kCh) child_tick_end<kGather>(a, L, CD, WD, b, a0, na, tnow);  // (before the watch scan: the slots a cascade frees)
     if constexpr (kWd) watch_tick_end(a, WD, b, a0, na, tnow, bltot, w, kGather, L.scratch);
     if constexpr (kSv)  // (after the barrier: every drain of the bucket has read this launch's clock)
@@ -4717,6 +4841,10 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
   // bucket runs every tick (its clock is the tick count), and a bucket never takes the skew launch.
   constexpr bool kTm = (KM & kTimersKM) != 0;  // (a flag of KM: agx_device.h)
   static_assert(!kTm || (!kWide && !kSkew && !kOwner && !kPrio && !kStash), "timers: single-rank fast launches, plain behaviours");
+  // kIdle: receive timeouts (agx_set_receive_timeout), on top of the timers: the tick's
+  // receive-timeout envelopes are written after each actor's TimerMsgs, as one more key after the last.
+  constexpr bool kIdle = (KM & kIdleKM) != 0;  // (a flag of KM: agx_device.h)
+  static_assert(!kIdle || kTm, "receive timeouts: on the timer instantiations only");
   // kWd: death watch (agx_set_death_watch) -- the same launches of an engine with death watch.
   // A bucket's inbox then ends with the tick's Terminated envelopes (written here from the due slots, in
   // (actor, slot) order), its backlog count carries their number (watch_tick_end), every bucket runs every
@@ -5064,7 +5192,7 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         const TimerDev TD = timer_dev(P, a.nb, a.bb);
         if (kLateAlive) reinterpret_cast<uint32_t*>(s_alive)[tid] = alive4;
         __syncthreads();
-        timer_tick_end<kGather>(a, TD, b, a0, na, TD.clock(b) + 1u, 0u, wpar, s_alive, scratch);
+        timer_tick_end<kGather, kIdle>(a, TD, b, a0, na, TD.clock(b) + 1u, 0u, wpar, s_alive, scratch);
         __syncthreads();
       }
       if constexpr ((KM & kChildKM) != 0) {  // (and the children of a parent that stopped in the tick before)
@@ -5174,6 +5302,20 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
               }
             }
           }
+          uint32_t rfm = 0, nrt = 0;  // kIdle: bit j: actor j's receive timeout fires; the envelopes this thread wrote
+          if constexpr (kIdle) {
+            uint4 n4 = make_uint4(kTmNone, kTmNone, kTmNone, kTmNone);
+            if ((uint32_t)tid * kBAct < na) n4 = *reinterpret_cast<const uint4*>(idle_dev(TD).next + a0 + tid * kBAct);
+            const uint32_t nx[kBAct] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+            for (int j = 0; j < kBAct; ++j) {
+              const uint32_t la = tid * kBAct + j, ab = (alive4 >> (8 * j)) & 0xFFu;
+              if (la < na && (ab & 1u) && nx[j] == now) {
+                rfm |= 1u << j;
+                ++tot;
+              }
+            }
+          }
           uint32_t t;
           uint32_t ex = block_excl_sum<kBThreads>(tot, scratch, &t);
           if (t < np) {
@@ -5201,7 +5343,28 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
               }
               ++ex;
             }
+            if constexpr (kIdle) {  // the envelope: sender = the actor; the task is one-shot, none is to come
+              if ((rfm >> j) & 1u) {
+                if (ex < np) {
+                  const uint32_t l = a0 + tid * kBAct + j;
+                  wk[ex] = l;
+                  wk[kBucket + ex] = l;
+                  wk[2 * kBucket + ex] = AGX_TAG_RECEIVE_TIMEOUT << 24;
+                  idle_dev(TD).next[l] = kTmNone;
+                  ++nrt;
+                }
+                ++ex;
+              }
+            }
           }
+          if constexpr (kIdle) {  // `fired` of the timers and of the receive timeouts, apart
+            uint32_t rtot;
+            block_excl_sum<kBThreads>(nrt, scratch, &rtot);
+            if (tid == 0) {
+              if (min(t, np) > rtot) atomicAdd(TD.ctr(0), (unsigned long long)(min(t, np) - rtot));
+              if (rtot) atomicAdd(idle_dev(TD).ctr(0), (unsigned long long)rtot);
+            }
+          } else
           if (tid == 0) atomicAdd(TD.ctr(0), (unsigned long long)min(t, np));
           __syncthreads();
         }

@@ -252,6 +252,36 @@ class GpuEngine:
         check(self.lib.agx_read_timers(self._h, actor_id, *(_ptr(x, ctypes.c_uint32) for x in a)))
         return dict(zip(("active", "remaining", "period", "payload", "generation"), a))
 
+    def set_receive_timeout(self, transparent_tags=()) -> None:
+        """Receive timeouts for every actor (agx_set_receive_timeout): context.setReceiveTimeout /
+        cancelReceiveTimeout (AA/dungeon/ReceiveTimeout.scala:18-74) on top of the timers -- call set_timers first.
+        Messages whose tag is in `transparent_tags` are NotInfluenceReceiveTimeout."""
+        mask = np.zeros(8, np.uint32)
+        for t in transparent_tags:
+            if not 0 <= int(t) <= 0xFF:
+                raise ValueError("a message tag has 8 bits")
+            mask[int(t) >> 5] |= np.uint32(1 << (int(t) & 31))
+        check(self.lib.agx_set_receive_timeout(self._h, _ptr(mask, ctypes.c_uint32)))
+
+    def start_receive_timeout(self, first: int, count: int, delay: int, payload: int = 0) -> None:
+        """agx_start_receive_timeout: every live actor of [first, first + count) sets (delay, payload) at the
+        current tick (a setup block); delay 0 cancels."""
+        check(self.lib.agx_start_receive_timeout(self._h, first, count, int(delay), int(payload) & 0xFFFFFFFF))
+
+    def receive_timeout_info(self) -> dict:
+        """agx_receive_timeout_info: totals fired / discarded, the actors with a timeout set / pending now."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        check(self.lib.agx_receive_timeout_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(("fired", "discarded", "set", "pending"), (int(x.value) for x in v)))
+
+    def read_receive_timeout(self, first: int = 0, count: int | None = None) -> dict:
+        """agx_read_receive_timeout: delay, remaining (ticks to the next fire, 0xFFFFFFFF when none is to come) and
+        payload of the actors [first, first + count)."""
+        count = self.cfg.n_actors - first if count is None else count
+        a = [np.zeros(count, np.uint32) for _ in range(3)]
+        check(self.lib.agx_read_receive_timeout(self._h, first, count, *(_ptr(x, ctypes.c_uint32) for x in a)))
+        return dict(zip(("delay", "remaining", "payload"), a))
+
     def set_death_watch(self, n_slots: int) -> None:
         """`n_slots` (1..4) watch slots for every actor (agx_set_death_watch): context.watch / watchWith / unwatch
         and the Terminated signal (AA/dungeon/DeathWatch.scala:19-113) in the timers' logical time.  Compiled

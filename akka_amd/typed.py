@@ -29,6 +29,10 @@ What lowers:
     ``context.child_at(x)`` and ``context.spawned`` (children on the death-watch engine): the
     spawned behaviours are lowered with their parents, ``Tables.spawn_sites`` goes to engine.set_children, and a
     case holds at most one of tell, spawn and stop;
+  * ``context.set_receive_timeout(delay, msg)`` and ``context.cancel_receive_timeout()`` (receive timeouts on the
+    timers engine); ``compile_behaviors(..., transparent=(MessageType, ...))`` names the
+    NotInfluenceReceiveTimeout types (``Tables.transparent_tags`` -> engine.set_receive_timeout, after
+    engine.set_timers(max(Tables.timer_keys, 1)));
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -76,6 +80,8 @@ A_SPAWN, A_STOP_CHILD = 13, 14
 TAG_CREATE, TAG_STOP = 0xFD, 0xFC  # the tags of Create / Stop envelopes: reserved when the tables use children
 MAX_CHILD_REGIONS, MAX_SPAWN_SITES = 8, 64
 SPAWN_ARG_BITS = 18          # a spawn's argument: its low 18 bits are added to the site's word-0 base
+A_SET_RECEIVE_TIMEOUT, A_CANCEL_RECEIVE_TIMEOUT = 15, 16
+TAG_RECEIVE_TIMEOUT = 0xFB   # the tag of a receive-timeout envelope: reserved when the tables use receive timeouts
 
 
 class AgxCase(ctypes.Structure):
@@ -470,6 +476,28 @@ class ActorContext:
         """The number of children the actor has spawned so far."""
         return Operand(V_SPAWNED)
 
+    # receive timeouts (engine.set_receive_timeout on top of engine.set_timers; AA/dungeon/ReceiveTimeout.scala:18-74,
+    # typed TY/internal/adapter/ActorContextAdapter.scala:120-131)
+    def set_receive_timeout(self, delay, msg) -> "Action":
+        """context.setReceiveTimeout(delay, msg): `msg` arrives, its sender the actor itself, once the actor has
+        processed no influencing message for `delay` ticks (an operand or a constant of at least 1), and again
+        every `delay` ticks while it stays idle.  Messages of the types named in
+        compile_behaviors(transparent=...) do not push the timeout back."""
+        if isinstance(msg, Message):
+            val, mask = msg.arg, msg.or_mask
+        else:
+            val, mask = lift(msg), 0
+        d = lift(delay)
+        if d.src == V_CONST and d.k < 1:
+            raise CompileError(f"a receive timeout is at least 1 tick, not {d.k}")
+        if d.src == V_CONST and d.k > MAX_TIMER_DELAY:
+            raise CompileError(f"a receive timeout is at most {MAX_TIMER_DELAY} ticks")
+        return Action(A_SET_RECEIVE_TIMEOUT, 0, val, d, mask)
+
+    def cancel_receive_timeout(self) -> "Action":
+        """context.cancelReceiveTimeout(): an envelope already enqueued stays in the mailbox and is discarded."""
+        return Action(A_CANCEL_RECEIVE_TIMEOUT, 0)
+
 
 context = ActorContext()
 
@@ -789,6 +817,7 @@ class Tables:
     supervisors: list = field(default_factory=list)  # per behaviour: its AgxSupervisor entries, inner first
     exception_classes: list = field(default_factory=list)  # the ExceptionTypes in use; the index is the class number
     spawn_sites: list = field(default_factory=list)  # (kind, word-0 base, word 1 or None: the parent's id) -> engine.set_children
+    transparent_tags: tuple = ()  # the tags of the NotInfluenceReceiveTimeout message types -> engine.set_receive_timeout
 
     @property
     def uses_supervision(self) -> bool:
@@ -822,6 +851,12 @@ class Tables:
             if A_TIMER_SINGLE <= a.op <= A_TIMER_CANCEL_ALL:
                 n = max(n, 1 if a.op == A_TIMER_CANCEL_ALL else a.word + 1)
         return n
+
+    @property
+    def uses_receive_timeout(self) -> bool:
+        """The behaviours set or cancel a receive timeout: the engine needs engine.set_receive_timeout(
+        tables.transparent_tags) on top of engine.set_timers(max(tables.timer_keys, 1))."""
+        return any(a.op in (A_SET_RECEIVE_TIMEOUT, A_CANCEL_RECEIVE_TIMEOUT) for a in self.acts[:self.n_acts])
 
     @property
     def uses_watch(self) -> bool:
@@ -867,10 +902,14 @@ def _reachable(roots) -> list:
     return order
 
 
-def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
+def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tables:
     """Lower `roots` and every behaviour they become into the engine's tables.  With `max_emit`
     (the engine's agx_cfg.max_emit), a case that tells more often than that is a CompileError:
-    the apply kernels reserve max_emit tell slots per message."""
+    the apply kernels reserve max_emit tell slots per message.  `transparent`: the MessageTypes that are
+    NotInfluenceReceiveTimeout for behaviours with a receive timeout (Tables.transparent_tags)."""
+    for mt in transparent:
+        if not isinstance(mt, MessageType):
+            raise CompileError(f"transparent= takes MessageTypes, not {mt!r}")
     behs = _reachable(roots)
     if len(behs) > MAX_BEHAVIORS:
         raise CompileError(f"more than {MAX_BEHAVIORS} behaviours")
@@ -929,6 +968,7 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
                np.asarray(first, dtype=np.uint32), len(acts))
     t.exception_classes = excs
     t.spawn_sites = [(KIND_COMPILED + bi, base, w1) for bi, base, w1 in sites]
+    t.transparent_tags = tuple(sorted({mt.tag for mt in transparent}))
     for b in behs:  # a supervisor of a class catches it and its descendants: the hierarchy as masks
         row = []
         for sv in b.supervisors:
@@ -961,7 +1001,22 @@ def compile_behaviors(roots, max_emit: int | None = None) -> Tables:
             if fs + sg > 1:
                 raise CompileError(f"behaviour {b.name!r}: a case that fails or stops and the largest PreRestart / PostStop "
                                    f"case tell {fs + sg} times together; an engine with supervision has max_emit 1")
-    if t.timer_keys:  # tag 0xFF is the TimerMsg's: no message type of these behaviours may carry it
+    if t.uses_receive_timeout:  # on the timer engine: max_emit 1, tag 0xFB is the envelope's
+        if t.stash_capacity or t.uses_watch or t.uses_children or t.uses_supervision or \
+                any(V_STASH in (a.src, a.dsrc) for a in acts) or any(V_STASH in (c.src1, c.src2, c.src3, c.src4) for c in cases):
+            raise CompileError("receive timeouts live on the timer engine, which shares an engine with neither a stash, death "
+                               "watch, children nor supervision: the behaviours use a receive timeout and one of them")
+        if max_emit is not None and max_emit > 1:
+            raise CompileError(f"receive timeouts need max_emit = 1, not {max_emit}")
+        named = any(a.or_mask >> 24 == TAG_RECEIVE_TIMEOUT for a in acts) or TAG_RECEIVE_TIMEOUT in t.transparent_tags
+        for c in cases:
+            for s1, k1, cmp, s2, k2 in ((c.src1, c.k1, c.cmp1, c.src2, c.k2), (c.src3, c.k3, c.cmp2, c.src4, c.k4)):
+                named |= cmp != CMP_ANY and ((s1 == V_TAG and k1 == 0 and s2 == V_CONST and k2 == TAG_RECEIVE_TIMEOUT) or
+                                             (s2 == V_TAG and k2 == 0 and s1 == V_CONST and k1 == TAG_RECEIVE_TIMEOUT))
+        if named:
+            raise CompileError("message tag 0xFB is reserved for the receive-timeout envelope in behaviours that use a "
+                               "receive timeout")
+    if t.timer_keys or t.uses_receive_timeout:  # tag 0xFF is the TimerMsg's: no message type of these behaviours may carry it
         for a in acts:
             if a.or_mask >> 24 == TAG_TIMER:
                 raise CompileError("message tag 0xFF is reserved for timer messages in behaviours that use timers")

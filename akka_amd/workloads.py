@@ -50,7 +50,9 @@ class Workload:
     mailbox_priorities: dict = field(default_factory=dict)
     stash: dict = field(default_factory=dict)  # class -> stash capacity (agx_set_stash: a deque-based mailbox)
     # timers (agx_set_timers / agx_start_timers): {"n_keys": k, "starts": [(first, count, key, periodic, delay,
-    # delays or None, payload)]} -- empty: no timers
+    # delays or None, payload)], "receive_timeout": {"transparent": message tags, "starts": [(first, count, delay,
+    # payload)]}} -- empty: no timers; without "receive_timeout": no receive timeouts (agx_set_receive_timeout /
+    # agx_start_receive_timeout, on top of the timers: behaviours that use only a receive timeout pass n_keys 1)
     timers: dict = field(default_factory=dict)
     # death watch (agx_set_death_watch / agx_start_watch): {"n_slots": k, "starts": [(first, count, watchees or
     # None, offset, message or None)]} -- empty: no death watch
@@ -62,6 +64,8 @@ class Workload:
     # first_child, max_children)], "sites": typed.Tables.spawn_sites, "spawns": [(first, count, site, arg)]} --
     # empty: no children
     children: dict = field(default_factory=dict)
+    # host tells that follow the clock: schedule[t] = (dst, src, payload) is staged before tick t + 1 (run_schedule)
+    schedule: list = field(default_factory=list)
 
     def engine_kwargs(self) -> dict:
         """Semantic parameters (shared by the GPU engine and the CPU oracles)."""
@@ -97,6 +101,11 @@ class Workload:
             target.set_timers(self.timers["n_keys"])
             for first, count, key, periodic, delay, delays, payload in self.timers.get("starts", ()):
                 target.start_timers(first, count, key, delay, periodic=periodic, delays=delays, payload=payload)
+            rt = self.timers.get("receive_timeout")
+            if rt is not None:
+                target.set_receive_timeout(rt.get("transparent", ()))
+                for first, count, delay, payload in rt.get("starts", ()):
+                    target.start_receive_timeout(first, count, delay, payload)
         if self.watch:  # (empty: targets without the calls are unaffected)
             target.set_death_watch(self.watch["n_slots"])
             if self.children:  # (before the setup watches: a child block's ids are "not created yet", not "dead")
@@ -126,6 +135,14 @@ class Workload:
     @property
     def n_tells(self) -> int:
         return 0 if self.tells is None else int(len(self.tells[0]))
+
+    def run_schedule(self, target):
+        """Stage schedule[t] and let one tick pass, for every t, then run to quiescence; the last run's stats."""
+        for dst, src, pay in self.schedule:
+            if len(dst):
+                target.tell(dst, pay, src)
+            target.run(1)
+        return target.run()
 
 
 # ------------------------------------------------------------------ C2
@@ -678,6 +695,68 @@ def heartbeat(n: int = 1 << 20, period: int = 16, seed: int = 1, throughput: int
                     outbound=(n, n_host) if n_host else None, bucket_actors=bucket_actors,
                     timers={"n_keys": tb.timer_keys,
                             "starts": [(0, n, 0, True, period, delays, (HB_TICK << 24))]})
+
+
+# ------------------------------------------------------------------ receive timeouts: entities that passivate
+PE_JOB, PE_IDLE, PE_PASSIVATE, PE_STOP = 1, 2, 3, 4
+
+
+def passivating_entity():
+    """A sharded entity and its shard (ShardRegion.Passivate's handshake, ShardRegion.scala:188-199): the entity
+    counts its jobs; idle for its receive timeout it receives Idle and tells its shard (state word 1) Passivate; the
+    shard counts it and answers the sender with StopEntity, on which the entity stops.  One tell per case."""
+    from . import typed
+    B = typed.Behaviors
+    job, idle, passivate, stop = (typed.MessageType(n, t) for n, t in
+                                  (("Job", PE_JOB), ("Idle", PE_IDLE), ("Passivate", PE_PASSIVATE), ("StopEntity", PE_STOP)))
+    es = typed.State("jobs", "shard")
+    entity = (typed.ReceiveBuilder.create(es)
+              .on_message(job, lambda m, s: [s.jobs.inc(), B.same])
+              .on_message(idle, lambda m, s: [s.shard.ref.tell(passivate()), B.same])
+              .on_message(stop, lambda m, s: [B.stopped])
+              .on_any_message(lambda m, s: [B.unhandled])
+              .build("entity"))
+    ss = typed.State("passivated", "unused")
+    shard = (typed.ReceiveBuilder.create(ss)
+             .on_message(passivate, lambda m, s: [s.passivated.inc(), m.sender.tell(stop()), B.same])
+             .on_any_message(lambda m, s: [B.unhandled])
+             .build("shard"))
+    return entity, shard
+
+
+def passivating_entities(n: int = 1 << 20, n_shards: int = 4096, idle: int = 8, seed: int = 1, throughput: int = 16,
+                         bucket_actors: int = 256, spread: int | None = None, set_timeouts: bool = True) -> Workload:
+    """Entities (ids 0..n-1, shard n + i mod n_shards) set a receive timeout of `idle` ticks (the setup block) and
+    count the jobs the host sends them by a decaying schedule (Workload.schedule, run_schedule): entity i gets one
+    job per tick up to a last tick drawn from a geometric distribution cut at `spread` ticks (default
+    min(256, max(8, n / 8)); about 4 / spread of the entities still busy fall silent per tick).  `idle` ticks
+    after its last job an entity receives Idle and passivates: Passivate to its shard, StopEntity back, stop.  The
+    run goes quiescent once every entity has passivated; the engine needs timer_keys 1 though no timer is used.
+    An engine with timers keeps a bucket's inbox within one 2048-message tile, and the shards of one bucket take
+    every Passivate of their entities in the tick it is sent: keep n * 4 / spread below 2048 * n_shards /
+    bucket_actors (the defaults: 16384 a tick on 16 buckets of shards).  A shard that gets more Passivates in a tick
+    than `throughput` answers the rest later; an entity still alive `idle` ticks on asks again, as the reference's
+    would.  `set_timeouts=False`: the same traffic on
+    the same engine with no timeout ever set (no entity passivates) -- what the per-message reset costs."""
+    from . import typed
+    rng = np.random.default_rng(seed)
+    entity, shard = passivating_entity()
+    tb = typed.compile_behaviors([entity, shard], max_emit=1)
+    spread = min(256, max(8, n // 8)) if spread is None else spread
+    decay = 1.0 - min(4.0 / spread, 0.5)
+    last = np.minimum(np.floor(np.log(1.0 - rng.random(n)) / np.log(decay)), spread - 1).astype(np.int64)
+    ids = np.arange(n, dtype=np.uint32)
+    schedule = []
+    for t in range(spread):
+        dst = ids[last >= t]
+        schedule.append((dst, np.full(dst.size, NO_SENDER, np.uint32), np.full(dst.size, PE_JOB << 24, np.uint32)))
+    init = np.zeros((n, 2), np.uint64)
+    init[:, 1] = n + ids % n_shards
+    rt = {"transparent": (), "starts": [(0, n, idle, PE_IDLE << 24)] if set_timeouts else []}
+    return Workload("passivating_entities", n + n_shards, 2, 1, throughput, 0,
+                    [(0, n, tb.kind_of(entity), init), (n, n_shards, tb.kind_of(shard), None)], behaviors=tb,
+                    bucket_actors=bucket_actors, schedule=schedule,
+                    timers={"n_keys": max(tb.timer_keys, 1), "receive_timeout": rt})
 
 
 # ------------------------------------------------------------------ death watch: pacts and a self-healing ring

@@ -170,8 +170,15 @@ enum agx_action_op {
    * d-operand, as a WATCH's.  Each sends one envelope through the case's tell slot: with max_emit = 1 a case
    * holds at most one of TELL, SPAWN and STOP_CHILD. */
   AGX_A_SPAWN = 13,      /* context.spawn(site behaviour) (TY/scaladsl/ActorContext.scala spawnAnonymous) */
-  AGX_A_STOP_CHILD = 14  /* context.stop(ref)           (ActorContextAdapter.scala:79-106) */
+  AGX_A_STOP_CHILD = 14, /* context.stop(ref)           (ActorContextAdapter.scala:79-106) */
+  /* Receive timeouts (engines with receive timeouts, agx_set_receive_timeout; AA/dungeon/ReceiveTimeout.scala:
+   * 18-74).  SET: the message payload is the operand as a TELL's payload, the delay in ticks is the d-operand,
+   * as a timer's (below 1 it counts as 1, above 2^31 - 1 it is clamped; a constant below 1 is refused). */
+  AGX_A_SET_RECEIVE_TIMEOUT = 15,   /* context.setReceiveTimeout(delay, msg) (ActorContextAdapter.scala:120-126) */
+  AGX_A_CANCEL_RECEIVE_TIMEOUT = 16 /* context.cancelReceiveTimeout()        (ActorContextAdapter.scala:128-131) */
 };
+#define AGX_TAG_RECEIVE_TIMEOUT 0xFBu /* the message tag of a receive-timeout envelope: reserved on an engine with
+                                         receive timeouts */
 #define AGX_TAG_CREATE 0xFDu    /* the message tag of a Create envelope: reserved on an engine with children */
 #define AGX_TAG_STOP 0xFCu      /* the message tag of a Stop envelope: reserved on an engine with children */
 #define AGX_MAX_CHILD_REGIONS 8u
@@ -556,6 +563,51 @@ agx_status agx_timer_info(agx_engine* eng, uint64_t* fired, uint64_t* discarded,
  * none is to come.  Slots past n_keys read as zero (remaining 0xFFFFFFFF).  Any pointer may be NULL. */
 agx_status agx_read_timers(agx_engine* eng, uint64_t actor_id, uint32_t active[4], uint32_t remaining[4],
                            uint32_t period[4], uint32_t payload[4], uint32_t generation[4]);
+
+/* Receive timeouts (context.setReceiveTimeout / cancelReceiveTimeout: AA/dungeon/ReceiveTimeout.scala:18-74, typed
+ * TY/internal/adapter/ActorContextAdapter.scala:120-131, ActorAdapter.scala:92-93; pinned by ReceiveTimeoutSpec.scala:
+ * 63-278 and ActorContextSpec.scala:565-610; DESIGN.md 2.7 has the contract).  On top of the timers: call
+ * agx_set_timers first; time is the timers' logical time.
+ * Every actor has a delay (ticks, 0: no timeout set), a message payload and a next fire (a tick, or none to come).
+ * AGX_A_SET_RECEIVE_TIMEOUT(d, msg) in a case run at tick s stores (d, msg) with next fire s + d, whatever the
+ * handled message is; AGX_A_CANCEL_RECEIVE_TIMEOUT sets delay 0 and none to come (an envelope already enqueued stays
+ * in the mailbox); any stop turns the timeout off, a become leaves it alone.
+ * Influence: every drained message whose tag is not transparent, drained at tick s by an actor with a timeout set
+ * (after its case ran, handled or not), moves the next fire to s + delay.  The tag is that of the payload the
+ * behaviour sees (an accepted TimerMsg: the slot's stored payload); the receive-timeout message itself influences;
+ * a transparent message that neither sets nor cancels leaves the next fire as it is, none to come included; queued
+ * messages left in the backlog, dead letters, discarded TimerMsgs and discarded envelopes do not influence.
+ * `transparent_tags` is a 256-bit mask over message tags (bit t of word t / 32: tag t is
+ * NotInfluenceReceiveTimeout); NULL: none.
+ * Fire: at tick s every alive actor with a timeout set and next fire s sends one envelope to its own mailbox:
+ * sender = the actor, payload = AGX_TAG_RECEIVE_TIMEOUT << 24, last in that tick's inbox (after the tick's TimerMsgs),
+ * admitted by position (a dead letter in a full bounded mailbox; the next processed message reschedules).  The next
+ * fire becomes none to come: the reference's task is one-shot and the next influencing receipt, normally the
+ * envelope's own, reschedules it -- an idle actor gets the message every d ticks until it cancels or stops.
+ * Receipt: a drained envelope takes a drain slot and counts as delivered.  With a timeout set at that point of the
+ * window the behaviour runs on the message stored now (there is no generation: a stale envelope is delivered with the
+ * replaced message, as in the reference) with sender = the actor, and influences; with none set it is discarded
+ * (`discarded`, not unhandled; the typed reference would hand the behaviour null here).
+ * Tag AGX_TAG_RECEIVE_TIMEOUT is reserved on such an engine as AGX_TAG_TIMER is: agx_stage_tells, agx_tell,
+ * agx_start_timers payloads and tables naming it are refused; a computed payload landing on it is taken for the envelope.
+ * Conservation: staged + emitted + timer fired + receive-timeout fired = delivered + dead_letters + in_flight.
+ * A pending receive timeout keeps the engine non-quiescent and agx_pump_idle rescheduling, as a pending timer does.
+ * AGX_EINVAL without timers ("receive timeouts need an engine with timers"), on a second call, or when tables, staged
+ * tells or recorded timer starts name the reserved tag; AGX_ESTATE after the first run; AGX_ENOMEM: the rows do not
+ * fit.  agx_set_timers cannot change the key count afterwards.  Tables that hold either action, or
+ * agx_start_receive_timeout, on an engine without receive timeouts make agx_run return AGX_EINVAL. */
+agx_status agx_set_receive_timeout(agx_engine* eng, const uint32_t transparent_tags[8]);
+/* The setup block: every live actor of [first_id, first_id + count) sets (delay, payload) at the current tick (before
+ * the first run or between runs); delay 0 cancels; a delay above 2^31 - 1 is clamped. */
+agx_status agx_start_receive_timeout(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t delay, uint32_t payload);
+/* Totals since agx_create: envelopes sent (those that died at admission included), envelopes discarded at receipt;
+ * right now: actors with a timeout set, and those of them with a fire still to come.  agx_timer_info keeps counting
+ * timer slots only.  Any pointer may be NULL. */
+agx_status agx_receive_timeout_info(agx_engine* eng, uint64_t* fired, uint64_t* discarded, uint64_t* set, uint64_t* pending);
+/* The timeouts of actors [first_id, first_id + count) (for tests and tools): remaining = ticks to the next fire,
+ * 0xFFFFFFFF when none is to come.  Any pointer may be NULL. */
+agx_status agx_read_receive_timeout(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t* delay, uint32_t* remaining,
+                                    uint32_t* payload);
 
 /* Death watch (context.watch / watchWith / unwatch and the Terminated signal: AA/dungeon/DeathWatch.scala:19-113,
  * :147-162; typed adapter TY/internal/adapter/ActorAdapter.scala:84-91,134-138,200-205; pinned by
