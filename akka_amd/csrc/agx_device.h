@@ -1127,6 +1127,13 @@ __device__ __noinline__ uint32_t sv_failed(const DevParams& P, uint32_t nb, uint
   return AGX_RES_STOPPED;
 }
 
+// Can a behaviour of the kind mask KM read its message's sender (`src` of apply_msg below)?  False
+// only for masks all of whose kinds provably ignore it there: RING (its case uses w, pay and self).
+// Compiled behaviours (an operand may be the sender), PingPong (replies to it), the CRDT kinds and
+// every mixed mask stay true.  A launch specialised to a sender-free mask need not load the inbox's
+// sender array (k_dense_fused / k_dense_apply); the tells it WRITES still carry their sender.
+constexpr bool km_reads_sender(uint32_t KM) { return KM != kb(AGX_KIND_RING); }
+
 // `kind` is the actor's current behaviour: a compiled behaviour's become updates it (the caller
 // keeps it for the rest of the drain and stores it back).
 template <uint32_t KM, typename Emit>

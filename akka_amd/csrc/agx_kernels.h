@@ -162,20 +162,34 @@ __device__ __forceinline__ void stg64(uint64_t* base, uint32_t i, uint64_t v) {
   *(__attribute__((address_space(1))) uint64_t*)((__attribute__((address_space(1))) char*)base + (i << 3)) = v;
 }
 
-// streaming (non-temporal) vector stores for the dense launches' state and tell stores (AGX_NT=0 A/B
-// build knob: plain stores).  Same-box A/B, 1M ring: superstep 16.0 -> 14.7 us -- the bucket's
-// write-once results stream out during the kernel instead of sitting dirty in L2 until its end
+// The dense launches' state and tell stores, by store policy kNt: 0 plain, 1 streaming
+// (non-temporal `nt`), 2 write-through (relaxed agent-scope atomic stores: `sc1`, no `nt`).
+// These are write-once results that the next superstep reads back.  Same-box A/Bs:
+// 1M ring, plain -> nt: superstep 16.0 -> 14.7 us -- the results stream out during the kernel
+// instead of sitting dirty in L2 until its end; round 15, 1M fused ring (k_dense_fused):
+// nt 11.3, plain 12.2, sc1 10.6 us; 100M multi-pass ring (k_dense_apply): nt 0.80, plain 0.83,
+// sc1 0.97 ms.  So the policy is chosen per pipeline (build knobs for A/Bs):
 #ifndef AGX_NT
-#define AGX_NT 1
+#define AGX_NT 1  // k_dense_apply, and every k_dense_fused instantiation not named below
 #endif
+#ifndef AGX_NT_FUSED
+#define AGX_NT_FUSED 2  // k_dense_fused<RING>, single rank (the C2 ring's superstep)
+#endif
+template <int kNt>
 __device__ __forceinline__ void st64x(uint64_t* base, uint32_t i, uint64_t v) {
-  if constexpr (AGX_NT != 0)
+  if constexpr (kNt == 2)
+    __hip_atomic_store((__attribute__((address_space(1))) uint64_t*)((__attribute__((address_space(1))) char*)base + (i << 3)), v,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else if constexpr (kNt != 0)
     __builtin_nontemporal_store(v, (__attribute__((address_space(1))) uint64_t*)((__attribute__((address_space(1))) char*)base + (i << 3)));
   else
     stg64(base, i, v);
 }
+template <int kNt>
 __device__ __forceinline__ void st32x(uint32_t* p, uint64_t i, uint32_t v) {
-  if constexpr (AGX_NT != 0)
+  if constexpr (kNt == 2)
+    __hip_atomic_store((__attribute__((address_space(1))) uint32_t*)p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else if constexpr (kNt != 0)
     __builtin_nontemporal_store(v, (__attribute__((address_space(1))) uint32_t*)p + i);
   else
     p[i] = v;
@@ -3608,7 +3622,7 @@ static __global__ void __launch_bounds__(kDenseThreads, AGX_DENSE_WPE) k_dense_a
         const bool bl = q < blc, ok = q < cnt;
         const uint32_t i = !ok ? 0u : bl ? blo + q : iv.at(bs + q - blc);
         k[r] = ldg(bl || !ok ? Bk : iv.m.key, i);
-        sv[r] = ldg(bl || !ok ? Bs : iv.m.src, i);
+        sv[r] = km_reads_sender(KM) ? ldg(bl || !ok ? Bs : iv.m.src, i) : 0u;  // (sender-free kinds: not loaded)
         pv[r] = ldg(bl || !ok ? Bp : iv.m.pay, i);
       }
     }
@@ -3677,7 +3691,7 @@ static __global__ void __launch_bounds__(kDenseThreads, AGX_DENSE_WPE) k_dense_a
         tv[r] = em;
         tk[r] = em ? d : 0u;
         tp[r] = em ? pv[r] - 1u : 0u;
-        if (on) st64x(P.state, l[r] * P.sa, x0[r] + 1ull);
+        if (on) st64x<AGX_NT>(P.state, l[r] * P.sa, x0[r] + 1ull);
       }
     } else {
 #pragma unroll
@@ -3699,8 +3713,8 @@ static __global__ void __launch_bounds__(kDenseThreads, AGX_DENSE_WPE) k_dense_a
       const uint32_t res = apply_msg<KM>(P, kc, self, l[r], wv2, sv[r], pv[r], em);
       if (res == AGX_RES_UNHANDLED) ++acc[2];
       if (res == AGX_RES_STOPPED) P.stopq[atomicAdd(P.nstop, 1u)] = l[r];
-      st64x(P.state, l[r] * P.sa, wv2[0]);
-      if (P.W > 1) st64x(P.state, l[r] * P.sa + w1off, wv2[1]);
+      st64x<AGX_NT>(P.state, l[r] * P.sa, wv2[0]);
+      if (P.W > 1) st64x<AGX_NT>(P.state, l[r] * P.sa + w1off, wv2[1]);
       if constexpr ((KM & kb(AGX_KIND_COMPILED)) != 0)
         if (kc != kd[r]) P.kind[l[r]] = (uint8_t)kc;
       acc[3] += em.n_all;
@@ -3733,9 +3747,9 @@ static __global__ void __launch_bounds__(kDenseThreads, AGX_DENSE_WPE) k_dense_a
 #pragma unroll
     for (int r = 0; r < kDenseIpt; ++r)
       if (tv[r]) {
-        st32x(a.em.key, embase + rk[r], tk[r]);
-        st32x(a.em.src, embase + rk[r], l[r]);
-        st32x(a.em.pay, embase + rk[r], tp[r]);
+        st32x<AGX_NT>(a.em.key, embase + rk[r], tk[r]);
+        st32x<AGX_NT>(a.em.src, embase + rk[r], l[r]);
+        st32x<AGX_NT>(a.em.pay, embase + rk[r], tp[r]);
         s_ck[rk[r]] = tk[r];
       }
     __syncthreads();  // (s_ck, s_nh complete; s_cnt read)
@@ -3876,6 +3890,9 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
   };
   if (!kEarlyRow && abort_test()) return;
   constexpr bool kKindNeeded = (KM & (KM - 1)) != 0 || (KM & kb(AGX_KIND_COMPILED)) != 0;
+  constexpr bool kSender = km_reads_sender(KM);  // (false: the inbox's sender array is never touched)
+  // the store policy of st32x / st64x (AGX_NT_FUSED where it was measured: the single-rank RING launches)
+  constexpr int kNt = !kOwner && KM == kb(AGX_KIND_RING) ? AGX_NT_FUSED : AGX_NT;
   const uint32_t w1off = P.W > 1 ? P.sw : 0u;
   uint32_t acc[kBStats] = {0u, 0u, 0u, 0u, 0u};
   if (tid == 0) s_bad = 0;
@@ -3916,6 +3933,7 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
       kd[r] = kKindNeeded ? P.kind[l] : 0u;
       gs[r] = kOwner ? P.gid[l] : l;  // the actor's global id (its tells' sender)
       x0[r] = ldg64(P.state, l * P.sa);
+      if constexpr (KM != kb(AGX_KIND_RING))  // (the RING apply below neither reads nor stores word 1: no load)
       x1[r] = ldg64(P.state, l * P.sa + w1off);  // (W = 1: word 0 again, zeroed at the apply; no branch between loads)
     }
     if (!tested) {  // (uniform; first bucket of the block)
@@ -3973,7 +3991,8 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
 #pragma unroll
       for (int r = 0; r < kDenseIpt; ++r) {
         k[r] = ldg(Ek, idx[r]);
-        sv[r] = ldg(Es, idx[r]);
+        // (a sender-free kind mask: the sender array is neither loaded nor placed -- 4 B per message)
+        sv[r] = kSender ? ldg(Es, idx[r]) : 0u;
         pv[r] = ldg(Ep, idx[r]);
       }
 #pragma unroll
@@ -3981,7 +4000,7 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
         if (r * kDenseThreads + tid < cnt) {
           const uint32_t la = k[r] & amask;
           if (atomicAdd(&s_hit[la], 1u)) bad = 1;  // a second message to the same actor
-          s_ks[la] = sv[r];
+          if constexpr (kSender) s_ks[la] = sv[r];
           s_ks[kBucket + la] = pv[r];
         }
     }
@@ -4022,12 +4041,14 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
     for (int r = 0; r < kDenseIpt; ++r) {
       const uint32_t la = r * kDenseThreads + tid;
       hv[r] = s_hit[la];
-      svv[r] = s_ks[la];
+      svv[r] = kSender ? s_ks[la] : 0u;
       pvv[r] = s_ks[kBucket + la];
     }
 #pragma unroll
-    for (int r = 0; r < kDenseIpt; ++r)  // (pinned here: the compiler would sink each read into its use, one wait each)
-      asm volatile("" : "+v"(hv[r]), "+v"(svv[r]), "+v"(pvv[r]));
+    for (int r = 0; r < kDenseIpt; ++r) {  // (pinned here: the compiler would sink each read into its use, one wait each)
+      if constexpr (kSender) asm volatile("" : "+v"(hv[r]), "+v"(svv[r]), "+v"(pvv[r]));
+      else asm volatile("" : "+v"(hv[r]), "+v"(pvv[r]));  // (a pinned sender would keep its whole load chain alive)
+    }
     if constexpr (KM == kb(AGX_KIND_RING)) {
       // RING-only populations (the C2 token ring): apply_msg<RING> through RegEmitter, branch-free --
       // w[0] += 1, Behaviors.same, one tell to self + stride while hops are left.  Its destination is
@@ -4050,7 +4071,7 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
         tv[r] = em;
         tk[r] = em ? (kOwner ? P.route[d] : d) : 0u;
         tp[r] = em ? pvv[r] - 1u : 0u;
-        if (on) st64x(P.state, l * P.sa, x0[r] + 1ull);
+        if (on) st64x<kNt>(P.state, l * P.sa, x0[r] + 1ull);
       }
     } else {
 #pragma unroll
@@ -4074,8 +4095,8 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
         if constexpr (kOwner) P.stopq[atomicAdd(P.nstop, 1u)] = l;  // (committed by the next superstep)
         else P.alive[l] = (uint8_t)(ab[r] & 0xFEu);  // (fused: only this block reads the bucket's flags)
       }
-      st64x(P.state, l * P.sa, wv2[0]);
-      if (P.W > 1) st64x(P.state, l * P.sa + w1off, wv2[1]);
+      st64x<kNt>(P.state, l * P.sa, wv2[0]);
+      if (P.W > 1) st64x<kNt>(P.state, l * P.sa + w1off, wv2[1]);
       if constexpr ((KM & kb(AGX_KIND_COMPILED)) != 0)
         if (kc != kd[r]) P.kind[l] = (uint8_t)kc;
       acc[3] += em.n_all;
@@ -4125,9 +4146,9 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
       for (int r = 0; r < kDenseIpt; ++r)
         if (tv[r]) {
           const uint64_t o = embase + s_oc[(dg[r] * kDenseIpt + r) * kDenseWaves + w] + rk[r];
-          st32x(g.eg[wpar].key, o, tk[r]);
-          st32x(g.eg[wpar].src, o, gs[r]);
-          st32x(g.eg[wpar].pay, o, tp[r]);
+          st32x<kNt>(g.eg[wpar].key, o, tk[r]);
+          st32x<kNt>(g.eg[wpar].src, o, gs[r]);
+          st32x<kNt>(g.eg[wpar].pay, o, tp[r]);
         }
       if (tid == 0 && g.emc[wpar]) g.emc[wpar][b] = emtot;
       if (tid == 0) {  // the bucket's tell chunk (in-flight accounting)
@@ -4179,9 +4200,9 @@ static __global__ void __launch_bounds__(kDenseThreads, kPersist ? 4 : 2) k_dens
         for (int r = 0; r < kDenseIpt; ++r)
           if (tv[r]) {
             const uint64_t o = embase + (dg[r] == X ? baseA + preA[r] + rkA[r] : baseB + preB[r] + rkB[r]);
-            st32x(g.eg[wpar].key, o, tk[r]);
-            st32x(g.eg[wpar].src, o, gs[r]);
-            st32x(g.eg[wpar].pay, o, tp[r]);
+            st32x<kNt>(g.eg[wpar].key, o, tk[r]);
+            st32x<kNt>(g.eg[wpar].src, o, gs[r]);
+            st32x<kNt>(g.eg[wpar].pay, o, tp[r]);
           }
         if (tid == 0 && totA) {
           g.tcnt[wpar][(size_t)X * g.tstride + b] = totA;
