@@ -108,6 +108,11 @@ SIGNATURES = {
     "agx_spawn_children": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
     "agx_children_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 8),
     "agx_read_children": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, c_u32p, c_u32p, c_u32p]),
+    "agx_set_receptionist": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
+    "agx_register_services": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
+    "agx_read_listing": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, c_u32p, ctypes.c_uint64, c_u64p]),
+    "agx_read_services": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_u8p]),
+    "agx_receptionist_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 6 + [c_u32p, c_u64p]),
     "agx_set_outbound": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "agx_take_outbound": (ctypes.c_int32, [ctypes.c_void_p, c_u32p, c_u32p, c_u32p, ctypes.c_uint64, c_u64p]),
     "agx_set_gossip": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]),

@@ -62,6 +62,10 @@ struct DevParams {
     // and only for a message that fails or stops: the strategy entries, the per-actor restart counts and
     // deadlines, the initial kinds and the counters (SuperDev below)
     uint32_t* super;
+    // the receptionist (agx_set_receptionist), read and written only by the receptionist k_bucket_apply
+    // instantiations and the rebuild kernels: the per-actor key masks, the listings and their bookkeeping
+    // (RecepDev below)
+    uint32_t* recep;
   };
   uint32_t* heap_top;       // [2] rows allocated in heap[parity]
   const uint32_t* step;     // superstep counter (bumped by the first kernel of a step)
@@ -672,6 +676,8 @@ constexpr uint32_t kSuperKM = 1u << 27;
 constexpr uint32_t kChildKM = 1u << 26;
 // KM flag (not a kind): the variant knows receive timeouts (agx_set_receive_timeout); only ever combined with kTimersKM.
 constexpr uint32_t kIdleKM = 1u << 25;
+// KM flag (not a kind): the variant knows the receptionist (agx_set_receptionist).  A flag of KM for the same reason.
+constexpr uint32_t kRecepKM = 1u << 24;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -1125,6 +1131,166 @@ __device__ __noinline__ uint32_t sv_failed(const DevParams& P, uint32_t nb, uint
   if (kind >= AGX_KIND_COMPILED) compiled_apply_s(P, kind, self, w, self, AGX_SIGNAL_POSTSTOP, true, none, emit);
   atomicAdd(SV.ctr(kScStops), 1ull);
   return AGX_RES_STOPPED;
+}
+
+// ---- the receptionist and group routers (agx_set_receptionist; TY/internal/receptionist/
+// LocalReceptionist.scala:147-248, TY/internal/routing/GroupRouterImpl.scala:114-146, RoutingLogic.scala:42-75).
+// DevParams.recep, an allocation of its own, u32 units:
+//   [0] n_keys   [1] capacity   [2] nb
+//   [3] flags: bit k = key k changed in the tick being drained (dirty, OR-ed by the drains); bit 8 + k = key k is
+//       being rebuilt (dirty_now: k_recep_scan moves the bit there, k_recep_fill reads it)
+//   [8..19]  six u64 counters: routed, no_routees, registered, deregistered, terminated, rebuilds
+//   [24..31] size[k] of the listing in force   [32..47] eight u64 version[k]
+//   [kRcCntOff + k * nb + b]  cnt: the members of key k in bucket b (written by the bucket's own block)
+//   then off[k * nb + b]: their offset in the listing (k_recep_scan), then list[k * capacity + i]: the listing of
+//   key k, ascending ids (k_recep_fill), then one mask byte per actor (nb << bb of them): bit k = registered
+// Only an actor's own lane writes its mask byte; the listings are written between two applies only.
+constexpr uint32_t kRcFlags = 3, kRcCtr = 8, kRcSize = 24, kRcVersion = 32, kRcCntOff = 64;
+constexpr uint32_t kRcRouted = 0, kRcNoRoutees = 1, kRcRegistered = 2, kRcDeregistered = 3, kRcTerminated = 4, kRcRebuilds = 5;
+constexpr uint32_t kRcNone = 0xFFFFFFFFu;
+__host__ __device__ __forceinline__ size_t rc_list_off(uint32_t nk, uint32_t nb) { return (size_t)kRcCntOff + 2ull * nk * nb; }
+__host__ __device__ __forceinline__ size_t rc_mask_off(uint32_t nk, uint32_t cap, uint32_t nb) {
+  return (rc_list_off(nk, nb) + (size_t)nk * cap + 3u) & ~(size_t)3;
+}
+struct RecepDev {
+  uint32_t* base;
+  uint8_t* mask;  // [nb << bb]
+  uint32_t nk, cap, nb;
+  __device__ __forceinline__ uint32_t* cnt(uint32_t k, uint32_t b) const { return base + kRcCntOff + (size_t)k * nb + b; }
+  __device__ __forceinline__ uint32_t* off(uint32_t k, uint32_t b) const { return base + kRcCntOff + (size_t)(nk + k) * nb + b; }
+  __device__ __forceinline__ uint32_t* list(uint32_t k) const { return base + rc_list_off(nk, nb) + (size_t)k * cap; }
+  __device__ __forceinline__ uint32_t size(uint32_t k) const { return k < nk ? base[kRcSize + k] : 0u; }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kRcCtr) + i;
+  }
+  // listing[x mod size] of key k (none: an empty listing)
+  __device__ __forceinline__ uint32_t at(uint32_t k, uint64_t x) const {
+    const uint32_t n = size(k);
+    return n ? list(k)[(uint32_t)(x % n)] : kRcNone;
+  }
+  // round robin: the smallest listed id >= cursor, else listing[0] (none: an empty listing)
+  __device__ __forceinline__ uint32_t successor(uint32_t k, uint64_t cursor) const {
+    const uint32_t n = size(k);
+    if (!n) return kRcNone;
+    const uint32_t* const ls = list(k);
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if ((uint64_t)ls[mid] < cursor) lo = mid + 1u;
+      else hi = mid;
+    }
+    return ls[lo == n ? 0u : lo];
+  }
+};
+__device__ __forceinline__ RecepDev recep_dev(uint32_t* base) {
+  RecepDev r;
+  r.base = base;
+  r.nk = base[0];
+  r.cap = base[1];
+  r.nb = base[2];
+  r.mask = reinterpret_cast<uint8_t*>(base + rc_mask_off(r.nk, r.cap, r.nb));
+  return r;
+}
+// what one thread's drains changed: counted in registers, added to the storage once per wave (recep_commit)
+struct RecepCount {
+  uint32_t routed, none, reg, dereg, term, chg;  // chg: the key bits that differ over an actor's window
+};
+
+// compiled_apply of the receptionist instantiations: compiled_apply plus the operands AGX_V_LISTING_SIZE /
+// AGX_V_SERVICE_AT and the actions AGX_A_REGISTER / AGX_A_DEREGISTER / AGX_A_ROUTE, against the actor's mask byte
+// `mk` (a register of the drain) and the listings in force.  A forward (AGX_ROUTE_KEEP_SENDER) emits with the
+// emitter's `self` replaced by the message's sender for that one call.  A function of its own: every other
+// instantiation compiles compiled_apply as before.
+__device__ __forceinline__ uint64_t rc_operand(const RecepDev& RD, uint32_t src, uint32_t word, int64_t k, uint32_t pay,
+                                               const uint64_t* w, uint32_t sender, uint32_t self) {
+  if (src == AGX_V_LISTING_SIZE) return (uint64_t)RD.size(word & 7u) + (uint64_t)k;
+  if (src == AGX_V_SERVICE_AT) {
+    const uint32_t sel = (word >> 3) & 3u;
+    const uint64_t x = sel <= AGX_SVC_WORD1 ? w[sel] : sel == AGX_SVC_ARG ? (uint64_t)(pay & 0xFFFFFFu) : 0ull;
+    return RD.at(word & 7u, x + (uint64_t)k);
+  }
+  return cb_operand(src, word, k, pay, w, sender, self);
+}
+template <typename Emit>
+__device__ __forceinline__ uint32_t compiled_apply_rc(const DevParams& P, const RecepDev& RD, uint32_t& kind, uint32_t self,
+                                                      uint64_t* w, uint32_t src, uint32_t pay, uint32_t& mk, RecepCount& rc,
+                                                      Emit& emit) {
+  const uint32_t b = kind - AGX_KIND_COMPILED;
+  if (b >= P.n_beh) return AGX_RES_UNHANDLED;
+  const uint32_t c1 = P.bfirst[b + 1];
+  for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
+    const agx_case C = P.bcase[c];
+    if (!cb_cmp(C.cmp1, rc_operand(RD, C.src1, C.word1, C.k1, pay, w, src, self),
+                rc_operand(RD, C.src2, C.word2, C.k2, pay, w, src, self)))
+      continue;
+    if (!cb_cmp(C.cmp2, rc_operand(RD, C.src3, C.word3, C.k3, pay, w, src, self),
+                rc_operand(RD, C.src4, C.word4, C.k4, pay, w, src, self)))
+      continue;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      const agx_act A = P.bact[i];
+      const uint64_t v = rc_operand(RD, A.src, A.sword, A.k, pay, w, src, self);
+      const uint32_t msg = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;
+      const uint32_t bit = 1u << (A.pad1 & 7u);
+      switch (A.op) {
+        case AGX_A_SET: w[A.word & 1u] = v; break;
+        case AGX_A_ADD: w[A.word & 1u] += v; break;
+        case AGX_A_MAX: w[A.word & 1u] = v > w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_MIN: w[A.word & 1u] = v < w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_REGISTER:
+          if (!(mk & bit)) {
+            mk |= bit;
+            ++rc.reg;
+          }
+          break;
+        case AGX_A_DEREGISTER:
+          if (mk & bit) {
+            mk &= ~bit;
+            ++rc.dereg;
+          }
+          break;
+        case AGX_A_TELL:
+        case AGX_A_ROUTE: {
+          uint64_t d = 0;
+          if (A.op == AGX_A_TELL || (A.pad0 & AGX_ROUTE_BY_INDEX)) {
+            if (A.dsrc == AGX_V_SELF && A.op == AGX_A_TELL) {  // (self + dk) mod n: ring neighbours
+              int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+              d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+            } else {
+              d = rc_operand(RD, A.dsrc, A.dword, A.dk, pay, w, src, self);
+            }
+          }
+          uint32_t ref = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
+          if (A.op == AGX_A_ROUTE) {
+            const uint32_t key = A.pad1 & 7u;
+            if (A.pad0 & AGX_ROUTE_BY_INDEX) {
+              ref = RD.at(key, d);
+            } else {
+              ref = RD.successor(key, w[A.word & 1u]);
+              if (ref != kRcNone) w[A.word & 1u] = (uint64_t)ref + 1ull;  // (no routee: the cursor stays)
+            }
+            if (ref == kRcNone) ++rc.none;
+            else ++rc.routed;
+          }
+          if (A.pad0 & AGX_ROUTE_KEEP_SENDER) {  // a forward: the envelope keeps the incoming message's sender
+            const uint32_t me = emit.self;
+            emit.self = src;
+            emit(ref, msg);
+            emit.self = me;
+          } else {
+            emit(ref, msg);
+          }
+          break;
+        }
+        default: break;
+      }
+    }
+    if (C.result == AGX_RES_BECOME) {
+      kind = AGX_KIND_COMPILED + C.next;
+      return AGX_RES_SAME;
+    }
+    return C.result;
+  }
+  return AGX_RES_UNHANDLED;
 }
 
 // Can a behaviour of the kind mask KM read its message's sender (`src` of apply_msg below)?  False

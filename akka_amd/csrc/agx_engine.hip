@@ -205,6 +205,18 @@ struct agx_engine {
   uint32_t beh_sv_tells = 0;           // the most tells a failing or stopping case and a supervision signal case of one behaviour make together
   uint64_t sv_ticks = 0;               // supersteps with mail so far (= agx_stats.supersteps)
   uint32_t sv_clock = 0;               // the device clock after the last run (every bucket's launch count)
+  // the receptionist (agx_set_receptionist): service keys, per-actor key masks, listings.  Such an engine launches
+  // the receptionist instantiation of the compiled catch-all variant, then the rebuild kernels, every superstep
+  uint32_t* d_recep = nullptr;   // DevParams.recep (agx_device.h RecepDev)
+  uint32_t rc_keys = 0, rc_cap = 0;
+  uint32_t beh_rc_keys = 0;      // the service keys the compiled tables use (the largest index + 1)
+  bool beh_recep = false;        // the compiled tables register, deregister, route, forward or read a listing
+  bool rc_bad_start = false;     // agx_register_services was called on an engine without the receptionist: agx_run refuses
+  struct RecepStart {
+    uint64_t first, count;
+    uint32_t key, on;
+  };
+  std::vector<RecepStart> rc_starts;  // agx_register_services calls not yet applied on the device
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -433,7 +445,7 @@ namespace {
 // of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
 // the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
 // apply_variant, launch_apply and make_params.
-enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_N, F_NONE = F_N };
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_N, F_NONE = F_N };
 
 struct FeatureRow {
   bool (*on)(const agx_engine*);
@@ -479,6 +491,10 @@ const FeatureRow kFeatures[F_N] = {
     // receive timeouts (agx_set_receive_timeout) come on top of the timers in the same way
     {[](const agx_engine* e) { return e->rt_on; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      kTimersKM | kIdleKM, false, F_TIMERS},
+    {[](const agx_engine* e) { return e->d_recep != nullptr; }, [](const agx_engine* e) -> const void* { return e->d_recep; },
+     "the receptionist needs", "the receptionist (agx_set_receptionist)", "the receptionist (agx_set_receptionist)", "",
+     AGX_ONCE "a route must take effect once", "which know no receptionist: set the receptionist", "the receptionist",
+     kRecepKM, false, F_NONE},
 };
 #undef AGX_ONCE
 
@@ -823,6 +839,129 @@ bool dense_on(const agx_engine* e, uint32_t vid) {
          (e->dense_launch == 1 || (e->dense_launch < 0 && vid == V_RING));
 }
 
+// ---- the receptionist (agx_set_receptionist): the rebuild of the sorted listings between two
+// supersteps.  apply -> k_recep_scan -> k_recep_fill -> the next apply are kernel boundaries: no polling between
+// workgroups, no grid barrier; the listings are rebuilt in place, stream order keeps readers and the writer apart.
+constexpr int kRcThreads = 256;
+// One block per key; returns at entry when the key is neither dirty nor marked as rebuilt (one word read).  A dirty
+// key: the exclusive scan of cnt[key][0..nb) into the per-bucket offsets, the size, the version, the capacity
+// error; its dirty bit moves to dirty_now.
+static __global__ void __launch_bounds__(kRcThreads) k_recep_scan(uint32_t* rc, unsigned long long* err) {
+  const uint32_t k = blockIdx.x, f = rc[kRcFlags];
+  const bool dirty = (f >> k) & 1u, now = (f >> (8u + k)) & 1u;
+  if (!dirty && !now) return;
+  if (!dirty) {  // rebuilt after the tick before: the mark goes
+    if (threadIdx.x == 0) atomicAnd(rc + kRcFlags, ~(1u << (8u + k)));
+    return;
+  }
+  const RecepDev RD = recep_dev(rc);
+  __shared__ uint32_t scratch[kRcThreads / kWave + 1];
+  uint32_t run = 0;
+  for (uint32_t b0 = 0; b0 < RD.nb; b0 += kRcThreads) {  // (block-uniform trip count)
+    const uint32_t b = b0 + threadIdx.x;
+    const uint32_t c = b < RD.nb ? *RD.cnt(k, b) : 0u;
+    uint32_t tot;
+    const uint32_t ex = block_excl_sum<kRcThreads>(c, scratch, &tot);
+    if (b < RD.nb) *RD.off(k, b) = run + ex;
+    run += tot;
+  }
+  if (threadIdx.x == 0) {
+    if (run > RD.cap) atomicOr(err, (unsigned long long)kErrRecepCap);  // (k_recep_fill writes the first `capacity` ids)
+    rc[kRcSize + k] = min(run, RD.cap);
+    reinterpret_cast<unsigned long long*>(rc + kRcVersion)[k] += 1ull;
+    atomicAdd(RD.ctr(kRcRebuilds), 1ull);
+    atomicOr(rc + kRcFlags, 1u << (8u + k));
+    atomicAnd(rc + kRcFlags, ~(1u << k));
+  }
+}
+// One block per bucket; returns at entry when no key is being rebuilt (one word read).  Else the bucket's members
+// of each such key go to the key's listing at the bucket's offset, in ascending id: ballot and lane rank within a
+// wave, the waves' counts through LDS.
+static __global__ void __launch_bounds__(kRcThreads) k_recep_fill(uint32_t* rc, uint32_t bb, uint32_t n_local) {
+  uint32_t now = (rc[kRcFlags] >> 8) & 0xFFu;
+  if (!now) return;
+  const RecepDev RD = recep_dev(rc);
+  now &= (1u << RD.nk) - 1u;
+  constexpr uint32_t kW = kRcThreads / kWave;
+  __shared__ uint32_t s_wc[AGX_MAX_SERVICE_KEYS][kW];
+  const uint32_t tid = threadIdx.x, w = tid / kWave, b = blockIdx.x, a0 = b << bb;
+  const uint32_t na = min(1u << bb, n_local - a0);
+  const uint64_t lt = lanemask_lt();
+  uint32_t run[AGX_MAX_SERVICE_KEYS] = {};
+  for (uint32_t c0 = 0; c0 < na; c0 += kRcThreads) {  // (block-uniform trip count)
+    const uint32_t la = c0 + tid;
+    const uint32_t m = la < na ? RD.mask[a0 + la] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+      if (!((now >> k) & 1u)) continue;
+      const uint64_t bal = __ballot((m >> k) & 1u);
+      if (lane_id() == 0) s_wc[k][w] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+      if (!((now >> k) & 1u)) continue;
+      const uint64_t bal = __ballot((m >> k) & 1u);
+      uint32_t pre = 0, tot = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < kW; ++i) {
+        const uint32_t t = s_wc[k][i];
+        pre += i < w ? t : 0u;
+        tot += t;
+      }
+      if ((m >> k) & 1u) {
+        const uint32_t pos = *RD.off(k, b) + run[k] + pre + (uint32_t)__popcll(bal & lt);
+        if (pos < RD.cap) RD.list(k)[pos] = a0 + la;
+      }
+      run[k] += tot;
+    }
+    __syncthreads();  // (s_wc is rewritten by the next chunk)
+  }
+}
+// agx_register_services on the device: one block per bucket the range touches sets or clears bit `key` of the
+// range's live actors, recounts the bucket's members of the key and marks the key dirty if a bit changed
+static __global__ void __launch_bounds__(kRcThreads) k_recep_start(uint32_t* rc, const uint8_t* alive, uint32_t bb, uint32_t n_local,
+                                                                   uint32_t first, uint32_t count, uint32_t key, uint32_t on,
+                                                                   uint32_t b_first) {
+  const RecepDev RD = recep_dev(rc);
+  const uint32_t tid = threadIdx.x, b = b_first + blockIdx.x, a0 = b << bb, bit = 1u << key;
+  const uint32_t na = min(1u << bb, n_local - a0);
+  __shared__ uint32_t s_n[3];  // members, bits set, bits cleared
+  if (tid < 3) s_n[tid] = 0u;
+  __syncthreads();
+  uint32_t members = 0, nset = 0, nclr = 0;
+  for (uint32_t la = tid; la < na; la += kRcThreads) {
+    const uint32_t l = a0 + la;
+    uint32_t m = RD.mask[l];
+    if (l >= first && l - first < count && (alive[l] & 1u)) {
+      const uint32_t m2 = on ? m | bit : m & ~bit;
+      if (m2 != m) {
+        RD.mask[l] = (uint8_t)m2;
+        nset += on ? 1u : 0u;
+        nclr += on ? 0u : 1u;
+        m = m2;
+      }
+    }
+    members += (m >> key) & 1u;
+  }
+  if (members) atomicAdd(&s_n[0], members);
+  if (nset) atomicAdd(&s_n[1], nset);
+  if (nclr) atomicAdd(&s_n[2], nclr);
+  __syncthreads();
+  if (tid == 0) {
+    *RD.cnt(key, b) = s_n[0];
+    if (s_n[1]) atomicAdd(RD.ctr(kRcRegistered), (unsigned long long)s_n[1]);
+    if (s_n[2]) atomicAdd(RD.ctr(kRcDeregistered), (unsigned long long)s_n[2]);
+    if (s_n[1] | s_n[2]) atomicOr(rc + kRcFlags, bit);
+  }
+}
+
+void launch_recep_rebuild(agx_engine* e) {
+  hipLaunchKernelGGL(k_recep_scan, dim3(e->rc_keys), dim3(kRcThreads), 0, e->stream, e->d_recep,
+                     reinterpret_cast<unsigned long long*>(e->d_stats + ST_ERROR));
+  hipLaunchKernelGGL(k_recep_fill, dim3(e->nb), dim3(kRcThreads), 0, e->stream, e->d_recep, e->bb, (uint32_t)e->n_local);
+}
+
 agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
   // the chunk histograms consumed by this step's first pass were zeroed by k_chunk_downsweep;
   // on the multi-rank path (no chunk pass) they are never read, so stale columns are harmless
@@ -1039,6 +1178,7 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
                          (const uint4*)e->d_orw, (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n);
     }
   }
+  if (e->d_recep) launch_recep_rebuild(e);  // (every superstep, captured or eager: the listings of the next tick)
   if (e->R == 1) e->par ^= 1u;  // the next superstep writes the other parity (fused and multi-pass)
   HIP_TRY(hipGetLastError());
   return AGX_OK;
@@ -1718,8 +1858,36 @@ agx_status flush_child_spawns(agx_engine* e) {
   return AGX_OK;
 }
 
+// ---- the receptionist (agx_set_receptionist)
+// apply the recorded agx_register_services calls: the actors' flags reach the device first when the host's are the
+// newer ones; each call is the start kernel over the buckets of its range, then the rebuild (the listing is in
+// force for the next tick)
+agx_status flush_recep_starts(agx_engine* e) {
+  if (e->rc_starts.empty()) return AGX_OK;
+  if (e->actors_dirty) HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
+  for (const auto& rs : e->rc_starts) {
+    if (!rs.count) continue;
+    const uint32_t b0 = (uint32_t)(rs.first >> e->bb), b1 = (uint32_t)((rs.first + rs.count - 1) >> e->bb);
+    hipLaunchKernelGGL(k_recep_start, dim3(b1 - b0 + 1), dim3(kRcThreads), 0, e->stream, e->d_recep, e->d_alive, e->bb,
+                       (uint32_t)e->n_local, (uint32_t)rs.first, (uint32_t)rs.count, rs.key, rs.on, b0);
+    launch_recep_rebuild(e);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->rc_starts.clear();
+  return AGX_OK;
+}
+
 // upload host mirrors / staged tells before a run
 agx_status prepare_run(agx_engine* e) {
+  if (e->rc_bad_start)
+    return set_err(AGX_EINVAL, "agx_register_services was called on an engine without the receptionist (agx_set_receptionist)");
+  if (e->beh_recep && !e->d_recep)  // (only the receptionist variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours register, deregister, route, forward or read a listing, but the engine "
+                   "has no receptionist (agx_set_receptionist)");
+  if (e->d_recep && e->beh_rc_keys > e->rc_keys)
+    return set_err(AGX_EINVAL, "the compiled behaviours use service key %u, but the receptionist has %u keys "
+                   "(agx_set_receptionist)", e->beh_rc_keys - 1u, e->rc_keys);
   if (e->ch_bad_spawn)
     return set_err(AGX_EINVAL, "agx_spawn_children was called on an engine without children (agx_set_children)");
   if (e->beh_child && !e->d_child)  // (only the children variant interprets those: loud, never wrong)
@@ -1823,6 +1991,7 @@ agx_status prepare_run(agx_engine* e) {
     AGX_TRY(alloc_super(e));
     AGX_TRY(upload_super_init(e));
   }
+  if (e->d_recep) AGX_TRY(flush_recep_starts(e));
   if (e->prio_dirty) {  // priority tables and the buckets that hold an actor of a prioritised class
     std::vector<uint8_t> pb(e->prio_tab);  // tables, then the bucket marks (kPrioBucketOff)
     pb.resize(kPrioBucketOff + e->nb, 0);
@@ -2078,6 +2247,13 @@ agx_status error_status(const agx_engine* e, uint64_t err) {
     return set_err(AGX_ECAPACITY, "a bucket of %u actors of an engine with supervision received more than one tile of %d "
                    "messages (backlog included): the launches for larger inboxes know no supervision (smaller "
                    "agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
+  if (err & kErrRecepTile)
+    return set_err(AGX_ECAPACITY, "a bucket of %u actors of an engine with the receptionist received more than one tile of "
+                   "%d messages (backlog included): the launches for larger inboxes know no receptionist (smaller "
+                   "agx_cfg.bucket_actors spread the load)", 1u << e->bb, kBucket);
+  if (err & kErrRecepCap)
+    return set_err(AGX_ECAPACITY, "a service key's listing would hold more than %u ids, the receptionist's capacity "
+                   "(agx_set_receptionist): the listing keeps its first %u ids", e->rc_cap, e->rc_cap);
   if (err & kErrWatchSlots)
     return set_err(AGX_ECAPACITY, "a watch found every one of its actor's %u watch slots taken: the watch is not recorded "
                    "(agx_set_death_watch; at most %u watched refs per actor)", e->wd_slots, AGX_MAX_WATCH_SLOTS);
@@ -3330,6 +3506,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_watch);
   hipFree(e->d_child);
   hipFree(e->d_super);
+  hipFree(e->d_recep);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -4044,6 +4221,101 @@ agx_status agx_read_children(agx_engine* e, uint64_t actor_id, uint32_t* parent,
   return AGX_OK;
 }
 
+// TY/internal/receptionist/LocalReceptionist.scala:147-248; TY/internal/routing/GroupRouterImpl.scala:114-146
+agx_status agx_set_receptionist(agx_engine* e, uint32_t n_keys, uint32_t capacity) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (n_keys < 1u || n_keys > AGX_MAX_SERVICE_KEYS || capacity < 1u)
+    return set_err(AGX_EINVAL, "the receptionist: %u service keys (1..%u), listings of %u ids (at least 1)", n_keys,
+                   AGX_MAX_SERVICE_KEYS, capacity);
+  if (e->d_recep) return set_err(AGX_EINVAL, "the receptionist is already set (%u service keys)", e->rc_keys);
+  AGX_TRY(refuse_feature(e, F_RECEP));
+  AGX_TRY(ensure_dev(e));
+  const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, e->n_global);  // (a listing never holds more ids than there are)
+  const size_t words = rc_mask_off(n_keys, cap, e->nb) + (((size_t)e->nb << e->bb) + 3u) / 4u;
+  if (hipMalloc((void**)&e->d_recep, words * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_recep = nullptr;
+    return set_err(AGX_ENOMEM, "the receptionist's storage (%u keys, listings of %u ids, %llu actors: %llu MB) does not fit "
+                   "on the device", n_keys, cap, (unsigned long long)e->n_global, (unsigned long long)(words >> 18));
+  }
+  const uint32_t head[3] = {n_keys, cap, e->nb};
+  HIP_TRY(hipMemsetAsync(e->d_recep, 0, words * 4ull, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_recep, head, sizeof(head), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->rc_keys = n_keys;
+  e->rc_cap = cap;
+  e->rc_starts.clear();
+  e->rc_bad_start = false;
+  drop_graphs(e);  // the variant, the storage and the rebuild kernels are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_register_services(agx_engine* e, uint64_t first_id, uint64_t count, uint32_t key, uint32_t on) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_recep) {
+    e->rc_bad_start = true;  // (agx_run refuses too: the rule of agx_start_watch)
+    return set_err(AGX_EINVAL, "agx_register_services needs an engine with the receptionist (agx_set_receptionist)");
+  }
+  if (first_id + count > e->n_global || first_id + count < first_id) return set_err(AGX_EINVAL, "bad actor range");
+  if (key >= e->rc_keys) return set_err(AGX_EINVAL, "service key %u of %u", key, e->rc_keys);
+  e->rc_starts.push_back({first_id, count, key, on ? 1u : 0u});
+  return AGX_OK;
+}
+
+agx_status agx_read_listing(agx_engine* e, uint32_t key, uint32_t* out_ids, uint64_t cap, uint64_t* out_n) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_recep) return set_err(AGX_EINVAL, "agx_read_listing needs an engine with the receptionist (agx_set_receptionist)");
+  if (key >= e->rc_keys) return set_err(AGX_EINVAL, "service key %u of %u", key, e->rc_keys);
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_recep_starts(e));
+  uint32_t n = 0;
+  AGX_TRY(copy_sync(e, &n, e->d_recep + kRcSize + key, 4, hipMemcpyDeviceToHost));
+  const uint64_t take = std::min<uint64_t>(n, out_ids ? cap : 0);
+  if (take)
+    AGX_TRY(copy_sync(e, out_ids, e->d_recep + rc_list_off(e->rc_keys, e->nb) + (size_t)key * e->rc_cap, take * 4ull,
+                      hipMemcpyDeviceToHost));
+  if (out_n) *out_n = n;
+  return AGX_OK;
+}
+
+agx_status agx_read_services(agx_engine* e, uint64_t first, uint64_t count, uint8_t* out_masks) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_recep) return set_err(AGX_EINVAL, "agx_read_services needs an engine with the receptionist (agx_set_receptionist)");
+  if (first + count > e->n_global || first + count < first || (count && !out_masks)) return set_err(AGX_EINVAL, "bad actor range");
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_recep_starts(e));
+  if (count)
+    AGX_TRY(copy_sync(e, out_masks, reinterpret_cast<const uint8_t*>(e->d_recep + rc_mask_off(e->rc_keys, e->rc_cap, e->nb)) + first,
+                      count, hipMemcpyDeviceToHost));
+  return AGX_OK;
+}
+
+agx_status agx_receptionist_info(agx_engine* e, uint64_t* routed, uint64_t* no_routees, uint64_t* registered,
+                                 uint64_t* deregistered, uint64_t* terminated, uint64_t* rebuilds, uint32_t size[8],
+                                 uint64_t version[8]) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint32_t h[kRcCntOff] = {0};
+  if (e->d_recep) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(flush_recep_starts(e));
+    AGX_TRY(copy_sync(e, h, e->d_recep, sizeof(h), hipMemcpyDeviceToHost));
+  }
+  uint64_t c[6], v[8];
+  memcpy(c, h + kRcCtr, sizeof(c));
+  memcpy(v, h + kRcVersion, sizeof(v));
+  if (routed) *routed = c[kRcRouted];
+  if (no_routees) *no_routees = c[kRcNoRoutees];
+  if (registered) *registered = c[kRcRegistered];
+  if (deregistered) *deregistered = c[kRcDeregistered];
+  if (terminated) *terminated = c[kRcTerminated];
+  if (rebuilds) *rebuilds = c[kRcRebuilds];
+  for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+    if (size) size[k] = h[kRcSize + k];
+    if (version) version[k] = v[k];
+  }
+  return AGX_OK;
+}
+
 agx_status agx_set_outbound(agx_engine* e, uint32_t first_host_id, uint32_t n_host, uint64_t capacity) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (n_host && (first_host_id < e->n_global || (uint64_t)first_host_id + n_host > (1ull << 31)))
@@ -4115,6 +4387,8 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   auto opnd_ok = [](uint32_t src, uint32_t word) {
     if (src == AGX_V_SPAWNED) return word <= 1u;
     if (src == AGX_V_CHILD) return word <= AGX_CHILD_NO_WORD;
+    if (src == AGX_V_LISTING_SIZE) return word < AGX_MAX_SERVICE_KEYS;
+    if (src == AGX_V_SERVICE_AT) return word < (AGX_MAX_SERVICE_KEYS << 2);
     return src == AGX_V_TIMER ? word < AGX_MAX_TIMER_KEYS : src <= AGX_V_STASH && word <= 1u;
   };
   // a supervision signal case (include/akka_gpu.h AGX_SIGNAL_PRERESTART): a signal case whose first test is
@@ -4142,7 +4416,11 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     const agx_act& A = acts[i];
     const bool tmop = A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL;  // (`word` is the key)
     const bool wdop = A.op >= AGX_A_WATCH && A.op <= AGX_A_UNWATCH;  // (the ref is the d-operand)
-    if (A.op < AGX_A_SET || A.op > AGX_A_CANCEL_RECEIVE_TIMEOUT || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+    const bool rcop = A.op >= AGX_A_REGISTER && A.op <= AGX_A_ROUTE;  // (`pad1` is the service key)
+    if (rcop && (A.pad1 >= AGX_MAX_SERVICE_KEYS || A.pad0 > (A.op == AGX_A_ROUTE ? (AGX_ROUTE_KEEP_SENDER | AGX_ROUTE_BY_INDEX) : 0u) ||
+                 (A.op == AGX_A_ROUTE && (A.pad0 & AGX_ROUTE_BY_INDEX) && !opnd_ok(A.dsrc, A.dword))))
+      return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (service keys 0..7, route flags 0..3)", i);
+    if (A.op < AGX_A_SET || A.op > AGX_A_ROUTE || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
         !opnd_ok(A.src, A.sword) ||
         ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop || A.op == AGX_A_STOP_CHILD ||
           A.op == AGX_A_SET_RECEIVE_TIMEOUT) &&
@@ -4202,6 +4480,36 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   if (e->d_child && ctl_tags)
     return set_err(AGX_EINVAL, "compiled behaviours: message tags 0xFD and 0xFC are reserved for Create and Stop envelopes on "
                    "an engine with children");
+  // the receptionist: a route sends one envelope through the case's tell slot; the service keys the tables use
+  bool uses_recep = false;
+  uint32_t rc_keys_used = 0;
+  auto rc_use = [&](uint32_t src, uint32_t word) {
+    if (src != AGX_V_LISTING_SIZE && src != AGX_V_SERVICE_AT) return;
+    uses_recep = true;
+    rc_keys_used = std::max(rc_keys_used, (word & 7u) + 1u);
+  };
+  for (uint32_t c = 0; c < n_cases; ++c) {
+    const agx_case& C = cases[c];
+    rc_use(C.src1, C.word1); rc_use(C.src2, C.word2); rc_use(C.src3, C.word3); rc_use(C.src4, C.word4);
+    uint32_t sends = 0;
+    bool route = false;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      sends += acts[i].op == AGX_A_TELL || acts[i].op == AGX_A_ROUTE;
+      route |= acts[i].op == AGX_A_ROUTE;
+    }
+    if (route && sends > 1u)
+      return set_err(AGX_EINVAL, "compiled behaviours: case %u holds %u of tell and route; an engine with the receptionist "
+                     "has max_emit 1", c, sends);
+  }
+  for (uint32_t i = 0; i < n_acts; ++i) {
+    rc_use(acts[i].src, acts[i].sword);
+    rc_use(acts[i].dsrc, acts[i].dword);
+    if (acts[i].op >= AGX_A_REGISTER && acts[i].op <= AGX_A_ROUTE) {
+      uses_recep = true;
+      rc_keys_used = std::max<uint32_t>(rc_keys_used, acts[i].pad1 + 1u);
+    }
+    uses_recep |= acts[i].op == AGX_A_TELL && (acts[i].pad0 & AGX_ROUTE_KEEP_SENDER) != 0;
+  }
   // the apply kernels reserve kmax tell slots per message (single pass: the tell overwrites the
   // message's own consumed LDS slot; otherwise a bucket's tells live in [lo*kmax, (lo+cnt)*kmax)):
   // a case that tells more often would overwrite unprocessed mail or the next bucket's tells
@@ -4256,6 +4564,8 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   for (uint32_t i = 0; i < n_acts; ++i)
     e->beh_rt |= acts[i].op == AGX_A_SET_RECEIVE_TIMEOUT || acts[i].op == AGX_A_CANCEL_RECEIVE_TIMEOUT;
   e->beh_rt_tag = rt_tag;
+  e->beh_recep = uses_recep;  // (checked against agx_set_receptionist at agx_run)
+  e->beh_rc_keys = rc_keys_used;
   e->beh_child = uses_child;  // (checked against agx_set_children at agx_run)
   e->beh_ctl_tags = ctl_tags;
   e->beh_watch = false;  // a watch action or a signal case (checked against agx_set_death_watch at agx_run)

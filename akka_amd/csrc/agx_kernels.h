@@ -59,6 +59,8 @@ constexpr uint64_t kErrTimerTile = 32;  // a bucket of an engine with timers exc
 constexpr uint64_t kErrWatchTile = 64;  // a bucket of an engine with death watch exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrWatchSlots = 128;  // a watch found every slot of its actor taken (AGX_ECAPACITY)
 constexpr uint64_t kErrSuperTile = 256;  // a bucket of an engine with supervision exceeded one LDS tile (AGX_ECAPACITY)
+constexpr uint64_t kErrRecepTile = 512;  // a bucket of an engine with the receptionist exceeded one LDS tile (AGX_ECAPACITY)
+constexpr uint64_t kErrRecepCap = 1024;  // a listing would exceed the receptionist's capacity (AGX_ECAPACITY)
 // per-block counters of k_bucket_apply: delivered, dead, unhandled, emitted, active
 constexpr int kBStats = 5;
 constexpr uint32_t kMaxApplyGrid = 4096;
@@ -1630,6 +1632,55 @@ __device__ __forceinline__ void child_tick_end(const BucketArgs& a, const Bucket
   }
 }
 
+// ---- the receptionist (agx_set_receptionist): what a thread's drains changed reaches the storage
+// once per wave -- the changed key bits as one atomic OR on the global dirty word (and the block's own "recount"
+// word in LDS), each counter as one atomic add.  A wave without a change or a route (the common case) does nothing.
+// Called by every thread of the block, after its drains.
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
+#pragma unroll
+  for (int d = kWave / 2; d > 0; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d, kWave);
+  return v;
+}
+__device__ __forceinline__ void recep_commit(const RecepDev& RD, const RecepCount& rc, uint32_t* changed) {
+  if (!__ballot((rc.chg | rc.routed | rc.none | rc.reg | rc.dereg | rc.term) != 0u)) return;  // (wave-uniform)
+  const uint32_t chg = wave_or_u32(rc.chg);
+  const uint32_t v[5] = {rc.routed, rc.none, rc.reg, rc.dereg, rc.term};
+  uint32_t t[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) t[i] = wave_incl_sum(v[i]);
+  if (lane_id() == kWave - 1) {
+    if (chg) {
+      atomicOr(RD.base + kRcFlags, chg);
+      atomicOr(changed, 1u);
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+      if (t[i]) atomicAdd(RD.ctr(i), (unsigned long long)t[i]);
+  }
+}
+// A block in which a mask changed recounts its bucket's members per key from the bucket's mask bytes (one u32 of
+// four actors per thread: coalesced; two keys share a packed wave sum) and writes cnt[key][bucket].  `tmp`: 32 u32
+// of LDS free after the drains.  Block-uniform call, after the barrier that follows the drains.
+__device__ __forceinline__ void recep_recount(const RecepDev& RD, uint32_t b, uint32_t a0, uint32_t na, uint32_t* tmp) {
+  const uint32_t tid = threadIdx.x, la0 = tid * 4u;
+  // (the mask array is padded to whole buckets and bytes past n_local are never set)
+  const uint32_t m4 = la0 < na ? *reinterpret_cast<const uint32_t*>(RD.mask + a0 + la0) : 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t c = (uint32_t)__popc(m4 & (0x01010101u << (2 * i))) | ((uint32_t)__popc(m4 & (0x01010101u << (2 * i + 1))) << 16);
+    const uint32_t s = wave_incl_sum(c);
+    if (lane_id() == kWave - 1) tmp[(tid / kWave) * 4 + i] = s;
+  }
+  __syncthreads();
+  if (tid < RD.nk) {
+    uint32_t n = 0;
+#pragma unroll
+    for (int w = 0; w < kBThreads / kWave; ++w) n += (tmp[w * 4 + (tid >> 1)] >> (16u * (tid & 1u))) & 0xFFFFu;
+    *RD.cnt(tid, b) = n;
+  }
+  __syncthreads();  // (tmp is the caller's again)
+}
+
 // kStash: deque-based mailboxes (agx_set_stash).  The inbox segment of an actor then
 // starts with its window: the buffered / parked messages this superstep processes instead of mailbox
 // mail (stash_window; k_bucket_apply put them there).  With a window every admitted mailbox message
@@ -1696,6 +1747,14 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     pre0 = pre1 = nullptr;  // (a born actor's state words are written to memory: the prefetch reads them there)
     child_classify<kGather>(a, L, CD, WD, b, a0, na, tnow, cnt, acc[0]);
   }
+  // kRc: the receptionist (agx_set_receptionist).  The inbox is the plain one; the drain keeps an
+  // actor's key mask in a register across its window, compiled cases register, deregister, find and route against
+  // the listings in force, and a block in which a mask changed recounts its bucket's members (L.rowtop is that
+  // block's "changed" word: plain behaviours allocate no snapshot rows).
+  constexpr bool kRc = (KM & kRecepKM) != 0;
+  static_assert(!kRc || (kLds && !kWide && !kOwner && !kStash && !kTm && !kWd && !kSv), "receptionist: single-rank fast launches, plain behaviours");
+  RecepDev RD{};
+  if constexpr (kRc) RD = recep_dev(P.recep);
   uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
   auto ikey = [&](uint32_t q) -> uint32_t { return kLds ? L.key[q] : a.scr.key[lo + q]; };
@@ -2093,6 +2152,18 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         rtd[j] = has ? ID.delay[a0 + la] : 0u;
       }
     }
+    // kRc: the key masks of this thread's actors with mail, fetched beside their state (striped as the drain is: a
+    // wave's 64 lanes read 64 consecutive bytes); byte j of rcm4 is actor j's
+    uint32_t rcm4 = 0;
+    RecepCount rcc{};
+    if constexpr (kRc) {
+#pragma unroll
+      for (int j = 0; j < kBAct; ++j) {
+        const uint32_t la = j * kBThreads + tid;
+        const bool has = la < na && (L.alive[la] & 1u) && L.seg[la + 1] != L.seg[la];
+        rcm4 |= has ? (uint32_t)RD.mask[a0 + la] << (8 * j) : 0u;
+      }
+    }
     auto sp_actor = [&](int j) {
       const uint32_t la = act_of(j);
       ecl[j] = 0;
@@ -2453,6 +2524,30 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
             break;
           }
         }
+      } else if constexpr (kRc) {
+        // the plain drain with compiled_apply_rc: the actor's key mask lives in a register across the window and is
+        // stored once, only if it changed (the net change is what moves a version); a stop clears every bit
+        const uint32_t mk0 = (rcm4 >> (8 * j)) & 0xFFu;
+        uint32_t mk = mk0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          const uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_rc(P, RD, kcur, self, wv, sv, pv, mk, rcc, em)
+                                                       : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          ++ndel;
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            rcc.term += (uint32_t)__popc(mk);  // RegisteredActorTerminated
+            mk = 0u;
+            break;
+          }
+        }
+        if (mk != mk0) {
+          RD.mask[l] = (uint8_t)mk;
+          rcc.chg |= mk ^ mk0;
+        }
       } else
       for (uint32_t q = 0; q < nd; ++q) {
         const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
@@ -2518,7 +2613,10 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       const uint32_t m = wave_min_u32(rtmin);
       if (lane_id() == 0 && m != kTmNone) atomicMin(&TD.earliest(b), m);
     }
+    if constexpr (kRc) recep_commit(RD, rcc, L.rowtop);
     __syncthreads();
+    if constexpr (kRc)  // (block-uniform; U is free: the state words were written back)
+      if (*L.rowtop) recep_recount(RD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));
     if constexpr (kStash) {
       // the bucket's pending count (read at its entry next superstep) joins its backlog count: the
       // next inbox has room for the windows, the bucket is visited and the run goes on while any
@@ -4877,6 +4975,10 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
   // skew launch.
   constexpr bool kSv = (KM & kSuperKM) != 0;  // (a flag of KM: agx_device.h)
   static_assert(!kSv || (!kWide && !kSkew && !kOwner && !kPrio && !kStash && !kTm && !kWd), "supervision: single-rank fast launches, plain behaviours");
+  // kRc: the receptionist (agx_set_receptionist) -- the same launches of an engine with the
+  // receptionist.  The inbox is the plain one, and a bucket never takes the skew launch.
+  constexpr bool kRc = (KM & kRecepKM) != 0;  // (a flag of KM: agx_device.h)
+  static_assert(!kRc || (!kWide && !kSkew && !kOwner && !kPrio && !kStash && !kTm && !kWd && !kSv), "receptionist: single-rank fast launches, plain behaviours");
   if (kOwner && a.halt && a.halt[0]) return;  // (device-resident multi-rank replay stopped)
   // key/src/pay carved from one array: group_tells reuses key+src as a 16 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t s_ksp[3 * kBucket];
@@ -4972,6 +5074,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
       if (tid == 0) s_flags = 2u;
     if constexpr (kSv)  // (nor is a supervised drain)
       if (tid == 0) s_flags = 2u;
+    if constexpr (kRc)  // (nor is a drain that registers and routes)
+      if (tid == 0) s_flags = 2u;
     for (uint32_t d = tid; d < kRadix; d += kBThreads) s_nh[d] = 0;
     uint32_t* my_tc = nullptr;  // (fused) this thread's table entry, zeroed once the bucket is processed
     // fused fast path, plain behaviours: state words 0 / 1 of the bucket's actors are loaded here,
@@ -5029,6 +5133,12 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
             if constexpr (kSv) {
               if (s_hi - s_lo > (uint32_t)kBucket) {  // the skew launches know no supervision: loud, the bucket's mail dropped
                 atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrSuperTile);
+                s_lo = s_hi = 0u;
+              }
+            }
+            if constexpr (kRc) {
+              if (s_hi - s_lo > (uint32_t)kBucket) {  // the skew launches know no receptionist: loud, the bucket's mail dropped
+                atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrRecepTile);
                 s_lo = s_hi = 0u;
               }
             }
@@ -5131,6 +5241,12 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
         if constexpr (kSv) {
           if (blc + tt + s_g[2] > (uint32_t)kBucket) {  // the skew launches know no supervision: loud, the bucket's mail dropped
             atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrSuperTile);
+            tt = 0u - blc - s_g[2];  // (cnt = 0 below)
+          }
+        }
+        if constexpr (kRc) {
+          if (blc + tt + s_g[2] > (uint32_t)kBucket) {  // the skew launches know no receptionist: loud, the bucket's mail dropped
+            atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrRecepTile);
             tt = 0u - blc - s_g[2];  // (cnt = 0 below)
           }
         }

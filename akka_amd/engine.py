@@ -379,6 +379,46 @@ class GpuEngine:
         check(self.lib.agx_read_children(self._h, actor_id, *(ctypes.byref(x) for x in v)))
         return dict(zip(("parent", "spawn_count", "created"), (int(x.value) for x in v)))
 
+    def set_receptionist(self, n_keys: int, capacity: int) -> None:
+        """agx_set_receptionist (before the first run, an engine of its own): `n_keys` service keys (1..8, typed
+        Tables.service_keys has them), listings of at most `capacity` ids.  Compiled behaviours may then
+        context.register / deregister / route / forward and read the listings."""
+        check(self.lib.agx_set_receptionist(self._h, n_keys, capacity))
+
+    def register_services(self, first: int, count: int, key: int, on: bool = True) -> None:
+        """agx_register_services: the live actors of the range register under (on=False: deregister from) service
+        key number `key` -- the setup block; the listing is in force for the next tick."""
+        check(self.lib.agx_register_services(self._h, first, count, key, 1 if on else 0))
+
+    def read_listing(self, key: int) -> np.ndarray:
+        """agx_read_listing: the listing of key number `key` in force for the next tick, ascending ids."""
+        n = ctypes.c_uint64()
+        check(self.lib.agx_read_listing(self._h, key, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(int(n.value), 1), np.uint32)
+        check(self.lib.agx_read_listing(self._h, key, _ptr(out, ctypes.c_uint32), int(n.value), ctypes.byref(n)))
+        return out[:int(n.value)]
+
+    def read_services(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """agx_read_services: the key masks (bit k = registered under key k) of actors [first, first + count)."""
+        count = self.cfg.n_actors - first if count is None else count
+        out = np.zeros(max(count, 1), np.uint8)
+        check(self.lib.agx_read_services(self._h, first, count, _ptr(out, ctypes.c_uint8)))
+        return out[:count]
+
+    RECEPTIONIST_INFO = ("routed", "no_routees", "registered", "deregistered", "terminated", "rebuilds")
+
+    def receptionist_info(self) -> dict:
+        """agx_receptionist_info: totals routed / no_routees / registered / deregistered / terminated / rebuilds, and
+        per key the size of the listing in force for the next tick and its version."""
+        v = [ctypes.c_uint64() for _ in range(6)]
+        size, version = np.zeros(8, np.uint32), np.zeros(8, np.uint64)
+        check(self.lib.agx_receptionist_info(self._h, *(ctypes.byref(x) for x in v), _ptr(size, ctypes.c_uint32),
+                                             _ptr(version, ctypes.c_uint64)))
+        d = dict(zip(self.RECEPTIONIST_INFO, (int(x.value) for x in v)))
+        d["size"] = [int(x) for x in size]
+        d["version"] = [int(x) for x in version]
+        return d
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""

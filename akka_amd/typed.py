@@ -33,6 +33,11 @@ What lowers:
     timers engine); ``compile_behaviors(..., transparent=(MessageType, ...))`` names the
     NotInfluenceReceiveTimeout types (``Tables.transparent_tags`` -> engine.set_receive_timeout, after
     engine.set_timers(max(Tables.timer_keys, 1)));
+  * ``ServiceKey(name)``, ``context.register(key)`` / ``deregister(key)``, ``context.listing_size(key)``,
+    ``context.service_at(key, x)``, ``context.route(key, msg, cursor=field)`` / ``route_by(key, index, msg)``,
+    ``ref.forward(msg)`` and ``Routers.group(key)`` (the receptionist and group routers): keys are
+    numbered in order of first appearance (``Tables.service_keys`` -> engine.set_receptionist), and a case holds at
+    most one of tell and route;
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -82,6 +87,11 @@ MAX_CHILD_REGIONS, MAX_SPAWN_SITES = 8, 64
 SPAWN_ARG_BITS = 18          # a spawn's argument: its low 18 bits are added to the site's word-0 base
 A_SET_RECEIVE_TIMEOUT, A_CANCEL_RECEIVE_TIMEOUT = 15, 16
 TAG_RECEIVE_TIMEOUT = 0xFB   # the tag of a receive-timeout envelope: reserved when the tables use receive timeouts
+V_LISTING_SIZE, V_SERVICE_AT = 11, 12  # engines with the receptionist; `word` = key | selector << 3
+SVC_WORD0, SVC_WORD1, SVC_ARG, SVC_CONST = 0, 1, 2, 3  # V_SERVICE_AT's selector: what x of listing[x mod size] is
+A_REGISTER, A_DEREGISTER, A_ROUTE = 17, 18, 19     # the service key is pad1
+ROUTE_KEEP_SENDER, ROUTE_BY_INDEX = 1, 2           # pad0 of A_ROUTE (KEEP_SENDER also of A_TELL: ref.forward)
+MAX_SERVICE_KEYS = 8
 
 
 class AgxCase(ctypes.Structure):
@@ -181,6 +191,8 @@ class Action:
     or_mask: int = 0
     site: object = None   # A_SPAWN: the _SpawnSite
     into: bool = False    # A_SPAWN: state word `word` receives the child's id
+    key: object = None    # A_REGISTER / A_DEREGISTER / A_ROUTE: the ServiceKey
+    flags: int = 0        # A_ROUTE / A_TELL: ROUTE_KEEP_SENDER, ROUTE_BY_INDEX (pad0)
 
 
 class Field(Operand):
@@ -225,6 +237,12 @@ class Ref:
 
     __call__ = tell
 
+    def forward(self, msg, tag: int | None = None):
+        """ref.forward(msg): a tell that keeps the incoming message's sender on the envelope (the typed message's
+        replyTo travels on).  The actors need an engine with the receptionist (engine.set_receptionist)."""
+        a = self.tell(msg, tag)
+        return Action(a.op, a.word, a.val, a.dst, a.or_mask, flags=ROUTE_KEEP_SENDER)
+
 
 def self_ref(offset: int = 0) -> Ref:
     """context.self, or the actor `offset` ids further on (mod the population)."""
@@ -258,6 +276,28 @@ class MessageType:
     def payload(self, arg: int = 0) -> int:
         """The u32 payload of an instance (for host tells)."""
         return (self.tag << 24) | (arg & 0xFFFFFF)
+
+
+@dataclass(frozen=True)
+class ServiceKey:
+    """ServiceKey[T](id) (TY/receptionist/Receptionist.scala): names a service; keys with the same name are the
+    same key.  The lowering numbers the keys in use, at most MAX_SERVICE_KEYS, in order of first appearance."""
+    name: str
+
+
+@dataclass(frozen=True)
+class _KeyOperand(Operand):
+    """An operand that reads a key's listing: `word` is filled in by the lowering (key index | selector << 3)."""
+    key: ServiceKey | None = None
+    sel: int = 0
+
+    def __add__(self, c):
+        if not isinstance(c, int):
+            raise CompileError("only a constant can be added to an operand")
+        return _KeyOperand(self.src, self.word, self.k + c, self.key, self.sel)
+
+    __eq__ = Operand.__eq__
+    __hash__ = object.__hash__
 
 
 class Incoming:
@@ -498,8 +538,97 @@ class ActorContext:
         """context.cancelReceiveTimeout(): an envelope already enqueued stays in the mailbox and is discarded."""
         return Action(A_CANCEL_RECEIVE_TIMEOUT, 0)
 
+    # the receptionist and group routers (engine.set_receptionist(len(tables.service_keys), capacity); TY/internal/
+    # receptionist/LocalReceptionist.scala:147-248, TY/internal/routing/GroupRouterImpl.scala:114-146)
+    @staticmethod
+    def _key(key) -> ServiceKey:
+        if not isinstance(key, ServiceKey):
+            raise CompileError(f"not a ServiceKey: {key!r}")
+        return key
+
+    def register(self, key) -> "Action":
+        """context.system.receptionist ! Receptionist.Register(key, context.self): the actor is in the key's listing
+        from the next tick on.  Idempotent; an actor only registers itself; no Registered acknowledgement."""
+        return Action(A_REGISTER, 0, key=self._key(key))
+
+    def deregister(self, key) -> "Action":
+        """receptionist ! Receptionist.Deregister(key, context.self): the actor leaves the listing from the next tick on."""
+        return Action(A_DEREGISTER, 0, key=self._key(key))
+
+    def listing_size(self, key) -> Operand:
+        """The size of the key's listing in force this tick (Receptionist.Find, read synchronously)."""
+        return _KeyOperand(V_LISTING_SIZE, 0, 0, self._key(key), 0)
+
+    def service_at(self, key, x) -> Ref:
+        """listing[x mod size] of the key's listing in force (x: a state field, the message's argument, each + a
+        constant, or a constant); 0xFFFFFFFF (a dead letter) when the listing is empty."""
+        key = self._key(key)
+        if isinstance(x, (int, np.integer)):
+            return Ref(_KeyOperand(V_SERVICE_AT, 0, int(x), key, SVC_CONST))
+        if isinstance(x, Operand) and x.src == V_WORD:
+            return Ref(_KeyOperand(V_SERVICE_AT, 0, x.k, key, SVC_WORD0 + x.word))
+        if isinstance(x, Operand) and x.src == V_ARG:
+            return Ref(_KeyOperand(V_SERVICE_AT, 0, x.k, key, SVC_ARG))
+        raise CompileError(f"service_at takes a state field, the message's argument or a constant, not {x!r}")
+
+    def _route(self, key, msg, word, dst, flags) -> "Action":
+        if isinstance(msg, Message):
+            val, mask = msg.arg, msg.or_mask
+        else:
+            val, mask = lift(msg), 0
+        return Action(A_ROUTE, word, val, dst, mask, key=self._key(key), flags=flags)
+
+    def route(self, key, msg, cursor, forward: bool = True) -> "Action":
+        """Round-robin routing over the key's listing in force: the routee is the smallest listed id >= the cursor
+        (a state field of the router), else listing[0]; the cursor becomes routee + 1.  An empty listing sends the
+        message to deadLetters (the reference's Dropped) and leaves the cursor.  `forward`: the envelope keeps the
+        incoming message's sender (a typed router passes the message, replyTo included, unchanged)."""
+        if not isinstance(cursor, Field):
+            raise CompileError(f"cursor= names a state field of the router, not {cursor!r}")
+        return self._route(key, msg, cursor.word, None, ROUTE_KEEP_SENDER if forward else 0)
+
+    def route_by(self, key, index, msg, forward: bool = True) -> "Action":
+        """Routing by index: the routee is listing[index mod size] -- the same index reaches the same routee while the
+        listing stands (the modulo stand-in for consistent hashing)."""
+        return self._route(key, msg, 0, lift(index), ROUTE_BY_INDEX | (ROUTE_KEEP_SENDER if forward else 0))
+
 
 context = ActorContext()
+
+
+class _GroupRouter:
+    """Routers.group(key) (TY/scaladsl/Routers.scala; GroupRouterImpl.scala:114-146): the builder."""
+
+    def __init__(self, key):
+        self.key, self.index = ActorContext._key(key), None
+
+    def with_round_robin_routing(self) -> "_GroupRouter":
+        """withRoundRobinRouting (RoutingLogic.scala:42-75): the default here."""
+        self.index = None
+        return self
+
+    def with_index_routing(self, index) -> "_GroupRouter":
+        """Routing by `index(m)` mod the listing's size, e.g. lambda m: m.arg."""
+        self.index = index
+        return self
+
+    def build(self, name: str = "group_router") -> "Behavior":
+        """The router as a Behavior over State("cursor", "routed"): every message is forwarded, payload unchanged,
+        to the routee the logic selects; `routed` counts the messages seen."""
+        st = State("cursor", "routed")
+        if self.index is None:
+            h = lambda m, s: [s.routed.inc(), context.route(self.key, m.payload, cursor=s.cursor), Behaviors.same]
+        else:
+            h = lambda m, s: [s.routed.inc(), context.route_by(self.key, self.index(m), m.payload), Behaviors.same]
+        return ReceiveBuilder.create(st).on_any_message(h).build(name)
+
+
+class Routers:
+    """Routers.group(key): a group router over the actors registered under `key` (pool routers: workloads.pool_router)."""
+
+    @staticmethod
+    def group(key) -> _GroupRouter:
+        return _GroupRouter(key)
 
 
 class Terminated:
@@ -818,6 +947,7 @@ class Tables:
     exception_classes: list = field(default_factory=list)  # the ExceptionTypes in use; the index is the class number
     spawn_sites: list = field(default_factory=list)  # (kind, word-0 base, word 1 or None: the parent's id) -> engine.set_children
     transparent_tags: tuple = ()  # the tags of the NotInfluenceReceiveTimeout message types -> engine.set_receive_timeout
+    service_keys: list = field(default_factory=list)  # the ServiceKeys in use; the index is the key number -> engine.set_receptionist
 
     @property
     def uses_supervision(self) -> bool:
@@ -833,8 +963,19 @@ class Tables:
     def max_tells(self) -> int:
         """The most tells one message can emit (the largest tell count of any case): the engine's
         max_emit must be at least this (agx_set_behaviors rejects the tables otherwise)."""
-        return max((sum(1 for i in range(c.act_first, c.act_first + c.act_count) if self.acts[i].op == A_TELL)
+        return max((sum(1 for i in range(c.act_first, c.act_first + c.act_count) if self.acts[i].op in (A_TELL, A_ROUTE))
                     for c in self.cases[:int(self.first[-1])]), default=0)
+
+    @property
+    def uses_forward(self) -> bool:
+        """A tell or a route keeps the incoming message's sender (ref.forward, route(forward=True))."""
+        return any(a.op in (A_TELL, A_ROUTE) and a.pad0 & ROUTE_KEEP_SENDER for a in self.acts[:self.n_acts])
+
+    @property
+    def uses_receptionist(self) -> bool:
+        """The behaviours register, deregister, route, forward or read a listing: the engine needs
+        engine.set_receptionist(len(tables.service_keys), capacity)."""
+        return bool(self.service_keys) or self.uses_forward
 
     @property
     def stash_capacity(self) -> int:
@@ -925,9 +1066,22 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
     exc_id = {id(x): i for i, x in enumerate(excs)}
     cases, acts, first = [], [], [0]
     sites = []  # the spawn sites in use, in order of appearance: (behaviour index, base, word 1)
+    skeys = []  # the service keys in use, in order of appearance
+
+    def key_no(key) -> int:
+        if key not in skeys:
+            if len(skeys) >= MAX_SERVICE_KEYS:
+                raise CompileError(f"more than {MAX_SERVICE_KEYS} service keys")
+            skeys.append(key)
+        return skeys.index(key)
+
+    def res_op(o: Operand) -> Operand:  # a listing operand's `word`: the key's number | the selector << 3
+        return Operand(o.src, key_no(o.key) | (o.sel << 3), o.k) if isinstance(o, _KeyOperand) else o
+
     for b in behs:
         for c in b.cases:
-            t = c.tests + [ALWAYS] * (2 - len(c.tests))
+            c_tests = [Test(x.cmp, res_op(x.lhs), res_op(x.rhs)) for x in c.tests]
+            t = c_tests + [ALWAYS] * (2 - len(c_tests))
             res = c.result
             if isinstance(res, Behavior):
                 code, nxt = RES_BECOME, index[id(res)]
@@ -949,7 +1103,9 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
                                  src4=t[1].rhs.src, word4=t[1].rhs.word, k4=t[1].rhs.k,
                                  result=code, next=nxt, act_first=len(acts), act_count=len(c.effects)))
             for e in c.effects:
-                d = e.dst or Operand(V_CONST)
+                d = res_op(e.dst or Operand(V_CONST))
+                if e.val is not res_op(e.val):
+                    e = Action(e.op, e.word, res_op(e.val), e.dst, e.or_mask, e.site, e.into, e.key, e.flags)
                 if e.op == A_SPAWN:  # dword: the site; pad0: the word `word` receives the child's id
                     key = (index[id(e.site.behavior)], e.site.base, e.site.word1)
                     if key not in sites:
@@ -960,7 +1116,8 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
                                        dsrc=V_CONST, dword=sites.index(key), dk=0, pad0=1 if e.into else 0))
                     continue
                 acts.append(AgxAct(op=e.op, word=e.word, src=e.val.src, sword=e.val.word, k=e.val.k,
-                                   dsrc=d.src, dword=d.word, dk=d.k, or_mask=e.or_mask))
+                                   dsrc=d.src, dword=d.word, dk=d.k, or_mask=e.or_mask, pad0=e.flags,
+                                   pad1=key_no(e.key) if e.key is not None else 0))
         first.append(len(cases))
     if len(cases) > MAX_CASES or len(acts) > MAX_ACTS:
         raise CompileError("tables too large")
@@ -969,6 +1126,7 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
     t.exception_classes = excs
     t.spawn_sites = [(KIND_COMPILED + bi, base, w1) for bi, base, w1 in sites]
     t.transparent_tags = tuple(sorted({mt.tag for mt in transparent}))
+    t.service_keys = skeys
     for b in behs:  # a supervisor of a class catches it and its descendants: the hierarchy as masks
         row = []
         for sv in b.supervisors:
@@ -1056,6 +1214,18 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
                                        (s2 == V_TAG and k2 == 0 and s1 == V_CONST and k1 in (TAG_CREATE, TAG_STOP))):
                     raise CompileError("message tags 0xFD and 0xFC are reserved for Create and Stop in behaviours that use "
                                        "children")
+    if t.uses_receptionist:  # an engine of its own: max_emit 1, a route goes through the case's tell slot
+        if t.stash_capacity or t.timer_keys or t.uses_receive_timeout or t.uses_watch or t.uses_children or t.uses_supervision or \
+                any(V_STASH in (a.src, a.dsrc) for a in acts) or any(V_STASH in (c.src1, c.src2, c.src3, c.src4) for c in cases):
+            raise CompileError("the receptionist shares an engine with neither a stash, timers, death watch, children nor "
+                               "supervision: the behaviours use the receptionist and one of them")
+        if max_emit is not None and max_emit > 1:
+            raise CompileError(f"the receptionist needs max_emit = 1, not {max_emit}")
+        for c in cases:
+            n = sum(1 for j in range(c.act_first, c.act_first + c.act_count) if acts[j].op in (A_TELL, A_ROUTE))
+            if n > 1:
+                raise CompileError(f"a case holds {n} of tell and route: each sends one envelope, and an engine with the "
+                                   "receptionist has max_emit 1")
     if max_emit is not None and t.max_tells > max(1, max_emit):
         raise CompileError(f"a case tells {t.max_tells} times per message but max_emit is {max_emit}")
     return t

@@ -64,6 +64,9 @@ class Workload:
     # first_child, max_children)], "sites": typed.Tables.spawn_sites, "spawns": [(first, count, site, arg)]} --
     # empty: no children
     children: dict = field(default_factory=dict)
+    # the receptionist (agx_set_receptionist / agx_register_services): {"n_keys": k, "capacity": ids per listing,
+    # "starts": [(first, count, key)]} -- empty: no receptionist
+    receptionist: dict = field(default_factory=dict)
     # host tells that follow the clock: schedule[t] = (dst, src, payload) is staged before tick t + 1 (run_schedule)
     schedule: list = field(default_factory=list)
 
@@ -97,6 +100,10 @@ class Workload:
             target.set_delta_crdt(self.delta_crdt)
         if self.behaviors is not None:
             target.set_behaviors(self.behaviors)
+        if self.receptionist:  # (empty: targets without the calls are unaffected)
+            target.set_receptionist(self.receptionist["n_keys"], self.receptionist["capacity"])
+            for first, count, key in self.receptionist.get("starts", ()):
+                target.register_services(first, count, key)
         if self.timers:  # (empty: targets without the calls are unaffected)
             target.set_timers(self.timers["n_keys"])
             for first, count, key, periodic, delay, delays, payload in self.timers.get("starts", ()):
@@ -948,3 +955,101 @@ def pool_watch_starts(n_routers: int, pool_size: int) -> list:
     """pool_router's setup watches: router r watches its routees 0 .. min(pool_size, 4) - 1."""
     r = np.arange(n_routers, dtype=np.uint32)
     return [(0, n_routers, n_routers + r * pool_size + k, 0, None) for k in range(min(pool_size, 4))]
+
+
+# ------------------------------------------------------------------ the receptionist and group routers (DESIGN.md §2.8)
+SP_JOB = 1
+SM_REG, SM_DEREG, SM_STOP, SM_ROUTE, SM_ROUTE_BY, SM_FIND, SM_WORK, SM_SIZE = 1, 2, 3, 4, 5, 6, 7, 8
+
+
+def service_pool(n_routers: int = 1 << 10, n_workers: int = 1 << 14, ticks: int = 16, quota: int = 0, throughput: int = 3,
+                 bucket_actors: int = 0, n_host: int = 0) -> Workload:
+    """Routers.group(key) with round-robin logic over workers that come and go (GroupRouterImpl.scala:114-146,
+    RoutingLogic.scala:42-75): the workers (ids n_routers ..) register in the setup block, every router (ids 0 ..
+    n_routers - 1) gets one Job per tick from the host schedule and forwards it to the next registered worker; the
+    routers' cursors start spread over the workers, so a tick's jobs spread too.  A worker counts its jobs and keeps
+    the last payload (with n_host > 0 it answers the job's sender, the forward's replyTo); with `quota` > 0 worker i
+    stops after 1 + i mod quota jobs, so the listing shrinks tick by tick; with quota 0 the listing is stable."""
+    from . import typed
+    B = typed.Behaviors
+    key = typed.ServiceKey("worker")
+    job = typed.MessageType("Job", SP_JOB)
+    router = typed.Routers.group(key).with_round_robin_routing().build("group_router")
+    ws = typed.State("left", "last")
+    done = lambda m, s: [s.left.add(-1), s.last.set(m.payload)] + ([m.sender.tell(m.payload)] if n_host else [])
+    worker = (typed.ReceiveBuilder.create(ws)
+              .on_message(job, lambda m, s: done(m, s) + [B.stopped], when=lambda m, s: s.left == 1)
+              .on_message(job, lambda m, s: done(m, s) + [B.same])
+              .on_any_message(lambda m, s: [B.unhandled])
+              .build("pool_worker"))
+    tb = typed.compile_behaviors([router, worker], max_emit=1)
+    n = n_routers + n_workers
+    r = np.arange(n_routers, dtype=np.uint64)
+    rinit = np.zeros((n_routers, 2), np.uint64)
+    rinit[:, 0] = n_routers + r * n_workers // max(n_routers, 1)
+    winit = np.zeros((n_workers, 2), np.uint64)
+    winit[:, 0] = 1 + np.arange(n_workers, dtype=np.uint64) % quota if quota else 0  # (0: never reaches 1 going down)
+    dst = np.arange(n_routers, dtype=np.uint32)
+    src = (n + dst % n_host).astype(np.uint32) if n_host else np.full(n_routers, NO_SENDER, np.uint32)
+    schedule = [(dst, src, np.full(n_routers, job.payload(t + 1), np.uint32)) for t in range(ticks)]
+    return Workload("service_pool", n, 2, 1, throughput, 0,
+                    [(0, n_routers, tb.kind_of(router), rinit), (n_routers, n_workers, tb.kind_of(worker), winit)],
+                    behaviors=tb, bucket_actors=bucket_actors, outbound=(n, n_host) if n_host else None,
+                    receptionist={"n_keys": 1, "capacity": n_workers, "starts": [(n_routers, n_workers, 0)]},
+                    schedule=schedule)
+
+
+def service_mesh(n: int = 4096, n_keys: int = 8, seed: int = 1, ticks: int = 40, throughput: int = 3, capacity: int = 16,
+                 bucket_actors: int = 64, n_host: int = 4) -> Workload:
+    """The differential workload of the receptionist: every actor runs one behaviour that, on host messages, registers
+    under or deregisters from key (arg mod n_keys), stops, routes a Work message round robin (cursor: state word 0) or
+    by index (its count, state word 1), finds a service (service_at) and tells it, or reports a listing's size to the
+    message's sender; Work counts.  The host schedule draws, per tick, random actors for each of these (registrations
+    outnumber stops, so listings grow, churn and shrink); a quarter of the actors are registered in the setup block.
+    Bounded mailboxes (`capacity`) keep a popular routee's backlog, and so its bucket's inbox, within one tile."""
+    from . import typed
+    B, ctx = typed.Behaviors, typed.context
+    keys = [typed.ServiceKey(f"svc{k}") for k in range(n_keys)]
+    st = typed.State("cursor", "count")
+    work = typed.MessageType("Work", SM_WORK)
+    rb = typed.ReceiveBuilder.create(st)
+    tag = lambda t: (lambda m: m.tag == t)
+    rb.on_any_message(lambda m, s: [s.count.inc(), B.stopped], test=tag(SM_STOP))
+    rb.on_any_message(lambda m, s: [s.count.inc(), B.same], test=tag(SM_WORK))
+    for k, key in enumerate(keys):
+        arg = (lambda k: (lambda m, s: m.arg == k))(k)
+        rb.on_any_message((lambda key: lambda m, s: [ctx.register(key), B.same])(key), test=tag(SM_REG), when=arg)
+        rb.on_any_message((lambda key: lambda m, s: [ctx.deregister(key), B.same])(key), test=tag(SM_DEREG), when=arg)
+        rb.on_any_message((lambda key: lambda m, s: [ctx.route(key, work(s.count), cursor=s.cursor, forward=False), B.same])(key),
+                          test=tag(SM_ROUTE), when=arg)
+        rb.on_any_message((lambda key: lambda m, s: [ctx.route_by(key, s.count, work(m.arg)), s.count.inc(), B.same])(key),
+                          test=tag(SM_ROUTE_BY), when=arg)
+        rb.on_any_message((lambda key: lambda m, s: [ctx.service_at(key, s.cursor + 1).tell(work(1)), B.same])(key),
+                          test=tag(SM_FIND), when=arg)
+        rb.on_any_message((lambda key: lambda m, s: [m.sender.tell(ctx.listing_size(key)), B.same])(key),
+                          test=tag(SM_SIZE), when=arg)
+    rb.on_any_message(lambda m, s: [B.unhandled])
+    node = rb.build("mesh_node")
+    tb = typed.compile_behaviors([node], max_emit=1)
+    rng = np.random.default_rng(seed)
+    init = np.zeros((n, 2), np.uint64)
+    init[:, 0] = rng.integers(0, n, n)
+    schedule = []
+    per = {SM_REG: n // 16, SM_DEREG: n // 32, SM_STOP: n // 128, SM_ROUTE: n // 16, SM_ROUTE_BY: n // 32, SM_FIND: n // 32,
+           SM_SIZE: max(n // 256, 1)}
+    for t in range(ticks):
+        dst, pay = [], []
+        for tg, cnt in per.items():
+            if tg == SM_REG and t >= ticks * 3 // 4:  # (the tail: listings only shrink)
+                continue
+            d = rng.integers(0, n, cnt)
+            dst.append(d)
+            pay.append((tg << 24) | rng.integers(0, n_keys, cnt))
+        dst = np.concatenate(dst).astype(np.uint32)
+        o = rng.permutation(dst.size)
+        src = (n + rng.integers(0, max(n_host, 1), dst.size)).astype(np.uint32)
+        schedule.append((dst[o], src[o], np.concatenate(pay).astype(np.uint32)[o]))
+    starts = [(int(f), int(n // (4 * n_keys)), k) for k, f in enumerate(rng.integers(0, n - n // (4 * n_keys), n_keys))]
+    return Workload("service_mesh", n, 2, 1, throughput, capacity, [(0, n, tb.kind_of(node), init)], behaviors=tb,
+                    bucket_actors=bucket_actors, outbound=(n, max(n_host, 1)),
+                    receptionist={"n_keys": n_keys, "capacity": n, "starts": starts}, schedule=schedule)

@@ -136,8 +136,18 @@ enum agx_operand { AGX_V_CONST = 0, AGX_V_PAYLOAD = 1, AGX_V_TAG = 2, AGX_V_ARG 
                    AGX_V_SPAWNED = 9 /* the actor's spawn count */,
                    AGX_V_CHILD = 10 /* the id of child number (value + k) mod spawn count of the actor; value =
                                        state word `word` (0, 1) or 0 (word = AGX_CHILD_NO_WORD); 0xFFFFFFFF with no
-                                       children */ };
+                                       children */,
+                   /* engines with the receptionist (agx_set_receptionist); `word` = key | selector << 3: */
+                   AGX_V_LISTING_SIZE = 11 /* the size of the listing of key `word & 7` in force this tick */,
+                   AGX_V_SERVICE_AT = 12 /* listing[x mod size] of key `word & 7`, x = the value the selector names
+                                            (AGX_SVC_WORD0 / WORD1: that state word, AGX_SVC_ARG: the message's
+                                            argument, AGX_SVC_CONST: 0) + k; 0xFFFFFFFF when the listing is empty */ };
 #define AGX_CHILD_NO_WORD 2u
+#define AGX_SVC_WORD0 0u
+#define AGX_SVC_WORD1 1u
+#define AGX_SVC_ARG 2u
+#define AGX_SVC_CONST 3u
+#define AGX_SVC_WORD(key, sel) ((uint8_t)((key) | ((sel) << 3)))
 enum agx_cmp { AGX_CMP_ANY = 0, AGX_CMP_EQ = 1, AGX_CMP_NE = 2, AGX_CMP_LT = 3, AGX_CMP_LE = 4, AGX_CMP_GT = 5,
                AGX_CMP_GE = 6 };
 enum agx_action_op {
@@ -175,8 +185,21 @@ enum agx_action_op {
    * 18-74).  SET: the message payload is the operand as a TELL's payload, the delay in ticks is the d-operand,
    * as a timer's (below 1 it counts as 1, above 2^31 - 1 it is clamped; a constant below 1 is refused). */
   AGX_A_SET_RECEIVE_TIMEOUT = 15,   /* context.setReceiveTimeout(delay, msg) (ActorContextAdapter.scala:120-126) */
-  AGX_A_CANCEL_RECEIVE_TIMEOUT = 16 /* context.cancelReceiveTimeout()        (ActorContextAdapter.scala:128-131) */
+  AGX_A_CANCEL_RECEIVE_TIMEOUT = 16, /* context.cancelReceiveTimeout()        (ActorContextAdapter.scala:128-131) */
+  /* The receptionist (engines with the receptionist, agx_set_receptionist).  The service key is
+   * pad1.  REGISTER / DEREGISTER set / clear the actor's own bit of the key.  ROUTE is selectRoutee(msg) ! msg: the
+   * payload is the operand as a TELL's; pad0 & AGX_ROUTE_KEEP_SENDER keeps the incoming message's sender on the
+   * envelope (a forward), else the sender is the router; pad0 & AGX_ROUTE_BY_INDEX takes listing[x mod size] with
+   * x the d-operand (dsrc, dword, dk), else round robin with the cursor in state word `word`.  A ROUTE sends
+   * through the case's tell slot: a case holds at most one of TELL and ROUTE.  AGX_ROUTE_KEEP_SENDER on a plain
+   * AGX_A_TELL (ref.forward(msg)) is accepted on an engine with the receptionist only. */
+  AGX_A_REGISTER = 17,   /* receptionist ! Register(key, self)   (LocalReceptionist.scala:147-175) */
+  AGX_A_DEREGISTER = 18, /* receptionist ! Deregister(key, self) (LocalReceptionist.scala:177-199) */
+  AGX_A_ROUTE = 19       /* group router: selectRoutee(msg) ! msg (GroupRouterImpl.scala:114-146) */
 };
+#define AGX_ROUTE_KEEP_SENDER 1u
+#define AGX_ROUTE_BY_INDEX 2u
+#define AGX_MAX_SERVICE_KEYS 8u
 #define AGX_TAG_RECEIVE_TIMEOUT 0xFBu /* the message tag of a receive-timeout envelope: reserved on an engine with
                                          receive timeouts */
 #define AGX_TAG_CREATE 0xFDu    /* the message tag of a Create envelope: reserved on an engine with children */
@@ -782,6 +805,34 @@ agx_status agx_children_info(agx_engine* eng, uint64_t* spawned, uint64_t* refus
 /* One actor: its computed parent (0xFFFFFFFF: none), its spawn count, whether it was ever created. */
 agx_status agx_read_children(agx_engine* eng, uint64_t actor_id, uint32_t* parent, uint32_t* spawn_count,
                              uint32_t* created);
+
+/* The receptionist and group routers (Receptionist / ServiceKey / Routers.group: TY/internal/receptionist/
+ * LocalReceptionist.scala:147-248, TY/internal/routing/GroupRouterImpl.scala:114-146, RoutingLogic.scala:42-75;
+ * pinned by LocalReceptionistSpec.scala:48-133,207-250, RoutersSpec.scala:120-207, RoutingLogicSpec.scala:20-123;
+ * DESIGN.md 2.8 has the contract).  A top-level feature: a single-rank engine with max_emit 1, no CRDT kinds, no
+ * other feature, no ring pool; call before the first agx_run (AGX_ESTATE afterwards); a second call is AGX_EINVAL.
+ * n_keys service keys (1..AGX_MAX_SERVICE_KEYS), every actor holds one bit per key.  AGX_A_REGISTER / DEREGISTER
+ * set / clear the actor's own bit; a stop of any cause clears all of them.  The listing of key k in force during
+ * tick t is the ids whose bit k was set at the end of tick t - 1, ascending; it holds at most `capacity` ids (a
+ * listing that would exceed it is cut to its first `capacity` ids and raises a sticky AGX_ECAPACITY).  version[k]
+ * grows by one at the end of every tick in which some actor's bit k differs from its value at the start of the
+ * tick.  A bucket's inbox is limited to one tile of 2048 messages (sticky AGX_ECAPACITY). */
+agx_status agx_set_receptionist(agx_engine* eng, uint32_t n_keys, uint32_t capacity);
+/* The setup block (Behaviors.setup { ctx => receptionist ! Register(key, ctx.self) }), before the first run or
+ * between runs: set (on != 0) or clear bit `key` of the live actors of [first_id, first_id + count); the listing
+ * is rebuilt at once, in force for the next tick. */
+agx_status agx_register_services(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t key, uint32_t on);
+/* The listing of `key` in force for the next tick: up to `cap` ids into out_ids, its size into out_n. */
+agx_status agx_read_listing(agx_engine* eng, uint32_t key, uint32_t* out_ids, uint64_t cap, uint64_t* out_n);
+/* The key masks (bit k = registered under key k) of actors [first, first + count). */
+agx_status agx_read_services(agx_engine* eng, uint64_t first, uint64_t count, uint8_t* out_masks);
+/* Totals since agx_create: routed (a ROUTE that found a routee), no_routees (one that found none: the reference's
+ * Dropped), registered (0 -> 1 changes of a bit), deregistered (1 -> 0 by an action or agx_register_services),
+ * terminated (1 -> 0 by a stop), rebuilds (listings rebuilt), and per key the size of the listing in force for the
+ * next tick and its version.  Any pointer may be NULL. */
+agx_status agx_receptionist_info(agx_engine* eng, uint64_t* routed, uint64_t* no_routees, uint64_t* registered,
+                                 uint64_t* deregistered, uint64_t* terminated, uint64_t* rebuilds, uint32_t size[8],
+                                 uint64_t version[8]);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
