@@ -318,7 +318,9 @@ __device__ __forceinline__ bool dl_group_row(const DevParams& P, const St32& s, 
     }
     if (!ph && last_add) row[hdr] = 1u | (cnt << 8), row[hdr + 1] = vmax;
     row[0] = nops;
-    if (!ph) row[P.pw - 1] = o;  // the row's used length (a queued group's row is copied forward that far)
+    // the row's used length: in an ORSet-only population a queued group's row is copied forward that
+    // far (bucket_finish, kBigRows).  Counter groups write none: their variants copy the whole pitch
+    if (!ph) row[P.pw - 1] = o;
   }
   if (ph) row[0] = 0x80000000u;
   return ph;

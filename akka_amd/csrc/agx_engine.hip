@@ -541,6 +541,17 @@ agx_status dalloc(T** p, uint64_t n) {
   return AGX_OK;
 }
 
+// CRDT row storage (the snapshot heap and the multi-rank row buffers).  AGX_HEAP_POISON=<0..255>
+// (test knob): every fresh allocation is filled with that byte, so a reader of a row word that no
+// writer wrote sees the same value on every run instead of whatever the allocator handed out.
+// Unset: hipMalloc alone, no further device call.
+agx_status dalloc_rows(uint32_t** p, uint64_t n) {
+  AGX_TRY(dalloc(p, n));
+  if (const char* s = getenv("AGX_HEAP_POISON"))
+    HIP_TRY(hipMemset(*p, std::min(255, std::max(0, atoi(s))), std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+  return AGX_OK;
+}
+
 agx_status alloc_msgs(DevMsgs& m, uint64_t n) {
   AGX_TRY(dalloc(&m.key, n));
   AGX_TRY(dalloc(&m.src, n));
@@ -2758,16 +2769,16 @@ agx_status mr_slabs(agx_engine* e, uint64_t want) {
     e->d_srows = nullptr;
     bool fits = code == 0 && e->heap_rows + std::max<uint64_t>(rr, e->rx_rows) < kHandleMask &&
                 2 * rr * e->pw * 4 <= budget;
-    if (fits && dalloc(&e->d_srows, rr * e->pw) != AGX_OK) fits = false;
+    if (fits && dalloc_rows(&e->d_srows, rr * e->pw) != AGX_OK) fits = false;
     if (fits && rr > e->rx_rows) {
       hipFree(e->d_rx);
       e->d_rx = nullptr;
-      if (dalloc(&e->d_rx, rr * e->pw) == AGX_OK) {
+      if (dalloc_rows(&e->d_rx, rr * e->pw) == AGX_OK) {
         e->rx_rows = rr;
       } else {  // (the host-planned path needs rx of cap rows again)
         fits = false;
         e->rx_rows = 0;
-        if (dalloc(&e->d_rx, e->cap * e->pw) == AGX_OK)
+        if (dalloc_rows(&e->d_rx, e->cap * e->pw) == AGX_OK)
           e->rx_rows = e->cap;
         else
           code = 2;
@@ -3094,11 +3105,11 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
   hipFree(e->d_s2rows);
   e->d_heap = e->d_rx = e->d_s2rows = nullptr;
   e->pw = 0;
-  AGX_TRY(dalloc(&e->d_heap, 2 * rows * pw));
+  AGX_TRY(dalloc_rows(&e->d_heap, 2 * rows * pw));
   e->heap_rows = rows;
   if (e->R > 1) {
-    AGX_TRY(dalloc(&e->d_rx, e->cap * pw));
-    AGX_TRY(dalloc(&e->d_s2rows, e->cap_emit * pw));
+    AGX_TRY(dalloc_rows(&e->d_rx, e->cap * pw));
+    AGX_TRY(dalloc_rows(&e->d_s2rows, e->cap_emit * pw));
     e->rx_rows = e->cap;
     hipFree(e->d_srows);
     e->d_srows = nullptr;

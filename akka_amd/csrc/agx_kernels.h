@@ -1837,8 +1837,15 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     }
     __syncthreads();
     // ORSet populations (2 KB rows): wave-uniform trip count, the row copies below take the whole
-    // wave; counters (64-128 B rows): a lane per message, as before
+    // wave; counters (64-128 B rows): a lane per message, as before.  Only a mask that names ORSet
+    // sets kBigRows: V_OR / V_OR_DELTA and the full-state V_CRDT.  The catch-all masks (V_ALL_DELTA,
+    // V_ALL_WIDE: KM_ALL holds the plain kinds, the CRDT kinds dispatch at run time) copy a lane per
+    // message at the whole pitch, so a mixed delta population, whose counter groups have no length
+    // word, never reads one (tests/test_gpu_delta_mixed.py)
     constexpr bool kBigRows = kWide && (KM & kb(AGX_KIND_ORSET)) != 0;
+    static_assert(!kBigRows || !(KM & kDeltaKM) || (KM & ~kDeltaKM) == kb(AGX_KIND_ORSET),
+                  "a delta variant that copies rows by their used length holds ORSet groups only: counter groups "
+                  "write no length word (dl_group_row)");
     const uint32_t qstart = kBigRows ? (uint32_t)tid - lane_id() : (uint32_t)tid;
     for (uint32_t qb = qstart; qb < cnt; qb += kBThreads) {  // queued messages, in actor order
       const uint32_t q = kBigRows ? qb + lane_id() : qb;
@@ -1888,7 +1895,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
               uint4* d = reinterpret_cast<uint4*>(H.wrow(hi));
               const uint32_t q4 = H.pw / 4;
               uint32_t n4 = q4;
-              if (pi & AGX_DELTA_ROW_BIT) {  // a DeltaPropagation: its used length (dl_group_row), not the pitch
+              // a DeltaPropagation: its used length (dl_group_row), not the pitch.  Delta rows reach a
+              // kBigRows variant only in V_OR_DELTA, where every one is an ORSet group (length written)
+              if (pi & AGX_DELTA_ROW_BIT) {
                 const uint32_t used = reinterpret_cast<const uint32_t*>(s)[H.pw - 1];
                 n4 = min(q4, (used + 3u) / 4u);
                 if (lane == 0 && n4 < q4) d[q4 - 1] = s[q4 - 1];  // (the length word travels too)

@@ -269,6 +269,54 @@ def crdt_delta(n: int = 1_000_000, kind: int = Kind.ORSET, rounds: int = 32, wri
                     bucket_actors=bucket_actors)
 
 
+def crdt_delta_mixed(counts=(320, 320, 320), rounds: int = 8, throughput: int = 1, capacity: int = 0,
+                     max_delta_size: int = 2, ops_per_replica: int = 3, gossip_rounds: int = 0, plain: int = 0,
+                     big: bool = True, bucket_actors: int = 512, seed: int = SEED) -> Workload:
+    """Delta-CRDT replication with all three data types in one engine: consecutive ranges of GCounter,
+    ORSet and PNCounter replicas (`counts`), keys of 8 replicas by id as in crdt_delta -- so a key may
+    straddle two ranges, and a group that reaches a replica of another type is Behaviors.unhandled --
+    and `plain` COUNTER actors after them.  Every replica applies `ops_per_replica` host updates of
+    its own type, then runs `rounds` writer DeltaPropagationTicks and, if `gossip_rounds`, that many
+    full-state GossipTicks.  Counter rows and ORSet rows share one row heap at the ORSet pitch; with a
+    low `throughput` the DeltaPropagations of every type wait in the mailboxes.
+    `big`: the counters start at 2^40 | id in the replica's own increment slot (PNCounter: also
+    3 * 2^41 | id in its own decrement slot), so both u32 halves of every delta value matter."""
+    kinds = (Kind.GCOUNTER, Kind.ORSET, Kind.PNCOUNTER)
+    W = CRDT_DELTA_WORDS[Kind.ORSET]
+    n_crdt = int(sum(counts))
+    n = n_crdt + plain
+    ranges, dsts, pays = [], [], []
+    first = 0
+    for kd, count in zip(kinds, counts):
+        ids = np.arange(first, first + count, dtype=np.uint32)
+        init = None
+        if big and kd != Kind.ORSET:
+            init = np.zeros((count, W), np.uint64)
+            rows = np.arange(count)
+            init[rows, ids % CRDT_NODES] = (np.uint64(1) << np.uint64(40)) | ids.astype(np.uint64)
+            if kd == Kind.PNCOUNTER:
+                init[rows, CRDT_NODES + ids % CRDT_NODES] = (np.uint64(3) << np.uint64(41)) | ids.astype(np.uint64)
+        ranges.append((first, count, kd, init))
+        if ops_per_replica:
+            dsts.append(np.repeat(ids, ops_per_replica))
+            pays.append(crdt_ops(count, kd, ops_per_replica, seed + first).reshape(-1))
+        first += count
+    if plain:
+        ranges.append((n_crdt, plain, Kind.COUNTER, None))
+    ids = np.arange(n_crdt, dtype=np.uint32)
+    if rounds:
+        dsts.append(ids)
+        pays.append(np.full(n_crdt, Op.make(Op.DELTA_TICK, (rounds - 1) | DELTA_WRITE), np.uint32))
+    if gossip_rounds:
+        dsts.append(ids)
+        pays.append(np.full(n_crdt, Op.make(Op.GOSSIP, gossip_rounds - 1), np.uint32))
+    dst = np.concatenate(dsts)
+    pay = np.concatenate(pays)
+    src = np.full(dst.size, NO_SENDER, np.uint32)
+    return Workload("crdt_delta_mixed", n, W, 4, throughput, capacity, ranges, gossip=(1, seed),
+                    delta_crdt=max_delta_size, tells=(dst, src, pay), bucket_actors=bucket_actors)
+
+
 def crdt_mixed(n: int = 4096, rounds: int = 4, seed: int = 3, throughput: int = 3, capacity: int = 0) -> Workload:
     """GCounter / PNCounter / ORSet replicas beside COUNTER and EVEN actors: gossips that
     land on a non-CRDT actor (or an ORSet op on a counter) are Behaviors.unhandled."""

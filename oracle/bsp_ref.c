@@ -178,6 +178,9 @@ typedef struct bsp_sim {
    * between two takes are kept, later ones are dropped and counted; the next take reports the drop
    * once (AGX_ECAPACITY) and clears it -- the run itself goes on */
   uint64_t outbox_since, outbox_lost;
+  /* census of queued DeltaPropagations (bsp_delta_backlog_census): per data type (payload >> 30:
+   * GCounter, PNCounter, ORSet), the envelope-supersteps that delta rows spent waiting in a backlog */
+  uint64_t delta_queued[4];
 } bsp_sim;
 
 bsp_sim* bsp_create(uint64_t n_actors, uint32_t throughput, uint32_t capacity, uint32_t n_words,
@@ -697,6 +700,12 @@ static int bsp_step(bsp_sim* s) {
   s->seg = seg;
   s->nseg = 2 * nt;
   s->nbl = nt;
+  /* census: the DeltaPropagations that this superstep left queued (the backlog runs) */
+  for (uint32_t t = 0; t < nt; ++t)
+    for (uint64_t i = 0; i < seg[t].n; ++i) {
+      const env_t* m = &seg[t].v[i];
+      if (ref_is_wide(m->src) && (m->payload & AGX_DELTA_ROW_BIT)) s->delta_queued[m->payload >> 30]++;
+    }
   free(parts);
   s->st.supersteps++;
   return 1;
@@ -708,6 +717,12 @@ int bsp_run(bsp_sim* s, uint32_t max_steps, agx_stats* out) {
   s->st.in_flight = bsp_in_flight(s);
   if (out) *out = s->st;
   return s->P.error ? AGX_ECAPACITY : 0;
+}
+
+/* out[k]: envelope-supersteps that DeltaPropagations of data type k (0 GCounter, 1 PNCounter, 2 ORSet)
+ * spent queued behind a throughput cap, summed over the supersteps since bsp_create */
+void bsp_delta_backlog_census(const bsp_sim* s, uint64_t* out) {
+  for (int k = 0; k < 3; ++k) out[k] = s->delta_queued[k];
 }
 
 void bsp_read_state(bsp_sim* s, uint64_t first, uint64_t count, uint64_t* words, uint8_t* alive) {

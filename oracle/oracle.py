@@ -90,6 +90,7 @@ def _load_bsp():
             "bsp_stage": (ctypes.c_int, [vp, P32, P32, P32, u64]),
             "bsp_run": (ctypes.c_int, [vp, u32, ctypes.POINTER(Stats)]),
             "bsp_read_state": (None, [vp, u64, u64, P64, P8]),
+            "bsp_delta_backlog_census": (None, [vp, P64]),
             "bsp_java_hash_decimal": (ctypes.c_int32, [u32]),
             "bsp_shard_id": (ctypes.c_int32, [u32, u32]),
             "bsp_owner": (u32, [u32, u32, u32]),
@@ -248,6 +249,14 @@ class BspOracle(_Base):
         a = np.zeros(count, np.uint8)
         self.lib.bsp_read_state(self.h, first, count, _p(w, ctypes.c_uint64), _p(a, ctypes.c_uint8))
         return w, a
+
+    def delta_backlog_census(self):
+        """(gcounter, pncounter, orset): the envelope-supersteps that DeltaPropagations of each data
+        type spent queued behind a throughput cap, over every superstep run so far -- a test's proof
+        that its reference run kept delta rows waiting in mailboxes."""
+        c = np.zeros(3, np.uint64)
+        self.lib.bsp_delta_backlog_census(self.h, _p(c, ctypes.c_uint64))
+        return tuple(int(x) for x in c)
 
 
 class FjpOracle(_Base):
