@@ -96,6 +96,9 @@ SIGNATURES = {
                                                    ctypes.c_uint32]),
     "agx_receive_timeout_info": (ctypes.c_int32, [ctypes.c_void_p, c_u64p, c_u64p, c_u64p, c_u64p]),
     "agx_read_receive_timeout": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_u32p, c_u32p, c_u32p]),
+    "agx_set_ask": (ctypes.c_int32, [ctypes.c_void_p]),
+    "agx_ask_info": (ctypes.c_int32, [ctypes.c_void_p, c_u64p, c_u64p, c_u64p, c_u64p]),
+    "agx_read_asks": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, c_u32p, c_u32p]),
     "agx_set_death_watch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32]),
     "agx_start_watch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_u32p, ctypes.c_int64,
                                          ctypes.c_int32, ctypes.c_uint32]),

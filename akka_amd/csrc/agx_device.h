@@ -287,6 +287,59 @@ __device__ __forceinline__ bool rt_transparent(const uint32_t (&m)[8], uint32_t 
   return (x >> (tag & 31u)) & 1u;
 }
 
+// ---- ask (agx_set_ask; TY/internal/ActorContextImpl.scala:203-218, TY/scaladsl/AskPattern.scala:
+// 109-162), on top of the timers: an outstanding ask is a single timer slot with one more fact about it, the
+// timeout is the slot's TimerMsg.  The timer storage of such an engine is longer: after agen[np] comes
+//     ask[key][np]  kAskIs (the slot's timer is an ask's timeout) | kAskHasTag | the adapt tag
+// read only while the slot is active; every start of a plain timer on the slot clears it.
+// Header words [8..15]: four u64 counters, asked, answered, timed out, late.
+constexpr uint32_t kAskCtr = 8;
+constexpr uint32_t kAskIs = 0x80000000u, kAskHasTag = 0x100u;
+enum : uint32_t { kAcAsked, kAcAnswered, kAcTimedOut, kAcLate, kAcN };
+struct AskDev {
+  uint32_t* row;  // [key * np + l]
+  unsigned long long* ctrs;
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const { return ctrs + i; }
+};
+__device__ __forceinline__ AskDev ask_dev(const TimerDev& TD) {
+  AskDev d;
+  d.row = TD.agen + TD.np;
+  d.ctrs = reinterpret_cast<unsigned long long*>(TD.base + kAskCtr);
+  return d;
+}
+// the ask ref: what the target sees as the sender of a request, and what a reply carries back
+__device__ __forceinline__ uint32_t ask_ref(uint32_t key, uint32_t gen, uint32_t id) {
+  return AGX_ASK_REF_BIT | (key << AGX_ASK_REF_KEY_SHIFT) | ((gen & AGX_ASK_REF_GEN_MASK) << AGX_ASK_REF_GEN_SHIFT) | id;
+}
+__device__ __forceinline__ bool is_ask_ref(uint32_t x) { return (x & AGX_ASK_REF_BIT) && x != AGX_NO_SENDER; }
+// what a thread's drains counted, in registers: added to the storage once per wave (ask_commit, agx_kernels.h)
+struct AskCount {
+  uint32_t c[kAcN];
+};
+// the ask of the case that runs: ARM leaves the ref its SEND puts into the envelope's sender field
+struct AskRegs {
+  AskDev AD;
+  uint32_t ref;
+  AskCount* cnt;
+};
+// The tells of an engine with ask go through this: a tell to an ask ref is the reply -- to the ref's id, with the ref
+// in the sender field (the replier's own id is not carried) -- whichever kind emits it; send() is the one envelope of
+// an ask, with the ref instead of the asker's id.  The emitter's `self` is swapped for that one call.
+template <typename Emit>
+struct AskEmit {
+  Emit& em;
+  __device__ __forceinline__ void send(uint32_t ref, uint32_t dst, uint32_t p) {
+    const uint32_t s = em.self;
+    em.self = ref;
+    em(dst, p);
+    em.self = s;
+  }
+  __device__ __forceinline__ void operator()(uint32_t dst, uint32_t p) {
+    if (is_ask_ref(dst)) send(dst, dst & AGX_ASK_REF_ID_MASK, p);
+    else em(dst, p);
+  }
+};
+
 // ---- death watch (agx_set_death_watch; AA/dungeon/DeathWatch.scala:19-113,147-162)
 // One superstep is one tick.  DevParams.watch, u32 units:
 //   [0]        n_slots: watch slots per actor (1..4)
@@ -678,6 +731,8 @@ constexpr uint32_t kChildKM = 1u << 26;
 constexpr uint32_t kIdleKM = 1u << 25;
 // KM flag (not a kind): the variant knows the receptionist (agx_set_receptionist).  A flag of KM for the same reason.
 constexpr uint32_t kRecepKM = 1u << 24;
+// KM flag (not a kind): the variant knows the ask pattern (agx_set_ask); only ever combined with kTimersKM.
+constexpr uint32_t kAskKM = 1u << 23;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -771,10 +826,14 @@ __device__ __forceinline__ uint64_t tm_operand(const TimerDev& TD, uint32_t l, u
 }
 // (kIdle: the receive-timeout instantiations, DESIGN.md §2.7 -- AGX_A_SET_RECEIVE_TIMEOUT / _CANCEL_ act on the
 // actor's timeout in the caller's registers, `rt`; every other instantiation compiles as before)
-template <bool kIdle = false, typename Emit>
+// (kAsk: the ask instantiations, DESIGN.md §2.9 -- AGX_A_ASK_ARM starts the key as a single timer marked as an ask
+// and leaves the ask ref in `ar`, AGX_A_ASK_SEND emits the case's one envelope with that ref as its sender; a plain
+// timer start clears the mark.  `emit` is then an AskEmit)
+template <bool kIdle = false, bool kAsk = false, typename Emit>
 __device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const TimerDev& TD, uint32_t l, uint32_t bkt,
                                                       uint32_t now, uint32_t& kind, uint32_t self, uint64_t* w,
-                                                      uint32_t src, uint32_t pay, Emit& emit, RtRegs* rt = nullptr) {
+                                                      uint32_t src, uint32_t pay, Emit& emit, RtRegs* rt = nullptr,
+                                                      AskRegs* ar = nullptr) {
   const uint32_t b = kind - AGX_KIND_COMPILED;
   if (b >= P.n_beh) return AGX_RES_UNHANDLED;
   const uint32_t c1 = P.bfirst[b + 1];
@@ -811,6 +870,7 @@ __device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const 
             TD.cancel(A.word, l, bkt);
             TD.start(A.word, l, bkt, now, tm_delay(tm_operand(TD, l, A.dsrc, A.dword, A.dk, pay, w, src, self)),
                      A.op == AGX_A_TIMER_PERIODIC, A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v);
+            if constexpr (kAsk) ar->AD.row[TD.at(A.word, l)] = 0u;  // (no ask's timeout any more)
           }
           break;
         case AGX_A_TIMER_CANCEL:
@@ -828,6 +888,27 @@ __device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const 
             } else if (A.op == AGX_A_CANCEL_RECEIVE_TIMEOUT) {
               rt->flags |= kRtChanged | (rt->delay ? kRtWasOff : 0u);
               rt->delay = 0u;
+            }
+          }
+          if constexpr (kAsk) {
+            const uint32_t msg = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;
+            if (A.op == AGX_A_ASK_ARM) {
+              if (A.word < TD.nk) {  // (a key past n_keys is refused at agx_run)
+                TD.cancel(A.word, l, bkt);
+                TD.start(A.word, l, bkt, now, tm_delay(tm_operand(TD, l, A.dsrc, A.dword, A.dk, pay, w, src, self)), false, msg);
+                ar->AD.row[TD.at(A.word, l)] = kAskIs | ((A.pad0 & 1u) ? kAskHasTag | (uint32_t)A.pad1 : 0u);
+                ar->ref = ask_ref(A.word, TD.agen[l], self);  // (start stored the slot's generation there)
+                ++ar->cnt->c[kAcAsked];
+              }
+            } else if (A.op == AGX_A_ASK_SEND) {  // (directly after its ARM: agx_run refuses other tables)
+              uint64_t d;
+              if (A.dsrc == AGX_V_SELF) {  // (self + dk) mod n, as a TELL's
+                int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+                d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+              } else {
+                d = tm_operand(TD, l, A.dsrc, A.dword, A.dk, pay, w, src, self);
+              }
+              emit.send(ar->ref, d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d, msg);
             }
           }
           break;

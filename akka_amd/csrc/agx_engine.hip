@@ -162,6 +162,11 @@ struct agx_engine {
     uint32_t delay, payload;
   };
   std::vector<RtStart> rt_starts;  // agx_start_receive_timeout calls not yet applied on the device (prepare_run)
+  // the ask pattern (agx_set_ask), on top of the timers: one [key][actor] row appended to the timer storage.  Such an
+  // engine launches the kTimers | kAsk instantiation
+  bool ask_on = false;
+  uint32_t beh_ask_keys = 0;      // the compiled tables hold ask actions on keys below this (0: none)
+  int64_t beh_ask_unpaired = -1;  // the first AGX_A_ASK_SEND not directly preceded by the ARM of its key, or ARM without its SEND
   // death watch (agx_set_death_watch): n_slots watch slots per actor.  Such an engine launches the watch
   // instantiation of the compiled catch-all variant and no wave / ring / dense / persistent launch
   uint32_t wd_slots = 0;
@@ -445,7 +450,7 @@ namespace {
 // of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
 // the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
 // apply_variant, launch_apply and make_params.
-enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_N, F_NONE = F_N };
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_ASK, F_N, F_NONE = F_N };
 
 struct FeatureRow {
   bool (*on)(const agx_engine*);
@@ -495,6 +500,9 @@ const FeatureRow kFeatures[F_N] = {
      "the receptionist needs", "the receptionist (agx_set_receptionist)", "the receptionist (agx_set_receptionist)", "",
      AGX_ONCE "a route must take effect once", "which know no receptionist: set the receptionist", "the receptionist",
      kRecepKM, false, F_NONE},
+    // the ask pattern (agx_set_ask) comes on top of the timers as receive timeouts do; the two exclude one another
+    {[](const agx_engine* e) { return e->ask_on; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+     kTimersKM | kAskKM, false, F_TIMERS},
 };
 #undef AGX_ONCE
 
@@ -1496,14 +1504,30 @@ static __global__ void __launch_bounds__(kThreads) k_rt_sync(uint32_t* tm, const
   }
 }
 
+// ---- the ask pattern (agx_set_ask): the row after the timers' (agx_device.h AskDev)
+// after agx_start_timers on an engine with ask: the started slots hold plain timers, no ask's timeout
+static __global__ void __launch_bounds__(kThreads) k_ask_clear(uint32_t* tm, const uint8_t* alive, uint32_t nb, uint32_t bb,
+                                                              uint32_t first, uint32_t count, uint32_t key) {
+  const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t l = first + i, np = nb << bb;
+  if (!(alive[l] & 1u)) return;  // (k_timer_start left a stopped actor's slot alone)
+  uint32_t* const row = tm + tm_slot_off(nb) + (4ull * tm[0] + 1ull) * np;
+  row[(size_t)key * np + l] = 0u;
+}
+
 size_t timers_words(const agx_engine* e) {
   const uint64_t npad = (uint64_t)e->nb << e->bb;
-  return tm_slot_off(e->nb) + (4ull * e->tm_keys + 1ull) * npad + (e->rt_on ? 3ull * npad + 8ull : 0ull);
+  return tm_slot_off(e->nb) + (4ull * e->tm_keys + 1ull) * npad + (e->rt_on ? 3ull * npad + 8ull : 0ull) +
+         (e->ask_on ? (uint64_t)e->tm_keys * npad : 0ull);
 }
 // the receive-timeout rows of the timer storage: rt_next, then rt_delay, rt_pay and the mask (agx_device.h IdleDev)
 size_t rt_row_off(const agx_engine* e) {
   return tm_slot_off(e->nb) + (4ull * e->tm_keys + 1ull) * ((uint64_t)e->nb << e->bb);
 }
+
+// the ask row of the timer storage, [key][actor] (agx_device.h AskDev; an engine has receive timeouts or ask, not both)
+size_t ask_row_off(const agx_engine* e) { return rt_row_off(e); }
 
 // The timer storage (agx_device.h TimerDev) -- allocated once, sized by n_local: counters, clocks and due counts
 // zero, every bucket's earliest fire and every slot's next fire "none", the slots inactive.
@@ -1550,6 +1574,9 @@ agx_status flush_timer_starts(agx_engine* e) {
       hipLaunchKernelGGL(k_timer_start, dim3((uint32_t)((ts.count + kThreads - 1) / kThreads)), dim3(kThreads), 0, e->stream,
                          e->d_timers, e->d_alive, e->nb, e->bb, (uint32_t)ts.first, (uint32_t)ts.count, ts.key, ts.periodic,
                          ts.delay, d_del, ts.payload);
+    if (ts.count && e->ask_on)
+      hipLaunchKernelGGL(k_ask_clear, dim3((uint32_t)((ts.count + kThreads - 1) / kThreads)), dim3(kThreads), 0, e->stream,
+                         e->d_timers, e->d_alive, e->nb, e->bb, (uint32_t)ts.first, (uint32_t)ts.count, ts.key);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (d_del) hipFree(d_del);
@@ -1943,6 +1970,14 @@ agx_status prepare_run(agx_engine* e) {
   if (e->rt_on && e->beh_rt_tag)
     return set_err(AGX_EINVAL, "the compiled behaviours name message tag 0xFB, reserved for receive-timeout envelopes on an "
                    "engine with receive timeouts");
+  if (e->beh_ask_keys && !e->ask_on)  // (only the ask variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours ask, but the engine has no ask pattern (agx_set_ask)");
+  if (e->beh_ask_unpaired >= 0)
+    return set_err(AGX_EINVAL, "the compiled behaviours' action %lld is half an ask: AGX_A_ASK_SEND comes directly after the "
+                   "AGX_A_ASK_ARM of the same key", (long long)e->beh_ask_unpaired);
+  if (e->beh_ask_keys > e->tm_keys)
+    return set_err(AGX_EINVAL, "the compiled behaviours ask on timer key %u, but the engine has %u slots per actor "
+                   "(agx_set_timers)", e->beh_ask_keys - 1u, e->tm_keys);
   if (e->tm_bad_start)
     return set_err(AGX_EINVAL, "agx_start_timers was called on an engine without timers (agx_set_timers)");
   if (e->beh_tm_keys > e->tm_keys)  // (only the timer variant interprets those: loud, never wrong)
@@ -3727,6 +3762,8 @@ agx_status agx_set_timers(agx_engine* e, uint32_t n_keys) {
   AGX_TRY(refuse_feature(e, F_TIMERS));
   if (e->rt_on && n_keys != e->tm_keys)
     return set_err(AGX_EINVAL, "timers: the key count cannot change once receive timeouts are set (agx_set_receive_timeout)");
+  if (e->ask_on && n_keys != e->tm_keys)
+    return set_err(AGX_EINVAL, "timers: the key count cannot change once the ask pattern is set (agx_set_ask)");
   AGX_TRY(ensure_dev(e));
   if (e->d_timers && n_keys != e->tm_keys) {
     hipFree(e->d_timers);
@@ -3829,6 +3866,9 @@ agx_status agx_set_receive_timeout(agx_engine* e, const uint32_t transparent_tag
   if (!e->tm_keys) return set_err(AGX_EINVAL, "receive timeouts need an engine with timers (agx_set_timers first)");
   if (e->started) return set_err(AGX_ESTATE, "set receive timeouts before the first agx_run");
   if (e->rt_on) return set_err(AGX_EINVAL, "receive timeouts are set already (agx_set_receive_timeout is called once)");
+  if (e->ask_on)
+    return set_err(AGX_EINVAL, "receive timeouts need an engine without the ask pattern (agx_set_ask): the two are features of "
+                   "their own on top of the timers");
   if (e->beh_rt_tag)
     return set_err(AGX_EINVAL, "receive timeouts: the compiled behaviours name message tag 0xFB, reserved for receive-timeout "
                    "envelopes");
@@ -3914,6 +3954,72 @@ agx_status agx_read_receive_timeout(agx_engine* e, uint64_t first_id, uint64_t c
   if (payload) AGX_TRY(copy_sync(e, payload, e->d_timers + rt_row_off(e) + 2ull * npad + first_id, count * 4ull, hipMemcpyDeviceToHost));
   if (remaining)
     for (uint64_t i = 0; i < count; ++i) remaining[i] = nx[i] == kTmNone ? 0xFFFFFFFFu : nx[i] - clk;
+  return AGX_OK;
+}
+
+// TY/internal/ActorContextImpl.scala:203-218, TY/scaladsl/AskPattern.scala:109-162
+agx_status agx_set_ask(agx_engine* e) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->tm_keys) return set_err(AGX_EINVAL, "the ask pattern needs an engine with timers (agx_set_timers first)");
+  if (e->started) return set_err(AGX_ESTATE, "set the ask pattern before the first agx_run");
+  if (e->ask_on) return set_err(AGX_EINVAL, "the ask pattern is set already (agx_set_ask is called once)");
+  if (e->rt_on)
+    return set_err(AGX_EINVAL, "the ask pattern needs an engine without receive timeouts (agx_set_receive_timeout): the two are "
+                   "features of their own on top of the timers");
+  if (e->n_global > AGX_ASK_MAX_ACTORS)
+    return set_err(AGX_EINVAL, "the ask pattern needs an engine of at most %u actors (it has %llu): an ask ref carries the "
+                   "asker's id in 22 bits", AGX_ASK_MAX_ACTORS, (unsigned long long)e->n_global);
+  AGX_TRY(ensure_dev(e));
+  // the storage grows by the ask row: allocated anew (no timer has run; recorded starts are kept)
+  hipFree(e->d_timers);
+  e->d_timers = nullptr;
+  e->ask_on = true;
+  const agx_status r = alloc_timers(e);  // (now: AGX_ENOMEM is this call's)
+  if (r != AGX_OK) {
+    e->ask_on = false;
+    (void)alloc_timers(e);
+    return r;
+  }
+  drop_graphs(e);  // the variant and the timer storage are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_ask_info(agx_engine* e, uint64_t* asked, uint64_t* answered, uint64_t* timed_out, uint64_t* late) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[kAcN] = {0, 0, 0, 0};
+  if (e->ask_on && e->d_timers) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(copy_sync(e, c, e->d_timers + kAskCtr, sizeof(c), hipMemcpyDeviceToHost));
+  }
+  if (asked) *asked = c[kAcAsked];
+  if (answered) *answered = c[kAcAnswered];
+  if (timed_out) *timed_out = c[kAcTimedOut];
+  if (late) *late = c[kAcLate];
+  return AGX_OK;
+}
+
+agx_status agx_read_asks(agx_engine* e, uint64_t actor_id, uint32_t is_ask[4], uint32_t adapt[4]) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (actor_id >= e->n_global) return set_err(AGX_EINVAL, "bad actor id");
+  for (uint32_t k = 0; k < AGX_MAX_TIMER_KEYS; ++k) {
+    if (is_ask) is_ask[k] = 0;
+    if (adapt) adapt[k] = 0xFFFFFFFFu;
+  }
+  if (!e->ask_on || !e->d_timers) return AGX_OK;
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_timer_starts(e));  // (starts recorded since the last run: applied now, nothing else is uploaded)
+  const uint64_t npad = (uint64_t)e->nb << e->bb, l = actor_id;  // (single rank: local = global)
+  uint32_t per[AGX_MAX_TIMER_KEYS], row[AGX_MAX_TIMER_KEYS];  // the actor's column of per[key][actor] and ask[key][actor]
+  HIP_TRY(hipMemcpy2DAsync(per, 4, e->d_timers + tm_slot_off(e->nb) + (uint64_t)e->tm_keys * npad + l, npad * 4ull, 4, e->tm_keys,
+                           hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpy2DAsync(row, 4, e->d_timers + ask_row_off(e) + l, npad * 4ull, 4, e->tm_keys, hipMemcpyDeviceToHost,
+                           e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t k = 0; k < e->tm_keys; ++k) {
+    const bool on = (per[k] & kTmActive) && (row[k] & kAskIs);
+    if (is_ask) is_ask[k] = on ? 1u : 0u;
+    if (adapt) adapt[k] = on && (row[k] & kAskHasTag) ? row[k] & 0xFFu : 0xFFFFFFFFu;
+  }
   return AGX_OK;
 }
 
@@ -4425,23 +4531,29 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   }
   for (uint32_t i = 0; i < n_acts; ++i) {
     const agx_act& A = acts[i];
-    const bool tmop = A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL;  // (`word` is the key)
+    const bool askop = A.op == AGX_A_ASK_ARM || A.op == AGX_A_ASK_SEND;  // (`word` is the key)
+    const bool tmop = (A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL) || askop;  // (`word` is the key)
     const bool wdop = A.op >= AGX_A_WATCH && A.op <= AGX_A_UNWATCH;  // (the ref is the d-operand)
     const bool rcop = A.op >= AGX_A_REGISTER && A.op <= AGX_A_ROUTE;  // (`pad1` is the service key)
     if (rcop && (A.pad1 >= AGX_MAX_SERVICE_KEYS || A.pad0 > (A.op == AGX_A_ROUTE ? (AGX_ROUTE_KEEP_SENDER | AGX_ROUTE_BY_INDEX) : 0u) ||
                  (A.op == AGX_A_ROUTE && (A.pad0 & AGX_ROUTE_BY_INDEX) && !opnd_ok(A.dsrc, A.dword))))
       return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (service keys 0..7, route flags 0..3)", i);
-    if (A.op < AGX_A_SET || A.op > AGX_A_ROUTE || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+    if (A.op < AGX_A_SET || A.op > AGX_A_ASK_SEND || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
         !opnd_ok(A.src, A.sword) ||
         ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop || A.op == AGX_A_STOP_CHILD ||
-          A.op == AGX_A_SET_RECEIVE_TIMEOUT) &&
+          A.op == AGX_A_SET_RECEIVE_TIMEOUT || askop) &&
          !opnd_ok(A.dsrc, A.dword)) ||
+        (A.op == AGX_A_ASK_ARM && A.pad0 > 1u) ||
         (A.op == AGX_A_SPAWN && A.dword >= AGX_MAX_SPAWN_SITES))
       return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (state words 0..1, timer keys 0..3, spawn sites 0..63)", i);
   }
   for (uint32_t i = 0; i < n_acts; ++i)
     if (acts[i].op == AGX_A_SET_RECEIVE_TIMEOUT && acts[i].dsrc == AGX_V_CONST && acts[i].dk < 1)
       return set_err(AGX_EINVAL, "compiled behaviours: action %u sets a receive timeout of %lld ticks (a constant delay is at "
+                     "least 1)", i, (long long)acts[i].dk);
+  for (uint32_t i = 0; i < n_acts; ++i)
+    if (acts[i].op == AGX_A_ASK_ARM && acts[i].dsrc == AGX_V_CONST && acts[i].dk < 1)
+      return set_err(AGX_EINVAL, "compiled behaviours: action %u asks with a timeout of %lld ticks (a constant timeout is at "
                      "least 1)", i, (long long)acts[i].dk);
   // receive timeouts: tag 0xFB named by a tag test or a message tag (refused on an engine with receive timeouts)
   bool rt_tag = false;
@@ -4527,7 +4639,7 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   for (uint32_t c = 0; c < n_cases; ++c) {
     uint32_t tells = 0;
     for (uint32_t i = cases[c].act_first; i < (uint32_t)cases[c].act_first + cases[c].act_count; ++i)
-      tells += acts[i].op == AGX_A_TELL;
+      tells += acts[i].op == AGX_A_TELL || acts[i].op == AGX_A_ASK_SEND;  // (an ask's request takes the tell slot)
     if (tells > e->kmax)
       return set_err(AGX_EINVAL, "compiled behaviours: case %u tells %u times per message, max_emit is %u", c, tells,
                      e->kmax);
@@ -4571,6 +4683,20 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     }
     e->beh_sv_tells = std::max(e->beh_sv_tells, fs + sg);
   }
+  e->beh_ask_keys = 0;  // (checked against agx_set_ask and the key count at agx_run)
+  e->beh_ask_unpaired = -1;
+  for (uint32_t c = 0; c < n_cases; ++c)
+    for (uint32_t i = cases[c].act_first; i < (uint32_t)cases[c].act_first + cases[c].act_count; ++i) {
+      const agx_act& A = acts[i];
+      if (A.op != AGX_A_ASK_ARM && A.op != AGX_A_ASK_SEND) continue;
+      e->beh_ask_keys = std::max<uint32_t>(e->beh_ask_keys, A.word + 1u);
+      // (within the case: ARM then the SEND of its key)
+      const bool paired = A.op == AGX_A_ASK_ARM
+                              ? i + 1u < (uint32_t)cases[c].act_first + cases[c].act_count && acts[i + 1].op == AGX_A_ASK_SEND &&
+                                    acts[i + 1].word == A.word
+                              : i > cases[c].act_first && acts[i - 1].op == AGX_A_ASK_ARM && acts[i - 1].word == A.word;
+      if (!paired && e->beh_ask_unpaired < 0) e->beh_ask_unpaired = (int64_t)i;
+    }
   e->beh_rt = false;  // (checked against agx_set_receive_timeout at agx_run)
   for (uint32_t i = 0; i < n_acts; ++i)
     e->beh_rt |= acts[i].op == AGX_A_SET_RECEIVE_TIMEOUT || acts[i].op == AGX_A_CANCEL_RECEIVE_TIMEOUT;
@@ -4597,6 +4723,7 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     tm_use(acts[i].dsrc, acts[i].dword);
     if (acts[i].op == AGX_A_TIMER_CANCEL_ALL) e->beh_tm_keys = std::max(e->beh_tm_keys, 1u);
     else if (acts[i].op >= AGX_A_TIMER_SINGLE && acts[i].op <= AGX_A_TIMER_CANCEL) e->beh_tm_keys = std::max<uint32_t>(e->beh_tm_keys, acts[i].word + 1u);
+    // (an ask's key is checked apart: beh_ask_keys)
   }
   drop_graphs(e);  // the tables are kernel parameters captured in the superstep graphs
   return AGX_OK;

@@ -1641,6 +1641,18 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
   for (int d = kWave / 2; d > 0; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d, kWave);
   return v;
 }
+// the ask counters of a wave's drains: one atomic per counter per wave that has something to add
+__device__ __forceinline__ void ask_commit(const AskDev& AD, const AskCount& ac) {
+  if (!__ballot((ac.c[kAcAsked] | ac.c[kAcAnswered] | ac.c[kAcTimedOut] | ac.c[kAcLate]) != 0u)) return;  // (wave-uniform)
+  uint32_t t[kAcN];
+#pragma unroll
+  for (uint32_t i = 0; i < kAcN; ++i) t[i] = wave_incl_sum(ac.c[i]);
+  if (lane_id() == kWave - 1) {
+#pragma unroll
+    for (uint32_t i = 0; i < kAcN; ++i)
+      if (t[i]) atomicAdd(AD.ctr(i), (unsigned long long)t[i]);
+  }
+}
 __device__ __forceinline__ void recep_commit(const RecepDev& RD, const RecepCount& rc, uint32_t* changed) {
   if (!__ballot((rc.chg | rc.routed | rc.none | rc.reg | rc.dereg | rc.term) != 0u)) return;  // (wave-uniform)
   const uint32_t chg = wave_or_u32(rc.chg);
@@ -1721,6 +1733,14 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
 #pragma unroll
     for (int i = 0; i < 8; ++i) rtmask[i] = ID.mask[i];
   }
+  // kAsk: the ask pattern (agx_set_ask), on top of the timers.  An outstanding ask is a single
+  // timer slot marked in the ask row; the drain intercepts replies (the sender field is an ask ref that names this
+  // actor) before the behaviour, and every tell goes through AskEmit.  Counted in registers, added once per wave.
+  constexpr bool kAsk = (KM & kAskKM) != 0;
+  static_assert(!kAsk || (kTm && !kIdle), "ask: on the timer instantiations only, not with receive timeouts");
+  AskDev AD{};
+  AskCount acn{};
+  if constexpr (kAsk) AD = ask_dev(TD);
   // kWd: death watch (agx_set_death_watch).  The tick's Terminated envelopes are the inbox's
   // last items (k_bucket_apply put them there); the drain intercepts them, compiled cases run the watch
   // actions against the slots, and the end of the tick turns answerable watching slots due.
@@ -2383,6 +2403,59 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         else if (touched && rn != kTmNone) rtmin = min(rtmin, rn);
         if (ndisc) atomicAdd(TD.ctr(1), (unsigned long long)ndisc);
         if (nrdisc) atomicAdd(ID.ctr(1), (unsigned long long)nrdisc);
+      } else if constexpr (kAsk) {
+        // the timer drain below with the reply intercept (AskPattern.scala:109-162: the PromiseActorRef and its
+        // timeout task).  A reply -- its sender field is an ask ref naming this actor -- takes a drain slot and
+        // counts as delivered; accepted (the key's slot is active, an ask's, of the ref's generation mod 2^7) it
+        // makes the slot inactive as a cancel does and the behaviour runs on the adapted payload with the actor
+        // itself as the sender; else it is late and discarded.  An accepted TimerMsg of an ask slot is the timeout.
+        AskEmit<EmitterLds> aem{em};
+        AskRegs ar{AD, self, &acn};
+        uint32_t ndisc = 0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          ++ndel;
+          if ((pv >> 24) == AGX_TAG_TIMER) {
+            const uint32_t key = (pv >> 22) & 3u;
+            const size_t i = TD.at(key < TD.nk ? key : 0u, l);
+            const uint32_t pr = key < TD.nk ? TD.per[i] : 0u;
+            if (!(pr & kTmActive) || ((TD.gen[i] ^ pv) & kTmGenMask)) {
+              ++ndisc;
+              continue;
+            }
+            if (!(pr & ~kTmActive)) {  // a single timer: inactive now (nothing of it is to come)
+              TD.per[i] = 0u;
+              acn.c[kAcTimedOut] += AD.row[i] >> 31;
+            }
+            sv = self;
+            pv = TD.pay[i];
+          } else if (is_ask_ref(sv) && (sv & AGX_ASK_REF_ID_MASK) == self) {
+            const uint32_t key = (sv >> AGX_ASK_REF_KEY_SHIFT) & 3u;
+            const size_t i = TD.at(key < TD.nk ? key : 0u, l);
+            const uint32_t pr = key < TD.nk ? TD.per[i] : 0u;
+            const uint32_t aw = AD.row[i];
+            if (!(pr & kTmActive) || !(aw & kAskIs) || ((TD.gen[i] ^ (sv >> AGX_ASK_REF_GEN_SHIFT)) & AGX_ASK_REF_GEN_MASK)) {
+              ++acn.c[kAcLate];
+              continue;
+            }
+            TD.cancel(key, l, b);
+            ++acn.c[kAcAnswered];
+            sv = self;
+            if (aw & kAskHasTag) pv = (pv & 0xFFFFFFu) | (aw << 24);
+          }
+          const uint32_t r = kcur >= AGX_KIND_COMPILED
+                                 ? compiled_apply_tm<false, true>(P, TD, l, b, tnow, kcur, self, wv, sv, pv, aem, nullptr, &ar)
+                                 : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, aem);
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            for (uint32_t k = 0; k < TD.nk; ++k) TD.cancel(k, l, b);  // cancelAll on PostStop: its asks are abandoned
+            break;
+          }
+        }
+        if (ndisc) atomicAdd(TD.ctr(1), (unsigned long long)ndisc);
       } else if constexpr (kTm) {
         // the drain with interceptTimerMsg (TimerSchedulerImpl.scala:145-172): a TimerMsg takes a drain
         // slot and counts as delivered; a stale one is discarded, else the behaviour runs on the slot's
@@ -2622,6 +2695,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       const uint32_t m = wave_min_u32(rtmin);
       if (lane_id() == 0 && m != kTmNone) atomicMin(&TD.earliest(b), m);
     }
+    if constexpr (kAsk) ask_commit(AD, acn);
     if constexpr (kRc) recep_commit(RD, rcc, L.rowtop);
     __syncthreads();
     if constexpr (kRc)  // (block-uniform; U is free: the state words were written back)

@@ -282,6 +282,24 @@ class GpuEngine:
         check(self.lib.agx_read_receive_timeout(self._h, first, count, *(_ptr(x, ctypes.c_uint32) for x in a)))
         return dict(zip(("delay", "remaining", "payload"), a))
 
+    def set_ask(self) -> None:
+        """The ask pattern for every actor (agx_set_ask): context.ask -- request-response with a timeout
+        (TY/internal/ActorContextImpl.scala:203-218, TY/scaladsl/AskPattern.scala:109-162) on top of
+        the timers -- call set_timers first.  An ask takes one of the actor's timer keys."""
+        check(self.lib.agx_set_ask(self._h))
+
+    def ask_info(self) -> dict:
+        """agx_ask_info: totals asked / answered / timed_out / late."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        check(self.lib.agx_ask_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(("asked", "answered", "timed_out", "late"), (int(x.value) for x in v)))
+
+    def read_asks(self, actor_id: int) -> dict:
+        """agx_read_asks: per timer key, is the slot active as an ask's timeout, and its adapt tag (0xFFFFFFFF: none)."""
+        a = [np.zeros(4, np.uint32) for _ in range(2)]
+        check(self.lib.agx_read_asks(self._h, actor_id, *(_ptr(x, ctypes.c_uint32) for x in a)))
+        return dict(zip(("is_ask", "adapt"), a))
+
     def set_death_watch(self, n_slots: int) -> None:
         """`n_slots` (1..4) watch slots for every actor (agx_set_death_watch): context.watch / watchWith / unwatch
         and the Terminated signal (AA/dungeon/DeathWatch.scala:19-113) in the timers' logical time.  Compiled

@@ -38,6 +38,10 @@ What lowers:
     ``ref.forward(msg)`` and ``Routers.group(key)`` (the receptionist and group routers): keys are
     numbered in order of first appearance (``Tables.service_keys`` -> engine.set_receptionist), and a case holds at
     most one of tell and route;
+  * ``context.ask(ref, msg, timeout, on_timeout=msg, on_success=MessageType | None, key=None)`` and
+    ``context.ask_pending(key)`` inside ``Behaviors.with_timers`` (the ask pattern on the timers engine, DESIGN.md
+    §2.9): an ask takes a timer key and lowers to ``A_ASK_ARM`` + ``A_ASK_SEND``; ``Tables.uses_ask`` ->
+    engine.set_ask(), after engine.set_timers(Tables.timer_keys);
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -91,6 +95,10 @@ V_LISTING_SIZE, V_SERVICE_AT = 11, 12  # engines with the receptionist; `word` =
 SVC_WORD0, SVC_WORD1, SVC_ARG, SVC_CONST = 0, 1, 2, 3  # V_SERVICE_AT's selector: what x of listing[x mod size] is
 A_REGISTER, A_DEREGISTER, A_ROUTE = 17, 18, 19     # the service key is pad1
 ROUTE_KEEP_SENDER, ROUTE_BY_INDEX = 1, 2           # pad0 of A_ROUTE (KEEP_SENDER also of A_TELL: ref.forward)
+A_ASK_ARM, A_ASK_SEND = 20, 21                     # context.ask: `word` is the timer key
+# the ask ref a target sees as the sender: ASK_REF_BIT | key << 29 | (generation mod 2^7) << 22 | the asker's id
+ASK_REF_BIT, ASK_REF_KEY_SHIFT, ASK_REF_GEN_SHIFT, ASK_REF_GEN_MASK, ASK_REF_ID_MASK = 1 << 31, 29, 22, 0x7F, (1 << 22) - 1
+ASK_MAX_ACTORS = (1 << 22) - 1
 MAX_SERVICE_KEYS = 8
 
 
@@ -193,6 +201,7 @@ class Action:
     into: bool = False    # A_SPAWN: state word `word` receives the child's id
     key: object = None    # A_REGISTER / A_DEREGISTER / A_ROUTE: the ServiceKey
     flags: int = 0        # A_ROUTE / A_TELL: ROUTE_KEEP_SENDER, ROUTE_BY_INDEX (pad0)
+    ask: object = None    # A_ASK_ARM: (the target's dst operand, the request's operand, its or_mask, adapt tag or None)
 
 
 class Field(Operand):
@@ -430,6 +439,9 @@ class TimerScheduler:
         return Operand(V_TIMER, self._key(key)) == 1
 
 
+_TIMER_SCOPES: list = []  # the TimerSchedulers of the with_timers blocks being built, innermost last (context.ask)
+
+
 class _Parent:
     """context.PARENT: a spawned child's state word 1 starts as its parent's id."""
 
@@ -537,6 +549,43 @@ class ActorContext:
     def cancel_receive_timeout(self) -> "Action":
         """context.cancelReceiveTimeout(): an envelope already enqueued stays in the mailbox and is discarded."""
         return Action(A_CANCEL_RECEIVE_TIMEOUT, 0)
+
+    # the ask pattern (engine.set_ask on top of engine.set_timers; TY/internal/ActorContextImpl.scala:203-218,
+    # TY/scaladsl/AskPattern.scala:109-162; DESIGN.md §2.9)
+    @staticmethod
+    def _scheduler() -> "TimerScheduler":
+        if not _TIMER_SCOPES:
+            raise CompileError("context.ask lives inside Behaviors.with_timers: an ask takes one of the actor's timer keys")
+        return _TIMER_SCOPES[-1]
+
+    def ask(self, ref, msg, timeout, on_timeout, on_success=None, key=None) -> "Action":
+        """context.ask(ref, createRequest)(mapResponse)(timeout): `msg` goes to `ref` with an ask ref as its sender
+        (the typed message's replyTo); whatever is told to that ref within `timeout` ticks (an operand or a constant
+        of at least 1; a round trip takes 2) comes back with the actor itself as the sender and, with `on_success` (a
+        MessageType), that type's tag over its argument; otherwise `on_timeout` arrives.  A later reply is dropped.
+        The ask takes a timer key: `key`, or one of its own per ask site; asking again on a key supersedes the
+        earlier ask.  It is the case's one envelope."""
+        ts = self._scheduler()
+        req, req_mask = (msg.arg, msg.or_mask) if isinstance(msg, Message) else (lift(msg), 0)
+        val, mask = (on_timeout.arg, on_timeout.or_mask) if isinstance(on_timeout, Message) else (lift(on_timeout), 0)
+        if on_success is not None and not isinstance(on_success, MessageType):
+            raise CompileError(f"on_success= takes a MessageType or None, not {on_success!r}")
+        d = lift(timeout)
+        if d.src == V_CONST and d.k < 1:
+            raise CompileError(f"an ask's timeout is at least 1 tick, not {d.k}")
+        if d.src == V_CONST and d.k > MAX_TIMER_DELAY:
+            raise CompileError(f"an ask's timeout is at most {MAX_TIMER_DELAY} ticks")
+        if key is None:
+            key = ("ask site", len(ts.keys), object())
+        if key not in ts.keys and len(ts.keys) >= MAX_TIMER_KEYS:
+            raise CompileError(f"an ask takes a timer key and an actor has at most {MAX_TIMER_KEYS}: this ask would be key "
+                               f"{len(ts.keys) + 1}")
+        return Action(A_ASK_ARM, ts._key(key), val, d, mask,
+                      ask=(self._ref(ref), req, req_mask, None if on_success is None else on_success.tag))
+
+    def ask_pending(self, key) -> Test:
+        """Is the ask made with key=`key` still outstanding (neither answered, timed out nor cancelled)?"""
+        return Operand(V_TIMER, self._scheduler()._key(key)) == 1
 
     # the receptionist and group routers (engine.set_receptionist(len(tables.service_keys), capacity); TY/internal/
     # receptionist/LocalReceptionist.scala:147-248, TY/internal/routing/GroupRouterImpl.scala:114-146)
@@ -778,7 +827,11 @@ class Behaviors:
         Starts made in the block that no handler uses as an effect are the setup starts of the actors that
         begin in the returned behaviour (Tables.initial_timers; engine.start_timers applies them)."""
         ts = TimerScheduler()
-        b = factory(ts)
+        _TIMER_SCOPES.append(ts)
+        try:
+            b = factory(ts)
+        finally:
+            _TIMER_SCOPES.pop()
         if not isinstance(b, Behavior):
             raise CompileError("with_timers' factory must return a Behavior")
         used = {id(e) for x in _reachable([b]) for c in x.cases for e in c.effects}
@@ -963,7 +1016,7 @@ class Tables:
     def max_tells(self) -> int:
         """The most tells one message can emit (the largest tell count of any case): the engine's
         max_emit must be at least this (agx_set_behaviors rejects the tables otherwise)."""
-        return max((sum(1 for i in range(c.act_first, c.act_first + c.act_count) if self.acts[i].op in (A_TELL, A_ROUTE))
+        return max((sum(1 for i in range(c.act_first, c.act_first + c.act_count) if self.acts[i].op in (A_TELL, A_ROUTE, A_ASK_SEND))
                     for c in self.cases[:int(self.first[-1])]), default=0)
 
     @property
@@ -991,7 +1044,14 @@ class Tables:
         for a in self.acts[:self.n_acts]:
             if A_TIMER_SINGLE <= a.op <= A_TIMER_CANCEL_ALL:
                 n = max(n, 1 if a.op == A_TIMER_CANCEL_ALL else a.word + 1)
+            if a.op == A_ASK_ARM:
+                n = max(n, a.word + 1)
         return n
+
+    @property
+    def uses_ask(self) -> bool:
+        """The behaviours ask: the engine needs engine.set_ask() on top of engine.set_timers(tables.timer_keys)."""
+        return any(a.op in (A_ASK_ARM, A_ASK_SEND) for a in self.acts[:self.n_acts])
 
     @property
     def uses_receive_timeout(self) -> bool:
@@ -1095,17 +1155,18 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
                 code, nxt = res.code, 0
             if c.signal:
                 code |= CASE_SIGNAL
-            if len(acts) + len(c.effects) > 0xFFFF:
+            n_acts_c = len(c.effects) + sum(1 for e in c.effects if e.ask is not None)  # (an ask lowers to ARM + SEND)
+            if len(acts) + n_acts_c > 0xFFFF:
                 raise CompileError("too many actions")
             cases.append(AgxCase(src1=t[0].lhs.src, word1=t[0].lhs.word, k1=t[0].lhs.k, cmp1=t[0].cmp,
                                  src2=t[0].rhs.src, word2=t[0].rhs.word, k2=t[0].rhs.k,
                                  src3=t[1].lhs.src, word3=t[1].lhs.word, k3=t[1].lhs.k, cmp2=t[1].cmp,
                                  src4=t[1].rhs.src, word4=t[1].rhs.word, k4=t[1].rhs.k,
-                                 result=code, next=nxt, act_first=len(acts), act_count=len(c.effects)))
+                                 result=code, next=nxt, act_first=len(acts), act_count=n_acts_c))
             for e in c.effects:
                 d = res_op(e.dst or Operand(V_CONST))
                 if e.val is not res_op(e.val):
-                    e = Action(e.op, e.word, res_op(e.val), e.dst, e.or_mask, e.site, e.into, e.key, e.flags)
+                    e = Action(e.op, e.word, res_op(e.val), e.dst, e.or_mask, e.site, e.into, e.key, e.flags, e.ask)
                 if e.op == A_SPAWN:  # dword: the site; pad0: the word `word` receives the child's id
                     key = (index[id(e.site.behavior)], e.site.base, e.site.word1)
                     if key not in sites:
@@ -1114,6 +1175,14 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
                         sites.append(key)
                     acts.append(AgxAct(op=e.op, word=e.word, src=e.val.src, sword=e.val.word, k=e.val.k,
                                        dsrc=V_CONST, dword=sites.index(key), dk=0, pad0=1 if e.into else 0))
+                    continue
+                if e.op == A_ASK_ARM:  # ARM: the timeout message and the timeout; SEND: the request to the target
+                    to, req, req_mask, adapt = e.ask
+                    acts.append(AgxAct(op=A_ASK_ARM, word=e.word, src=e.val.src, sword=e.val.word, k=e.val.k,
+                                       dsrc=d.src, dword=d.word, dk=d.k, or_mask=e.or_mask,
+                                       pad0=0 if adapt is None else 1, pad1=0 if adapt is None else adapt))
+                    acts.append(AgxAct(op=A_ASK_SEND, word=e.word, src=req.src, sword=req.word, k=req.k,
+                                       dsrc=to.src, dword=to.word, dk=to.k, or_mask=req_mask))
                     continue
                 acts.append(AgxAct(op=e.op, word=e.word, src=e.val.src, sword=e.val.word, k=e.val.k,
                                    dsrc=d.src, dword=d.word, dk=d.k, or_mask=e.or_mask, pad0=e.flags,
@@ -1139,6 +1208,20 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
                     e.reset[w] = v
             row.append(e)
         t.supervisors.append(row)
+    if t.uses_ask:  # on the timer engine: max_emit 1, the request is the case's one envelope
+        if t.stash_capacity or t.uses_watch or t.uses_children or t.uses_supervision or t.uses_receptionist or \
+                t.uses_receive_timeout or any(V_STASH in (a.src, a.dsrc) for a in acts) or \
+                any(V_STASH in (c.src1, c.src2, c.src3, c.src4) for c in cases):
+            raise CompileError("ask lives on the timer engine, which shares an engine with neither a stash, death watch, "
+                               "children, supervision, the receptionist nor receive timeouts: the behaviours ask and use "
+                               "one of them")
+        if max_emit is not None and max_emit > 1:
+            raise CompileError(f"ask needs max_emit = 1, not {max_emit}")
+        for c in cases:
+            n = sum(1 for j in range(c.act_first, c.act_first + c.act_count) if acts[j].op in (A_TELL, A_ASK_SEND))
+            if n > 1 and any(acts[j].op == A_ASK_SEND for j in range(c.act_first, c.act_first + c.act_count)):
+                raise CompileError(f"a case holds {n} of tell and ask: an ask's request is the case's one envelope, and an "
+                                   "engine with ask has max_emit 1")
     if t.uses_supervision:
         if t.uses_watch or t.timer_keys or t.stash_capacity or \
                 any(V_STASH in (a.src, a.dsrc) for a in acts) or \

@@ -52,7 +52,8 @@ class Workload:
     # timers (agx_set_timers / agx_start_timers): {"n_keys": k, "starts": [(first, count, key, periodic, delay,
     # delays or None, payload)], "receive_timeout": {"transparent": message tags, "starts": [(first, count, delay,
     # payload)]}} -- empty: no timers; without "receive_timeout": no receive timeouts (agx_set_receive_timeout /
-    # agx_start_receive_timeout, on top of the timers: behaviours that use only a receive timeout pass n_keys 1)
+    # agx_start_receive_timeout, on top of the timers: behaviours that use only a receive timeout pass n_keys 1);
+    # "ask": True -- the ask pattern (agx_set_ask, on top of the timers; not together with "receive_timeout")
     timers: dict = field(default_factory=dict)
     # death watch (agx_set_death_watch / agx_start_watch): {"n_slots": k, "starts": [(first, count, watchees or
     # None, offset, message or None)]} -- empty: no death watch
@@ -106,6 +107,8 @@ class Workload:
                 target.register_services(first, count, key)
         if self.timers:  # (empty: targets without the calls are unaffected)
             target.set_timers(self.timers["n_keys"])
+            if self.timers.get("ask"):  # (the ask pattern, on top of the timers: agx_set_ask)
+                target.set_ask()
             for first, count, key, periodic, delay, delays, payload in self.timers.get("starts", ()):
                 target.start_timers(first, count, key, delay, periodic=periodic, delays=delays, payload=payload)
             rt = self.timers.get("receive_timeout")
@@ -812,6 +815,112 @@ def passivating_entities(n: int = 1 << 20, n_shards: int = 4096, idle: int = 8, 
                     [(0, n, tb.kind_of(entity), init), (n, n_shards, tb.kind_of(shard), None)], behaviors=tb,
                     bucket_actors=bucket_actors, schedule=schedule,
                     timers={"n_keys": max(tb.timer_keys, 1), "receive_timeout": rt})
+
+
+# ------------------------------------------------------------------ the ask pattern: clients that bound their wait
+AP_TICK, AP_REQUEST, AP_REPLY, AP_ANSWER, AP_TIMEOUT, AP_START = 1, 2, 3, 4, 5, 6
+AP_TIMEOUT_UNIT = 1 << 32  # a client's word 0: answers in the low half, timeouts in the high half
+
+
+def ask_client(timeout: int, period: int = 0, last_server: int | None = None):
+    """A client (Behaviors.withTimers + context.ask): state word 0 counts answers (low half) and timeouts (high
+    half), word 1 is the server it asks.  `period` > 0: every Tick of its periodic timer "tick" (key 0) it asks its
+    server on key 1 (ask_pool).  `last_server` given: Start makes it ask; on a timeout it asks the next server, up to
+    `last_server`, then counts the failure (ask_retry).  A reply comes back as Answer."""
+    from . import typed
+    B = typed.Behaviors
+    tick, request, answer, timed_out, start = (typed.MessageType(n, t) for n, t in
+                                               (("Tick", AP_TICK), ("Request", AP_REQUEST), ("Answer", AP_ANSWER),
+                                                ("TimedOut", AP_TIMEOUT), ("Start", AP_START)))
+    st = typed.State("count", "server")
+
+    def ask(s):
+        return typed.context.ask(s.server.ref, request(s.count), timeout, on_timeout=timed_out(), on_success=answer, key="ask")
+
+    def build(timers):
+        rb = typed.ReceiveBuilder.create(st)
+        if period:
+            timers.start_timer_with_fixed_delay("tick", tick(), period)  # (the setup start: Workload.timers["starts"])
+            rb.on_message(tick, lambda m, s: [ask(s), B.same])
+            rb.on_message(timed_out, lambda m, s: [s.count.add(AP_TIMEOUT_UNIT), B.same])
+        else:
+            rb.on_message(start, lambda m, s: [ask(s), B.same])
+            rb.on_message(timed_out, lambda m, s: [s.server.inc(), ask(s), B.same], when=lambda m, s: s.server < last_server)
+            rb.on_message(timed_out, lambda m, s: [s.count.add(AP_TIMEOUT_UNIT), B.same])
+        return (rb.on_message(answer, lambda m, s: [s.count.inc(), B.same])
+                .on_any_message(lambda m, s: [B.unhandled]).build("ask_client"))
+    return B.with_timers(build)
+
+
+def ask_server(silent: bool = False):
+    """A server: counts the request and, unless `silent`, answers its sender -- the ask ref -- with Reply."""
+    from . import typed
+    B = typed.Behaviors
+    request, reply = typed.MessageType("Request", AP_REQUEST), typed.MessageType("Reply", AP_REPLY)
+    st = typed.State("served", "unused")
+    rb = typed.ReceiveBuilder.create(st)
+    if silent:
+        rb.on_message(request, lambda m, s: [s.served.inc(), B.same])
+    else:
+        rb.on_message(request, lambda m, s: [s.served.inc(), m.sender.tell(reply(m.arg)), B.same])
+    return rb.on_any_message(lambda m, s: [B.unhandled]).build("silent_server" if silent else "ask_server")
+
+
+def _ask_servers(tb, loud, quiet, first: int, n_servers: int, silent_every: int) -> list:
+    """The servers' ranges: every `silent_every`-th one (the last of each group) never answers; 0: all answer."""
+    if not silent_every:
+        return [(first, n_servers, tb.kind_of(loud), None)]
+    ranges = []
+    for j in range(0, n_servers, silent_every):
+        g = min(silent_every, n_servers - j)
+        if g == silent_every:
+            if g > 1:
+                ranges.append((first + j, g - 1, tb.kind_of(loud), None))
+            ranges.append((first + j + g - 1, 1, tb.kind_of(quiet), None))
+        else:
+            ranges.append((first + j, g, tb.kind_of(loud), None))
+    return ranges
+
+
+def ask_pool(n_clients: int = 3 << 18, n_servers: int = 1 << 18, timeout: int = 4, silent_every: int = 8, period: int = 8,
+             seed: int = 1, throughput: int = 4, bucket_actors: int = 0, asking: bool = True) -> Workload:
+    """Clients (ids 0..n_clients-1) ask server n_clients + i mod n_servers every `period` ticks (a periodic Tick on
+    key 0, staggered phases; the ask on key 1) and wait at most `timeout` ticks; every `silent_every`-th server never
+    answers (0: all answer).  A client's word 0 counts its answers (low half) and timeouts (high half).  The
+    periodic timers never let the engine go quiescent: run it with a budget.  A server bucket takes n_clients /
+    n_servers / period requests per server and tick, well inside the timers engine's 2048-message tile at the default 2048-actor buckets
+    (measured at 2^20 actors: 0.22 ms per tick there, 0.40 at 1024, 0.94 at 256: DESIGN.md §8 round 18).  `asking=False`: the same population on
+    the same engine with no timer started, so nothing is ever asked -- what the instantiation costs at rest."""
+    from . import typed
+    rng = np.random.default_rng(seed)
+    client, loud, quiet = ask_client(timeout, period=period), ask_server(), ask_server(silent=True)
+    tb = typed.compile_behaviors([client, loud, quiet], max_emit=1)
+    init = np.zeros((n_clients, 2), np.uint64)
+    init[:, 1] = n_clients + np.arange(n_clients, dtype=np.uint64) % n_servers
+    delays = (1 + rng.integers(0, period, n_clients)).astype(np.uint32)
+    starts = [(0, n_clients, 0, True, period, delays, AP_TICK << 24)] if asking else []
+    return Workload("ask_pool", n_clients + n_servers, 2, 1, throughput, 0,
+                    [(0, n_clients, tb.kind_of(client), init)] + _ask_servers(tb, loud, quiet, n_clients, n_servers, silent_every),
+                    behaviors=tb, bucket_actors=bucket_actors, timers={"n_keys": tb.timer_keys, "starts": starts, "ask": True})
+
+
+def ask_retry(n_clients: int = 1 << 16, n_servers: int = 64, timeout: int = 3, silent_every: int = 2,
+              throughput: int = 4, bucket_actors: int = 256) -> Workload:
+    """Every client is told Start and asks server n_clients + i mod n_servers; on a timeout it asks the next server,
+    and gives up (a counted timeout) past the last one.  Every `silent_every`-th server never answers.  The run goes
+    quiescent once every client has its answer or has given up."""
+    from . import typed
+    last = n_clients + n_servers - 1
+    client, loud, quiet = ask_client(timeout, last_server=last), ask_server(), ask_server(silent=True)
+    tb = typed.compile_behaviors([client, loud, quiet], max_emit=1)
+    init = np.zeros((n_clients, 2), np.uint64)
+    init[:, 1] = n_clients + np.arange(n_clients, dtype=np.uint64) % n_servers
+    ids = np.arange(n_clients, dtype=np.uint32)
+    tells = (ids, np.full(n_clients, NO_SENDER, np.uint32), np.full(n_clients, AP_START << 24, np.uint32))
+    return Workload("ask_retry", n_clients + n_servers, 2, 1, throughput, 0,
+                    [(0, n_clients, tb.kind_of(client), init)] + _ask_servers(tb, loud, quiet, n_clients, n_servers, silent_every),
+                    behaviors=tb, tells=tells, bucket_actors=bucket_actors,
+                    timers={"n_keys": tb.timer_keys, "ask": True})
 
 
 # ------------------------------------------------------------------ death watch: pacts and a self-healing ring

@@ -195,8 +195,22 @@ enum agx_action_op {
    * AGX_A_TELL (ref.forward(msg)) is accepted on an engine with the receptionist only. */
   AGX_A_REGISTER = 17,   /* receptionist ! Register(key, self)   (LocalReceptionist.scala:147-175) */
   AGX_A_DEREGISTER = 18, /* receptionist ! Deregister(key, self) (LocalReceptionist.scala:177-199) */
-  AGX_A_ROUTE = 19       /* group router: selectRoutee(msg) ! msg (GroupRouterImpl.scala:114-146) */
+  AGX_A_ROUTE = 19,      /* group router: selectRoutee(msg) ! msg (GroupRouterImpl.scala:114-146) */
+  /* The ask pattern (engines with ask, agx_set_ask).  context.ask lowers to ARM directly followed by
+   * the SEND of the same key.  ARM: `word` is the key; the operand and or_mask hold the timeout message as a
+   * TIMER_SINGLE's, the d-operand is the timeout in ticks as a timer's delay; pad0 & 1: the reply's tag is replaced
+   * by pad1 (the adapt tag).  SEND: a TELL's layout with `word` = the key; its envelope carries the ask ref as the
+   * sender.  It is the case's one envelope: a case holds at most one of TELL and ASK_SEND. */
+  AGX_A_ASK_ARM = 20,    /* context.ask: the promise ref and its timeout task (AskPattern.scala:109-162) */
+  AGX_A_ASK_SEND = 21    /* context.ask: target ! createRequest(ref) (ActorContextImpl.scala:203-218) */
 };
+/* The ask ref: AGX_ASK_REF_BIT | key << 29 | (generation mod 2^7) << 22 | the asker's id. */
+#define AGX_ASK_REF_BIT 0x80000000u
+#define AGX_ASK_REF_KEY_SHIFT 29u
+#define AGX_ASK_REF_GEN_SHIFT 22u
+#define AGX_ASK_REF_GEN_MASK 0x7Fu
+#define AGX_ASK_REF_ID_MASK 0x3FFFFFu
+#define AGX_ASK_MAX_ACTORS 0x3FFFFFu /* an engine with ask has at most 2^22 - 1 actors: the ref carries the id */
 #define AGX_ROUTE_KEEP_SENDER 1u
 #define AGX_ROUTE_BY_INDEX 2u
 #define AGX_MAX_SERVICE_KEYS 8u
@@ -631,6 +645,39 @@ agx_status agx_receive_timeout_info(agx_engine* eng, uint64_t* fired, uint64_t* 
  * 0xFFFFFFFF when none is to come.  Any pointer may be NULL. */
 agx_status agx_read_receive_timeout(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t* delay, uint32_t* remaining,
                                     uint32_t* payload);
+
+/* The ask pattern: request-response with a timeout (ActorContext.ask: TY/internal/ActorContextImpl.scala:203-218;
+ * AskPattern.ask: TY/scaladsl/AskPattern.scala:109-162; pinned by ActorContextAskSpec.scala:41-189 and AskSpec.scala:
+ * 64-110; DESIGN.md 2.9 has the contract).  On top of the timers: call agx_set_timers first; time is the timers'.
+ * An ask uses one of the actor's timer keys, so an actor has at most n_keys asks outstanding.
+ * AGX_A_ASK_ARM(k, t, m, a) + AGX_A_ASK_SEND(k, d, p) in a case run at tick s: key k is started as a single timer
+ * (the previous occupant is cancelled, the slot gets the actor's next generation g, next fire s + t, stored payload
+ * m) and marked as an ask with adapt tag a or none; one envelope (d, p) is emitted whose sender field is the ask
+ * ref AGX_ASK_REF_BIT | k << 29 | (g mod 2^7) << 22 | the actor's id.  The target sees the ref as the sender and may
+ * keep it in a state word.
+ * Answering: every tell emitted on such an engine, by whichever kind, whose destination has bit 31 set and is not
+ * 0xFFFFFFFF is a reply: it is emitted to the ref's id with the ref as the sender field (the replier's id is not
+ * carried).  Receipt: a drained envelope whose sender field is a ref that names the receiving actor is a reply (an
+ * actor that asks itself gets its request as the reply).  It takes a drain slot and counts as delivered.  Slot k
+ * active, an ask, and of the ref's generation mod 2^7: the slot becomes inactive as a cancel makes it, the behaviour
+ * runs with sender = the actor on (payload & 0xFFFFFF) | a << 24, or on the payload unchanged without an adapt tag.
+ * Otherwise the reply is late: counted, discarded, not unhandled.  The timeout is the slot's TimerMsg: accepted, the
+ * behaviour runs on m with sender = the actor.  The inbox order is the timers': a reply that arrives in the tick of
+ * the fire wins.  A round trip takes two ticks, so t = 1 always times out.
+ * Cancelling the key abandons the ask; a stop of the asker cancels its slots; AGX_V_TIMER on the key reads "ask
+ * outstanding".  Conservation and quiescence are the timers': the request counts as emitted, the timeout as fired,
+ * and an outstanding ask is a pending single timer.
+ * AGX_EINVAL without timers, on a second call, together with receive timeouts (either order) or with more than
+ * AGX_ASK_MAX_ACTORS actors; AGX_ESTATE after the first run; AGX_ENOMEM: the row does not fit.  agx_set_timers cannot
+ * change the key count afterwards.  Tables that hold an ask action on an engine without ask, an ASK_SEND not directly
+ * preceded by the ASK_ARM of its key, or an ask key >= n_keys make agx_run return AGX_EINVAL. */
+agx_status agx_set_ask(agx_engine* eng);
+/* Totals since agx_create: asks made, replies accepted, timeouts delivered, late replies discarded.  Any pointer may
+ * be NULL. */
+agx_status agx_ask_info(agx_engine* eng, uint64_t* asked, uint64_t* answered, uint64_t* timed_out, uint64_t* late);
+/* The ask marks of an actor's timer slots (for tests and tools): is_ask[k] = 1 when slot k is active as an ask's
+ * timeout, adapt[k] = its adapt tag, 0xFFFFFFFF without one or when the slot is no ask.  Any pointer may be NULL. */
+agx_status agx_read_asks(agx_engine* eng, uint64_t actor_id, uint32_t is_ask[4], uint32_t adapt[4]);
 
 /* Death watch (context.watch / watchWith / unwatch and the Terminated signal: AA/dungeon/DeathWatch.scala:19-113,
  * :147-162; typed adapter TY/internal/adapter/ActorAdapter.scala:84-91,134-138,200-205; pinned by
