@@ -733,6 +733,8 @@ constexpr uint32_t kIdleKM = 1u << 25;
 constexpr uint32_t kRecepKM = 1u << 24;
 // KM flag (not a kind): the variant knows the ask pattern (agx_set_ask); only ever combined with kTimersKM.
 constexpr uint32_t kAskKM = 1u << 23;
+// KM flag (not a kind): the variant knows pub-sub topics (agx_set_topics); only ever combined with kRecepKM.
+constexpr uint32_t kTopicKM = 1u << 22;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -1329,6 +1331,145 @@ __device__ __forceinline__ uint32_t compiled_apply_rc(const DevParams& P, const 
             ++rc.dereg;
           }
           break;
+        case AGX_A_TELL:
+        case AGX_A_ROUTE: {
+          uint64_t d = 0;
+          if (A.op == AGX_A_TELL || (A.pad0 & AGX_ROUTE_BY_INDEX)) {
+            if (A.dsrc == AGX_V_SELF && A.op == AGX_A_TELL) {  // (self + dk) mod n: ring neighbours
+              int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+              d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+            } else {
+              d = rc_operand(RD, A.dsrc, A.dword, A.dk, pay, w, src, self);
+            }
+          }
+          uint32_t ref = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
+          if (A.op == AGX_A_ROUTE) {
+            const uint32_t key = A.pad1 & 7u;
+            if (A.pad0 & AGX_ROUTE_BY_INDEX) {
+              ref = RD.at(key, d);
+            } else {
+              ref = RD.successor(key, w[A.word & 1u]);
+              if (ref != kRcNone) w[A.word & 1u] = (uint64_t)ref + 1ull;  // (no routee: the cursor stays)
+            }
+            if (ref == kRcNone) ++rc.none;
+            else ++rc.routed;
+          }
+          if (A.pad0 & AGX_ROUTE_KEEP_SENDER) {  // a forward: the envelope keeps the incoming message's sender
+            const uint32_t me = emit.self;
+            emit.self = src;
+            emit(ref, msg);
+            emit.self = me;
+          } else {
+            emit(ref, msg);
+          }
+          break;
+        }
+        default: break;
+      }
+    }
+    if (C.result == AGX_RES_BECOME) {
+      kind = AGX_KIND_COMPILED + C.next;
+      return AGX_RES_SAME;
+    }
+    return C.result;
+  }
+  return AGX_RES_UNHANDLED;
+}
+
+// ---- pub-sub topics (agx_set_topics; TY/internal/pubsub/TopicImpl.scala:60-143), on top of the
+// receptionist: a topic is a service key, its subscribers are the key's registered actors.  An allocation of its
+// own whose address stands in words [kRcTopicPtr, kRcTopicPtr + 2) of the receptionist's storage, u32 units:
+//   [0] log_capacity   [1] nb
+//   [4] cursor: the publications staged by the drains of the tick being drained   [5] mail: a bucket had mail in
+//       this superstep (it is a tick)   [6] n_log: the entries of the pending log   (one 16-byte load: k_topic_plan)
+//   [8..15]  four u64 counters: published, fanned_out, no_subscribers, host_published
+//   [16..19] two u64: what the pending log added to fanned_out / no_subscribers (a re-plan takes it back)
+//   [24..31] pubs[k]: the pending log's publications per key
+//   [kTpDueOff + b]  due: the deliveries of the pending log to bucket b, part of the bucket's backlog count
+//   then log[i] (uint4: key, sender, payload, 0), log_capacity entries: the publications the next tick delivers,
+//   device publications in (publisher, window index) order, then host publications in call order
+//   then stage[i] (uint4: publisher, window index, key, payload), log_capacity entries, in no order
+// The drains only append to `stage`; k_topic_plan (after the apply) turns it into the log; the blocks of the next
+// apply read the log, their own due word and their own mask bytes.
+constexpr uint32_t kRcTopicPtr = 4;
+constexpr uint32_t kTpCursor = 4, kTpMail = 5, kTpNLog = 6, kTpCtr = 8, kTpLast = 16, kTpPubs = 24, kTpDueOff = 32;
+constexpr uint32_t kTpPublished = 0, kTpFannedOut = 1, kTpNoSubscribers = 2, kTpHostPublished = 3;
+constexpr uint32_t kTpDueMax = 1u << 20;  // (a due count above one tile is an error either way: no 32-bit overflow)
+__host__ __device__ __forceinline__ size_t tp_log_off(uint32_t nb) { return ((size_t)kTpDueOff + nb + 3u) & ~(size_t)3; }
+__host__ __device__ __forceinline__ size_t tp_stage_off(uint32_t cap, uint32_t nb) { return tp_log_off(nb) + 4ull * cap; }
+__host__ __device__ __forceinline__ size_t tp_words(uint32_t cap, uint32_t nb) { return tp_stage_off(cap, nb) + 4ull * cap; }
+struct TopicDev {
+  uint32_t* base;
+  uint32_t cap, nb;
+  __device__ __forceinline__ uint32_t* due(uint32_t b) const { return base + kTpDueOff + b; }
+  __device__ __forceinline__ uint4* log() const { return reinterpret_cast<uint4*>(base + tp_log_off(nb)); }
+  __device__ __forceinline__ uint4* stage() const { return reinterpret_cast<uint4*>(base + tp_stage_off(cap, nb)); }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kTpCtr) + i;
+  }
+  __device__ __forceinline__ unsigned long long* last(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kTpLast) + i;
+  }
+};
+__device__ __forceinline__ TopicDev topic_dev(uint32_t* base) {
+  TopicDev t;
+  t.base = base;
+  t.cap = base[0];
+  t.nb = base[1];
+  return t;
+}
+__device__ __forceinline__ TopicDev topic_dev_of(const uint32_t* recep) {
+  return topic_dev(*reinterpret_cast<uint32_t* const*>(recep + kRcTopicPtr));
+}
+
+// compiled_apply of the topic instantiations: compiled_apply_rc plus AGX_A_PUBLISH, which appends (publisher, index
+// within the publisher's drained window `q`, key, payload) to the tick's staging area and does not touch the
+// emitter; an entry past log_capacity is not stored (k_topic_plan raises the error from the cursor).  `npub`: the
+// thread's publish actions, added to the counter once per wave (topic_commit).  A function of its own: every other
+// instantiation compiles compiled_apply_rc as before.
+template <typename Emit>
+__device__ __forceinline__ uint32_t compiled_apply_tp(const DevParams& P, const RecepDev& RD, const TopicDev& TP, uint32_t& kind,
+                                                      uint32_t self, uint64_t* w, uint32_t src, uint32_t pay, uint32_t& mk,
+                                                      RecepCount& rc, uint32_t q, uint32_t& npub, Emit& emit) {
+  const uint32_t b = kind - AGX_KIND_COMPILED;
+  if (b >= P.n_beh) return AGX_RES_UNHANDLED;
+  const uint32_t c1 = P.bfirst[b + 1];
+  for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
+    const agx_case C = P.bcase[c];
+    if (!cb_cmp(C.cmp1, rc_operand(RD, C.src1, C.word1, C.k1, pay, w, src, self),
+                rc_operand(RD, C.src2, C.word2, C.k2, pay, w, src, self)))
+      continue;
+    if (!cb_cmp(C.cmp2, rc_operand(RD, C.src3, C.word3, C.k3, pay, w, src, self),
+                rc_operand(RD, C.src4, C.word4, C.k4, pay, w, src, self)))
+      continue;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      const agx_act A = P.bact[i];
+      const uint64_t v = rc_operand(RD, A.src, A.sword, A.k, pay, w, src, self);
+      const uint32_t msg = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;
+      const uint32_t bit = 1u << (A.pad1 & 7u);
+      switch (A.op) {
+        case AGX_A_SET: w[A.word & 1u] = v; break;
+        case AGX_A_ADD: w[A.word & 1u] += v; break;
+        case AGX_A_MAX: w[A.word & 1u] = v > w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_MIN: w[A.word & 1u] = v < w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_REGISTER:
+          if (!(mk & bit)) {
+            mk |= bit;
+            ++rc.reg;
+          }
+          break;
+        case AGX_A_DEREGISTER:
+          if (mk & bit) {
+            mk &= ~bit;
+            ++rc.dereg;
+          }
+          break;
+        case AGX_A_PUBLISH: {
+          const uint32_t slot = atomicAdd(TP.base + kTpCursor, 1u);
+          if (slot < TP.cap) TP.stage()[slot] = make_uint4(self, q, A.pad1 & 7u, msg);
+          ++npub;
+          break;
+        }
         case AGX_A_TELL:
         case AGX_A_ROUTE: {
           uint64_t d = 0;

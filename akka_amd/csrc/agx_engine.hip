@@ -222,6 +222,13 @@ struct agx_engine {
     uint32_t key, on;
   };
   std::vector<RecepStart> rc_starts;  // agx_register_services calls not yet applied on the device
+  // pub-sub topics (agx_set_topics), on top of the receptionist: the publication log, the per-bucket due counts.
+  // Such an engine launches the kRecep | kTopic instantiation, then k_topic_plan beside the rebuild kernels
+  uint32_t* d_topic = nullptr;   // (its address stands in the receptionist's storage: agx_device.h TopicDev)
+  uint32_t tp_cap = 0;           // log_capacity
+  bool beh_publish = false;      // the compiled tables publish
+  struct TopicPub { uint32_t key, sender, payload; };
+  std::vector<TopicPub> tp_pubs;  // agx_publish calls not yet applied on the device
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -450,7 +457,7 @@ namespace {
 // of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
 // the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
 // apply_variant, launch_apply and make_params.
-enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_ASK, F_N, F_NONE = F_N };
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_ASK, F_TOPIC, F_N, F_NONE = F_N };
 
 struct FeatureRow {
   bool (*on)(const agx_engine*);
@@ -503,6 +510,9 @@ const FeatureRow kFeatures[F_N] = {
     // the ask pattern (agx_set_ask) comes on top of the timers as receive timeouts do; the two exclude one another
     {[](const agx_engine* e) { return e->ask_on; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      kTimersKM | kAskKM, false, F_TIMERS},
+    // pub-sub topics (agx_set_topics) come on top of the receptionist in the same way
+    {[](const agx_engine* e) { return e->d_topic != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+     nullptr, kRecepKM | kTopicKM, false, F_RECEP},
 };
 #undef AGX_ONCE
 
@@ -981,6 +991,126 @@ void launch_recep_rebuild(agx_engine* e) {
   hipLaunchKernelGGL(k_recep_fill, dim3(e->nb), dim3(kRcThreads), 0, e->stream, e->d_recep, e->bb, (uint32_t)e->n_local);
 }
 
+// ---- pub-sub topics (agx_set_topics): the plan between two supersteps.  apply -> k_topic_plan -> the
+// next apply are kernel boundaries: no polling between workgroups, no grid barrier; the drains of the apply only
+// append to the staging area, the blocks of the next apply only read the log, their due word and their masks.
+constexpr int kTpThreads = 1024;
+// due[b] = sum over keys of pubs[key] x cnt[key][b] for every bucket, which joins the bucket's backlog count (`blc`:
+// the counts the next apply reads); what the pending log adds to fanned_out / no_subscribers replaces what it
+// added before (`replan`: the old due counts leave the backlog counts first).  Every thread of the block calls.
+__device__ __forceinline__ void topic_due(const TopicDev& TP, const RecepDev& RD, uint32_t* blc, bool replan, uint32_t* s_mem,
+                                          unsigned long long* s_fan) {
+  const uint32_t tid = threadIdx.x;
+  if (tid < AGX_MAX_SERVICE_KEYS) s_mem[tid] = 0u;
+  if (tid == 0) *s_fan = 0ull;
+  __syncthreads();
+  uint32_t pubs[AGX_MAX_SERVICE_KEYS], mem[AGX_MAX_SERVICE_KEYS] = {};
+#pragma unroll
+  for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) pubs[k] = k < RD.nk ? TP.base[kTpPubs + k] : 0u;
+  unsigned long long fan = 0ull;
+  for (uint32_t b = tid; b < TP.nb; b += kTpThreads) {
+    unsigned long long d = 0ull;
+#pragma unroll
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k)
+      if (pubs[k]) {  // (block-uniform)
+        const uint32_t c = *RD.cnt(k, b);
+        mem[k] += c;
+        d += (unsigned long long)pubs[k] * c;
+      }
+    const uint32_t dn = (uint32_t)(d < kTpDueMax ? d : kTpDueMax), old = replan ? *TP.due(b) : 0u;
+    *TP.due(b) = dn;
+    if (dn | old) {
+      const uint32_t x = blc[b];
+      blc[b] = x - min(old, x) + dn;
+    }
+    fan += dn;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k)
+    if (mem[k]) atomicAdd(&s_mem[k], mem[k]);
+  if (fan) atomicAdd(s_fan, fan);
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long nosub = 0ull;
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k)
+      if (pubs[k] && !s_mem[k]) nosub += pubs[k];
+    const unsigned long long f = *s_fan;
+    *TP.ctr(kTpFannedOut) += f - *TP.last(0);      // (one block, one writer; wraps back when the plan shrinks)
+    *TP.ctr(kTpNoSubscribers) += nosub - *TP.last(1);
+    *TP.last(0) = f;
+    *TP.last(1) = nosub;
+  }
+}
+// One block, after every apply.  Nothing staged and no pending log: returns after one 16-byte load.  A pending log
+// whose tick has not come (no bucket had mail in this superstep) stays.  Else the log is consumed: with nothing
+// staged it is emptied; else the staged publications are ranked by (publisher, window index) into the log (each
+// thread counts the entries before its own: n^2 / 1024 compares per thread, n <= log_capacity), counted per key,
+// and planned (topic_due).  More staged than log_capacity: the sticky error, the log keeps log_capacity of them.
+// replan != 0 (after agx_register_services / agx_publish between two runs): the pending log planned again.
+static __global__ void __launch_bounds__(kTpThreads) k_topic_plan(uint32_t* rc, uint32_t* blc, unsigned long long* err,
+                                                                  uint32_t replan) {
+  const RecepDev RD = recep_dev(rc);
+  const TopicDev TP = topic_dev_of(rc);
+  const uint32_t tid = threadIdx.x;
+  __shared__ uint32_t s_mem[AGX_MAX_SERVICE_KEYS], s_pubs[AGX_MAX_SERVICE_KEYS];
+  __shared__ unsigned long long s_fan;
+  const uint4 h = *reinterpret_cast<const uint4*>(TP.base + kTpCursor);  // cursor, mail, n_log
+  if (replan) {
+    if (h.z) topic_due(TP, RD, blc, true, s_mem, &s_fan);  // (block-uniform)
+    return;
+  }
+  const uint32_t ns = h.x;
+  if (!ns && (!h.z || !h.y)) return;
+  const uint32_t n = min(ns, TP.cap);
+  if (tid < AGX_MAX_SERVICE_KEYS) s_pubs[tid] = 0u;
+  __syncthreads();
+  const uint4* const st = TP.stage();
+  uint4* const lg = TP.log();
+  for (uint32_t i = tid; i < n; i += kTpThreads) {
+    const uint4 me = st[i];
+    const unsigned long long mk = ((unsigned long long)me.x << 32) | me.y;
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < n; ++j) {  // (a publisher's window indices differ: the keys are distinct)
+      const uint4 o = st[j];
+      rank += (((unsigned long long)o.x << 32) | o.y) < mk ? 1u : 0u;
+    }
+    lg[rank] = make_uint4(me.z, me.x, me.w, 0u);
+    atomicAdd(&s_pubs[me.z & 7u], 1u);
+  }
+  __syncthreads();
+  if (tid < AGX_MAX_SERVICE_KEYS) TP.base[kTpPubs + tid] = s_pubs[tid];
+  if (tid == 0) {
+    if (ns > TP.cap) atomicOr(err, (unsigned long long)kErrTopicLog);
+    TP.base[kTpCursor] = 0u;
+    TP.base[kTpMail] = 0u;
+    TP.base[kTpNLog] = n;
+    *TP.last(0) = 0ull;  // (a fresh log: nothing of it is counted yet)
+    *TP.last(1) = 0ull;
+  }
+  __threadfence();
+  __syncthreads();
+  topic_due(TP, RD, blc, false, s_mem, &s_fan);
+}
+// agx_publish on the device: the publication joins the pending log after what the device left there
+static __global__ void k_topic_host_pub(uint32_t* rc, uint32_t key, uint32_t sender, uint32_t payload, unsigned long long* err) {
+  const TopicDev TP = topic_dev_of(rc);
+  const uint32_t n = TP.base[kTpNLog];
+  atomicAdd(TP.ctr(kTpHostPublished), 1ull);
+  if (n >= TP.cap) {
+    atomicOr(err, (unsigned long long)kErrTopicLog);
+    return;
+  }
+  TP.log()[n] = make_uint4(key, sender, payload, 0u);
+  TP.base[kTpNLog] = n + 1u;
+  TP.base[kTpPubs + key] += 1u;
+  TP.base[kTpMail] = 0u;  // (the log's tick is the next superstep with mail)
+}
+
+void launch_topic_plan(agx_engine* e, uint32_t* blc, uint32_t replan) {
+  hipLaunchKernelGGL(k_topic_plan, dim3(1), dim3(kTpThreads), 0, e->stream, e->d_recep, blc,
+                     reinterpret_cast<unsigned long long*>(e->d_stats + ST_ERROR), replan);
+}
+
 agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
   // the chunk histograms consumed by this step's first pass were zeroed by k_chunk_downsweep;
   // on the multi-rank path (no chunk pass) they are never read, so stale columns are harmless
@@ -1198,6 +1328,8 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
     }
   }
   if (e->d_recep) launch_recep_rebuild(e);  // (every superstep, captured or eager: the listings of the next tick)
+  // (... and the tick's publications: the backlog counts this superstep wrote carry the next tick's deliveries)
+  if (e->d_topic) launch_topic_plan(e, e->fused ? e->d_blc[e->par] : e->d_chunk_cnt, 0u);
   if (e->R == 1) e->par ^= 1u;  // the next superstep writes the other parity (fused and multi-pass)
   HIP_TRY(hipGetLastError());
   return AGX_OK;
@@ -1901,8 +2033,8 @@ agx_status flush_child_spawns(agx_engine* e) {
 // newer ones; each call is the start kernel over the buckets of its range, then the rebuild (the listing is in
 // force for the next tick)
 agx_status flush_recep_starts(agx_engine* e) {
-  if (e->rc_starts.empty()) return AGX_OK;
-  if (e->actors_dirty) HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
+  if (e->rc_starts.empty() && e->tp_pubs.empty()) return AGX_OK;
+  if (e->actors_dirty && !e->rc_starts.empty()) HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
   for (const auto& rs : e->rc_starts) {
     if (!rs.count) continue;
     const uint32_t b0 = (uint32_t)(rs.first >> e->bb), b1 = (uint32_t)((rs.first + rs.count - 1) >> e->bb);
@@ -1911,8 +2043,17 @@ agx_status flush_recep_starts(agx_engine* e) {
     launch_recep_rebuild(e);
     HIP_TRY(hipGetLastError());
   }
+  if (e->d_topic) {  // the host's publications join the pending log; then the log is planned against the new counts
+    for (const auto& tp : e->tp_pubs)
+      hipLaunchKernelGGL(k_topic_host_pub, dim3(1), dim3(1), 0, e->stream, e->d_recep, tp.key, tp.sender, tp.payload,
+                         reinterpret_cast<unsigned long long*>(e->d_stats + ST_ERROR));
+    launch_topic_plan(e, next_backlog_counts(e), 1u);
+    HIP_TRY(hipGetLastError());
+    e->inflight_known = false;
+  }
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->rc_starts.clear();
+  e->tp_pubs.clear();
   return AGX_OK;
 }
 
@@ -1926,6 +2067,8 @@ agx_status prepare_run(agx_engine* e) {
   if (e->d_recep && e->beh_rc_keys > e->rc_keys)
     return set_err(AGX_EINVAL, "the compiled behaviours use service key %u, but the receptionist has %u keys "
                    "(agx_set_receptionist)", e->beh_rc_keys - 1u, e->rc_keys);
+  if (e->beh_publish && !e->d_topic)  // (only the topic variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours publish, but the engine has no topics (agx_set_topics)");
   if (e->ch_bad_spawn)
     return set_err(AGX_EINVAL, "agx_spawn_children was called on an engine without children (agx_set_children)");
   if (e->beh_child && !e->d_child)  // (only the children variant interprets those: loud, never wrong)
@@ -2300,6 +2443,9 @@ agx_status error_status(const agx_engine* e, uint64_t err) {
   if (err & kErrRecepCap)
     return set_err(AGX_ECAPACITY, "a service key's listing would hold more than %u ids, the receptionist's capacity "
                    "(agx_set_receptionist): the listing keeps its first %u ids", e->rc_cap, e->rc_cap);
+  if (err & kErrTopicLog)
+    return set_err(AGX_ECAPACITY, "a tick's publications would exceed the topics' log capacity of %u entries (agx_set_topics): "
+                   "the publications past it are lost", e->tp_cap);
   if (err & kErrWatchSlots)
     return set_err(AGX_ECAPACITY, "a watch found every one of its actor's %u watch slots taken: the watch is not recorded "
                    "(agx_set_death_watch; at most %u watched refs per actor)", e->wd_slots, AGX_MAX_WATCH_SLOTS);
@@ -3553,6 +3699,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_child);
   hipFree(e->d_super);
   hipFree(e->d_recep);
+  hipFree(e->d_topic);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -4367,6 +4514,82 @@ agx_status agx_set_receptionist(agx_engine* e, uint32_t n_keys, uint32_t capacit
   return AGX_OK;
 }
 
+// TY/internal/pubsub/TopicImpl.scala:60-143
+agx_status agx_set_topics(agx_engine* e, uint32_t log_capacity) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (log_capacity < 1u || log_capacity > AGX_MAX_TOPIC_LOG)
+    return set_err(AGX_EINVAL, "topics: a log of %u publications per tick (1..%u)", log_capacity, AGX_MAX_TOPIC_LOG);
+  if (e->d_topic) return set_err(AGX_EINVAL, "topics are already set (a log of %u publications)", e->tp_cap);
+  if (!e->d_recep)
+    return set_err(AGX_EINVAL, "topics need an engine with the receptionist (agx_set_receptionist): a topic is a service key");
+  if (e->started) return set_err(AGX_ESTATE, "set topics before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  const size_t words = tp_words(log_capacity, e->nb);
+  if (hipMalloc((void**)&e->d_topic, words * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_topic = nullptr;
+    return set_err(AGX_ENOMEM, "the topics' storage (a log of %u publications, %u buckets: %llu KB) does not fit on the device",
+                   log_capacity, e->nb, (unsigned long long)(words >> 8));
+  }
+  const uint32_t head[2] = {log_capacity, e->nb};
+  const unsigned long long addr = (unsigned long long)(uintptr_t)e->d_topic;
+  HIP_TRY(hipMemsetAsync(e->d_topic, 0, words * 4ull, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_topic, head, sizeof(head), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_recep + kRcTopicPtr, &addr, sizeof(addr), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->tp_cap = log_capacity;
+  e->tp_pubs.clear();
+  drop_graphs(e);  // the variant, the storage and the plan kernel are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_publish(agx_engine* e, uint32_t key, uint32_t sender, uint32_t payload) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_topic) return set_err(AGX_EINVAL, "agx_publish needs an engine with topics (agx_set_topics)");
+  if (key >= e->rc_keys) return set_err(AGX_EINVAL, "topic %u of %u", key, e->rc_keys);
+  e->tp_pubs.push_back({key, sender, payload});
+  return AGX_OK;
+}
+
+agx_status agx_topic_info(agx_engine* e, uint64_t* published, uint64_t* fanned_out, uint64_t* no_subscribers,
+                          uint64_t* host_published) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[4] = {0, 0, 0, 0};
+  if (e->d_topic) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(flush_recep_starts(e));
+    AGX_TRY(copy_sync(e, c, e->d_topic + kTpCtr, sizeof(c), hipMemcpyDeviceToHost));
+  }
+  if (published) *published = c[kTpPublished];
+  if (fanned_out) *fanned_out = c[kTpFannedOut];
+  if (no_subscribers) *no_subscribers = c[kTpNoSubscribers];
+  if (host_published) *host_published = c[kTpHostPublished];
+  return AGX_OK;
+}
+
+agx_status agx_read_topic_log(agx_engine* e, uint32_t* out_key, uint32_t* out_sender, uint32_t* out_payload, uint64_t cap,
+                              uint64_t* out_n) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_topic) return set_err(AGX_EINVAL, "agx_read_topic_log needs an engine with topics (agx_set_topics)");
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_recep_starts(e));
+  uint32_t n = 0;
+  AGX_TRY(copy_sync(e, &n, e->d_topic + kTpNLog, 4, hipMemcpyDeviceToHost));
+  n = std::min(n, e->tp_cap);
+  const uint64_t take = std::min<uint64_t>(n, cap);
+  if (take) {
+    std::vector<uint32_t> lg(take * 4ull);
+    AGX_TRY(copy_sync(e, lg.data(), e->d_topic + tp_log_off(e->nb), take * 16ull, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < take; ++i) {
+      if (out_key) out_key[i] = lg[4 * i];
+      if (out_sender) out_sender[i] = lg[4 * i + 1];
+      if (out_payload) out_payload[i] = lg[4 * i + 2];
+    }
+  }
+  if (out_n) *out_n = n;
+  return AGX_OK;
+}
+
 agx_status agx_register_services(agx_engine* e, uint64_t first_id, uint64_t count, uint32_t key, uint32_t on) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (!e->d_recep) {
@@ -4534,11 +4757,11 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     const bool askop = A.op == AGX_A_ASK_ARM || A.op == AGX_A_ASK_SEND;  // (`word` is the key)
     const bool tmop = (A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL) || askop;  // (`word` is the key)
     const bool wdop = A.op >= AGX_A_WATCH && A.op <= AGX_A_UNWATCH;  // (the ref is the d-operand)
-    const bool rcop = A.op >= AGX_A_REGISTER && A.op <= AGX_A_ROUTE;  // (`pad1` is the service key)
+    const bool rcop = (A.op >= AGX_A_REGISTER && A.op <= AGX_A_ROUTE) || A.op == AGX_A_PUBLISH;  // (`pad1` is the service key)
     if (rcop && (A.pad1 >= AGX_MAX_SERVICE_KEYS || A.pad0 > (A.op == AGX_A_ROUTE ? (AGX_ROUTE_KEEP_SENDER | AGX_ROUTE_BY_INDEX) : 0u) ||
                  (A.op == AGX_A_ROUTE && (A.pad0 & AGX_ROUTE_BY_INDEX) && !opnd_ok(A.dsrc, A.dword))))
       return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (service keys 0..7, route flags 0..3)", i);
-    if (A.op < AGX_A_SET || A.op > AGX_A_ASK_SEND || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+    if (A.op < AGX_A_SET || A.op > AGX_A_PUBLISH || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
         !opnd_ok(A.src, A.sword) ||
         ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop || A.op == AGX_A_STOP_CHILD ||
           A.op == AGX_A_SET_RECEIVE_TIMEOUT || askop) &&
@@ -4604,7 +4827,7 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     return set_err(AGX_EINVAL, "compiled behaviours: message tags 0xFD and 0xFC are reserved for Create and Stop envelopes on "
                    "an engine with children");
   // the receptionist: a route sends one envelope through the case's tell slot; the service keys the tables use
-  bool uses_recep = false;
+  bool uses_recep = false, uses_publish = false;
   uint32_t rc_keys_used = 0;
   auto rc_use = [&](uint32_t src, uint32_t word) {
     if (src != AGX_V_LISTING_SIZE && src != AGX_V_SERVICE_AT) return;
@@ -4615,11 +4838,15 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     const agx_case& C = cases[c];
     rc_use(C.src1, C.word1); rc_use(C.src2, C.word2); rc_use(C.src3, C.word3); rc_use(C.src4, C.word4);
     uint32_t sends = 0;
-    bool route = false;
+    bool route = false, publish = false;
     for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
-      sends += acts[i].op == AGX_A_TELL || acts[i].op == AGX_A_ROUTE;
+      sends += acts[i].op == AGX_A_TELL || acts[i].op == AGX_A_ROUTE || acts[i].op == AGX_A_PUBLISH;
       route |= acts[i].op == AGX_A_ROUTE;
+      publish |= acts[i].op == AGX_A_PUBLISH;
     }
+    if (publish && sends > 1u)
+      return set_err(AGX_EINVAL, "compiled behaviours: case %u holds %u of tell, route and publish; an engine with topics has "
+                     "max_emit 1", c, sends);
     if (route && sends > 1u)
       return set_err(AGX_EINVAL, "compiled behaviours: case %u holds %u of tell and route; an engine with the receptionist "
                      "has max_emit 1", c, sends);
@@ -4627,7 +4854,8 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   for (uint32_t i = 0; i < n_acts; ++i) {
     rc_use(acts[i].src, acts[i].sword);
     rc_use(acts[i].dsrc, acts[i].dword);
-    if (acts[i].op >= AGX_A_REGISTER && acts[i].op <= AGX_A_ROUTE) {
+    uses_publish |= acts[i].op == AGX_A_PUBLISH;
+    if ((acts[i].op >= AGX_A_REGISTER && acts[i].op <= AGX_A_ROUTE) || acts[i].op == AGX_A_PUBLISH) {
       uses_recep = true;
       rc_keys_used = std::max<uint32_t>(rc_keys_used, acts[i].pad1 + 1u);
     }
@@ -4703,6 +4931,7 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   e->beh_rt_tag = rt_tag;
   e->beh_recep = uses_recep;  // (checked against agx_set_receptionist at agx_run)
   e->beh_rc_keys = rc_keys_used;
+  e->beh_publish = uses_publish;  // (checked against agx_set_topics at agx_run)
   e->beh_child = uses_child;  // (checked against agx_set_children at agx_run)
   e->beh_ctl_tags = ctl_tags;
   e->beh_watch = false;  // a watch action or a signal case (checked against agx_set_death_watch at agx_run)

@@ -61,6 +61,7 @@ constexpr uint64_t kErrWatchSlots = 128;  // a watch found every slot of its act
 constexpr uint64_t kErrSuperTile = 256;  // a bucket of an engine with supervision exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrRecepTile = 512;  // a bucket of an engine with the receptionist exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrRecepCap = 1024;  // a listing would exceed the receptionist's capacity (AGX_ECAPACITY)
+constexpr uint64_t kErrTopicLog = 2048;  // a tick's publications would exceed the topics' log capacity (AGX_ECAPACITY)
 // per-block counters of k_bucket_apply: delivered, dead, unhandled, emitted, active
 constexpr int kBStats = 5;
 constexpr uint32_t kMaxApplyGrid = 4096;
@@ -1670,6 +1671,65 @@ __device__ __forceinline__ void recep_commit(const RecepDev& RD, const RecepCoun
       if (t[i]) atomicAdd(RD.ctr(i), (unsigned long long)t[i]);
   }
 }
+// the publish actions of a wave's drains: one atomic add per wave that published
+__device__ __forceinline__ void topic_commit(const TopicDev& TP, uint32_t npub) {
+  if (!__ballot(npub != 0u)) return;  // (wave-uniform)
+  const uint32_t t = wave_incl_sum(npub);
+  if (lane_id() == kWave - 1) atomicAdd(TP.ctr(kTpPublished), (unsigned long long)t);
+}
+// The tick's deliveries of bucket b, staged as the inbox's last `np` items into wk ([3][kBucket]: key, sender,
+// payload): for each entry of the pending log in order, one item per actor of the bucket whose mask bit `key` is
+// set, in ascending id (a thread holds four consecutive actors' mask bytes in one register; per key the threads'
+// counts are scanned once through `scratch`).  The count matches the bucket's due word unless a mask byte was
+// changed from outside the engine's own steps: loud then, and the missing items defined.  Block-uniform call.
+__device__ __forceinline__ void topic_stage(const BucketArgs& a, const RecepDev& RD, const TopicDev& TP, uint32_t a0, uint32_t na,
+                                            uint32_t np, uint32_t* wk, uint32_t* scratch) {
+  const uint32_t tid = threadIdx.x, la0 = tid * 4u;
+  const uint32_t nlog = min(TP.base[kTpNLog], TP.cap);
+  // (the mask array is padded to whole buckets and bytes past n_local are never set)
+  const uint32_t m4 = la0 < na ? *reinterpret_cast<const uint32_t*>(RD.mask + a0 + la0) : 0u;
+  uint32_t pre[AGX_MAX_SERVICE_KEYS], tot[AGX_MAX_SERVICE_KEYS];
+#pragma unroll
+  for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+    pre[k] = tot[k] = 0u;
+    if (k < RD.nk && TP.base[kTpPubs + k] != 0u) {  // (block-uniform)
+      pre[k] = block_excl_sum<kBThreads>((uint32_t)__popc(m4 & (0x01010101u << k)), scratch, &tot[k]);
+    }
+  }
+  const uint4* const lg = TP.log();
+  uint32_t off = 0;
+  for (uint32_t i = 0; i < nlog; ++i) {  // (every thread reads the same entries: broadcast loads)
+    const uint4 e = lg[i];
+    const uint32_t k = e.x & 7u;
+    uint32_t pk = 0, tk = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < AGX_MAX_SERVICE_KEYS; ++x) {  // (registers, no dynamic index)
+      pk = k == x ? pre[x] : pk;
+      tk = k == x ? tot[x] : tk;
+    }
+    uint32_t o = off + pk;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+      if ((m4 >> (8u * j + k)) & 1u) {
+        if (o < np) {
+          wk[o] = a0 + la0 + j;
+          wk[kBucket + o] = e.y;
+          wk[2 * kBucket + o] = e.z;
+        }
+        ++o;
+      }
+    off += tk;
+  }
+  if (off < np) {
+    if (tid == 0) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
+    for (uint32_t i = off + tid; i < np; i += kBThreads) {
+      wk[i] = a0;
+      wk[kBucket + i] = AGX_NO_SENDER;
+      wk[2 * kBucket + i] = 0u;
+    }
+  }
+  __syncthreads();
+}
 // A block in which a mask changed recounts its bucket's members per key from the bucket's mask bytes (one u32 of
 // four actors per thread: coalesced; two keys share a packed wave sum) and writes cnt[key][bucket].  `tmp`: 32 u32
 // of LDS free after the drains.  Block-uniform call, after the barrier that follows the drains.
@@ -1775,6 +1835,14 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
   static_assert(!kRc || (kLds && !kWide && !kOwner && !kStash && !kTm && !kWd && !kSv), "receptionist: single-rank fast launches, plain behaviours");
   RecepDev RD{};
   if constexpr (kRc) RD = recep_dev(P.recep);
+  // kTp: pub-sub topics (agx_set_topics), on top of the receptionist.  The tick's deliveries are
+  // the inbox's last items (k_bucket_apply put them there); compiled cases publish into the tick's staging area
+  // (k_topic_plan, after the apply, turns it into the next tick's log and due counts).
+  constexpr bool kTp = (KM & kTopicKM) != 0;
+  static_assert(!kTp || kRc, "topics: on the receptionist instantiations only");
+  TopicDev TP{};
+  uint32_t npub = 0;  // kTp: this thread's publish actions
+  if constexpr (kTp) TP = topic_dev_of(P.recep);
   uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
   auto ikey = [&](uint32_t q) -> uint32_t { return kLds ? L.key[q] : a.scr.key[lo + q]; };
@@ -2606,6 +2674,29 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
             break;
           }
         }
+      } else if constexpr (kTp) {
+        // the receptionist's drain (below) with compiled_apply_tp: a publish knows its index within the window
+        const uint32_t mk0 = (rcm4 >> (8 * j)) & 0xFFu;
+        uint32_t mk = mk0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          const uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_tp(P, RD, TP, kcur, self, wv, sv, pv, mk, rcc, q, npub, em)
+                                                       : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          ++ndel;
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            rcc.term += (uint32_t)__popc(mk);  // SubscriberTerminated / RegisteredActorTerminated
+            mk = 0u;
+            break;
+          }
+        }
+        if (mk != mk0) {
+          RD.mask[l] = (uint8_t)mk;
+          rcc.chg |= mk ^ mk0;
+        }
       } else if constexpr (kRc) {
         // the plain drain with compiled_apply_rc: the actor's key mask lives in a register across the window and is
         // stored once, only if it changed (the net change is what moves a version); a stop clears every bit
@@ -2697,6 +2788,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     }
     if constexpr (kAsk) ask_commit(AD, acn);
     if constexpr (kRc) recep_commit(RD, rcc, L.rowtop);
+    if constexpr (kTp) topic_commit(TP, npub);
     __syncthreads();
     if constexpr (kRc)  // (block-uniform; U is free: the state words were written back)
       if (*L.rowtop) recep_recount(RD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));
@@ -5062,6 +5154,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
   // receptionist.  The inbox is the plain one, and a bucket never takes the skew launch.
   constexpr bool kRc = (KM & kRecepKM) != 0;  // (a flag of KM: agx_device.h)
   static_assert(!kRc || (!kWide && !kSkew && !kOwner && !kPrio && !kStash && !kTm && !kWd && !kSv), "receptionist: single-rank fast launches, plain behaviours");
+  // kTp: pub-sub topics (agx_set_topics), on top of the receptionist.  A bucket's inbox then ends
+  // with the deliveries of the pending log (written here from the log and the bucket's own mask bytes, in log order
+  // and ascending id), and its backlog count carries their number (k_topic_plan, after the apply before).
+  constexpr bool kTp = (KM & kTopicKM) != 0;  // (a flag of KM: agx_device.h)
+  static_assert(!kTp || kRc, "topics: on the receptionist instantiations only");
   if (kOwner && a.halt && a.halt[0]) return;  // (device-resident multi-rank replay stopped)
   // key/src/pay carved from one array: group_tells reuses key+src as a 16 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t s_ksp[3 * kBucket];
@@ -5219,6 +5316,13 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
                 s_lo = s_hi = 0u;
               }
             }
+            if constexpr (kTp) {  // the backlog count carries the log's deliveries: [backlog][mail][deliveries]
+              const uint32_t np = min(*topic_dev_of(P.recep).due(b), blc);
+              s_rowtop = np;
+              s_g[0] = blc - np;
+              if (s_hi - s_lo > (uint32_t)kBucket) s_rowtop = 0u;  // (the error below: the bucket's mail dropped)
+              if (s_hi != s_lo) topic_dev_of(P.recep).base[kTpMail] = 1u;  // (this superstep is a tick)
+            }
             if constexpr (kRc) {
               if (s_hi - s_lo > (uint32_t)kBucket) {  // the skew launches know no receptionist: loud, the bucket's mail dropped
                 atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrRecepTile);
@@ -5288,6 +5392,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           s_rowtop = np;
           s_g[0] -= np;
         }
+        if constexpr (kTp) {  // (as the multi-pass launch above)
+          const uint32_t np = min(*topic_dev_of(P.recep).due(b), s_g[0]);
+          s_rowtop = np;
+          s_g[0] -= np;
+        }
         s_g[1] = g.blo[rpar][b];
         s_g[2] = g.stg_cnt[b];
         s_g[3] = g.stg_off[b];
@@ -5326,6 +5435,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
             atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrSuperTile);
             tt = 0u - blc - s_g[2];  // (cnt = 0 below)
           }
+        }
+        if constexpr (kTp) {  // (the log's deliveries are part of the inbox; tt is not read again)
+          tt += s_rowtop;
+          if (blc + tt + s_g[2] > (uint32_t)kBucket) s_rowtop = 0u;  // (the error below: the bucket's mail dropped)
+          else if (blc + tt + s_g[2] != 0u) topic_dev_of(P.recep).base[kTpMail] = 1u;  // (this superstep is a tick)
         }
         if constexpr (kRc) {
           if (blc + tt + s_g[2] > (uint32_t)kBucket) {  // the skew launches know no receptionist: loud, the bucket's mail dropped
@@ -5645,6 +5759,13 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           __syncthreads();
         }
       }
+      // kTp: the inbox's last np items are the deliveries of the pending log, in (log entry, actor) order (the stable
+      // sort leaves them at the tail of each actor's segment, in log order), staged here from the log
+      if constexpr (kTp) {
+        const uint32_t np = s_rowtop;
+        if (np)  // (block-uniform)
+          topic_stage(a, recep_dev(P.recep), topic_dev_of(P.recep), a0, na, np, reinterpret_cast<uint32_t*>(U), scratch);
+      }
       {  // locate every item first (LDS only), then issue all 3 x kBIpt loads back to back: selected
          // base pointers and no branches around the loads (per-item if/else made the compiler wait
          // for each item's loads before the next item's: 8 dependent round trips instead of 1)
@@ -5654,6 +5775,18 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           const uint32_t q = wbase + r * kWave + lane;
           sel[r] = 0;
           idx[r] = 0;
+          if constexpr (kTp) {  // (the last s_rowtop items are the log's deliveries, filled in below)
+            if (q < cnt - s_rowtop) {
+              if (kGather) {
+                idx[r] = gv.locate(q, sel[r]);
+              } else if (q < xblc) {
+                idx[r] = xblo + q;
+              } else {
+                sel[r] = 1;
+                idx[r] = iv.at(xbst + q - xblc);
+              }
+            }
+          } else
           if constexpr (kTm || kWd) {  // (the last s_rowtop items are the TimerMsgs / Terminated envelopes, filled in below)
             if (q < cnt - s_rowtop) {
               if (kGather) {
@@ -5740,6 +5873,19 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
             }
           }
         }
+        if constexpr (kTp) {
+          const uint32_t nm = cnt - s_rowtop;
+          const uint32_t* const wk = reinterpret_cast<const uint32_t*>(U);
+#pragma unroll
+          for (int r = 0; r < kBIpt; ++r) {
+            const uint32_t q = wbase + r * kWave + lane;
+            if (q >= nm && q < cnt) {
+              k[r] = wk[q - nm];
+              sv[r] = wk[kBucket + q - nm];
+              pv[r] = wk[2 * kBucket + q - nm];
+            }
+          }
+        }
         if constexpr (kTm || kWd) {
           const uint32_t nm = cnt - s_rowtop;
           const uint32_t* const wk = reinterpret_cast<const uint32_t*>(U);
@@ -5756,6 +5902,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
       }
       if (kLateAlive) reinterpret_cast<uint32_t*>(s_alive)[tid] = alive4;
       __syncthreads();  // (fused) the segment list in s_pay is read before the items overwrite it
+      if constexpr (kTp)  // (every thread has read the count: the word is the drains' "a mask changed" mark again)
+        if (tid == 0) s_rowtop = 0u;
       // in-order copy + sortedness check: local topologies (rings, stencils) arrive already in
       // actor order, and then the wave multisplit ranking is unnecessary (same result)
       for (uint32_t i = tid; i < kBucket + 4; i += kBThreads) s_seg[i] = 0;

@@ -437,6 +437,33 @@ class GpuEngine:
         d["version"] = [int(x) for x in version]
         return d
 
+    def set_topics(self, log_capacity: int = 1024) -> None:
+        """agx_set_topics (after set_receptionist, before the first run): the engine's service keys are pub-sub topics
+        as well; compiled behaviours may then context.publish, at most `log_capacity` (1..65536) publications per
+        tick."""
+        check(self.lib.agx_set_topics(self._h, log_capacity))
+
+    def publish(self, key: int, payload: int, sender: int = NO_SENDER) -> None:
+        """agx_publish: a publication from the host to topic number `key`, delivered in the next tick to every
+        subscriber, after the device's own publications of the tick before."""
+        check(self.lib.agx_publish(self._h, key, sender, payload))
+
+    TOPIC_INFO = ("published", "fanned_out", "no_subscribers", "host_published")
+
+    def topic_info(self) -> dict:
+        """agx_topic_info: totals published / fanned_out / no_subscribers / host_published."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        check(self.lib.agx_topic_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(self.TOPIC_INFO, (int(x.value) for x in v)))
+
+    def read_topic_log(self) -> np.ndarray:
+        """agx_read_topic_log: the pending log, one (key, sender, payload) row per publication, in delivery order."""
+        n = ctypes.c_uint64()
+        check(self.lib.agx_read_topic_log(self._h, None, None, None, 0, ctypes.byref(n)))
+        k, s, p = (np.zeros(max(int(n.value), 1), np.uint32) for _ in range(3))
+        check(self.lib.agx_read_topic_log(self._h, *(_ptr(x, ctypes.c_uint32) for x in (k, s, p)), int(n.value), ctypes.byref(n)))
+        return np.stack([k, s, p], axis=1)[:int(n.value)]
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""

@@ -42,6 +42,10 @@ What lowers:
     ``context.ask_pending(key)`` inside ``Behaviors.with_timers`` (the ask pattern on the timers engine, DESIGN.md
     §2.9): an ask takes a timer key and lowers to ``A_ASK_ARM`` + ``A_ASK_SEND``; ``Tables.uses_ask`` ->
     engine.set_ask(), after engine.set_timers(Tables.timer_keys);
+  * ``Topic(name)``, ``context.subscribe(topic)`` / ``unsubscribe(topic)``, ``context.publish(topic, msg)`` and
+    ``context.subscriber_count(topic)`` (pub-sub topics on the receptionist's engine): a topic is
+    numbered with the ServiceKeys, subscribing lowers to ``A_REGISTER``, and a case holds at most one of tell, route
+    and publish; ``Tables.uses_topics`` -> engine.set_topics(log_capacity), after engine.set_receptionist;
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -96,6 +100,7 @@ SVC_WORD0, SVC_WORD1, SVC_ARG, SVC_CONST = 0, 1, 2, 3  # V_SERVICE_AT's selector
 A_REGISTER, A_DEREGISTER, A_ROUTE = 17, 18, 19     # the service key is pad1
 ROUTE_KEEP_SENDER, ROUTE_BY_INDEX = 1, 2           # pad0 of A_ROUTE (KEEP_SENDER also of A_TELL: ref.forward)
 A_ASK_ARM, A_ASK_SEND = 20, 21                     # context.ask: `word` is the timer key
+A_PUBLISH = 22                                     # context.publish: the topic's key is pad1
 # the ask ref a target sees as the sender: ASK_REF_BIT | key << 29 | (generation mod 2^7) << 22 | the asker's id
 ASK_REF_BIT, ASK_REF_KEY_SHIFT, ASK_REF_GEN_SHIFT, ASK_REF_GEN_MASK, ASK_REF_ID_MASK = 1 << 31, 29, 22, 0x7F, (1 << 22) - 1
 ASK_MAX_ACTORS = (1 << 22) - 1
@@ -291,6 +296,14 @@ class MessageType:
 class ServiceKey:
     """ServiceKey[T](id) (TY/receptionist/Receptionist.scala): names a service; keys with the same name are the
     same key.  The lowering numbers the keys in use, at most MAX_SERVICE_KEYS, in order of first appearance."""
+    name: str
+
+
+@dataclass(frozen=True)
+class Topic:
+    """Topic[T](name) (TY/pubsub/Topic.scala; TopicImpl.scala:60-143): names a pub-sub topic; topics with the same
+    name are the same topic.  A topic is a service key of its own (the reference's topicServiceKey): the lowering
+    numbers topics and ServiceKeys together, at most MAX_SERVICE_KEYS of both, in order of first appearance."""
     name: str
 
 
@@ -640,6 +653,36 @@ class ActorContext:
         """Routing by index: the routee is listing[index mod size] -- the same index reaches the same routee while the
         listing stands (the modulo stand-in for consistent hashing)."""
         return self._route(key, msg, 0, lift(index), ROUTE_BY_INDEX | (ROUTE_KEEP_SENDER if forward else 0))
+
+
+    # pub-sub topics (engine.set_topics after engine.set_receptionist; TY/internal/pubsub/TopicImpl.scala:60-143)
+    @staticmethod
+    def _topic(topic) -> Topic:
+        if not isinstance(topic, Topic):
+            raise CompileError(f"not a Topic: {topic!r}")
+        return topic
+
+    def subscribe(self, topic) -> "Action":
+        """topic ! Topic.Subscribe(context.self): the actor receives what is published from this tick on (a
+        publication of this very tick included).  Idempotent; a stop unsubscribes."""
+        return Action(A_REGISTER, 0, key=self._topic(topic))
+
+    def unsubscribe(self, topic) -> "Action":
+        """topic ! Topic.Unsubscribe(context.self): the publications of this tick no longer reach the actor."""
+        return Action(A_DEREGISTER, 0, key=self._topic(topic))
+
+    def publish(self, topic, msg) -> "Action":
+        """topic ! Topic.Publish(msg): every subscriber receives `msg` in the next tick, with this actor as its
+        sender.  It is the case's one envelope: a case holds at most one of tell, route and publish."""
+        if isinstance(msg, Message):
+            val, mask = msg.arg, msg.or_mask
+        else:
+            val, mask = lift(msg), 0
+        return Action(A_PUBLISH, 0, val, None, mask, key=self._topic(topic))
+
+    def subscriber_count(self, topic) -> Operand:
+        """The topic's subscribers as of the end of the tick before (Topic.GetTopicStats, read synchronously)."""
+        return _KeyOperand(V_LISTING_SIZE, 0, 0, self._topic(topic), 0)
 
 
 context = ActorContext()
@@ -1031,6 +1074,12 @@ class Tables:
         return bool(self.service_keys) or self.uses_forward
 
     @property
+    def uses_topics(self) -> bool:
+        """The behaviours publish or name a Topic: the engine needs engine.set_topics(log_capacity) after
+        engine.set_receptionist(len(tables.service_keys), capacity)."""
+        return any(isinstance(k, Topic) for k in self.service_keys) or any(a.op == A_PUBLISH for a in self.acts[:self.n_acts])
+
+    @property
     def stash_capacity(self) -> int:
         """The largest capacity of the stash buffers these behaviours use (0: none): the stash the
         actors' mailbox class needs (engine.set_stash)."""
@@ -1309,6 +1358,10 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
             if n > 1:
                 raise CompileError(f"a case holds {n} of tell and route: each sends one envelope, and an engine with the "
                                    "receptionist has max_emit 1")
+            p = sum(1 for j in range(c.act_first, c.act_first + c.act_count) if acts[j].op == A_PUBLISH)
+            if p and n + p > 1:
+                raise CompileError(f"a case holds {n + p} of tell, route and publish: a publication is the case's one "
+                                   "envelope, and an engine with topics has max_emit 1")
     if max_emit is not None and t.max_tells > max(1, max_emit):
         raise CompileError(f"a case tells {t.max_tells} times per message but max_emit is {max_emit}")
     return t

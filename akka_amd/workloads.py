@@ -68,6 +68,9 @@ class Workload:
     # the receptionist (agx_set_receptionist / agx_register_services): {"n_keys": k, "capacity": ids per listing,
     # "starts": [(first, count, key)]} -- empty: no receptionist
     receptionist: dict = field(default_factory=dict)
+    # pub-sub topics (agx_set_topics, on top of `receptionist`): {"log_capacity": publications per tick} -- empty: no
+    # topics
+    topics: dict = field(default_factory=dict)
     # host tells that follow the clock: schedule[t] = (dst, src, payload) is staged before tick t + 1 (run_schedule)
     schedule: list = field(default_factory=list)
 
@@ -105,6 +108,8 @@ class Workload:
             target.set_receptionist(self.receptionist["n_keys"], self.receptionist["capacity"])
             for first, count, key in self.receptionist.get("starts", ()):
                 target.register_services(first, count, key)
+        if self.topics:  # (empty: targets without the call are unaffected)
+            target.set_topics(self.topics["log_capacity"])
         if self.timers:  # (empty: targets without the calls are unaffected)
             target.set_timers(self.timers["n_keys"])
             if self.timers.get("ask"):  # (the ask pattern, on top of the timers: agx_set_ask)
@@ -1210,3 +1215,105 @@ def service_mesh(n: int = 4096, n_keys: int = 8, seed: int = 1, ticks: int = 40,
     return Workload("service_mesh", n, 2, 1, throughput, capacity, [(0, n, tb.kind_of(node), init)], behaviors=tb,
                     bucket_actors=bucket_actors, outbound=(n, max(n_host, 1)),
                     receptionist={"n_keys": n_keys, "capacity": n, "starts": starts}, schedule=schedule)
+
+
+# ------------------------------------------------------------------ pub-sub topics
+TB_TICK, TB_NOTE = 1, 2
+TM_SUB, TM_UNSUB, TM_STOP, TM_PUB, TM_COUNT, TM_NOTE, TM_SUBPUB, TM_PUBUNSUB = 1, 2, 3, 4, 5, 6, 7, 8
+
+
+def topic_broadcast(n_publishers: int = 1, n_subscribers: int = 1 << 14, n_topics: int = 1, period: int = 1, ticks: int = 16,
+                    throughput: int = 3, bucket_actors: int = 0, log_capacity: int = 1024) -> Workload:
+    """Topic broadcast (TopicImpl.scala:60-143): publisher p (ids 0 .. n_publishers - 1) publishes Note(t) to topic
+    p mod n_topics whenever the host schedule ticks it, every `period`-th tick; the subscribers (ids n_publishers ..)
+    are subscribed in the setup block, the k-th block of n_subscribers / n_topics ids to topic k; a subscriber counts
+    what it receives (state word 0) and sums the arguments (state word 1).  One publication then becomes n_subscribers / n_topics envelopes in the next tick."""
+    from . import typed
+    B, ctx = typed.Behaviors, typed.context
+    topics = [typed.Topic(f"topic{k}") for k in range(n_topics)]
+    tick, note = typed.MessageType("Tick", TB_TICK), typed.MessageType("Note", TB_NOTE)
+    ps = typed.State("sent", "topic")
+    rb = typed.ReceiveBuilder.create(ps)
+    for k, tp in enumerate(topics):
+        rb.on_message(tick, (lambda tp: lambda m, s: [s.sent.inc(), ctx.publish(tp, note(m.arg)), B.same])(tp),
+                      when=(lambda k: lambda m, s: s.topic == k)(k))
+    rb.on_any_message(lambda m, s: [B.unhandled])
+    publisher = rb.build("topic_publisher")
+    ss = typed.State("count", "sum")
+    subscriber = (typed.ReceiveBuilder.create(ss)
+                  .on_message(note, lambda m, s: [s.count.inc(), s.sum.add(m.arg), B.same])
+                  .on_any_message(lambda m, s: [B.unhandled])
+                  .build("topic_subscriber"))
+    tb = typed.compile_behaviors([publisher, subscriber], max_emit=1)
+    n = n_publishers + n_subscribers
+    pinit = np.zeros((n_publishers, 2), np.uint64)
+    pinit[:, 1] = np.arange(n_publishers, dtype=np.uint64) % n_topics
+    dst = np.arange(n_publishers, dtype=np.uint32)
+    none = np.zeros(0, np.uint32)
+    schedule = [(dst, np.full(n_publishers, NO_SENDER, np.uint32), np.full(n_publishers, tick.payload(t + 1), np.uint32))
+                if t % period == 0 else (none, none, none) for t in range(ticks)]
+    per = n_subscribers // n_topics
+    starts = [(n_publishers + k * per, per if k < n_topics - 1 else n_subscribers - k * per, k) for k in range(n_topics)]
+    return Workload("topic_broadcast", n, 2, 1, throughput, 0,
+                    [(0, n_publishers, tb.kind_of(publisher), pinit), (n_publishers, n_subscribers, tb.kind_of(subscriber), None)],
+                    behaviors=tb, bucket_actors=bucket_actors,
+                    receptionist={"n_keys": n_topics, "capacity": n_subscribers, "starts": starts},
+                    topics={"log_capacity": log_capacity}, schedule=schedule)
+
+
+def topic_mesh(n: int = 1024, n_keys: int = 8, seed: int = 1, ticks: int = 40, throughput: int = 3, capacity: int = 4,
+               bucket_actors: int = 64, n_host: int = 4, log_capacity: int = 1024) -> Workload:
+    """The differential workload of the topics: every actor runs one behaviour that, on host messages, subscribes to
+    or unsubscribes from topic (arg mod n_keys), stops, publishes Note(its count) to the topic, subscribes and
+    publishes or publishes and unsubscribes in one case, or reports the topic's subscriber count to the message's
+    sender; a Note is counted (state word 0) and its payload kept (state word 1: order-sensitive).  The host schedule
+    draws, per tick, random actors for each of these; a few actors are subscribed in the setup block, and topic
+    n_keys - 1 is only ever published to, so some publications find no subscriber.  Bounded mailboxes (`capacity`)
+    turn the deliveries past a subscriber's capacity into dead letters and keep a bucket's inbox within one tile."""
+    from . import typed
+    B, ctx = typed.Behaviors, typed.context
+    topics = [typed.Topic(f"mesh{k}") for k in range(n_keys)]
+    st = typed.State("count", "last")
+    note = typed.MessageType("Note", TM_NOTE)
+    rb = typed.ReceiveBuilder.create(st)
+    tag = lambda t: (lambda m: m.tag == t)
+    rb.on_any_message(lambda m, s: [s.count.inc(), B.stopped], test=tag(TM_STOP))
+    rb.on_any_message(lambda m, s: [s.count.inc(), s.last.set(m.payload), B.same], test=tag(TM_NOTE))
+    for k, tp in enumerate(topics):
+        arg = (lambda k: (lambda m, s: m.arg == k))(k)
+        rb.on_any_message((lambda tp: lambda m, s: [ctx.subscribe(tp), B.same])(tp), test=tag(TM_SUB), when=arg)
+        rb.on_any_message((lambda tp: lambda m, s: [ctx.unsubscribe(tp), B.same])(tp), test=tag(TM_UNSUB), when=arg)
+        rb.on_any_message((lambda tp: lambda m, s: [ctx.publish(tp, note(s.count)), B.same])(tp), test=tag(TM_PUB), when=arg)
+        rb.on_any_message((lambda tp: lambda m, s: [ctx.subscribe(tp), ctx.publish(tp, note(s.count + 1)), B.same])(tp),
+                          test=tag(TM_SUBPUB), when=arg)
+        rb.on_any_message((lambda tp: lambda m, s: [ctx.publish(tp, note(s.count + 2)), ctx.unsubscribe(tp), B.same])(tp),
+                          test=tag(TM_PUBUNSUB), when=arg)
+        rb.on_any_message((lambda tp: lambda m, s: [m.sender.tell(ctx.subscriber_count(tp)), B.same])(tp),
+                          test=tag(TM_COUNT), when=arg)
+    rb.on_any_message(lambda m, s: [B.unhandled])
+    node = rb.build("topic_mesh_node")
+    tb = typed.compile_behaviors([node], max_emit=1)
+    rng = np.random.default_rng(seed)
+    nsub = max(n_keys - 1, 1)  # (the last topic has no subscriber)
+    per = {TM_SUB: max(n // 64, 1), TM_UNSUB: max(n // 128, 1), TM_STOP: max(n // 256, 1), TM_PUB: max(n // 256, 2),
+           TM_SUBPUB: 1, TM_PUBUNSUB: 1, TM_COUNT: max(n // 256, 1)}
+    schedule = []
+    for t in range(ticks):
+        dst, pay = [], []
+        for tg, cnt in per.items():
+            if tg == TM_SUB and t >= ticks * 3 // 4:  # (the tail: the topics only lose subscribers)
+                continue
+            d = rng.integers(0, n, cnt)
+            dst.append(d)
+            keys = rng.integers(0, n_keys if tg == TM_PUB else nsub, cnt)
+            pay.append((tg << 24) | keys)
+        dst = np.concatenate(dst).astype(np.uint32)
+        o = rng.permutation(dst.size)
+        src = (n + rng.integers(0, max(n_host, 1), dst.size)).astype(np.uint32)
+        schedule.append((dst[o], src[o], np.concatenate(pay).astype(np.uint32)[o]))
+    cnt0 = max(n // (16 * n_keys), 1)
+    starts = [(int(f), cnt0, k) for k, f in enumerate(rng.integers(0, n - cnt0, nsub))]
+    return Workload("topic_mesh", n, 2, 1, throughput, capacity, [(0, n, tb.kind_of(node), None)], behaviors=tb,
+                    bucket_actors=bucket_actors, outbound=(n, max(n_host, 1)),
+                    receptionist={"n_keys": n_keys, "capacity": n, "starts": starts},
+                    topics={"log_capacity": log_capacity}, schedule=schedule)

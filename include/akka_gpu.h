@@ -202,7 +202,12 @@ enum agx_action_op {
    * by pad1 (the adapt tag).  SEND: a TELL's layout with `word` = the key; its envelope carries the ask ref as the
    * sender.  It is the case's one envelope: a case holds at most one of TELL and ASK_SEND. */
   AGX_A_ASK_ARM = 20,    /* context.ask: the promise ref and its timeout task (AskPattern.scala:109-162) */
-  AGX_A_ASK_SEND = 21    /* context.ask: target ! createRequest(ref) (ActorContextImpl.scala:203-218) */
+  AGX_A_ASK_SEND = 21,   /* context.ask: target ! createRequest(ref) (ActorContextImpl.scala:203-218) */
+  /* Pub-sub topics (engines with topics, agx_set_topics).  PUBLISH is topic ! Publish(msg): pad1 is
+   * the key (the topic), pad0 must be 0, the payload is the operand as a TELL's, there is no destination.  The
+   * envelope every subscriber receives in the next tick carries the publisher as its sender.  A case holds at most
+   * one of TELL, ROUTE and PUBLISH. */
+  AGX_A_PUBLISH = 22     /* topic ! Topic.Publish(msg) (TopicImpl.scala:60-143) */
 };
 /* The ask ref: AGX_ASK_REF_BIT | key << 29 | (generation mod 2^7) << 22 | the asker's id. */
 #define AGX_ASK_REF_BIT 0x80000000u
@@ -880,6 +885,36 @@ agx_status agx_read_services(agx_engine* eng, uint64_t first, uint64_t count, ui
 agx_status agx_receptionist_info(agx_engine* eng, uint64_t* routed, uint64_t* no_routees, uint64_t* registered,
                                  uint64_t* deregistered, uint64_t* terminated, uint64_t* rebuilds, uint32_t size[8],
                                  uint64_t version[8]);
+
+/* Pub-sub topics (akka.actor.typed.pubsub.Topic: TY/internal/pubsub/TopicImpl.scala:60-143; pinned by
+ * LocalPubSubSpec.scala:20-50,95-156; DESIGN.md 2.10 has the contract), on top of the receptionist: call after
+ * agx_set_receptionist and before the first agx_run (AGX_ESTATE afterwards); a second call and a call without the
+ * receptionist are AGX_EINVAL.  The engine's service keys are topics as well: subscribing is registering
+ * (AGX_A_REGISTER / AGX_A_DEREGISTER, agx_register_services; a stop unsubscribes), AGX_V_LISTING_SIZE is the
+ * subscriber count.  The publications of tick s (AGX_A_PUBLISH, agx_publish) are delivered in tick s + 1, each to
+ * every actor whose bit `key` is set when the inbox of tick s + 1 is formed (the publisher included, if subscribed),
+ * as the last items of the inbox: device publications in (publisher id, index within its drained window) order,
+ * then host publications in call order.  Admission is unchanged; the sender of a delivery is the publisher.
+ * A tick holds at most log_capacity publications (1..65536; one more raises a sticky AGX_ECAPACITY); a bucket's
+ * inbox, deliveries included, is limited to one tile of 2048 messages as on every engine with the receptionist.
+ * Conservation: staged + emitted + fanned_out = delivered + dead_letters + in_flight; planned deliveries are in
+ * flight, and an engine with any pending is not quiescent. */
+#define AGX_MAX_TOPIC_LOG 65536u
+agx_status agx_set_topics(agx_engine* eng, uint32_t log_capacity);
+/* topic ! Publish(msg) from the host, before the first run or between runs: appended to the log the next tick
+ * delivers, after any publication the device left there.  `sender` may be AGX_NO_SENDER.  AGX_EINVAL on an engine
+ * without topics or for a key the receptionist does not have. */
+agx_status agx_publish(agx_engine* eng, uint32_t key, uint32_t sender, uint32_t payload);
+/* Totals since agx_create: published (AGX_A_PUBLISH actions run), fanned_out (delivery envelopes created),
+ * no_subscribers (publications that found no recipient: the reference's Dropped; neither dead letters nor emitted),
+ * host_published (agx_publish calls applied).  A re-plan after agx_register_services between a publication and its
+ * delivery corrects fanned_out and no_subscribers.  Any pointer may be NULL; zeros on an engine without topics. */
+agx_status agx_topic_info(agx_engine* eng, uint64_t* published, uint64_t* fanned_out, uint64_t* no_subscribers,
+                          uint64_t* host_published);
+/* The pending log (the publications the next tick delivers), in delivery order: up to `cap` entries into out_key /
+ * out_sender / out_payload (each may be NULL), their number into out_n. */
+agx_status agx_read_topic_log(agx_engine* eng, uint32_t* out_key, uint32_t* out_sender, uint32_t* out_payload,
+                              uint64_t cap, uint64_t* out_n);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
