@@ -120,6 +120,10 @@ SIGNATURES = {
     "agx_publish": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "agx_topic_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 4),
     "agx_read_topic_log": (ctypes.c_int32, [ctypes.c_void_p, c_u32p, c_u32p, c_u32p, ctypes.c_uint64, c_u64p]),
+    "agx_set_listings": (ctypes.c_int32, [ctypes.c_void_p, c_u32p, ctypes.c_uint32]),
+    "agx_subscribe_listings": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
+    "agx_listing_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 4),
+    "agx_read_subscriptions": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_u8p, c_u8p]),
     "agx_set_outbound": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "agx_take_outbound": (ctypes.c_int32, [ctypes.c_void_p, c_u32p, c_u32p, c_u32p, ctypes.c_uint64, c_u64p]),
     "agx_set_gossip": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]),

@@ -735,6 +735,8 @@ constexpr uint32_t kRecepKM = 1u << 24;
 constexpr uint32_t kAskKM = 1u << 23;
 // KM flag (not a kind): the variant knows pub-sub topics (agx_set_topics); only ever combined with kRecepKM.
 constexpr uint32_t kTopicKM = 1u << 22;
+// KM flag (not a kind): the variant knows Subscribe / Listing (agx_set_listings); only ever with kRecepKM | kTopicKM.
+constexpr uint32_t kListKM = 1u << 21;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -1284,6 +1286,8 @@ struct RecepCount {
 // `mk` (a register of the drain) and the listings in force.  A forward (AGX_ROUTE_KEEP_SENDER) emits with the
 // emitter's `self` replaced by the message's sender for that one call.  A function of its own: every other
 // instantiation compiles compiled_apply as before.
+// (compiled_apply_rc's cases are copied into compiled_apply_tp and compiled_apply_ls below: a fix to the set, tell,
+// route or register cases belongs in all three.)
 __device__ __forceinline__ uint64_t rc_operand(const RecepDev& RD, uint32_t src, uint32_t word, int64_t k, uint32_t pay,
                                                const uint64_t* w, uint32_t sender, uint32_t self) {
   if (src == AGX_V_LISTING_SIZE) return (uint64_t)RD.size(word & 7u) + (uint64_t)k;
@@ -1427,6 +1431,8 @@ __device__ __forceinline__ TopicDev topic_dev_of(const uint32_t* recep) {
 // emitter; an entry past log_capacity is not stored (k_topic_plan raises the error from the cursor).  `npub`: the
 // thread's publish actions, added to the counter once per wave (topic_commit).  A function of its own: every other
 // instantiation compiles compiled_apply_rc as before.
+// (The set / tell / route / register / publish cases stand in three copies: compiled_apply_rc, this one and
+// compiled_apply_ls.  A fix to one of them belongs in all three.)
 template <typename Emit>
 __device__ __forceinline__ uint32_t compiled_apply_tp(const DevParams& P, const RecepDev& RD, const TopicDev& TP, uint32_t& kind,
                                                       uint32_t self, uint64_t* w, uint32_t src, uint32_t pay, uint32_t& mk,
@@ -1470,6 +1476,185 @@ __device__ __forceinline__ uint32_t compiled_apply_tp(const DevParams& P, const 
           ++npub;
           break;
         }
+        case AGX_A_TELL:
+        case AGX_A_ROUTE: {
+          uint64_t d = 0;
+          if (A.op == AGX_A_TELL || (A.pad0 & AGX_ROUTE_BY_INDEX)) {
+            if (A.dsrc == AGX_V_SELF && A.op == AGX_A_TELL) {  // (self + dk) mod n: ring neighbours
+              int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+              d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+            } else {
+              d = rc_operand(RD, A.dsrc, A.dword, A.dk, pay, w, src, self);
+            }
+          }
+          uint32_t ref = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
+          if (A.op == AGX_A_ROUTE) {
+            const uint32_t key = A.pad1 & 7u;
+            if (A.pad0 & AGX_ROUTE_BY_INDEX) {
+              ref = RD.at(key, d);
+            } else {
+              ref = RD.successor(key, w[A.word & 1u]);
+              if (ref != kRcNone) w[A.word & 1u] = (uint64_t)ref + 1ull;  // (no routee: the cursor stays)
+            }
+            if (ref == kRcNone) ++rc.none;
+            else ++rc.routed;
+          }
+          if (A.pad0 & AGX_ROUTE_KEEP_SENDER) {  // a forward: the envelope keeps the incoming message's sender
+            const uint32_t me = emit.self;
+            emit.self = src;
+            emit(ref, msg);
+            emit.self = me;
+          } else {
+            emit(ref, msg);
+          }
+          break;
+        }
+        default: break;
+      }
+    }
+    if (C.result == AGX_RES_BECOME) {
+      kind = AGX_KIND_COMPILED + C.next;
+      return AGX_RES_SAME;
+    }
+    return C.result;
+  }
+  return AGX_RES_UNHANDLED;
+}
+
+// ---- Receptionist.Subscribe / Find and the Listing message (agx_set_listings; TY/internal/
+// receptionist/LocalReceptionist.scala:152-171,209-220,233-238), on top of topics.  An allocation of its own whose
+// address stands in words [kRcListPtr, kRcListPtr + 2) of the receptionist's storage, u32 units:
+//   [0] n_keys   [1] nb   [2] bb
+//   [4] mail: a bucket had mail in this superstep (it is a tick)   [5] changed: bit k = the Listings of the next
+//       tick announce a change of key k   [6] pend: a pending bit was set since the last plan   [7] planned: the
+//       standing plan holds deliveries (words [16..19] are not zero)   (one 16-byte load: k_listing_plan)
+//   [8..15]  four u64 counters: subscribes, finds, listings_sent, notified
+//   [16..19] two u64: what the standing plan added to listings_sent / notified (a re-plan takes it back)
+//   [24..31] payload[k]: the payload of a Listing envelope of key k
+//   [32..47] eight u64 seen[k]: the version of key k at the start of the host's calls between two runs (a key whose
+//       version differs at their end was changed by them: the re-plan adds it to `changed` once)
+//   [kLsDueOff + b]  due: the Listings planned for bucket b, part of the bucket's backlog count
+//   then cnt_u[k * nb + b]: the actors of bucket b with bit k of sub | pending, then cnt_p[k * nb + b]: with bit k of
+//   pending (both written by the bucket's own block), then one `sub` byte per actor (nb << bb of them), then one
+//   `pending` byte per actor.
+// Only an actor's own lane, or its bucket's block while it forms the inbox, writes its two bytes; k_listing_plan
+// (after the apply) reads the counts and writes `due`, `changed` and `seen`.
+constexpr uint32_t kRcListPtr = 6;
+constexpr uint32_t kLsMail = 4, kLsChanged = 5, kLsPend = 6, kLsPlanned = 7, kLsCtr = 8, kLsLast = 16, kLsPayload = 24,
+                   kLsSeen = 32, kLsDueOff = 48;
+constexpr uint32_t kLsSubscribes = 0, kLsFinds = 1, kLsSent = 2, kLsNotified = 3;
+__host__ __device__ __forceinline__ size_t ls_cnt_off(uint32_t nb) { return ((size_t)kLsDueOff + nb + 3u) & ~(size_t)3; }
+__host__ __device__ __forceinline__ size_t ls_mask_off(uint32_t nk, uint32_t nb) { return ls_cnt_off(nb) + 2ull * nk * nb; }
+__host__ __device__ __forceinline__ size_t ls_words(uint32_t nk, uint32_t nb, uint32_t bb) {
+  return ((ls_mask_off(nk, nb) + 3u) & ~(size_t)3) + 2ull * (((size_t)nb << bb) / 4u);
+}
+struct ListDev {
+  uint32_t* base;
+  uint8_t *sub, *pend;  // [nb << bb] each
+  uint32_t nk, nb;
+  __device__ __forceinline__ uint32_t* due(uint32_t b) const { return base + kLsDueOff + b; }
+  __device__ __forceinline__ uint32_t* cnt_u(uint32_t k, uint32_t b) const { return base + ls_cnt_off(nb) + (size_t)k * nb + b; }
+  __device__ __forceinline__ uint32_t* cnt_p(uint32_t k, uint32_t b) const {
+    return base + ls_cnt_off(nb) + (size_t)(nk + k) * nb + b;
+  }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kLsCtr) + i;
+  }
+  __device__ __forceinline__ unsigned long long* last(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kLsLast) + i;
+  }
+  __device__ __forceinline__ unsigned long long* seen(uint32_t k) const {
+    return reinterpret_cast<unsigned long long*>(base + kLsSeen) + k;
+  }
+};
+__device__ __forceinline__ ListDev list_dev(uint32_t* base) {
+  ListDev d;
+  d.base = base;
+  d.nk = base[0];
+  d.nb = base[1];
+  d.sub = reinterpret_cast<uint8_t*>(base + ((ls_mask_off(d.nk, d.nb) + 3u) & ~(size_t)3));
+  d.pend = d.sub + ((size_t)d.nb << base[2]);
+  return d;
+}
+__device__ __forceinline__ ListDev list_dev_of(const uint32_t* recep) {
+  return list_dev(*reinterpret_cast<uint32_t* const*>(recep + kRcListPtr));
+}
+// the same for a caller that knows the shape (the receptionist's n_keys and nb, the launch's bb): the address is the
+// only load, beside the receptionist's own header and not after it
+__device__ __forceinline__ uint32_t* list_base_of(const uint32_t* recep) {
+  return *reinterpret_cast<uint32_t* const*>(recep + kRcListPtr);
+}
+__device__ __forceinline__ ListDev list_dev_with(const uint32_t* recep, uint32_t nk, uint32_t nb, uint32_t bb) {
+  ListDev d;
+  d.base = list_base_of(recep);
+  d.nk = nk;
+  d.nb = nb;
+  d.sub = reinterpret_cast<uint8_t*>(d.base + ((ls_mask_off(nk, nb) + 3u) & ~(size_t)3));
+  d.pend = d.sub + ((size_t)nb << bb);
+  return d;
+}
+// what one thread's drains did: counted in registers, added to the storage once per wave (listing_commit)
+struct ListCount {
+  uint32_t sub, find, chg, pend;  // chg: a mask byte was stored; pend: a pending bit was set
+};
+
+// compiled_apply of the listings instantiations: compiled_apply_tp plus AGX_A_SUBSCRIBE_LISTING / AGX_A_FIND against
+// the actor's two mask bytes `sb` / `pd` (registers of the drain); neither touches the emitter.  A function of its
+// own: every other instantiation compiles compiled_apply_tp / compiled_apply_rc as before.
+// (The third copy of those cases: a fix here belongs in compiled_apply_rc and compiled_apply_tp too.)
+template <typename Emit>
+__device__ __forceinline__ uint32_t compiled_apply_ls(const DevParams& P, const RecepDev& RD, const TopicDev& TP, uint32_t& kind,
+                                                      uint32_t self, uint64_t* w, uint32_t src, uint32_t pay, uint32_t& mk,
+                                                      RecepCount& rc, uint32_t q, uint32_t& npub, uint32_t& sb, uint32_t& pd,
+                                                      ListCount& lc, Emit& emit) {
+  const uint32_t b = kind - AGX_KIND_COMPILED;
+  if (b >= P.n_beh) return AGX_RES_UNHANDLED;
+  const uint32_t c1 = P.bfirst[b + 1];
+  for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
+    const agx_case C = P.bcase[c];
+    if (!cb_cmp(C.cmp1, rc_operand(RD, C.src1, C.word1, C.k1, pay, w, src, self),
+                rc_operand(RD, C.src2, C.word2, C.k2, pay, w, src, self)))
+      continue;
+    if (!cb_cmp(C.cmp2, rc_operand(RD, C.src3, C.word3, C.k3, pay, w, src, self),
+                rc_operand(RD, C.src4, C.word4, C.k4, pay, w, src, self)))
+      continue;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      const agx_act A = P.bact[i];
+      const uint64_t v = rc_operand(RD, A.src, A.sword, A.k, pay, w, src, self);
+      const uint32_t msg = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;
+      const uint32_t bit = 1u << (A.pad1 & 7u);
+      switch (A.op) {
+        case AGX_A_SET: w[A.word & 1u] = v; break;
+        case AGX_A_ADD: w[A.word & 1u] += v; break;
+        case AGX_A_MAX: w[A.word & 1u] = v > w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_MIN: w[A.word & 1u] = v < w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_REGISTER:
+          if (!(mk & bit)) {
+            mk |= bit;
+            ++rc.reg;
+          }
+          break;
+        case AGX_A_DEREGISTER:
+          if (mk & bit) {
+            mk &= ~bit;
+            ++rc.dereg;
+          }
+          break;
+        case AGX_A_PUBLISH: {
+          const uint32_t slot = atomicAdd(TP.base + kTpCursor, 1u);
+          if (slot < TP.cap) TP.stage()[slot] = make_uint4(self, q, A.pad1 & 7u, msg);
+          ++npub;
+          break;
+        }
+        case AGX_A_SUBSCRIBE_LISTING:  // Subscribe(key, self): the immediate reply is owed on every Subscribe
+          sb |= bit;
+          pd |= bit;
+          ++lc.sub;
+          break;
+        case AGX_A_FIND:  // Find(key, self)
+          pd |= bit;
+          ++lc.find;
+          break;
         case AGX_A_TELL:
         case AGX_A_ROUTE: {
           uint64_t d = 0;

@@ -229,6 +229,15 @@ struct agx_engine {
   bool beh_publish = false;      // the compiled tables publish
   struct TopicPub { uint32_t key, sender, payload; };
   std::vector<TopicPub> tp_pubs;  // agx_publish calls not yet applied on the device
+  // Subscribe / Listing (agx_set_listings), on top of topics: the sub and pending masks, the per-bucket counts and due
+  // words.  Such an engine launches the kRecep | kTopic | kList instantiation, then k_listing_plan after k_topic_plan
+  uint32_t* d_list = nullptr;    // (its address stands in the receptionist's storage: agx_device.h ListDev)
+  bool beh_listing = false;      // the compiled tables subscribe to or find a listing
+  struct ListStart {
+    uint64_t first, count;
+    uint32_t key, on;
+  };
+  std::vector<ListStart> ls_starts;  // agx_subscribe_listings calls not yet applied on the device
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -457,7 +466,7 @@ namespace {
 // of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
 // the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
 // apply_variant, launch_apply and make_params.
-enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_ASK, F_TOPIC, F_N, F_NONE = F_N };
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_ASK, F_LIST, F_TOPIC, F_N, F_NONE = F_N };
 
 struct FeatureRow {
   bool (*on)(const agx_engine*);
@@ -510,6 +519,10 @@ const FeatureRow kFeatures[F_N] = {
     // the ask pattern (agx_set_ask) comes on top of the timers as receive timeouts do; the two exclude one another
     {[](const agx_engine* e) { return e->ask_on; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      kTimersKM | kAskKM, false, F_TIMERS},
+    // Subscribe / Listing (agx_set_listings) comes on top of topics, which come on top of the receptionist: its row
+    // stands before theirs, so launched_feature (the first row that is on) selects the listings instantiation
+    {[](const agx_engine* e) { return e->d_list != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+     nullptr, kRecepKM | kTopicKM | kListKM, false, F_RECEP},
     // pub-sub topics (agx_set_topics) come on top of the receptionist in the same way
     {[](const agx_engine* e) { return e->d_topic != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      nullptr, kRecepKM | kTopicKM, false, F_RECEP},
@@ -1111,6 +1124,133 @@ void launch_topic_plan(agx_engine* e, uint32_t* blc, uint32_t replan) {
                      reinterpret_cast<unsigned long long*>(e->d_stats + ST_ERROR), replan);
 }
 
+// ---- Subscribe / Listing (agx_set_listings): the plan between two supersteps, after k_recep_scan /
+// k_recep_fill / k_topic_plan.  Kernel boundaries again: the drains of the apply store their own actors' sub and
+// pending bytes and their bucket's counts, the blocks of the next apply read their due word, the changed-keys word and
+// their own bytes.
+// One block.  replan == 0, after every apply: the keys rebuilt in this superstep (the dirty_now bits of the
+// receptionist's flags word) are the changes the next tick's Listings announce; they replace the word of the tick
+// before if this superstep was a tick (its Listings were served), else they join it.  No rebuilt key, no new pending
+// bit, no changed key waiting and nothing of a served plan to take back: returns after the header's 16-byte load and
+// the flags word -- two small loads, not one -- and the mail mark may then stay set.  A stale mark is harmless: it
+// only decides whether a waiting changed-keys word is replaced or joined, the early return needs that word to be
+// empty, and a superstep without mail has no recipient to tell (agx_run launches no superstep on a quiescent engine;
+// the empty supersteps at the tail of a replayed batch drain nothing).  Else due[b] = the sum over changed keys
+// of cnt_u[k][b] plus the sum over the others of cnt_p[k][b], which joins the bucket's backlog count (`blc`: the
+// counts the next apply reads).  replan != 0 (after host calls between two runs): the keys whose version moved since
+// k_listing_mark join the word -- each change becomes deliveries once, however many rebuilds the host's calls ran and
+// whichever dirty_now bits they left --, the old due counts leave the backlog counts, and what the plan added to
+// listings_sent / notified before is replaced.
+static __global__ void __launch_bounds__(kTpThreads) k_listing_plan(uint32_t* rc, uint32_t* blc, uint32_t replan) {
+  const ListDev LD = list_dev_of(rc);
+  const uint32_t tid = threadIdx.x;
+  const uint4 h = *reinterpret_cast<const uint4*>(LD.base + kLsMail);  // mail, changed, pend, planned
+  const uint32_t nkm = (1u << LD.nk) - 1u;
+  uint32_t chg = h.y;
+  if (replan) {
+    for (uint32_t k = 0; k < LD.nk; ++k)  // (every thread reads the same words: broadcast loads)
+      if (reinterpret_cast<const unsigned long long*>(rc + kRcVersion)[k] != *LD.seen(k)) chg |= 1u << k;
+  } else {
+    const uint32_t now = (rc[kRcFlags] >> 8) & nkm;
+    if (!now && !h.y && !h.z && !h.w) return;
+    chg = (h.x ? 0u : chg) | now;
+  }
+  __shared__ uint32_t s_rcp[AGX_MAX_SERVICE_KEYS];
+  __shared__ unsigned long long s_sent;
+  if (tid < AGX_MAX_SERVICE_KEYS) s_rcp[tid] = 0u;
+  if (tid == 0) s_sent = 0ull;
+  __syncthreads();
+  if (replan || chg || h.z) {  // (block-uniform)
+    uint32_t rcp[AGX_MAX_SERVICE_KEYS] = {};
+    unsigned long long sent = 0ull;
+    for (uint32_t b = tid; b < LD.nb; b += kTpThreads) {
+      uint32_t d = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k)
+        if (k < LD.nk) {  // (block-uniform)
+          const bool c = (chg >> k) & 1u;
+          const uint32_t n = c ? *LD.cnt_u(k, b) : *LD.cnt_p(k, b);
+          if (c) rcp[k] += n;
+          d += n;
+        }
+      const uint32_t old = replan ? *LD.due(b) : 0u;
+      if (d | old) {
+        *LD.due(b) = d;
+        const uint32_t x = blc[b];
+        blc[b] = x - min(old, x) + d;
+      }
+      sent += d;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k)
+      if (rcp[k]) atomicAdd(&s_rcp[k], rcp[k]);
+    if (sent) atomicAdd(&s_sent, sent);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long ntf = 0ull;
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) ntf += s_rcp[k] ? 1ull : 0ull;
+    const unsigned long long l0 = replan ? *LD.last(0) : 0ull, l1 = replan ? *LD.last(1) : 0ull;
+    *LD.ctr(kLsSent) += s_sent - l0;  // (one block, one writer; wraps back when the plan shrinks)
+    *LD.ctr(kLsNotified) += ntf - l1;
+    *LD.last(0) = s_sent;
+    *LD.last(1) = ntf;
+    LD.base[kLsChanged] = chg;
+    LD.base[kLsPlanned] = (s_sent | ntf) != 0ull ? 1u : 0u;
+    if (!replan) {
+      LD.base[kLsMail] = 0u;
+      LD.base[kLsPend] = 0u;
+    } else {
+      for (uint32_t k = 0; k < LD.nk; ++k) *LD.seen(k) = reinterpret_cast<const unsigned long long*>(rc + kRcVersion)[k];
+    }
+  }
+}
+// before the host's calls between two runs are applied: the versions as they stand (k_listing_plan's re-plan compares)
+static __global__ void k_listing_mark(uint32_t* rc) {
+  const ListDev LD = list_dev_of(rc);
+  if (threadIdx.x < LD.nk) *LD.seen(threadIdx.x) = reinterpret_cast<const unsigned long long*>(rc + kRcVersion)[threadIdx.x];
+}
+// agx_subscribe_listings on the device: one block per bucket the range touches sets bit `key` of sub and pending
+// (on) or clears it in sub (off) for the range's live actors, and recounts the bucket's two counts of the key
+static __global__ void __launch_bounds__(kRcThreads) k_listing_start(uint32_t* rc, const uint8_t* alive, uint32_t bb, uint32_t n_local,
+                                                                     uint32_t first, uint32_t count, uint32_t key, uint32_t on,
+                                                                     uint32_t b_first) {
+  const ListDev LD = list_dev_of(rc);
+  const uint32_t tid = threadIdx.x, b = b_first + blockIdx.x, a0 = b << bb, bit = 1u << key;
+  const uint32_t na = min(1u << bb, n_local - a0);
+  __shared__ uint32_t s_n[3];  // sub | pending, pending, members changed by on
+  if (tid < 3) s_n[tid] = 0u;
+  __syncthreads();
+  uint32_t nu = 0, np = 0, nc = 0;
+  for (uint32_t la = tid; la < na; la += kRcThreads) {
+    const uint32_t l = a0 + la;
+    uint32_t sb = LD.sub[l], pd = LD.pend[l];
+    if (l >= first && l - first < count && (alive[l] & 1u)) {
+      const uint32_t sb2 = on ? sb | bit : sb & ~bit, pd2 = on ? pd | bit : pd;
+      if (sb2 != sb) LD.sub[l] = (uint8_t)sb2;
+      if (pd2 != pd) LD.pend[l] = (uint8_t)pd2;
+      nc += (on && (sb2 != sb || pd2 != pd)) ? 1u : 0u;
+      sb = sb2;
+      pd = pd2;
+    }
+    nu += ((sb | pd) >> key) & 1u;
+    np += (pd >> key) & 1u;
+  }
+  if (nu) atomicAdd(&s_n[0], nu);
+  if (np) atomicAdd(&s_n[1], np);
+  if (nc) atomicAdd(&s_n[2], nc);
+  __syncthreads();
+  if (tid == 0) {
+    *LD.cnt_u(key, b) = s_n[0];
+    *LD.cnt_p(key, b) = s_n[1];
+    if (s_n[2]) atomicAdd(LD.ctr(kLsSubscribes), (unsigned long long)s_n[2]);
+  }
+}
+
+void launch_listing_plan(agx_engine* e, uint32_t* blc, uint32_t replan) {
+  hipLaunchKernelGGL(k_listing_plan, dim3(1), dim3(kTpThreads), 0, e->stream, e->d_recep, blc, replan);
+}
+
 agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
   // the chunk histograms consumed by this step's first pass were zeroed by k_chunk_downsweep;
   // on the multi-rank path (no chunk pass) they are never read, so stale columns are harmless
@@ -1330,6 +1470,7 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
   if (e->d_recep) launch_recep_rebuild(e);  // (every superstep, captured or eager: the listings of the next tick)
   // (... and the tick's publications: the backlog counts this superstep wrote carry the next tick's deliveries)
   if (e->d_topic) launch_topic_plan(e, e->fused ? e->d_blc[e->par] : e->d_chunk_cnt, 0u);
+  if (e->d_list) launch_listing_plan(e, e->fused ? e->d_blc[e->par] : e->d_chunk_cnt, 0u);  // (... and the owed Listings)
   if (e->R == 1) e->par ^= 1u;  // the next superstep writes the other parity (fused and multi-pass)
   HIP_TRY(hipGetLastError());
   return AGX_OK;
@@ -2033,8 +2174,9 @@ agx_status flush_child_spawns(agx_engine* e) {
 // newer ones; each call is the start kernel over the buckets of its range, then the rebuild (the listing is in
 // force for the next tick)
 agx_status flush_recep_starts(agx_engine* e) {
-  if (e->rc_starts.empty() && e->tp_pubs.empty()) return AGX_OK;
-  if (e->actors_dirty && !e->rc_starts.empty()) HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
+  if (e->rc_starts.empty() && e->tp_pubs.empty() && e->ls_starts.empty()) return AGX_OK;
+  if (e->d_list) hipLaunchKernelGGL(k_listing_mark, dim3(1), dim3(AGX_MAX_SERVICE_KEYS), 0, e->stream, e->d_recep);
+  if (e->actors_dirty && !(e->rc_starts.empty() && e->ls_starts.empty())) HIP_TRY(hipMemcpyAsync(e->d_alive, e->h_alive.data(), e->n_local, hipMemcpyHostToDevice, e->stream));
   for (const auto& rs : e->rc_starts) {
     if (!rs.count) continue;
     const uint32_t b0 = (uint32_t)(rs.first >> e->bb), b1 = (uint32_t)((rs.first + rs.count - 1) >> e->bb);
@@ -2051,9 +2193,21 @@ agx_status flush_recep_starts(agx_engine* e) {
     HIP_TRY(hipGetLastError());
     e->inflight_known = false;
   }
+  if (e->d_list) {  // the host's subscriptions; then the Listings are planned against the new counts and versions
+    for (const auto& ls : e->ls_starts) {
+      if (!ls.count) continue;
+      const uint32_t b0 = (uint32_t)(ls.first >> e->bb), b1 = (uint32_t)((ls.first + ls.count - 1) >> e->bb);
+      hipLaunchKernelGGL(k_listing_start, dim3(b1 - b0 + 1), dim3(kRcThreads), 0, e->stream, e->d_recep, e->d_alive, e->bb,
+                         (uint32_t)e->n_local, (uint32_t)ls.first, (uint32_t)ls.count, ls.key, ls.on, b0);
+    }
+    launch_listing_plan(e, next_backlog_counts(e), 1u);
+    HIP_TRY(hipGetLastError());
+    e->inflight_known = false;
+  }
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->rc_starts.clear();
   e->tp_pubs.clear();
+  e->ls_starts.clear();
   return AGX_OK;
 }
 
@@ -2069,6 +2223,9 @@ agx_status prepare_run(agx_engine* e) {
                    "(agx_set_receptionist)", e->beh_rc_keys - 1u, e->rc_keys);
   if (e->beh_publish && !e->d_topic)  // (only the topic variant interprets those: loud, never wrong)
     return set_err(AGX_EINVAL, "the compiled behaviours publish, but the engine has no topics (agx_set_topics)");
+  if (e->beh_listing && !e->d_list)  // (only the listings variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours subscribe to or find a listing, but the engine has no listings "
+                   "(agx_set_listings)");
   if (e->ch_bad_spawn)
     return set_err(AGX_EINVAL, "agx_spawn_children was called on an engine without children (agx_set_children)");
   if (e->beh_child && !e->d_child)  // (only the children variant interprets those: loud, never wrong)
@@ -3700,6 +3857,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_super);
   hipFree(e->d_recep);
   hipFree(e->d_topic);
+  hipFree(e->d_list);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -4590,6 +4748,86 @@ agx_status agx_read_topic_log(agx_engine* e, uint32_t* out_key, uint32_t* out_se
   return AGX_OK;
 }
 
+// TY/internal/receptionist/LocalReceptionist.scala:152-171,209-220,233-238
+agx_status agx_set_listings(agx_engine* e, const uint32_t* listing_payload, uint32_t n_keys) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!listing_payload) return set_err(AGX_EINVAL, "listings: null listing_payload");
+  if (e->d_list) return set_err(AGX_EINVAL, "listings are already set (%u keys)", e->rc_keys);
+  if (!e->d_topic)
+    return set_err(AGX_EINVAL, "listings need an engine with topics (agx_set_topics after agx_set_receptionist): a Listing "
+                   "is injected as a publication's delivery is");
+  if (n_keys != e->rc_keys)
+    return set_err(AGX_EINVAL, "listings: %u Listing payloads, but the receptionist has %u keys (agx_set_receptionist)", n_keys,
+                   e->rc_keys);
+  if (e->started) return set_err(AGX_ESTATE, "set listings before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_recep_starts(e));  // (what the host registered before this call is no change a subscriber is told of)
+  const size_t words = ls_words(n_keys, e->nb, e->bb);
+  if (hipMalloc((void**)&e->d_list, words * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_list = nullptr;
+    return set_err(AGX_ENOMEM, "the listings' storage (%u keys, %u buckets: %llu KB) does not fit on the device", n_keys, e->nb,
+                   (unsigned long long)(words >> 8));
+  }
+  const uint32_t head[3] = {n_keys, e->nb, e->bb};
+  const unsigned long long addr = (unsigned long long)(uintptr_t)e->d_list;
+  hipError_t he = hipMemsetAsync(e->d_list, 0, words * 4ull, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(e->d_list, head, sizeof(head), hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(e->d_list + kLsPayload, listing_payload, 4ull * n_keys, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(e->d_recep + kRcListPtr, &addr, sizeof(addr), hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) {  // (no half-set listings: the engine stays one without them, and the call may be repeated)
+    const unsigned long long none = 0ull;
+    (void)hipMemcpy(e->d_recep + kRcListPtr, &none, sizeof(none), hipMemcpyHostToDevice);
+    (void)hipFree(e->d_list);
+    e->d_list = nullptr;
+    HIP_TRY(he);
+  }
+  e->ls_starts.clear();
+  drop_graphs(e);  // the variant, the storage and the plan kernel are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_subscribe_listings(agx_engine* e, uint64_t first_id, uint64_t count, uint32_t key, uint32_t on) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_list) return set_err(AGX_EINVAL, "agx_subscribe_listings needs an engine with listings (agx_set_listings)");
+  if (key >= e->rc_keys) return set_err(AGX_EINVAL, "service key %u of %u", key, e->rc_keys);
+  if (first_id > e->n_local || count > e->n_local - first_id)
+    return set_err(AGX_EINVAL, "actors [%llu, %llu) of %llu", (unsigned long long)first_id,
+                   (unsigned long long)(first_id + count), (unsigned long long)e->n_local);
+  e->ls_starts.push_back({first_id, count, key, on ? 1u : 0u});
+  return AGX_OK;
+}
+
+agx_status agx_listing_info(agx_engine* e, uint64_t* subscribes, uint64_t* finds, uint64_t* listings_sent, uint64_t* notified) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_list) return set_err(AGX_EINVAL, "agx_listing_info needs an engine with listings (agx_set_listings)");
+  uint64_t c[4] = {0, 0, 0, 0};
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_recep_starts(e));
+  AGX_TRY(copy_sync(e, c, e->d_list + kLsCtr, sizeof(c), hipMemcpyDeviceToHost));
+  if (subscribes) *subscribes = c[kLsSubscribes];
+  if (finds) *finds = c[kLsFinds];
+  if (listings_sent) *listings_sent = c[kLsSent];
+  if (notified) *notified = c[kLsNotified];
+  return AGX_OK;
+}
+
+agx_status agx_read_subscriptions(agx_engine* e, uint64_t first, uint64_t count, uint8_t* sub_out, uint8_t* pending_out) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_list) return set_err(AGX_EINVAL, "agx_read_subscriptions needs an engine with listings (agx_set_listings)");
+  if (first > e->n_local || count > e->n_local - first)
+    return set_err(AGX_EINVAL, "actors [%llu, %llu) of %llu", (unsigned long long)first, (unsigned long long)(first + count),
+                   (unsigned long long)e->n_local);
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_recep_starts(e));
+  if (!count) return AGX_OK;
+  const uint8_t* const sub = reinterpret_cast<const uint8_t*>(e->d_list + ((ls_mask_off(e->rc_keys, e->nb) + 3u) & ~(size_t)3));
+  if (sub_out) AGX_TRY(copy_sync(e, sub_out, sub + first, count, hipMemcpyDeviceToHost));
+  if (pending_out) AGX_TRY(copy_sync(e, pending_out, sub + ((size_t)e->nb << e->bb) + first, count, hipMemcpyDeviceToHost));
+  return AGX_OK;
+}
+
 agx_status agx_register_services(agx_engine* e, uint64_t first_id, uint64_t count, uint32_t key, uint32_t on) {
   if (!e) return set_err(AGX_EINVAL, "null engine");
   if (!e->d_recep) {
@@ -4757,11 +4995,11 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     const bool askop = A.op == AGX_A_ASK_ARM || A.op == AGX_A_ASK_SEND;  // (`word` is the key)
     const bool tmop = (A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL) || askop;  // (`word` is the key)
     const bool wdop = A.op >= AGX_A_WATCH && A.op <= AGX_A_UNWATCH;  // (the ref is the d-operand)
-    const bool rcop = (A.op >= AGX_A_REGISTER && A.op <= AGX_A_ROUTE) || A.op == AGX_A_PUBLISH;  // (`pad1` is the service key)
+    const bool rcop = (A.op >= AGX_A_REGISTER && A.op <= AGX_A_ROUTE) || (A.op >= AGX_A_PUBLISH && A.op <= AGX_A_FIND);  // (`pad1` is the service key)
     if (rcop && (A.pad1 >= AGX_MAX_SERVICE_KEYS || A.pad0 > (A.op == AGX_A_ROUTE ? (AGX_ROUTE_KEEP_SENDER | AGX_ROUTE_BY_INDEX) : 0u) ||
                  (A.op == AGX_A_ROUTE && (A.pad0 & AGX_ROUTE_BY_INDEX) && !opnd_ok(A.dsrc, A.dword))))
       return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (service keys 0..7, route flags 0..3)", i);
-    if (A.op < AGX_A_SET || A.op > AGX_A_PUBLISH || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+    if (A.op < AGX_A_SET || A.op > AGX_A_FIND || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
         !opnd_ok(A.src, A.sword) ||
         ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop || A.op == AGX_A_STOP_CHILD ||
           A.op == AGX_A_SET_RECEIVE_TIMEOUT || askop) &&
@@ -4827,7 +5065,7 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     return set_err(AGX_EINVAL, "compiled behaviours: message tags 0xFD and 0xFC are reserved for Create and Stop envelopes on "
                    "an engine with children");
   // the receptionist: a route sends one envelope through the case's tell slot; the service keys the tables use
-  bool uses_recep = false, uses_publish = false;
+  bool uses_recep = false, uses_publish = false, uses_listing = false;
   uint32_t rc_keys_used = 0;
   auto rc_use = [&](uint32_t src, uint32_t word) {
     if (src != AGX_V_LISTING_SIZE && src != AGX_V_SERVICE_AT) return;
@@ -4855,7 +5093,8 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     rc_use(acts[i].src, acts[i].sword);
     rc_use(acts[i].dsrc, acts[i].dword);
     uses_publish |= acts[i].op == AGX_A_PUBLISH;
-    if ((acts[i].op >= AGX_A_REGISTER && acts[i].op <= AGX_A_ROUTE) || acts[i].op == AGX_A_PUBLISH) {
+    uses_listing |= acts[i].op == AGX_A_SUBSCRIBE_LISTING || acts[i].op == AGX_A_FIND;
+    if ((acts[i].op >= AGX_A_REGISTER && acts[i].op <= AGX_A_ROUTE) || (acts[i].op >= AGX_A_PUBLISH && acts[i].op <= AGX_A_FIND)) {
       uses_recep = true;
       rc_keys_used = std::max<uint32_t>(rc_keys_used, acts[i].pad1 + 1u);
     }
@@ -4932,6 +5171,7 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   e->beh_recep = uses_recep;  // (checked against agx_set_receptionist at agx_run)
   e->beh_rc_keys = rc_keys_used;
   e->beh_publish = uses_publish;  // (checked against agx_set_topics at agx_run)
+  e->beh_listing = uses_listing;  // (checked against agx_set_listings at agx_run)
   e->beh_child = uses_child;  // (checked against agx_set_children at agx_run)
   e->beh_ctl_tags = ctl_tags;
   e->beh_watch = false;  // a watch action or a signal case (checked against agx_set_death_watch at agx_run)

@@ -1730,6 +1730,111 @@ __device__ __forceinline__ void topic_stage(const BucketArgs& a, const RecepDev&
   }
   __syncthreads();
 }
+// ---- Subscribe / Listing (agx_set_listings).  What a wave's drains did reaches the storage once:
+// the two counters as one atomic add each, "a mask byte was stored" as bit 1 of the block's recount word, "a pending
+// bit was set" as the plan's hint.  A wave without a subscribe, a find or a stop of a subscriber does nothing.
+__device__ __forceinline__ void listing_commit(const ListDev& LD, const ListCount& lc, uint32_t* changed) {
+  if (!__ballot((lc.sub | lc.find | lc.chg | lc.pend) != 0u)) return;  // (wave-uniform)
+  const uint32_t t0 = wave_incl_sum(lc.sub), t1 = wave_incl_sum(lc.find);
+  const uint32_t c = wave_or_u32((lc.chg ? 1u : 0u) | (lc.pend ? 2u : 0u));
+  if (lane_id() == kWave - 1) {
+    if (t0) atomicAdd(LD.ctr(kLsSubscribes), (unsigned long long)t0);
+    if (t1) atomicAdd(LD.ctr(kLsFinds), (unsigned long long)t1);
+    if (c & 1u) atomicOr(changed, 2u);
+    if (c & 2u) LD.base[kLsPend] = 1u;  // (every writer stores the same value)
+  }
+}
+// The owed Listings of bucket b, staged as items [off, off + nl) of the inbox's tail in wk ([3][kBucket]: actor,
+// sender, payload) after the publications: in ascending key, one item per actor of the bucket whose pending bit k is
+// set, or whose sub bit k is set while the plan's changed-keys word has bit k, in ascending id (a thread holds four
+// consecutive actors' bytes in one register; per key the threads' counts are scanned once through `scratch`).  Every
+// pending bit of the bucket is served: the bytes are cleared, and a bucket that had any recounts what the plan
+// reads.  The count matches the bucket's due word unless a byte was changed from outside the engine's own steps:
+// loud then (the generic capacity error, as topic_stage: its text does not name the listings), and the missing items
+// defined.  A bucket whose inbox exceeds the tile is not staged at all (the caller's count is 0): its due word and
+// pending bits stay as they are, which is acceptable only because that error is sticky and ends the engine's runs.
+// Block-uniform call.
+__device__ __forceinline__ void listing_stage(const BucketArgs& a, const ListDev& LD, uint32_t b, uint32_t a0, uint32_t na,
+                                              uint32_t off, uint32_t nl, uint32_t* wk, uint32_t* scratch) {
+  const uint32_t tid = threadIdx.x, la0 = tid * 4u, end = off + nl;
+  const uint32_t chg = LD.base[kLsChanged] & 0xFFu;
+  // (the byte arrays are padded to whole buckets and bytes past n_local are never set)
+  const uint32_t s4 = la0 < na ? *reinterpret_cast<const uint32_t*>(LD.sub + a0 + la0) : 0u;
+  const uint32_t p4 = la0 < na ? *reinterpret_cast<const uint32_t*>(LD.pend + a0 + la0) : 0u;
+  const uint32_t m4 = p4 | (s4 & (chg * 0x01010101u));
+  uint32_t o = off;
+  bool anyp = false;
+#pragma unroll
+  for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+    if (k >= LD.nk) continue;
+    const uint32_t cp = *LD.cnt_p(k, b);
+    anyp |= cp != 0u;
+    if (!(((chg >> k) & 1u) ? *LD.cnt_u(k, b) : cp)) continue;  // (block-uniform)
+    uint32_t tot;
+    uint32_t x = o + block_excl_sum<kBThreads>((uint32_t)__popc(m4 & (0x01010101u << k)), scratch, &tot);
+    const uint32_t pay = LD.base[kLsPayload + k];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+      if ((m4 >> (8u * j + k)) & 1u) {
+        if (x < end) {
+          wk[x] = a0 + la0 + j;
+          wk[kBucket + x] = AGX_NO_SENDER;
+          wk[2 * kBucket + x] = pay;
+        }
+        ++x;
+      }
+    o += tot;
+  }
+  if (o < end) {
+    if (tid == 0) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
+    for (uint32_t i = o + tid; i < end; i += kBThreads) {
+      wk[i] = a0;
+      wk[kBucket + i] = AGX_NO_SENDER;
+      wk[2 * kBucket + i] = 0u;
+    }
+  }
+  if (p4) *reinterpret_cast<uint32_t*>(LD.pend + a0 + la0) = 0u;
+  if (anyp) {  // (block-uniform) no pending bit is left: both counts are the subscribers'
+#pragma unroll
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+      if (k >= LD.nk) continue;
+      uint32_t tot;
+      block_excl_sum<kBThreads>((uint32_t)__popc(s4 & (0x01010101u << k)), scratch, &tot);
+      if (tid == 0) {
+        *LD.cnt_u(k, b) = tot;
+        *LD.cnt_p(k, b) = 0u;
+      }
+    }
+  }
+  __syncthreads();  // (every thread has read the due word)
+  if (tid == 0) *LD.due(b) = 0u;
+}
+// A block in which a sub or pending byte was stored recounts, per key, its bucket's actors with the bit in
+// sub | pending and in pending (as recep_recount: one u32 of four actors per thread, two keys share a packed wave
+// sum).  `tmp`: 64 u32 of LDS free after the drains.  Block-uniform call, after the barrier that follows the drains.
+__device__ __forceinline__ void listing_recount(const ListDev& LD, uint32_t b, uint32_t a0, uint32_t na, uint32_t* tmp) {
+  const uint32_t tid = threadIdx.x, la0 = tid * 4u;
+  const uint32_t p4 = la0 < na ? *reinterpret_cast<const uint32_t*>(LD.pend + a0 + la0) : 0u;
+  const uint32_t u4 = p4 | (la0 < na ? *reinterpret_cast<const uint32_t*>(LD.sub + a0 + la0) : 0u);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t m4 = i < 4 ? u4 : p4;
+    const int h = i & 3;
+    const uint32_t c = (uint32_t)__popc(m4 & (0x01010101u << (2 * h))) | ((uint32_t)__popc(m4 & (0x01010101u << (2 * h + 1))) << 16);
+    const uint32_t s = wave_incl_sum(c);
+    if (lane_id() == kWave - 1) tmp[(tid / kWave) * 8 + i] = s;
+  }
+  __syncthreads();
+  if (tid < 2u * LD.nk) {
+    const uint32_t k = tid >> 1, p = tid & 1u;
+    uint32_t n = 0;
+#pragma unroll
+    for (int w = 0; w < kBThreads / kWave; ++w) n += (tmp[w * 8 + p * 4 + (k >> 1)] >> (16u * (k & 1u))) & 0xFFFFu;
+    if (p) *LD.cnt_p(k, b) = n;
+    else *LD.cnt_u(k, b) = n;
+  }
+  __syncthreads();  // (tmp is the caller's again)
+}
 // A block in which a mask changed recounts its bucket's members per key from the bucket's mask bytes (one u32 of
 // four actors per thread: coalesced; two keys share a packed wave sum) and writes cnt[key][bucket].  `tmp`: 32 u32
 // of LDS free after the drains.  Block-uniform call, after the barrier that follows the drains.
@@ -1843,6 +1948,13 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
   TopicDev TP{};
   uint32_t npub = 0;  // kTp: this thread's publish actions
   if constexpr (kTp) TP = topic_dev_of(P.recep);
+  // kLs: Subscribe / Listing (agx_set_listings), on top of topics.  The owed Listings are ordinary
+  // items of the inbox's tail (k_bucket_apply put them there); compiled cases subscribe and find against the actor's
+  // sub / pending bytes, and a block in which one was stored recounts what k_listing_plan (after the apply) reads.
+  constexpr bool kLs = (KM & kListKM) != 0;
+  static_assert(!kLs || kTp, "listings: on the topic instantiations only");
+  ListDev LD{};
+  if constexpr (kLs) LD = list_dev_with(P.recep, RD.nk, RD.nb, a.bb);
   uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
   auto ikey = [&](uint32_t q) -> uint32_t { return kLds ? L.key[q] : a.scr.key[lo + q]; };
@@ -2261,6 +2373,18 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         rcm4 |= has ? (uint32_t)RD.mask[a0 + la] << (8 * j) : 0u;
       }
     }
+    // kLs: their sub and pending bytes beside it (byte j of lss4 / lsp4 is actor j's)
+    uint32_t lss4 = 0, lsp4 = 0;
+    ListCount lsc{};
+    if constexpr (kLs) {
+#pragma unroll
+      for (int j = 0; j < kBAct; ++j) {
+        const uint32_t la = j * kBThreads + tid;
+        const bool has = la < na && (L.alive[la] & 1u) && L.seg[la + 1] != L.seg[la];
+        lss4 |= has ? (uint32_t)LD.sub[a0 + la] << (8 * j) : 0u;
+        lsp4 |= has ? (uint32_t)LD.pend[a0 + la] << (8 * j) : 0u;
+      }
+    }
     auto sp_actor = [&](int j) {
       const uint32_t la = act_of(j);
       ecl[j] = 0;
@@ -2674,6 +2798,35 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
             break;
           }
         }
+      } else if constexpr (kLs) {
+        // the topics' drain (below) with compiled_apply_ls: the actor's sub and pending bytes live in registers across
+        // the window beside its key mask and are stored once, only if they changed; a stop clears all three
+        const uint32_t mk0 = (rcm4 >> (8 * j)) & 0xFFu, sb0 = (lss4 >> (8 * j)) & 0xFFu, pd0 = (lsp4 >> (8 * j)) & 0xFFu;
+        uint32_t mk = mk0, sb = sb0, pd = pd0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          const uint32_t r = kcur >= AGX_KIND_COMPILED
+                                 ? compiled_apply_ls(P, RD, TP, kcur, self, wv, sv, pv, mk, rcc, q, npub, sb, pd, lsc, em)
+                                 : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          ++ndel;
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            rcc.term += (uint32_t)__popc(mk);  // SubscriberTerminated / RegisteredActorTerminated
+            mk = sb = pd = 0u;
+            break;
+          }
+        }
+        if (mk != mk0) {
+          RD.mask[l] = (uint8_t)mk;
+          rcc.chg |= mk ^ mk0;
+        }
+        if (sb != sb0) LD.sub[l] = (uint8_t)sb;
+        if (pd != pd0) LD.pend[l] = (uint8_t)pd;
+        lsc.chg |= (sb ^ sb0) | (pd ^ pd0);
+        lsc.pend |= pd & ~pd0;
       } else if constexpr (kTp) {
         // the receptionist's drain (below) with compiled_apply_tp: a publish knows its index within the window
         const uint32_t mk0 = (rcm4 >> (8 * j)) & 0xFFu;
@@ -2789,7 +2942,12 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     if constexpr (kAsk) ask_commit(AD, acn);
     if constexpr (kRc) recep_commit(RD, rcc, L.rowtop);
     if constexpr (kTp) topic_commit(TP, npub);
+    if constexpr (kLs) listing_commit(LD, lsc, L.rowtop);
     __syncthreads();
+    if constexpr (kLs) {  // (block-uniform; bit 0: a key mask changed, bit 1: a sub or pending byte)
+      if (*L.rowtop & 1u) recep_recount(RD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));
+      if (*L.rowtop & 2u) listing_recount(LD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));
+    } else
     if constexpr (kRc)  // (block-uniform; U is free: the state words were written back)
       if (*L.rowtop) recep_recount(RD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));
     if constexpr (kStash) {
@@ -5159,6 +5317,11 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
   // and ascending id), and its backlog count carries their number (k_topic_plan, after the apply before).
   constexpr bool kTp = (KM & kTopicKM) != 0;  // (a flag of KM: agx_device.h)
   static_assert(!kTp || kRc, "topics: on the receptionist instantiations only");
+  // kLs: Subscribe / Listing (agx_set_listings), on top of topics.  The owed Listings follow the
+  // publications at the end of the inbox (written here from the bucket's own sub / pending bytes and the plan's
+  // changed-keys word), and the backlog count carries their number too (k_listing_plan, after the apply before).
+  constexpr bool kLs = (KM & kListKM) != 0;  // (a flag of KM: agx_device.h)
+  static_assert(!kLs || kTp, "listings: on the topic instantiations only");
   if (kOwner && a.halt && a.halt[0]) return;  // (device-resident multi-rank replay stopped)
   // key/src/pay carved from one array: group_tells reuses key+src as a 16 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t s_ksp[3 * kBucket];
@@ -5317,11 +5480,15 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
               }
             }
             if constexpr (kTp) {  // the backlog count carries the log's deliveries: [backlog][mail][deliveries]
-              const uint32_t np = min(*topic_dev_of(P.recep).due(b), blc);
+              uint32_t due = *topic_dev_of(P.recep).due(b);
+              if constexpr (kLs) due += list_base_of(P.recep)[kLsDueOff + b];  // (... and the owed Listings after them)
+              const uint32_t np = min(due, blc);
               s_rowtop = np;
               s_g[0] = blc - np;
               if (s_hi - s_lo > (uint32_t)kBucket) s_rowtop = 0u;  // (the error below: the bucket's mail dropped)
               if (s_hi != s_lo) topic_dev_of(P.recep).base[kTpMail] = 1u;  // (this superstep is a tick)
+              if constexpr (kLs)
+                if (s_hi != s_lo) list_base_of(P.recep)[kLsMail] = 1u;
             }
             if constexpr (kRc) {
               if (s_hi - s_lo > (uint32_t)kBucket) {  // the skew launches know no receptionist: loud, the bucket's mail dropped
@@ -5393,7 +5560,9 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           s_g[0] -= np;
         }
         if constexpr (kTp) {  // (as the multi-pass launch above)
-          const uint32_t np = min(*topic_dev_of(P.recep).due(b), s_g[0]);
+          uint32_t due = *topic_dev_of(P.recep).due(b);
+          if constexpr (kLs) due += list_base_of(P.recep)[kLsDueOff + b];
+          const uint32_t np = min(due, s_g[0]);
           s_rowtop = np;
           s_g[0] -= np;
         }
@@ -5440,6 +5609,8 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
           tt += s_rowtop;
           if (blc + tt + s_g[2] > (uint32_t)kBucket) s_rowtop = 0u;  // (the error below: the bucket's mail dropped)
           else if (blc + tt + s_g[2] != 0u) topic_dev_of(P.recep).base[kTpMail] = 1u;  // (this superstep is a tick)
+          if constexpr (kLs)
+            if (blc + tt + s_g[2] <= (uint32_t)kBucket && blc + tt + s_g[2] != 0u) list_base_of(P.recep)[kLsMail] = 1u;
         }
         if constexpr (kRc) {
           if (blc + tt + s_g[2] > (uint32_t)kBucket) {  // the skew launches know no receptionist: loud, the bucket's mail dropped
@@ -5763,6 +5934,15 @@ static __global__ void __launch_bounds__(kBThreads, kWide ? AGX_WIDE_WPE : 4) k_
       // sort leaves them at the tail of each actor's segment, in log order), staged here from the log
       if constexpr (kTp) {
         const uint32_t np = s_rowtop;
+        if constexpr (kLs) {  // (the publications first, then the Listings: DESIGN.md §2.11)
+          if (np) {  // (block-uniform)
+            const RecepDev RD = recep_dev(P.recep);
+            const ListDev LD = list_dev_with(P.recep, RD.nk, RD.nb, a.bb);
+            const uint32_t nl = min(*LD.due(b), np);
+            if (np - nl) topic_stage(a, RD, topic_dev_of(P.recep), a0, na, np - nl, reinterpret_cast<uint32_t*>(U), scratch);
+            if (nl) listing_stage(a, LD, b, a0, na, np - nl, nl, reinterpret_cast<uint32_t*>(U), scratch);
+          }
+        } else
         if (np)  // (block-uniform)
           topic_stage(a, recep_dev(P.recep), topic_dev_of(P.recep), a0, na, np, reinterpret_cast<uint32_t*>(U), scratch);
       }

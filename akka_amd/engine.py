@@ -464,6 +464,33 @@ class GpuEngine:
         check(self.lib.agx_read_topic_log(self._h, *(_ptr(x, ctypes.c_uint32) for x in (k, s, p)), int(n.value), ctypes.byref(n)))
         return np.stack([k, s, p], axis=1)[:int(n.value)]
 
+    def set_listings(self, listing_payloads) -> None:
+        """agx_set_listings (after set_topics, before the first run): compiled behaviours may then
+        context.receptionist_subscribe / receptionist_find; listing_payloads[k] is the payload of a Listing envelope of
+        key k, one per key of the receptionist (Tables.listing_payloads)."""
+        p = np.ascontiguousarray(listing_payloads, dtype=np.uint32)
+        check(self.lib.agx_set_listings(self._h, _ptr(p, ctypes.c_uint32), int(p.size)))
+
+    def subscribe_listings(self, first: int, count: int, key: int, on: bool = True) -> None:
+        """agx_subscribe_listings: the setup block -- the live actors of [first, first + count) subscribe to key
+        number `key` and are owed its Listing at the next tick (on), or no longer subscribe to it (off)."""
+        check(self.lib.agx_subscribe_listings(self._h, first, count, key, 1 if on else 0))
+
+    LISTING_INFO = ("subscribes", "finds", "listings_sent", "notified")
+
+    def listing_info(self) -> dict:
+        """agx_listing_info: totals subscribes / finds / listings_sent / notified."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        check(self.lib.agx_listing_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(self.LISTING_INFO, (int(x.value) for x in v)))
+
+    def read_subscriptions(self, first: int = 0, count: int | None = None):
+        """agx_read_subscriptions: the (sub, pending) masks of actors [first, first + count)."""
+        count = self.cfg.n_actors - first if count is None else count
+        sub, pend = np.zeros(max(count, 1), np.uint8), np.zeros(max(count, 1), np.uint8)
+        check(self.lib.agx_read_subscriptions(self._h, first, count, _ptr(sub, ctypes.c_uint8), _ptr(pend, ctypes.c_uint8)))
+        return sub[:count], pend[:count]
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""

@@ -46,6 +46,11 @@ What lowers:
     ``context.subscriber_count(topic)`` (pub-sub topics on the receptionist's engine): a topic is
     numbered with the ServiceKeys, subscribing lowers to ``A_REGISTER``, and a case holds at most one of tell, route
     and publish; ``Tables.uses_topics`` -> engine.set_topics(log_capacity), after engine.set_receptionist;
+  * ``context.receptionist_subscribe(key, ListingMsg)`` / ``context.receptionist_find(key, ListingMsg)``
+    (Receptionist.Subscribe / Find and the Listing message): ``A_SUBSCRIBE_LISTING`` / ``A_FIND``
+    with the key as pad1; the Listing of key k arrives as ``ListingMsg(k)``, one message type per key, and its
+    handler reads ``context.listing_size(key)`` / ``service_at(key, x)``; ``Tables.uses_listings`` ->
+    engine.set_listings(tables.listing_payloads), after engine.set_topics;
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -101,6 +106,7 @@ A_REGISTER, A_DEREGISTER, A_ROUTE = 17, 18, 19     # the service key is pad1
 ROUTE_KEEP_SENDER, ROUTE_BY_INDEX = 1, 2           # pad0 of A_ROUTE (KEEP_SENDER also of A_TELL: ref.forward)
 A_ASK_ARM, A_ASK_SEND = 20, 21                     # context.ask: `word` is the timer key
 A_PUBLISH = 22                                     # context.publish: the topic's key is pad1
+A_SUBSCRIBE_LISTING, A_FIND = 23, 24               # context.receptionist_subscribe / _find: the key is pad1
 # the ask ref a target sees as the sender: ASK_REF_BIT | key << 29 | (generation mod 2^7) << 22 | the asker's id
 ASK_REF_BIT, ASK_REF_KEY_SHIFT, ASK_REF_GEN_SHIFT, ASK_REF_GEN_MASK, ASK_REF_ID_MASK = 1 << 31, 29, 22, 0x7F, (1 << 22) - 1
 ASK_MAX_ACTORS = (1 << 22) - 1
@@ -207,6 +213,7 @@ class Action:
     key: object = None    # A_REGISTER / A_DEREGISTER / A_ROUTE: the ServiceKey
     flags: int = 0        # A_ROUTE / A_TELL: ROUTE_KEEP_SENDER, ROUTE_BY_INDEX (pad0)
     ask: object = None    # A_ASK_ARM: (the target's dst operand, the request's operand, its or_mask, adapt tag or None)
+    listing: object = None  # A_SUBSCRIBE_LISTING / A_FIND: the MessageType of the key's Listing
 
 
 class Field(Operand):
@@ -655,6 +662,26 @@ class ActorContext:
         return self._route(key, msg, 0, lift(index), ROUTE_BY_INDEX | (ROUTE_KEEP_SENDER if forward else 0))
 
 
+    # Subscribe / Find and the Listing message (engine.set_listings after engine.set_topics; TY/internal/receptionist/
+    # LocalReceptionist.scala:152-171,209-220)
+    def _listing(self, op: int, key, listing_msg) -> "Action":
+        if isinstance(key, Topic):
+            raise CompileError(f"a Topic has no Listing: subscribe to it with context.subscribe ({key!r})")
+        if not isinstance(listing_msg, MessageType):
+            raise CompileError(f"the Listing of a key is a MessageType: {listing_msg!r}")
+        return Action(op, 0, key=self._key(key), listing=listing_msg)
+
+    def receptionist_subscribe(self, key, listing_msg) -> "Action":
+        """receptionist ! Receptionist.Subscribe(key, context.self): the actor receives `listing_msg(key number)` in
+        the next tick (the current listing, on every Subscribe) and after every tick in which the key's listing
+        changed, until it stops; the handler reads the set with context.listing_size(key) / service_at(key, x).  Not
+        an envelope of the case."""
+        return self._listing(A_SUBSCRIBE_LISTING, key, listing_msg)
+
+    def receptionist_find(self, key, listing_msg) -> "Action":
+        """receptionist ! Receptionist.Find(key, context.self): one `listing_msg(key number)` in the next tick."""
+        return self._listing(A_FIND, key, listing_msg)
+
     # pub-sub topics (engine.set_topics after engine.set_receptionist; TY/internal/pubsub/TopicImpl.scala:60-143)
     @staticmethod
     def _topic(topic) -> Topic:
@@ -1044,6 +1071,7 @@ class Tables:
     spawn_sites: list = field(default_factory=list)  # (kind, word-0 base, word 1 or None: the parent's id) -> engine.set_children
     transparent_tags: tuple = ()  # the tags of the NotInfluenceReceiveTimeout message types -> engine.set_receive_timeout
     service_keys: list = field(default_factory=list)  # the ServiceKeys in use; the index is the key number -> engine.set_receptionist
+    listing_types: dict = field(default_factory=dict)  # key number -> the MessageType of its Listing -> engine.set_listings
 
     @property
     def uses_supervision(self) -> bool:
@@ -1078,6 +1106,18 @@ class Tables:
         """The behaviours publish or name a Topic: the engine needs engine.set_topics(log_capacity) after
         engine.set_receptionist(len(tables.service_keys), capacity)."""
         return any(isinstance(k, Topic) for k in self.service_keys) or any(a.op == A_PUBLISH for a in self.acts[:self.n_acts])
+
+    @property
+    def uses_listings(self) -> bool:
+        """The behaviours subscribe to or find a listing: the engine needs engine.set_listings(tables.listing_payloads)
+        after engine.set_topics(log_capacity)."""
+        return any(a.op in (A_SUBSCRIBE_LISTING, A_FIND) for a in self.acts[:self.n_acts])
+
+    @property
+    def listing_payloads(self) -> list:
+        """Per service key the payload of its Listing envelope: the key's message type with the key number as the
+        argument (0 for a key nobody subscribes to or finds)."""
+        return [self.listing_types[k].payload(k) if k in self.listing_types else 0 for k in range(len(self.service_keys))]
 
     @property
     def stash_capacity(self) -> int:
@@ -1176,6 +1216,7 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
     cases, acts, first = [], [], [0]
     sites = []  # the spawn sites in use, in order of appearance: (behaviour index, base, word 1)
     skeys = []  # the service keys in use, in order of appearance
+    ltypes = {}  # key number -> the MessageType of the key's Listing
 
     def key_no(key) -> int:
         if key not in skeys:
@@ -1215,7 +1256,7 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
             for e in c.effects:
                 d = res_op(e.dst or Operand(V_CONST))
                 if e.val is not res_op(e.val):
-                    e = Action(e.op, e.word, res_op(e.val), e.dst, e.or_mask, e.site, e.into, e.key, e.flags, e.ask)
+                    e = Action(e.op, e.word, res_op(e.val), e.dst, e.or_mask, e.site, e.into, e.key, e.flags, e.ask, e.listing)
                 if e.op == A_SPAWN:  # dword: the site; pad0: the word `word` receives the child's id
                     key = (index[id(e.site.behavior)], e.site.base, e.site.word1)
                     if key not in sites:
@@ -1233,6 +1274,11 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
                     acts.append(AgxAct(op=A_ASK_SEND, word=e.word, src=req.src, sword=req.word, k=req.k,
                                        dsrc=to.src, dword=to.word, dk=to.k, or_mask=req_mask))
                     continue
+                if e.op in (A_SUBSCRIBE_LISTING, A_FIND):  # one Listing message type per key
+                    kn = key_no(e.key)
+                    if ltypes.setdefault(kn, e.listing) != e.listing:
+                        raise CompileError(f"the Listing of {e.key!r} is {ltypes[kn]!r} and {e.listing!r}: one message type "
+                                           "per key")
                 acts.append(AgxAct(op=e.op, word=e.word, src=e.val.src, sword=e.val.word, k=e.val.k,
                                    dsrc=d.src, dword=d.word, dk=d.k, or_mask=e.or_mask, pad0=e.flags,
                                    pad1=key_no(e.key) if e.key is not None else 0))
@@ -1245,6 +1291,7 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
     t.spawn_sites = [(KIND_COMPILED + bi, base, w1) for bi, base, w1 in sites]
     t.transparent_tags = tuple(sorted({mt.tag for mt in transparent}))
     t.service_keys = skeys
+    t.listing_types = ltypes
     for b in behs:  # a supervisor of a class catches it and its descendants: the hierarchy as masks
         row = []
         for sv in b.supervisors:

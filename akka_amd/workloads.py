@@ -71,6 +71,9 @@ class Workload:
     # pub-sub topics (agx_set_topics, on top of `receptionist`): {"log_capacity": publications per tick} -- empty: no
     # topics
     topics: dict = field(default_factory=dict)
+    # Subscribe / Listing (agx_set_listings / agx_subscribe_listings, on top of `topics`): {"payloads": the Listing
+    # payload per key (typed.Tables.listing_payloads), "starts": [(first, count, key)]} -- empty: no listings
+    listings: dict = field(default_factory=dict)
     # host tells that follow the clock: schedule[t] = (dst, src, payload) is staged before tick t + 1 (run_schedule)
     schedule: list = field(default_factory=list)
 
@@ -110,6 +113,10 @@ class Workload:
                 target.register_services(first, count, key)
         if self.topics:  # (empty: targets without the call are unaffected)
             target.set_topics(self.topics["log_capacity"])
+        if self.listings:  # (empty: targets without the calls are unaffected)
+            target.set_listings(self.listings["payloads"])
+            for first, count, key in self.listings.get("starts", ()):
+                target.subscribe_listings(first, count, key)
         if self.timers:  # (empty: targets without the calls are unaffected)
             target.set_timers(self.timers["n_keys"])
             if self.timers.get("ask"):  # (the ask pattern, on top of the timers: agx_set_ask)
@@ -1317,3 +1324,92 @@ def topic_mesh(n: int = 1024, n_keys: int = 8, seed: int = 1, ticks: int = 40, t
                     bucket_actors=bucket_actors, outbound=(n, max(n_host, 1)),
                     receptionist={"n_keys": n_keys, "capacity": n, "starts": starts},
                     topics={"log_capacity": log_capacity}, schedule=schedule)
+
+
+# ------------------------------------------------------------------ Subscribe / Listing
+SW_LISTING, SW_STOP, SW_DEREG, SW_REG = 1, 2, 3, 4
+DW_LISTING, DW_GO, DW_JOB, DW_STOP = 1, 2, 3, 4
+
+
+def service_watchers(n_services: int = 64, n_watchers: int = 1 << 14, ticks: int = 16, period: int = 1, throughput: int = 3,
+                     bucket_actors: int = 0, stop: bool = False) -> Workload:
+    """Watchers of one service key (LocalReceptionist.scala:152-166,213-220): the services (ids 0 .. n_services - 1)
+    are registered and the watchers (ids n_services ..) subscribed in the setup block; a watcher keeps the size of
+    the listing it was told last (state word 1) and counts its Listings (state word 0).  Every `period`-th tick the
+    host tells one service to leave -- Deregister, or a stop with `stop` --, service t mod n_services in turn (a
+    service that has left registers again when it is told a second time), so one key changes per such tick and
+    every watcher receives one Listing in the tick after."""
+    from . import typed
+    B, ctx = typed.Behaviors, typed.context
+    key = typed.ServiceKey("watched")
+    listing = typed.MessageType("Listing", SW_LISTING)
+    leave, stopm = typed.MessageType("Leave", SW_DEREG), typed.MessageType("Stop", SW_STOP)
+    ss = typed.State("told", "member")
+    service = (typed.ReceiveBuilder.create(ss)
+               .on_message(stopm, lambda m, s: [B.stopped])
+               .on_message(leave, lambda m, s: [s.told.inc(), s.member.set(0), ctx.deregister(key), B.same], when=lambda m, s: s.member == 1)
+               .on_message(leave, lambda m, s: [s.told.inc(), s.member.set(1), ctx.register(key), B.same])
+               .on_any_message(lambda m, s: [B.unhandled])
+               .build("watched_service"))
+    ws = typed.State("listings", "size")
+    watcher = (typed.ReceiveBuilder.create(ws)
+               .on_message(listing, lambda m, s: [s.listings.inc(), s.size.set(ctx.listing_size(key)), B.same])
+               .on_message(typed.MessageType("Subscribe", SW_REG), lambda m, s: [ctx.receptionist_subscribe(key, listing), B.same])
+               .on_any_message(lambda m, s: [B.unhandled])
+               .build("service_watcher"))
+    tb = typed.compile_behaviors([service, watcher], max_emit=1)
+    n = n_services + n_watchers
+    sinit = np.zeros((n_services, 2), np.uint64)
+    sinit[:, 1] = 1
+    none = np.zeros(0, np.uint32)
+    schedule = []
+    for t in range(ticks):
+        if t % period:
+            schedule.append((none, none, none))
+            continue
+        who = (t // period) % n_services
+        msg = stopm if stop else leave
+        schedule.append((np.asarray([who], np.uint32), np.asarray([NO_SENDER], np.uint32), np.asarray([msg.payload()], np.uint32)))
+    return Workload("service_watchers", n, 2, 1, throughput, 0,
+                    [(0, n_services, tb.kind_of(service), sinit), (n_services, n_watchers, tb.kind_of(watcher), None)],
+                    behaviors=tb, bucket_actors=bucket_actors,
+                    receptionist={"n_keys": 1, "capacity": n_services, "starts": [(0, n_services, 0)]},
+                    topics={"log_capacity": 1},
+                    listings={"payloads": tb.listing_payloads, "starts": [(n_services, n_watchers, 0)]}, schedule=schedule)
+
+
+def discovery_workers(n_services: int = 16, n_workers: int = 1 << 10, jobs: int = 4, throughput: int = 3,
+                      bucket_actors: int = 0) -> Workload:
+    """Wait for the first listing (the pattern the group router's initial stash stands for; GroupRouterImpl.scala:
+    114-146, LocalReceptionist.scala:168-171,209-211): a worker told Go(x) finds the key and keeps x (state word 1);
+    when the Listing arrives it sends Job(x) to service_at(x) and counts it (state word 0), `jobs` times over: with
+    each job it finds the key again, and the next Listing brings the next job.  The services (ids 0 .. n_services - 1) are registered in the setup block and count
+    their jobs (state word 0) and sum the arguments (state word 1).  The host tells every worker Go once."""
+    from . import typed
+    B, ctx = typed.Behaviors, typed.context
+    key = typed.ServiceKey("workers_service")
+    listing, go, job = (typed.MessageType("Listing", DW_LISTING), typed.MessageType("Go", DW_GO), typed.MessageType("Job", DW_JOB))
+    ss = typed.State("jobs", "sum")
+    service = (typed.ReceiveBuilder.create(ss)
+               .on_message(job, lambda m, s: [s.jobs.inc(), s.sum.add(m.arg), B.same])
+               .on_any_message(lambda m, s: [B.unhandled])
+               .build("discovered_service"))
+    ws = typed.State("sent", "x")
+    rb = typed.ReceiveBuilder.create(ws)
+    rb.on_message(go, lambda m, s: [s.x.set(m.arg), ctx.receptionist_find(key, listing), B.same])
+    # the Listing, and then every job's own echo: send the next job while any is left
+    rb.on_message(listing, lambda m, s: [s.sent.inc(), ctx.service_at(key, s.x).tell(job(s.x)), ctx.receptionist_find(key, listing), B.same],
+                  when=lambda m, s: s.sent < jobs)
+    rb.on_message(listing, lambda m, s: [B.same])
+    rb.on_any_message(lambda m, s: [B.unhandled])
+    worker = rb.build("discovery_worker")
+    tb = typed.compile_behaviors([service, worker], max_emit=1)
+    n = n_services + n_workers
+    dst = np.arange(n_services, n, dtype=np.uint32)
+    pay = ((DW_GO << 24) | (np.arange(n_workers, dtype=np.uint32) & 0xFFFFFF)).astype(np.uint32)
+    schedule = [(dst, np.full(n_workers, NO_SENDER, np.uint32), pay)]
+    return Workload("discovery_workers", n, 2, 1, throughput, 0,
+                    [(0, n_services, tb.kind_of(service), None), (n_services, n_workers, tb.kind_of(worker), None)],
+                    behaviors=tb, bucket_actors=bucket_actors,
+                    receptionist={"n_keys": 1, "capacity": n_services, "starts": [(0, n_services, 0)]},
+                    topics={"log_capacity": 1}, listings={"payloads": tb.listing_payloads}, schedule=schedule)

@@ -207,7 +207,12 @@ enum agx_action_op {
    * the key (the topic), pad0 must be 0, the payload is the operand as a TELL's, there is no destination.  The
    * envelope every subscriber receives in the next tick carries the publisher as its sender.  A case holds at most
    * one of TELL, ROUTE and PUBLISH. */
-  AGX_A_PUBLISH = 22     /* topic ! Topic.Publish(msg) (TopicImpl.scala:60-143) */
+  AGX_A_PUBLISH = 22,    /* topic ! Topic.Publish(msg) (TopicImpl.scala:60-143) */
+  /* Subscribe / Find and the Listing message (engines with listings, agx_set_listings).  pad1 is the
+   * key, pad0 must be 0; an actor subscribes or asks for itself only.  Neither is an envelope of the case: a case may
+   * hold them beside its one TELL, ROUTE or PUBLISH. */
+  AGX_A_SUBSCRIBE_LISTING = 23, /* receptionist ! Subscribe(key, self) (LocalReceptionist.scala:213-220) */
+  AGX_A_FIND = 24               /* receptionist ! Find(key, self)      (LocalReceptionist.scala:209-211) */
 };
 /* The ask ref: AGX_ASK_REF_BIT | key << 29 | (generation mod 2^7) << 22 | the asker's id. */
 #define AGX_ASK_REF_BIT 0x80000000u
@@ -915,6 +920,38 @@ agx_status agx_topic_info(agx_engine* eng, uint64_t* published, uint64_t* fanned
  * out_sender / out_payload (each may be NULL), their number into out_n. */
 agx_status agx_read_topic_log(agx_engine* eng, uint32_t* out_key, uint32_t* out_sender, uint32_t* out_payload,
                               uint64_t cap, uint64_t* out_n);
+
+/* Receptionist.Subscribe / Find and the Listing message (TY/internal/receptionist/LocalReceptionist.scala:152-171,
+ * 209-220,233-238; pinned by LocalReceptionistSpec.scala:81-175; DESIGN.md 2.11 has the contract), on top of topics:
+ * call after agx_set_topics and before the first agx_run (AGX_ESTATE afterwards); a second call, a call without
+ * topics and an n_keys other than the receptionist's are AGX_EINVAL.  listing_payload[k] is the payload of a Listing
+ * envelope of key k (its message tag in bits 24..31); its sender is AGX_NO_SENDER.  Every actor holds two more masks:
+ * `sub` (bit k: subscribed to key k) and `pending` (bit k: one Listing of key k is owed at the next tick).
+ * AGX_A_SUBSCRIBE_LISTING sets both of the actor's own bits (also when repeated), AGX_A_FIND the pending bit only; a
+ * stop of any cause clears both masks; there is no unsubscribe on the device.  Key k changed in tick s when
+ * version[k] moved at the end of tick s, or when agx_register_services changed a bit between two runs.  When the inbox
+ * of tick s + 1 is formed, an alive actor receives exactly one Listing(k) if its pending bit k is set, or if k changed
+ * and its sub bit k is set; the pending bits served are cleared.  The Listings are the last items of the inbox, after
+ * the publications, in ascending key and, per key, ascending id; admission is by position.  The handler reads the set
+ * through AGX_V_LISTING_SIZE / AGX_V_SERVICE_AT: the listing in force in the tick the message is drained (a Listing
+ * queued by a throughput cap sees a newer one).  Owed Listings are in flight: staged + emitted + fanned_out +
+ * listings_sent = delivered + dead_letters + in_flight.  A bucket's inbox, Listings included, is limited to one tile
+ * of 2048 messages as on every engine with the receptionist.  Tables with the two actions on an engine without
+ * listings, or with a key the receptionist does not have, make agx_run return AGX_EINVAL. */
+agx_status agx_set_listings(agx_engine* eng, const uint32_t* listing_payload, uint32_t n_keys);
+/* The setup block (Behaviors.setup { ctx => receptionist ! Subscribe(key, ctx.self) }), before the first run or
+ * between runs, for the live actors of [first_id, first_id + count): on != 0 sets `sub` and `pending` (the initial
+ * Listing arrives in the next tick); on == 0 clears `sub` (a convenience of the host; a pending bit stays).
+ * AGX_EINVAL on an engine without listings or for a key the receptionist does not have. */
+agx_status agx_subscribe_listings(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t key, uint32_t on);
+/* Totals since agx_create: subscribes / finds (actions run, plus the members of an agx_subscribe_listings range with
+ * on != 0 whose masks changed), listings_sent (Listing envelopes created), notified (key-ticks in which a changed key
+ * had at least one recipient).  A re-plan after a host call between a change and its Listings corrects listings_sent
+ * and notified.  Any pointer may be NULL.  AGX_EINVAL on an engine without listings. */
+agx_status agx_listing_info(agx_engine* eng, uint64_t* subscribes, uint64_t* finds, uint64_t* listings_sent,
+                            uint64_t* notified);
+/* The `sub` and `pending` masks of actors [first, first + count) (either pointer may be NULL). */
+agx_status agx_read_subscriptions(agx_engine* eng, uint64_t first, uint64_t count, uint8_t* sub_out, uint8_t* pending_out);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
