@@ -124,6 +124,9 @@ SIGNATURES = {
     "agx_subscribe_listings": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
     "agx_listing_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 4),
     "agx_read_subscriptions": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_u8p, c_u8p]),
+    "agx_set_router_logics": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
+    "agx_router_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 3 + [c_u32p]),
+    "agx_read_hash_ring": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, c_u32p, c_u32p, ctypes.c_uint64, c_u64p]),
     "agx_set_outbound": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]),
     "agx_take_outbound": (ctypes.c_int32, [ctypes.c_void_p, c_u32p, c_u32p, c_u32p, ctypes.c_uint64, c_u64p]),
     "agx_set_gossip": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]),
@@ -169,7 +172,7 @@ SIGNATURES = {
 
 # entry points newer than some A/B diagnostic builds (tools/build_variant.sh of an older checkout)
 OPTIONAL = {"agx_tell", "agx_pump_idle", "agx_pump_cancel", "agx_exchange_info", "agx_run_timed", "agx_build_hash",
-            "agx_persist_info"}
+            "agx_persist_info", "agx_set_router_logics", "agx_router_info", "agx_read_hash_ring"}
 
 
 def load():

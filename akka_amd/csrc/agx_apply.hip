@@ -94,6 +94,7 @@ hipError_t feature_dispatch(uint32_t vid, uint32_t mode, uint32_t km_flags, bool
         case kWatchKM | kChildKM: return launch_feature<V_ALL_COMPILED, kWatchKM | kChildKM, false>(mode, g, s, ba);
         case kSuperKM: return launch_feature<V_ALL_COMPILED, kSuperKM, false>(mode, g, s, ba);
         case kRecepKM: return launch_feature<V_ALL_COMPILED, kRecepKM, false>(mode, g, s, ba);
+        case kRecepKM | kHashKM: return launch_feature<V_ALL_COMPILED, kRecepKM | kHashKM, false>(mode, g, s, ba);
         case kRecepKM | kTopicKM: return launch_feature<V_ALL_COMPILED, kRecepKM | kTopicKM, false>(mode, g, s, ba);
         case kRecepKM | kTopicKM | kListKM:
           return launch_feature<V_ALL_COMPILED, kRecepKM | kTopicKM | kListKM, false>(mode, g, s, ba);

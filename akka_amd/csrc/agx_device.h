@@ -737,6 +737,9 @@ constexpr uint32_t kAskKM = 1u << 23;
 constexpr uint32_t kTopicKM = 1u << 22;
 // KM flag (not a kind): the variant knows Subscribe / Listing (agx_set_listings); only ever with kRecepKM | kTopicKM.
 constexpr uint32_t kListKM = 1u << 21;
+// KM flag (not a kind): the variant knows consistent-hashing and random routing (agx_set_router_logics); only ever
+// combined with kRecepKM.
+constexpr uint32_t kHashKM = 1u << 20;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -1670,6 +1673,218 @@ __device__ __forceinline__ uint32_t compiled_apply_ls(const DevParams& P, const 
           if (A.op == AGX_A_ROUTE) {
             const uint32_t key = A.pad1 & 7u;
             if (A.pad0 & AGX_ROUTE_BY_INDEX) {
+              ref = RD.at(key, d);
+            } else {
+              ref = RD.successor(key, w[A.word & 1u]);
+              if (ref != kRcNone) w[A.word & 1u] = (uint64_t)ref + 1ull;  // (no routee: the cursor stays)
+            }
+            if (ref == kRcNone) ++rc.none;
+            else ++rc.routed;
+          }
+          if (A.pad0 & AGX_ROUTE_KEEP_SENDER) {  // a forward: the envelope keeps the incoming message's sender
+            const uint32_t me = emit.self;
+            emit.self = src;
+            emit(ref, msg);
+            emit.self = me;
+          } else {
+            emit(ref, msg);
+          }
+          break;
+        }
+        default: break;
+      }
+    }
+    if (C.result == AGX_RES_BECOME) {
+      kind = AGX_KIND_COMPILED + C.next;
+      return AGX_RES_SAME;
+    }
+    return C.result;
+  }
+  return AGX_RES_UNHANDLED;
+}
+
+// ---- consistent-hashing and random routing (agx_set_router_logics; TY/internal/routing/
+// RoutingLogic.scala:77-112, akka-actor routing/ConsistentHash.scala:25-139, routing/MurmurHash.scala:37-129), on top of
+// the receptionist.  An allocation of its own whose address stands in words [kRcHashPtr, kRcHashPtr + 2) of the
+// receptionist's storage, u32 units:
+//   [0] hashed_keys_mask   [1] virtual_nodes_factor   [2] npts: the ring points of all actors (n_actors x factor; 0
+//       with an empty mask)   [3] nseg: segments of kHrSeg points   [4..5] the seed of random routing (u64)
+//   [8..13]  three u64 counters: hashed, random, ring_rebuilds   [16..23] ring_size[k] of the ring in force
+//   [kHrSegOff + slot * nseg + s]  segcnt: the members of the key in segment s of the static ring (k_hash_count), then
+//   segoff[slot * nseg + s]: their offset in the key's ring (k_hash_scan); slot = the key's rank among the hashed keys
+//   then the static ring, npts hashes and npts ids sorted by (signed hash, id): every actor's points, built once
+//   then per slot the key's ring, npts hashes and npts ids: the stable compaction of the static ring by the key's
+//   mask bit (k_hash_fill), rewritten between two applies only
+// The drains only read the rings in force and the header.
+constexpr uint32_t kRcHashPtr = 20;
+constexpr uint32_t kHrMask = 0, kHrFactor = 1, kHrNpts = 2, kHrNseg = 3, kHrSeed = 4, kHrCtr = 8, kHrSize = 16, kHrSegOff = 32;
+constexpr uint32_t kHrHashed = 0, kHrRandom = 1, kHrRebuilds = 2;
+constexpr uint32_t kHrSeg = 1024;
+constexpr uint32_t kHrRandomTag = 0x02000000u;  // fanout_rand's domain of random routing (0: fan-out, 0x04.., 0x08..: gossip)
+__host__ __device__ __forceinline__ size_t hr_static_off(uint32_t nslots, uint32_t nseg) {
+  return (size_t)kHrSegOff + 2ull * nslots * nseg;
+}
+__host__ __device__ __forceinline__ size_t hr_words(uint32_t nslots, uint32_t nseg, uint32_t npts) {
+  return hr_static_off(nslots, nseg) + 2ull * npts * (1ull + nslots);
+}
+struct HashDev {
+  uint32_t* base;
+  uint32_t hmask, npts, nseg, nslots;
+  __device__ __forceinline__ uint32_t slot(uint32_t k) const { return (uint32_t)__popc(hmask & ((1u << k) - 1u)); }
+  __device__ __forceinline__ uint32_t* segcnt(uint32_t sl) const { return base + kHrSegOff + (size_t)sl * nseg; }
+  __device__ __forceinline__ uint32_t* segoff(uint32_t sl) const { return base + kHrSegOff + (size_t)(nslots + sl) * nseg; }
+  __device__ __forceinline__ uint32_t* st_hash() const { return base + hr_static_off(nslots, nseg); }
+  __device__ __forceinline__ uint32_t* st_id() const { return st_hash() + npts; }
+  __device__ __forceinline__ uint32_t* ring_hash(uint32_t sl) const { return st_hash() + 2ull * npts * (1ull + sl); }
+  __device__ __forceinline__ uint32_t* ring_id(uint32_t sl) const { return ring_hash(sl) + npts; }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kHrCtr) + i;
+  }
+};
+__device__ __forceinline__ HashDev hash_dev(uint32_t* base) {
+  HashDev h;
+  h.base = base;
+  h.hmask = base[kHrMask];
+  h.npts = base[kHrNpts];
+  h.nseg = base[kHrNseg];
+  h.nslots = (uint32_t)__popc(h.hmask);
+  return h;
+}
+__device__ __forceinline__ uint32_t* hash_base_of(const uint32_t* recep) {
+  return *reinterpret_cast<uint32_t* const*>(recep + kRcHashPtr);
+}
+
+// MurmurHash.scala:37-100 in wrapping 32-bit arithmetic (Java Int: `>>>` is the unsigned shift)
+__host__ __device__ __forceinline__ uint32_t mm_extend(uint32_t h, uint32_t v, uint32_t ma, uint32_t mb) {
+  const uint32_t x = v * ma;
+  return (h ^ (((x << 11) | (x >> 21)) * mb)) * 3u + 0x52dce729u;
+}
+__host__ __device__ __forceinline__ uint32_t mm_finalize(uint32_t h) {
+  uint32_t i = h ^ (h >> 16);
+  i *= 0x85ebca6bu;
+  i ^= i >> 13;
+  i *= 0xc2b2ae35u;
+  i ^= i >> 16;
+  return i;
+}
+// MurmurHash.stringHash (MurmurHash.scala:115-129) of x as an unsigned decimal string without padding: the digits as
+// ten BCD nibbles (divisions by constants), two characters per extendHash step, an odd last one alone
+__host__ __device__ __forceinline__ uint32_t mm_decimal_hash(uint32_t x) {
+  uint64_t bcd = 0;
+  uint32_t len = 1, r = x;
+#pragma unroll
+  for (uint32_t i = 0; i < 10; ++i) {
+    const uint32_t q = r / 10u, d = r - q * 10u;
+    bcd |= (uint64_t)d << (4u * i);
+    len = d ? i + 1u : len;
+    r = q;
+  }
+  uint32_t h = (len * 0xf7ca7fd2u) ^ 0x971e137bu, c = 0x95543787u, k = 0x2ad7eb25u, j = 0;
+  for (; j + 1u < len; j += 2u) {  // (character j is nibble len - 1 - j)
+    const uint32_t c0 = 0x30u + (uint32_t)((bcd >> (4u * (len - 1u - j))) & 15u);
+    const uint32_t c1 = 0x30u + (uint32_t)((bcd >> (4u * (len - 2u - j))) & 15u);
+    h = mm_extend(h, (c0 << 16) + c1, c, k);
+    c = c * 5u + 0x7b7d159cu;
+    k = k * 5u + 0x6bce6396u;
+  }
+  if (j < len) h = mm_extend(h, 0x30u + (uint32_t)(bcd & 15u), c, k);
+  return mm_finalize(h);
+}
+// ConsistentHash.concatenateNodeHash (ConsistentHash.scala:134-139)
+__host__ __device__ __forceinline__ uint32_t mm_node_point(uint32_t node_hash, uint32_t vnode) {
+  return mm_finalize(mm_extend(node_hash ^ 0x971e137bu, vnode, 0x95543787u, 0x2ad7eb25u));
+}
+// ConsistentHash.nodeFor(x.toString) (ConsistentHash.scala:76-83,100-110) on the ring of n points: the id of the first
+// entry with hash >= stringHash(str(x)) as signed integers, else of entry 0 (none: an empty ring).  Inlined: kept out
+// of line the two instantiations spill more (81 / 64 VGPRs against 62 / 62: the call keeps the drain's registers live
+// across it).
+__device__ __forceinline__ uint32_t hr_node_for(const uint32_t* rh, const uint32_t* rid, uint32_t n, uint32_t x) {
+  if (!n) return kRcNone;
+  const int32_t h = (int32_t)mm_decimal_hash(x);
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if ((int32_t)rh[mid] < h) lo = mid + 1u;
+    else hi = mid;
+  }
+  return rid[lo == n ? 0u : lo];
+}
+// what one thread's drains routed by the two logics: added to the counters once per wave (hash_commit)
+struct HashCount {
+  uint32_t hashed, random;
+};
+
+// compiled_apply of the router-logics instantiations: compiled_apply_rc plus AGX_ROUTE_HASHED and AGX_ROUTE_RANDOM on
+// AGX_A_ROUTE.  A function of its own: every other instantiation compiles compiled_apply_rc as before.  (Its other
+// cases are compiled_apply_rc's: a fix to one of them belongs in both.)
+template <typename Emit>
+__device__ __forceinline__ uint32_t compiled_apply_hr(const DevParams& P, const RecepDev& RD, const HashDev& HD, uint32_t& kind,
+                                                      uint32_t self, uint64_t* w, uint32_t src, uint32_t pay, uint32_t& mk,
+                                                      RecepCount& rc, HashCount& hc, Emit& emit) {
+  const uint32_t b = kind - AGX_KIND_COMPILED;
+  if (b >= P.n_beh) return AGX_RES_UNHANDLED;
+  const uint32_t c1 = P.bfirst[b + 1];
+  for (uint32_t c = P.bfirst[b]; c < c1; ++c) {
+    const agx_case C = P.bcase[c];
+    if (!cb_cmp(C.cmp1, rc_operand(RD, C.src1, C.word1, C.k1, pay, w, src, self),
+                rc_operand(RD, C.src2, C.word2, C.k2, pay, w, src, self)))
+      continue;
+    if (!cb_cmp(C.cmp2, rc_operand(RD, C.src3, C.word3, C.k3, pay, w, src, self),
+                rc_operand(RD, C.src4, C.word4, C.k4, pay, w, src, self)))
+      continue;
+    for (uint32_t i = C.act_first; i < (uint32_t)C.act_first + C.act_count; ++i) {
+      const agx_act A = P.bact[i];
+      const uint64_t v = rc_operand(RD, A.src, A.sword, A.k, pay, w, src, self);
+      const uint32_t msg = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;
+      const uint32_t bit = 1u << (A.pad1 & 7u);
+      switch (A.op) {
+        case AGX_A_SET: w[A.word & 1u] = v; break;
+        case AGX_A_ADD: w[A.word & 1u] += v; break;
+        case AGX_A_MAX: w[A.word & 1u] = v > w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_MIN: w[A.word & 1u] = v < w[A.word & 1u] ? v : w[A.word & 1u]; break;
+        case AGX_A_REGISTER:
+          if (!(mk & bit)) {
+            mk |= bit;
+            ++rc.reg;
+          }
+          break;
+        case AGX_A_DEREGISTER:
+          if (mk & bit) {
+            mk &= ~bit;
+            ++rc.dereg;
+          }
+          break;
+        case AGX_A_TELL:
+        case AGX_A_ROUTE: {
+          uint64_t d = 0;
+          if (A.op == AGX_A_TELL || (A.pad0 & (AGX_ROUTE_BY_INDEX | AGX_ROUTE_HASHED))) {
+            if (A.dsrc == AGX_V_SELF && A.op == AGX_A_TELL) {  // (self + dk) mod n: ring neighbours
+              int64_t x = ((int64_t)self + A.dk) % (int64_t)P.n_global;
+              d = (uint64_t)(x < 0 ? x + (int64_t)P.n_global : x);
+            } else {
+              d = rc_operand(RD, A.dsrc, A.dword, A.dk, pay, w, src, self);
+            }
+          }
+          uint32_t ref = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
+          if (A.op == AGX_A_ROUTE) {
+            const uint32_t key = A.pad1 & 7u;
+            if (A.pad0 & AGX_ROUTE_HASHED) {  // (a key outside the mask was refused at agx_run)
+              const uint32_t sl = HD.slot(key);
+              ref = ((HD.hmask >> key) & 1u) ? hr_node_for(HD.ring_hash(sl), HD.ring_id(sl), HD.base[kHrSize + key], (uint32_t)d)
+                                             : kRcNone;
+              if (ref != kRcNone) ++hc.hashed;
+            } else if (A.pad0 & AGX_ROUTE_RANDOM) {
+              const uint32_t n = RD.size(key);
+              if (n) {  // (no routee: the counter stays)
+                const uint64_t seed = *reinterpret_cast<const uint64_t*>(HD.base + kHrSeed);
+                const uint32_t cn = (uint32_t)w[A.word & 1u];
+                ref = RD.list(key)[(uint32_t)(fanout_rand(seed, self, (cn & 0x00FFFFFFu) | kHrRandomTag, 0) % n)];
+                w[A.word & 1u] += 1ull;
+                ++hc.random;
+              } else {
+                ref = kRcNone;
+              }
+            } else if (A.pad0 & AGX_ROUTE_BY_INDEX) {
               ref = RD.at(key, d);
             } else {
               ref = RD.successor(key, w[A.word & 1u]);

@@ -238,6 +238,13 @@ struct agx_engine {
     uint32_t key, on;
   };
   std::vector<ListStart> ls_starts;  // agx_subscribe_listings calls not yet applied on the device
+  // consistent-hashing and random routing (agx_set_router_logics), on top of the receptionist: the hash rings.  Such
+  // an engine launches the kRecep | kHash instantiation, and the ring kernels after the rebuild kernels
+  uint32_t* d_hash = nullptr;    // (its address stands in the receptionist's storage: agx_device.h HashDev)
+  uint32_t hr_mask = 0, hr_factor = 0, hr_npts = 0, hr_nseg = 0;
+  bool beh_router = false;       // the compiled tables route by consistent hashing or at random
+  uint32_t beh_hashed_keys = 0;  // the keys they route through by consistent hashing (a mask)
+  int64_t beh_route_two = -1;    // the first action with two of BY_INDEX / HASHED / RANDOM (-1: none)
   // the reply path (agx_set_outbound): host-side actor ids and the outbox
   uint32_t host_lo = 0, host_n = 0;
   uint64_t outbox_cap = 0;
@@ -466,7 +473,7 @@ namespace {
 // of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
 // the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
 // apply_variant, launch_apply and make_params.
-enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_ASK, F_LIST, F_TOPIC, F_N, F_NONE = F_N };
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_ASK, F_LIST, F_TOPIC, F_HASH, F_N, F_NONE = F_N };
 
 struct FeatureRow {
   bool (*on)(const agx_engine*);
@@ -526,6 +533,10 @@ const FeatureRow kFeatures[F_N] = {
     // pub-sub topics (agx_set_topics) come on top of the receptionist in the same way
     {[](const agx_engine* e) { return e->d_topic != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      nullptr, kRecepKM | kTopicKM, false, F_RECEP},
+    // consistent-hashing and random routing (agx_set_router_logics) come on top of the receptionist too; they and
+    // topics exclude one another
+    {[](const agx_engine* e) { return e->d_hash != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+     nullptr, kRecepKM | kHashKM, false, F_RECEP},
 };
 #undef AGX_ONCE
 
@@ -998,10 +1009,127 @@ static __global__ void __launch_bounds__(kRcThreads) k_recep_start(uint32_t* rc,
   }
 }
 
+// ---- consistent-hashing routing (agx_set_router_logics): the rings of the hashed keys being rebuilt
+// (dirty_now after k_recep_scan, or `force`) are rewritten as the stable compaction of the static ring by the key's
+// mask bit.  k_recep_fill -> k_hash_count -> k_hash_scan -> k_hash_fill -> the next apply are kernel boundaries.
+// Each kernel returns at entry when no hashed key is being rebuilt (one flags word and the header read).
+static_assert(kHrSeg % kRcThreads == 0, "a segment is whole chunks of one block");
+__device__ __forceinline__ uint32_t hash_keys_now(const uint32_t* rc, const uint32_t* hb, uint32_t force) {
+  return (((rc[kRcFlags] >> 8) & 0xFFu) | force) & hb[kHrMask];
+}
+// One block per segment of the static ring: the segment's members of each such key (a gather of one mask byte per point)
+static __global__ void __launch_bounds__(kRcThreads) k_hash_count(uint32_t* rc, uint32_t force) {
+  uint32_t* const hb = hash_base_of(rc);
+  const uint32_t now = hash_keys_now(rc, hb, force);
+  if (!now) return;
+  const RecepDev RD = recep_dev(rc);
+  const HashDev HD = hash_dev(hb);
+  __shared__ uint32_t s_c[AGX_MAX_SERVICE_KEYS];
+  const uint32_t tid = threadIdx.x, s = blockIdx.x, p0 = s * kHrSeg;
+  if (tid < AGX_MAX_SERVICE_KEYS) s_c[tid] = 0u;
+  __syncthreads();
+  const uint32_t* const sid = HD.st_id();
+  uint32_t cnt[AGX_MAX_SERVICE_KEYS] = {};
+  for (uint32_t c0 = 0; c0 < kHrSeg; c0 += kRcThreads) {
+    const uint32_t p = p0 + c0 + tid;
+    const uint32_t m = p < HD.npts ? RD.mask[sid[p]] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) cnt[k] += (m >> k) & 1u;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+    if (!((now >> k) & 1u)) continue;  // (block-uniform)
+    const uint32_t t = wave_incl_sum(cnt[k]);
+    if (lane_id() == kWave - 1 && t) atomicAdd(&s_c[k], t);
+  }
+  __syncthreads();
+  if (tid < AGX_MAX_SERVICE_KEYS && ((now >> tid) & 1u)) HD.segcnt(HD.slot(tid))[s] = s_c[tid];
+}
+// One block per key: the exclusive scan of the key's segment counts into the segment offsets, the ring's size
+static __global__ void __launch_bounds__(kRcThreads) k_hash_scan(uint32_t* rc, uint32_t force) {
+  uint32_t* const hb = hash_base_of(rc);
+  const uint32_t k = blockIdx.x;
+  if (!((hash_keys_now(rc, hb, force) >> k) & 1u)) return;
+  const HashDev HD = hash_dev(hb);
+  const uint32_t sl = HD.slot(k);
+  __shared__ uint32_t scratch[kRcThreads / kWave + 1];
+  uint32_t run = 0;
+  for (uint32_t s0 = 0; s0 < HD.nseg; s0 += kRcThreads) {  // (block-uniform trip count)
+    const uint32_t s = s0 + threadIdx.x;
+    const uint32_t c = s < HD.nseg ? HD.segcnt(sl)[s] : 0u;
+    uint32_t tot;
+    const uint32_t ex = block_excl_sum<kRcThreads>(c, scratch, &tot);
+    if (s < HD.nseg) HD.segoff(sl)[s] = run + ex;
+    run += tot;
+  }
+  if (threadIdx.x == 0) {
+    hb[kHrSize + k] = run;
+    if (!((force >> k) & 1u)) atomicAdd(HD.ctr(kHrRebuilds), 1ull);  // (not the first build of the setter)
+  }
+}
+// One block per segment: the segment's members of each such key go to the key's ring at the segment's offset, in the
+// static ring's order: ballot and lane rank within a wave, the waves' counts through LDS (as k_recep_fill)
+static __global__ void __launch_bounds__(kRcThreads) k_hash_fill(uint32_t* rc, uint32_t force) {
+  uint32_t* const hb = hash_base_of(rc);
+  const uint32_t now = hash_keys_now(rc, hb, force);
+  if (!now) return;
+  const RecepDev RD = recep_dev(rc);
+  const HashDev HD = hash_dev(hb);
+  constexpr uint32_t kW = kRcThreads / kWave;
+  __shared__ uint32_t s_wc[AGX_MAX_SERVICE_KEYS][kW];
+  const uint32_t tid = threadIdx.x, w = tid / kWave, s = blockIdx.x, p0 = s * kHrSeg;
+  const uint64_t lt = lanemask_lt();
+  const uint32_t* const sh = HD.st_hash();
+  const uint32_t* const sid = HD.st_id();
+  uint32_t run[AGX_MAX_SERVICE_KEYS] = {};
+  for (uint32_t c0 = 0; c0 < kHrSeg; c0 += kRcThreads) {  // (block-uniform trip count)
+    const uint32_t p = p0 + c0 + tid;
+    const uint32_t id = p < HD.npts ? sid[p] : 0u;
+    const uint32_t m = p < HD.npts ? RD.mask[id] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+      if (!((now >> k) & 1u)) continue;
+      const uint64_t bal = __ballot((m >> k) & 1u);
+      if (lane_id() == 0) s_wc[k][w] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k) {
+      if (!((now >> k) & 1u)) continue;
+      const uint64_t bal = __ballot((m >> k) & 1u);
+      uint32_t pre = 0, tot = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < kW; ++i) {
+        const uint32_t t = s_wc[k][i];
+        pre += i < w ? t : 0u;
+        tot += t;
+      }
+      if ((m >> k) & 1u) {
+        const uint32_t sl = HD.slot(k);
+        const uint32_t pos = HD.segoff(sl)[s] + run[k] + pre + (uint32_t)__popcll(bal & lt);
+        if (pos < HD.npts) {
+          HD.ring_hash(sl)[pos] = sh[p];
+          HD.ring_id(sl)[pos] = id;
+        }
+      }
+      run[k] += tot;
+    }
+    __syncthreads();  // (s_wc is rewritten by the next chunk)
+  }
+}
+
+void launch_hash_rebuild(agx_engine* e, uint32_t force) {
+  if (!e->hr_nseg) return;  // (random routing only: no ring)
+  hipLaunchKernelGGL(k_hash_count, dim3(e->hr_nseg), dim3(kRcThreads), 0, e->stream, e->d_recep, force);
+  hipLaunchKernelGGL(k_hash_scan, dim3(e->rc_keys), dim3(kRcThreads), 0, e->stream, e->d_recep, force);
+  hipLaunchKernelGGL(k_hash_fill, dim3(e->hr_nseg), dim3(kRcThreads), 0, e->stream, e->d_recep, force);
+}
+
 void launch_recep_rebuild(agx_engine* e) {
   hipLaunchKernelGGL(k_recep_scan, dim3(e->rc_keys), dim3(kRcThreads), 0, e->stream, e->d_recep,
                      reinterpret_cast<unsigned long long*>(e->d_stats + ST_ERROR));
   hipLaunchKernelGGL(k_recep_fill, dim3(e->nb), dim3(kRcThreads), 0, e->stream, e->d_recep, e->bb, (uint32_t)e->n_local);
+  if (e->d_hash) launch_hash_rebuild(e, 0u);  // (the rings of the hashed keys that k_recep_scan marked)
 }
 
 // ---- pub-sub topics (agx_set_topics): the plan between two supersteps.  apply -> k_topic_plan -> the
@@ -2221,6 +2349,16 @@ agx_status prepare_run(agx_engine* e) {
   if (e->d_recep && e->beh_rc_keys > e->rc_keys)
     return set_err(AGX_EINVAL, "the compiled behaviours use service key %u, but the receptionist has %u keys "
                    "(agx_set_receptionist)", e->beh_rc_keys - 1u, e->rc_keys);
+  if (e->beh_route_two >= 0)
+    return set_err(AGX_EINVAL, "compiled behaviours: route action %lld sets more than one of AGX_ROUTE_BY_INDEX, "
+                   "AGX_ROUTE_HASHED and AGX_ROUTE_RANDOM", (long long)e->beh_route_two);
+  if (e->beh_router && !e->d_hash)  // (only the router-logics variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours route by consistent hashing or at random, but the engine has no "
+                   "router logics (agx_set_router_logics)");
+  if (e->beh_hashed_keys & ~e->hr_mask)
+    return set_err(AGX_EINVAL, "the compiled behaviours route by consistent hashing through service key %u, which is not a "
+                   "hashed key (agx_set_router_logics: hashed_keys_mask 0x%x)",
+                   (uint32_t)__builtin_ctz(e->beh_hashed_keys & ~e->hr_mask), e->hr_mask);
   if (e->beh_publish && !e->d_topic)  // (only the topic variant interprets those: loud, never wrong)
     return set_err(AGX_EINVAL, "the compiled behaviours publish, but the engine has no topics (agx_set_topics)");
   if (e->beh_listing && !e->d_list)  // (only the listings variant interprets those: loud, never wrong)
@@ -3858,6 +3996,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_recep);
   hipFree(e->d_topic);
   hipFree(e->d_list);
+  hipFree(e->d_hash);
   hipFree(e->d_chunk_off); hipFree(e->d_chunk_cnt); hipFree(e->d_hist_c); hipFree(e->d_hist_d); hipFree(e->d_tot); hipFree(e->d_bstart); hipFree(e->d_dbg);
   hipFree(e->d_moff0); hipFree(e->d_moff1); hipFree(e->d_blpre); hipFree(e->d_ninbox); hipFree(e->d_n); hipFree(e->d_total);
   hipFree(e->d_stats); hipFree(e->d_bstats); hipFree(e->d_cvec); hipFree(e->d_cmat);
@@ -4680,6 +4819,9 @@ agx_status agx_set_topics(agx_engine* e, uint32_t log_capacity) {
   if (e->d_topic) return set_err(AGX_EINVAL, "topics are already set (a log of %u publications)", e->tp_cap);
   if (!e->d_recep)
     return set_err(AGX_EINVAL, "topics need an engine with the receptionist (agx_set_receptionist): a topic is a service key");
+  if (e->d_hash)
+    return set_err(AGX_EINVAL, "topics need an engine without router logics (agx_set_router_logics): the hashed and random "
+                   "routes know no topics");
   if (e->started) return set_err(AGX_ESTATE, "set topics before the first agx_run");
   AGX_TRY(ensure_dev(e));
   const size_t words = tp_words(log_capacity, e->nb);
@@ -4825,6 +4967,113 @@ agx_status agx_read_subscriptions(agx_engine* e, uint64_t first, uint64_t count,
   const uint8_t* const sub = reinterpret_cast<const uint8_t*>(e->d_list + ((ls_mask_off(e->rc_keys, e->nb) + 3u) & ~(size_t)3));
   if (sub_out) AGX_TRY(copy_sync(e, sub_out, sub + first, count, hipMemcpyDeviceToHost));
   if (pending_out) AGX_TRY(copy_sync(e, pending_out, sub + ((size_t)e->nb << e->bb) + first, count, hipMemcpyDeviceToHost));
+  return AGX_OK;
+}
+
+// TY/internal/routing/RoutingLogic.scala:77-112; akka-actor routing/ConsistentHash.scala:25-139
+agx_status agx_set_router_logics(agx_engine* e, uint32_t hashed_keys_mask, uint32_t virtual_nodes_factor, uint64_t seed) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_recep)
+    return set_err(AGX_EINVAL, "router logics need an engine with the receptionist (agx_set_receptionist): a router routes "
+                   "through a service key");
+  if (e->d_topic)
+    return set_err(AGX_EINVAL, "router logics need an engine without topics (agx_set_topics): the hashed and random routes "
+                   "know no topics");
+  if (e->d_hash) return set_err(AGX_EINVAL, "router logics are already set (hashed_keys_mask 0x%x)", e->hr_mask);
+  if (hashed_keys_mask >> e->rc_keys)
+    return set_err(AGX_EINVAL, "router logics: hashed_keys_mask 0x%x names a service key past the receptionist's %u",
+                   hashed_keys_mask, e->rc_keys);
+  if (hashed_keys_mask && (virtual_nodes_factor < 1u || virtual_nodes_factor > AGX_MAX_VIRTUAL_NODES))
+    return set_err(AGX_EINVAL, "router logics: a virtual_nodes_factor of %u (1..%u)", virtual_nodes_factor, AGX_MAX_VIRTUAL_NODES);
+  if (hashed_keys_mask && e->n_global * (uint64_t)virtual_nodes_factor > AGX_MAX_RING_POINTS)
+    return set_err(AGX_EINVAL, "router logics: %llu actors x a virtual_nodes_factor of %u are more than %u ring points",
+                   (unsigned long long)e->n_global, virtual_nodes_factor, AGX_MAX_RING_POINTS);
+  if (e->started) return set_err(AGX_ESTATE, "set router logics before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_recep_starts(e));  // (what was registered before this call is in the first rings: no ring_rebuilds for it)
+  const uint32_t factor = hashed_keys_mask ? virtual_nodes_factor : 0u;
+  const uint32_t npts = (uint32_t)(e->n_global * factor), nseg = (npts + kHrSeg - 1u) / kHrSeg;
+  const uint32_t nslots = (uint32_t)__builtin_popcount(hashed_keys_mask);
+  const size_t words = hr_words(nslots, nseg, npts);
+  // the ring of all actors, built once on the host: every id's points, sorted by (signed hash, id)
+  std::vector<uint64_t> pts(npts);
+  for (uint64_t a = 0; a < (npts ? e->n_global : 0); ++a) {
+    const uint32_t nh = mm_decimal_hash((uint32_t)a);
+    for (uint32_t v = 1; v <= factor; ++v)
+      pts[a * factor + v - 1u] = ((uint64_t)(mm_node_point(nh, v) ^ 0x80000000u) << 32) | a;  // (the sign bit flipped: signed order)
+  }
+  std::sort(pts.begin(), pts.end());
+  std::vector<uint32_t> st(2ull * npts);
+  for (uint32_t i = 0; i < npts; ++i) {
+    st[i] = (uint32_t)(pts[i] >> 32) ^ 0x80000000u;
+    st[npts + i] = (uint32_t)pts[i];
+  }
+  if (hipMalloc((void**)&e->d_hash, words * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_hash = nullptr;
+    return set_err(AGX_ENOMEM, "the hash rings' storage (%u hashed keys, %u ring points: %llu MB) does not fit on the device",
+                   nslots, npts, (unsigned long long)(words >> 18));
+  }
+  uint32_t head[6] = {hashed_keys_mask, factor, npts, nseg, (uint32_t)seed, (uint32_t)(seed >> 32)};
+  const unsigned long long addr = (unsigned long long)(uintptr_t)e->d_hash;
+  hipError_t he = hipMemsetAsync(e->d_hash, 0, words * 4ull, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(e->d_hash, head, sizeof(head), hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess && npts)
+    he = hipMemcpyAsync(e->d_hash + hr_static_off(nslots, nseg), st.data(), st.size() * 4ull, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(e->d_recep + kRcHashPtr, &addr, sizeof(addr), hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);  // (`st` and `head` are read until here)
+  if (he != hipSuccess) {
+    const unsigned long long none = 0ull;
+    (void)hipMemcpy(e->d_recep + kRcHashPtr, &none, sizeof(none), hipMemcpyHostToDevice);
+    (void)hipFree(e->d_hash);
+    e->d_hash = nullptr;
+    HIP_TRY(he);
+  }
+  e->hr_mask = hashed_keys_mask;
+  e->hr_factor = factor;
+  e->hr_npts = npts;
+  e->hr_nseg = nseg;
+  launch_hash_rebuild(e, hashed_keys_mask);  // (the rings of what is registered already)
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  drop_graphs(e);  // the variant, the storage and the ring kernels are captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_router_info(agx_engine* e, uint64_t* hashed, uint64_t* random, uint64_t* ring_rebuilds, uint32_t ring_size[8]) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint32_t h[kHrSegOff] = {0};
+  if (e->d_hash) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(flush_recep_starts(e));
+    AGX_TRY(copy_sync(e, h, e->d_hash, sizeof(h), hipMemcpyDeviceToHost));
+  }
+  uint64_t c[3];
+  memcpy(c, h + kHrCtr, sizeof(c));
+  if (hashed) *hashed = c[kHrHashed];
+  if (random) *random = c[kHrRandom];
+  if (ring_rebuilds) *ring_rebuilds = c[kHrRebuilds];
+  for (uint32_t k = 0; k < AGX_MAX_SERVICE_KEYS; ++k)
+    if (ring_size) ring_size[k] = h[kHrSize + k];
+  return AGX_OK;
+}
+
+agx_status agx_read_hash_ring(agx_engine* e, uint32_t key, uint32_t* out_hash, uint32_t* out_id, uint64_t cap, uint64_t* out_n) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->d_hash) return set_err(AGX_EINVAL, "agx_read_hash_ring needs an engine with router logics (agx_set_router_logics)");
+  if (key >= AGX_MAX_SERVICE_KEYS || !((e->hr_mask >> key) & 1u))
+    return set_err(AGX_EINVAL, "service key %u is not a hashed key (hashed_keys_mask 0x%x)", key, e->hr_mask);
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(flush_recep_starts(e));
+  uint32_t n = 0;
+  AGX_TRY(copy_sync(e, &n, e->d_hash + kHrSize + key, 4, hipMemcpyDeviceToHost));
+  n = std::min(n, e->hr_npts);
+  const uint64_t take = std::min<uint64_t>(n, cap);
+  const uint32_t nslots = (uint32_t)__builtin_popcount(e->hr_mask), sl = (uint32_t)__builtin_popcount(e->hr_mask & ((1u << key) - 1u));
+  const uint32_t* const ring = e->d_hash + hr_static_off(nslots, e->hr_nseg) + 2ull * e->hr_npts * (1ull + sl);
+  if (take && out_hash) AGX_TRY(copy_sync(e, out_hash, ring, take * 4ull, hipMemcpyDeviceToHost));
+  if (take && out_id) AGX_TRY(copy_sync(e, out_id, ring + e->hr_npts, take * 4ull, hipMemcpyDeviceToHost));
+  if (out_n) *out_n = n;
   return AGX_OK;
 }
 
@@ -4996,7 +5245,11 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     const bool tmop = (A.op >= AGX_A_TIMER_SINGLE && A.op <= AGX_A_TIMER_CANCEL_ALL) || askop;  // (`word` is the key)
     const bool wdop = A.op >= AGX_A_WATCH && A.op <= AGX_A_UNWATCH;  // (the ref is the d-operand)
     const bool rcop = (A.op >= AGX_A_REGISTER && A.op <= AGX_A_ROUTE) || (A.op >= AGX_A_PUBLISH && A.op <= AGX_A_FIND);  // (`pad1` is the service key)
-    if (rcop && (A.pad1 >= AGX_MAX_SERVICE_KEYS || A.pad0 > (A.op == AGX_A_ROUTE ? (AGX_ROUTE_KEEP_SENDER | AGX_ROUTE_BY_INDEX) : 0u) ||
+    constexpr uint32_t kRouteFlags = AGX_ROUTE_KEEP_SENDER | AGX_ROUTE_BY_INDEX | AGX_ROUTE_HASHED | AGX_ROUTE_RANDOM;
+    if (rcop && A.op == AGX_A_ROUTE && A.pad1 < AGX_MAX_SERVICE_KEYS && A.pad0 > (AGX_ROUTE_KEEP_SENDER | AGX_ROUTE_BY_INDEX) &&
+        (A.pad0 > kRouteFlags || ((A.pad0 & (AGX_ROUTE_BY_INDEX | AGX_ROUTE_HASHED)) && !opnd_ok(A.dsrc, A.dword))))
+      return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (service keys 0..7, route flags 0..15)", i);
+    if (rcop && (A.pad1 >= AGX_MAX_SERVICE_KEYS || A.pad0 > (A.op == AGX_A_ROUTE ? kRouteFlags : 0u) ||
                  (A.op == AGX_A_ROUTE && (A.pad0 & AGX_ROUTE_BY_INDEX) && !opnd_ok(A.dsrc, A.dword))))
       return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (service keys 0..7, route flags 0..3)", i);
     if (A.op < AGX_A_SET || A.op > AGX_A_FIND || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
@@ -5172,6 +5425,16 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   e->beh_rc_keys = rc_keys_used;
   e->beh_publish = uses_publish;  // (checked against agx_set_topics at agx_run)
   e->beh_listing = uses_listing;  // (checked against agx_set_listings at agx_run)
+  e->beh_router = false;  // a hashed or random route (checked against agx_set_router_logics at agx_run)
+  e->beh_hashed_keys = 0;
+  e->beh_route_two = -1;
+  for (uint32_t i = 0; i < n_acts; ++i) {
+    if (acts[i].op != AGX_A_ROUTE) continue;
+    const uint32_t sel = acts[i].pad0 & (AGX_ROUTE_BY_INDEX | AGX_ROUTE_HASHED | AGX_ROUTE_RANDOM);
+    if ((sel & (sel - 1u)) && e->beh_route_two < 0) e->beh_route_two = i;
+    e->beh_router |= (sel & (AGX_ROUTE_HASHED | AGX_ROUTE_RANDOM)) != 0;
+    if (sel & AGX_ROUTE_HASHED) e->beh_hashed_keys |= 1u << (acts[i].pad1 & 7u);
+  }
   e->beh_child = uses_child;  // (checked against agx_set_children at agx_run)
   e->beh_ctl_tags = ctl_tags;
   e->beh_watch = false;  // a watch action or a signal case (checked against agx_set_death_watch at agx_run)

@@ -1677,6 +1677,15 @@ __device__ __forceinline__ void topic_commit(const TopicDev& TP, uint32_t npub) 
   const uint32_t t = wave_incl_sum(npub);
   if (lane_id() == kWave - 1) atomicAdd(TP.ctr(kTpPublished), (unsigned long long)t);
 }
+// the hashed and random routes of a wave's drains: one atomic add per counter and wave that routed so
+__device__ __forceinline__ void hash_commit(const HashDev& HD, const HashCount& hc) {
+  if (!__ballot((hc.hashed | hc.random) != 0u)) return;  // (wave-uniform)
+  const uint32_t th = wave_incl_sum(hc.hashed), tr = wave_incl_sum(hc.random);
+  if (lane_id() == kWave - 1) {
+    if (th) atomicAdd(HD.ctr(kHrHashed), (unsigned long long)th);
+    if (tr) atomicAdd(HD.ctr(kHrRandom), (unsigned long long)tr);
+  }
+}
 // The tick's deliveries of bucket b, staged as the inbox's last `np` items into wk ([3][kBucket]: key, sender,
 // payload): for each entry of the pending log in order, one item per actor of the bucket whose mask bit `key` is
 // set, in ascending id (a thread holds four consecutive actors' mask bytes in one register; per key the threads'
@@ -1955,6 +1964,14 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
   static_assert(!kLs || kTp, "listings: on the topic instantiations only");
   ListDev LD{};
   if constexpr (kLs) LD = list_dev_with(P.recep, RD.nk, RD.nb, a.bb);
+  // kHr: consistent-hashing and random routing (agx_set_router_logics), on top of the receptionist.
+  // The inbox and the rebuild protocol are the receptionist's; a hashed route searches the key's ring in force, a
+  // random one draws from the listing in force.
+  constexpr bool kHr = (KM & kHashKM) != 0;
+  static_assert(!kHr || (kRc && !kTp), "router logics: on the plain receptionist instantiations only");
+  HashDev HD{};
+  HashCount hcc{};  // kHr: this thread's hashed and random routes
+  if constexpr (kHr) HD = hash_dev(hash_base_of(P.recep));
   uint32_t* const winl = reinterpret_cast<uint32_t*>(L.U) + kBucket;  // kStash: window per actor (beside blpre)
   const uint32_t nhmask = (1u << a.nx_bits) - 1u;
   auto ikey = [&](uint32_t q) -> uint32_t { return kLds ? L.key[q] : a.scr.key[lo + q]; };
@@ -2850,6 +2867,29 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           RD.mask[l] = (uint8_t)mk;
           rcc.chg |= mk ^ mk0;
         }
+      } else if constexpr (kHr) {
+        // the receptionist's drain (below) with compiled_apply_hr
+        const uint32_t mk0 = (rcm4 >> (8 * j)) & 0xFFu;
+        uint32_t mk = mk0;
+        for (uint32_t q = 0; q < nd; ++q) {
+          const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          const uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_hr(P, RD, HD, kcur, self, wv, sv, pv, mk, rcc, hcc, em)
+                                                       : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          ++ndel;
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            rcc.term += (uint32_t)__popc(mk);  // RegisteredActorTerminated
+            mk = 0u;
+            break;
+          }
+        }
+        if (mk != mk0) {
+          RD.mask[l] = (uint8_t)mk;
+          rcc.chg |= mk ^ mk0;
+        }
       } else if constexpr (kRc) {
         // the plain drain with compiled_apply_rc: the actor's key mask lives in a register across the window and is
         // stored once, only if it changed (the net change is what moves a version); a stop clears every bit
@@ -2943,6 +2983,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     if constexpr (kRc) recep_commit(RD, rcc, L.rowtop);
     if constexpr (kTp) topic_commit(TP, npub);
     if constexpr (kLs) listing_commit(LD, lsc, L.rowtop);
+    if constexpr (kHr) hash_commit(HD, hcc);
     __syncthreads();
     if constexpr (kLs) {  // (block-uniform; bit 0: a key mask changed, bit 1: a sub or pending byte)
       if (*L.rowtop & 1u) recep_recount(RD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));

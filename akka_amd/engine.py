@@ -491,6 +491,35 @@ class GpuEngine:
         check(self.lib.agx_read_subscriptions(self._h, first, count, _ptr(sub, ctypes.c_uint8), _ptr(pend, ctypes.c_uint8)))
         return sub[:count], pend[:count]
 
+    def set_router_logics(self, hashed_keys_mask: int, virtual_nodes_factor: int = 0, seed: int = 0) -> None:
+        """agx_set_router_logics (after set_receptionist, before the first run; not with topics): the keys of
+        `hashed_keys_mask` (typed Tables.hashed_keys_mask) get a consistent-hash ring of `virtual_nodes_factor` points
+        per registered actor; `seed` seeds random routing.  Compiled behaviours may then context.route_hashed /
+        route_random."""
+        check(self.lib.agx_set_router_logics(self._h, hashed_keys_mask, virtual_nodes_factor, seed))
+
+    ROUTER_INFO = ("hashed", "random", "ring_rebuilds")
+
+    def router_info(self) -> dict:
+        """agx_router_info: totals hashed / random / ring_rebuilds, and per key the size of the hash ring in force for
+        the next tick (in ring points)."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        size = np.zeros(8, np.uint32)
+        check(self.lib.agx_router_info(self._h, *(ctypes.byref(x) for x in v), _ptr(size, ctypes.c_uint32)))
+        d = dict(zip(self.ROUTER_INFO, (int(x.value) for x in v)))
+        d["ring_size"] = [int(x) for x in size]
+        return d
+
+    def read_hash_ring(self, key: int) -> tuple:
+        """agx_read_hash_ring: (hashes, ids) of the ring of hashed key number `key` in force for the next tick, in ring
+        order (the hashes as the unsigned 32-bit patterns of the signed values the ring is ordered by)."""
+        n = ctypes.c_uint64()
+        check(self.lib.agx_read_hash_ring(self._h, key, None, None, 0, ctypes.byref(n)))
+        hs, ids = np.zeros(max(int(n.value), 1), np.uint32), np.zeros(max(int(n.value), 1), np.uint32)
+        check(self.lib.agx_read_hash_ring(self._h, key, _ptr(hs, ctypes.c_uint32), _ptr(ids, ctypes.c_uint32), int(n.value),
+                                          ctypes.byref(n)))
+        return hs[:int(n.value)], ids[:int(n.value)]
+
     def set_outbound(self, first_host_id: int, n_host: int, capacity: int = 1 << 20) -> None:
         """Host-side actor ids [first_host_id, +n_host): GPU tells to them go to the outbox
         (agx_set_outbound; the reply path of sender() ! reply, ActorCell.scala:583-587)."""

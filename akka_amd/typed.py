@@ -51,6 +51,11 @@ What lowers:
     with the key as pad1; the Listing of key k arrives as ``ListingMsg(k)``, one message type per key, and its
     handler reads ``context.listing_size(key)`` / ``service_at(key, x)``; ``Tables.uses_listings`` ->
     engine.set_listings(tables.listing_payloads), after engine.set_topics;
+  * ``context.route_hashed(key, hash_key, msg)`` / ``context.route_random(key, msg, counter=field)`` and
+    ``Routers.group(key).with_consistent_hash_routing(factor, mapping)`` / ``.with_random_routing()`` (DESIGN.md
+    §2.12): ``A_ROUTE`` with ``ROUTE_HASHED`` / ``ROUTE_RANDOM``; ``Tables.uses_router_logics`` ->
+    engine.set_router_logics(tables.hashed_keys_mask, tables.virtual_nodes_factor, seed), after
+    engine.set_receptionist; not together with topics or listings;
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -104,6 +109,8 @@ V_LISTING_SIZE, V_SERVICE_AT = 11, 12  # engines with the receptionist; `word` =
 SVC_WORD0, SVC_WORD1, SVC_ARG, SVC_CONST = 0, 1, 2, 3  # V_SERVICE_AT's selector: what x of listing[x mod size] is
 A_REGISTER, A_DEREGISTER, A_ROUTE = 17, 18, 19     # the service key is pad1
 ROUTE_KEEP_SENDER, ROUTE_BY_INDEX = 1, 2           # pad0 of A_ROUTE (KEEP_SENDER also of A_TELL: ref.forward)
+ROUTE_HASHED, ROUTE_RANDOM = 4, 8                  # pad0 of A_ROUTE on an engine with router logics
+MAX_VIRTUAL_NODES = 64
 A_ASK_ARM, A_ASK_SEND = 20, 21                     # context.ask: `word` is the timer key
 A_PUBLISH = 22                                     # context.publish: the topic's key is pad1
 A_SUBSCRIBE_LISTING, A_FIND = 23, 24               # context.receptionist_subscribe / _find: the key is pad1
@@ -214,6 +221,7 @@ class Action:
     flags: int = 0        # A_ROUTE / A_TELL: ROUTE_KEEP_SENDER, ROUTE_BY_INDEX (pad0)
     ask: object = None    # A_ASK_ARM: (the target's dst operand, the request's operand, its or_mask, adapt tag or None)
     listing: object = None  # A_SUBSCRIBE_LISTING / A_FIND: the MessageType of the key's Listing
+    vnf: int = 0          # A_ROUTE with ROUTE_HASHED: the router's virtualNodesFactor (0: whatever the tables' other routers say)
 
 
 class Field(Operand):
@@ -661,6 +669,25 @@ class ActorContext:
         listing stands (the modulo stand-in for consistent hashing)."""
         return self._route(key, msg, 0, lift(index), ROUTE_BY_INDEX | (ROUTE_KEEP_SENDER if forward else 0))
 
+    # consistent-hashing and random routing (engine.set_router_logics after engine.set_receptionist; TY/internal/
+    # routing/RoutingLogic.scala:77-112)
+    def route_hashed(self, key, hash_key, msg, forward: bool = True, virtual_nodes_factor: int = 0) -> "Action":
+        """Consistent-hashing routing: the routee is nodeFor(str(hash_key mod 2^32)) on the key's hash ring in force --
+        a change of the listing moves only the hash keys of the nodes that came or went.  An empty ring is an empty
+        listing."""
+        if isinstance(virtual_nodes_factor, bool) or not isinstance(virtual_nodes_factor, (int, np.integer)) or virtual_nodes_factor < 0:
+            raise CompileError("virtualNodesFactor has to be a positive integer")
+        if virtual_nodes_factor > MAX_VIRTUAL_NODES:
+            raise CompileError(f"virtualNodesFactor is at most {MAX_VIRTUAL_NODES}, not {virtual_nodes_factor}")
+        a = self._route(key, msg, 0, lift(hash_key), ROUTE_HASHED | (ROUTE_KEEP_SENDER if forward else 0))
+        return Action(a.op, a.word, a.val, a.dst, a.or_mask, key=a.key, flags=a.flags, vnf=int(virtual_nodes_factor))
+
+    def route_random(self, key, msg, counter, forward: bool = True) -> "Action":
+        """Random routing: the routee is listing[r mod size], r drawn from the engine's seed, the router's id and the
+        counter (a state field of the router), which then grows by one; it stays when there is no routee."""
+        if not isinstance(counter, Field):
+            raise CompileError(f"counter= names a state field of the router, not {counter!r}")
+        return self._route(key, msg, counter.word, None, ROUTE_RANDOM | (ROUTE_KEEP_SENDER if forward else 0))
 
     # Subscribe / Find and the Listing message (engine.set_listings after engine.set_topics; TY/internal/receptionist/
     # LocalReceptionist.scala:152-171,209-220)
@@ -720,22 +747,41 @@ class _GroupRouter:
 
     def __init__(self, key):
         self.key, self.index = ActorContext._key(key), None
+        self.logic, self.vnf = "round_robin", 0
 
     def with_round_robin_routing(self) -> "_GroupRouter":
         """withRoundRobinRouting (RoutingLogic.scala:42-75): the default here."""
-        self.index = None
+        self.index, self.logic = None, "round_robin"
         return self
 
     def with_index_routing(self, index) -> "_GroupRouter":
         """Routing by `index(m)` mod the listing's size, e.g. lambda m: m.arg."""
-        self.index = index
+        self.index, self.logic = index, "index"
+        return self
+
+    def with_random_routing(self) -> "_GroupRouter":
+        """withRandomRouting (RoutingLogic.scala:77-91): a counter-based draw per message (word 0 of the router)."""
+        self.index, self.logic = None, "random"
+        return self
+
+    def with_consistent_hash_routing(self, virtual_nodes_factor: int, mapping) -> "_GroupRouter":
+        """withConsistentHashingRouting(virtualNodesFactor, mapping) (RoutingLogic.scala:93-112): `mapping(m)` is the
+        operand whose low 32 bits, as a decimal string, are the message's hash key, e.g. lambda m: m.arg."""
+        if isinstance(virtual_nodes_factor, bool) or not isinstance(virtual_nodes_factor, (int, np.integer)) or virtual_nodes_factor < 1:
+            raise CompileError("virtualNodesFactor has to be a positive integer")
+        self.index, self.logic, self.vnf = mapping, "hashed", int(virtual_nodes_factor)
         return self
 
     def build(self, name: str = "group_router") -> "Behavior":
         """The router as a Behavior over State("cursor", "routed"): every message is forwarded, payload unchanged,
         to the routee the logic selects; `routed` counts the messages seen."""
         st = State("cursor", "routed")
-        if self.index is None:
+        if self.logic == "random":
+            h = lambda m, s: [s.routed.inc(), context.route_random(self.key, m.payload, counter=s.cursor), Behaviors.same]
+        elif self.logic == "hashed":
+            h = lambda m, s: [s.routed.inc(), context.route_hashed(self.key, self.index(m), m.payload,
+                                                                   virtual_nodes_factor=self.vnf), Behaviors.same]
+        elif self.index is None:
             h = lambda m, s: [s.routed.inc(), context.route(self.key, m.payload, cursor=s.cursor), Behaviors.same]
         else:
             h = lambda m, s: [s.routed.inc(), context.route_by(self.key, self.index(m), m.payload), Behaviors.same]
@@ -1072,6 +1118,8 @@ class Tables:
     transparent_tags: tuple = ()  # the tags of the NotInfluenceReceiveTimeout message types -> engine.set_receive_timeout
     service_keys: list = field(default_factory=list)  # the ServiceKeys in use; the index is the key number -> engine.set_receptionist
     listing_types: dict = field(default_factory=dict)  # key number -> the MessageType of its Listing -> engine.set_listings
+    hashed_keys: list = field(default_factory=list)  # the key numbers routed through by consistent hashing -> engine.set_router_logics
+    virtual_nodes_factor: int = 0  # the hashed routers' virtualNodesFactor (0: none named one) -> engine.set_router_logics
 
     @property
     def uses_supervision(self) -> bool:
@@ -1100,6 +1148,16 @@ class Tables:
         """The behaviours register, deregister, route, forward or read a listing: the engine needs
         engine.set_receptionist(len(tables.service_keys), capacity)."""
         return bool(self.service_keys) or self.uses_forward
+
+    @property
+    def uses_router_logics(self) -> bool:
+        """A route is hashed or random: the engine needs engine.set_router_logics(tables.hashed_keys_mask,
+        tables.virtual_nodes_factor, seed) after engine.set_receptionist."""
+        return any(a.op == A_ROUTE and a.pad0 & (ROUTE_HASHED | ROUTE_RANDOM) for a in self.acts[:self.n_acts])
+
+    @property
+    def hashed_keys_mask(self) -> int:
+        return sum(1 << k for k in self.hashed_keys)
 
     @property
     def uses_topics(self) -> bool:
@@ -1217,6 +1275,7 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
     sites = []  # the spawn sites in use, in order of appearance: (behaviour index, base, word 1)
     skeys = []  # the service keys in use, in order of appearance
     ltypes = {}  # key number -> the MessageType of the key's Listing
+    hkeys, vnfs = [], []  # the key numbers of the hashed routes; the virtualNodesFactors they name
 
     def key_no(key) -> int:
         if key not in skeys:
@@ -1256,7 +1315,7 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
             for e in c.effects:
                 d = res_op(e.dst or Operand(V_CONST))
                 if e.val is not res_op(e.val):
-                    e = Action(e.op, e.word, res_op(e.val), e.dst, e.or_mask, e.site, e.into, e.key, e.flags, e.ask, e.listing)
+                    e = Action(e.op, e.word, res_op(e.val), e.dst, e.or_mask, e.site, e.into, e.key, e.flags, e.ask, e.listing, e.vnf)
                 if e.op == A_SPAWN:  # dword: the site; pad0: the word `word` receives the child's id
                     key = (index[id(e.site.behavior)], e.site.base, e.site.word1)
                     if key not in sites:
@@ -1279,6 +1338,14 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
                     if ltypes.setdefault(kn, e.listing) != e.listing:
                         raise CompileError(f"the Listing of {e.key!r} is {ltypes[kn]!r} and {e.listing!r}: one message type "
                                            "per key")
+                if e.op == A_ROUTE and e.flags & ROUTE_HASHED:  # one virtualNodesFactor per engine
+                    if key_no(e.key) not in hkeys:
+                        hkeys.append(key_no(e.key))
+                    if e.vnf and e.vnf not in vnfs:
+                        vnfs.append(e.vnf)
+                    if len(vnfs) > 1:
+                        raise CompileError(f"two hashed routers with the virtualNodesFactors {vnfs[0]} and {vnfs[1]}: an "
+                                           "engine has one")
                 acts.append(AgxAct(op=e.op, word=e.word, src=e.val.src, sword=e.val.word, k=e.val.k,
                                    dsrc=d.src, dword=d.word, dk=d.k, or_mask=e.or_mask, pad0=e.flags,
                                    pad1=key_no(e.key) if e.key is not None else 0))
@@ -1292,6 +1359,8 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
     t.transparent_tags = tuple(sorted({mt.tag for mt in transparent}))
     t.service_keys = skeys
     t.listing_types = ltypes
+    t.hashed_keys = sorted(hkeys)
+    t.virtual_nodes_factor = vnfs[0] if vnfs else 0
     for b in behs:  # a supervisor of a class catches it and its descendants: the hierarchy as masks
         row = []
         for sv in b.supervisors:
@@ -1409,6 +1478,9 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
             if p and n + p > 1:
                 raise CompileError(f"a case holds {n + p} of tell, route and publish: a publication is the case's one "
                                    "envelope, and an engine with topics has max_emit 1")
+    if t.uses_router_logics and (t.uses_topics or t.uses_listings):
+        raise CompileError("hashed and random routes share an engine with neither topics nor listings: the behaviours use "
+                           "router logics and one of them")
     if max_emit is not None and t.max_tells > max(1, max_emit):
         raise CompileError(f"a case tells {t.max_tells} times per message but max_emit is {max_emit}")
     return t

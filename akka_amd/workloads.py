@@ -74,6 +74,9 @@ class Workload:
     # Subscribe / Listing (agx_set_listings / agx_subscribe_listings, on top of `topics`): {"payloads": the Listing
     # payload per key (typed.Tables.listing_payloads), "starts": [(first, count, key)]} -- empty: no listings
     listings: dict = field(default_factory=dict)
+    # consistent-hashing and random routing (agx_set_router_logics, on top of `receptionist`, not with `topics`):
+    # {"hashed_keys_mask": m, "virtual_nodes_factor": f, "seed": s} -- empty: no router logics
+    router_logics: dict = field(default_factory=dict)
     # host tells that follow the clock: schedule[t] = (dst, src, payload) is staged before tick t + 1 (run_schedule)
     schedule: list = field(default_factory=list)
 
@@ -111,6 +114,9 @@ class Workload:
             target.set_receptionist(self.receptionist["n_keys"], self.receptionist["capacity"])
             for first, count, key in self.receptionist.get("starts", ()):
                 target.register_services(first, count, key)
+        if self.router_logics:  # (empty: targets without the call are unaffected)
+            target.set_router_logics(self.router_logics["hashed_keys_mask"], self.router_logics.get("virtual_nodes_factor", 0),
+                                     self.router_logics.get("seed", 0))
         if self.topics:  # (empty: targets without the call are unaffected)
             target.set_topics(self.topics["log_capacity"])
         if self.listings:  # (empty: targets without the calls are unaffected)
@@ -1166,6 +1172,99 @@ def service_pool(n_routers: int = 1 << 10, n_workers: int = 1 << 14, ticks: int 
                     behaviors=tb, bucket_actors=bucket_actors, outbound=(n, n_host) if n_host else None,
                     receptionist={"n_keys": 1, "capacity": n_workers, "starts": [(n_routers, n_workers, 0)]},
                     schedule=schedule)
+
+
+# ------------------------------------------------------------------ consistent-hashing and random routing
+SS_TICK, SS_REQUEST, SS_JOIN = 1, 2, 3
+
+
+def sticky_sessions(n_clients: int = 1 << 12, n_routers: int = 64, n_workers: int = 1 << 10, n_spare: int = 0, quota: int = 0,
+                    virtual_nodes_factor: int = 10, ticks: int = 16, join_at: int = 0, seed: int = 1, throughput: int = 3,
+                    bucket_actors: int = 0) -> Workload:
+    """Sticky sessions over a changing worker pool (Routers.group(key).withConsistentHashingRouting, RoutingLogic.scala:
+    93-112): client c (ids 0 ..) holds a session number and, on every Tick of the host schedule, sends Request(session)
+    to router c mod n_routers (ids n_clients ..), a group router with consistent-hashing logic keyed by the session; the
+    worker (ids n_clients + n_routers ..) counts down `left` and keeps the last session it served.  The first n_workers
+    - n_spare workers register in the setup block; with `quota` > 0 worker i stops after 1 + i mod quota requests, so
+    ring points leave tick by tick; the n_spare last workers register when the host's Join reaches them before tick
+    `join_at` + 1.  A session stays with its worker while that worker is registered."""
+    from . import typed
+    B, ctx = typed.Behaviors, typed.context
+    key = typed.ServiceKey("session_worker")
+    tick, request, join = (typed.MessageType("Tick", SS_TICK), typed.MessageType("Request", SS_REQUEST),
+                           typed.MessageType("Join", SS_JOIN))
+    cs = typed.State("session", "router")
+    client = (typed.ReceiveBuilder.create(cs)
+              .on_message(tick, lambda m, s: [typed.Ref(s.router).tell(request(s.session)), B.same])
+              .on_any_message(lambda m, s: [B.unhandled])
+              .build("session_client"))
+    router = typed.Routers.group(key).with_consistent_hash_routing(virtual_nodes_factor, lambda m: m.arg).build("hash_router")
+    ws = typed.State("left", "last")
+    worker = (typed.ReceiveBuilder.create(ws)
+              .on_message(request, lambda m, s: [s.left.add(-1), s.last.set(m.arg), B.stopped], when=lambda m, s: s.left == 1)
+              .on_message(request, lambda m, s: [s.left.add(-1), s.last.set(m.arg), B.same])
+              .on_message(join, lambda m, s: [ctx.register(key), B.same])
+              .on_any_message(lambda m, s: [B.unhandled])
+              .build("session_worker"))
+    tb = typed.compile_behaviors([client, router, worker], max_emit=1)
+    n = n_clients + n_routers + n_workers
+    c = np.arange(n_clients, dtype=np.uint64)
+    cinit = np.zeros((n_clients, 2), np.uint64)
+    cinit[:, 0] = splitmix64_np(c + np.uint64(seed)) & np.uint64(0xFFFFFF)
+    cinit[:, 1] = n_clients + c % max(n_routers, 1)
+    winit = np.zeros((n_workers, 2), np.uint64)
+    winit[:, 0] = 1 + np.arange(n_workers, dtype=np.uint64) % quota if quota else 0  # (0: never reaches 1 going down)
+    w0 = n_clients + n_routers
+    dst = np.arange(n_clients, dtype=np.uint32)
+    none = np.full(n_clients, NO_SENDER, np.uint32)
+    schedule = []
+    for t in range(ticks):
+        d, sr, py = dst, none, np.full(n_clients, tick.payload(t + 1), np.uint32)
+        if n_spare and t == join_at:
+            jd = np.arange(w0 + n_workers - n_spare, w0 + n_workers, dtype=np.uint32)
+            d = np.concatenate([d, jd])
+            sr = np.concatenate([sr, np.full(n_spare, NO_SENDER, np.uint32)])
+            py = np.concatenate([py, np.full(n_spare, join.payload(), np.uint32)])
+        schedule.append((d, sr, py))
+    return Workload("sticky_sessions", n, 2, 1, throughput, 0,
+                    [(0, n_clients, tb.kind_of(client), cinit), (n_clients, n_routers, tb.kind_of(router), None),
+                     (w0, n_workers, tb.kind_of(worker), winit)],
+                    behaviors=tb, bucket_actors=bucket_actors,
+                    receptionist={"n_keys": 1, "capacity": n_workers, "starts": [(w0, n_workers - n_spare, 0)]},
+                    router_logics={"hashed_keys_mask": tb.hashed_keys_mask, "virtual_nodes_factor": tb.virtual_nodes_factor,
+                                   "seed": seed},
+                    schedule=schedule)
+
+
+def random_pool(n_routers: int = 1 << 10, n_workers: int = 1 << 14, ticks: int = 16, quota: int = 0, seed: int = 1,
+                throughput: int = 3, bucket_actors: int = 0) -> Workload:
+    """service_pool with Routers.group(key).withRandomRouting (RoutingLogic.scala:77-91): every router gets one Job per
+    tick and forwards it to a worker drawn from the listing in force; with `quota` > 0 worker i stops after 1 + i mod
+    quota jobs, so the listing shrinks tick by tick."""
+    from . import typed
+    B = typed.Behaviors
+    key = typed.ServiceKey("worker")
+    job = typed.MessageType("Job", SP_JOB)
+    router = typed.Routers.group(key).with_random_routing().build("random_router")
+    ws = typed.State("left", "last")
+    done = lambda m, s: [s.left.add(-1), s.last.set(m.payload)]
+    worker = (typed.ReceiveBuilder.create(ws)
+              .on_message(job, lambda m, s: done(m, s) + [B.stopped], when=lambda m, s: s.left == 1)
+              .on_message(job, lambda m, s: done(m, s) + [B.same])
+              .on_any_message(lambda m, s: [B.unhandled])
+              .build("pool_worker"))
+    tb = typed.compile_behaviors([router, worker], max_emit=1)
+    n = n_routers + n_workers
+    winit = np.zeros((n_workers, 2), np.uint64)
+    winit[:, 0] = 1 + np.arange(n_workers, dtype=np.uint64) % quota if quota else 0  # (0: never reaches 1 going down)
+    dst = np.arange(n_routers, dtype=np.uint32)
+    src = np.full(n_routers, NO_SENDER, np.uint32)
+    schedule = [(dst, src, np.full(n_routers, job.payload(t + 1), np.uint32)) for t in range(ticks)]
+    return Workload("random_pool", n, 2, 1, throughput, 0,
+                    [(0, n_routers, tb.kind_of(router), None), (n_routers, n_workers, tb.kind_of(worker), winit)],
+                    behaviors=tb, bucket_actors=bucket_actors,
+                    receptionist={"n_keys": 1, "capacity": n_workers, "starts": [(n_routers, n_workers, 0)]},
+                    router_logics={"hashed_keys_mask": 0, "seed": seed}, schedule=schedule)
 
 
 def service_mesh(n: int = 4096, n_keys: int = 8, seed: int = 1, ticks: int = 40, throughput: int = 3, capacity: int = 16,

@@ -192,7 +192,11 @@ enum agx_action_op {
    * envelope (a forward), else the sender is the router; pad0 & AGX_ROUTE_BY_INDEX takes listing[x mod size] with
    * x the d-operand (dsrc, dword, dk), else round robin with the cursor in state word `word`.  A ROUTE sends
    * through the case's tell slot: a case holds at most one of TELL and ROUTE.  AGX_ROUTE_KEEP_SENDER on a plain
-   * AGX_A_TELL (ref.forward(msg)) is accepted on an engine with the receptionist only. */
+   * AGX_A_TELL (ref.forward(msg)) is accepted on an engine with the receptionist only.  On an engine with router
+   * logics (agx_set_router_logics) pad0 & AGX_ROUTE_HASHED takes nodeFor(stringHash(str(x))) of the
+   * key's hash ring, x the low 32 bits of the d-operand; pad0 & AGX_ROUTE_RANDOM takes listing[r mod size] with r
+   * drawn from the counter in state word `word`, which then grows by one.  BY_INDEX, HASHED and RANDOM exclude one
+   * another (agx_run refuses tables that set two of them on one action). */
   AGX_A_REGISTER = 17,   /* receptionist ! Register(key, self)   (LocalReceptionist.scala:147-175) */
   AGX_A_DEREGISTER = 18, /* receptionist ! Deregister(key, self) (LocalReceptionist.scala:177-199) */
   AGX_A_ROUTE = 19,      /* group router: selectRoutee(msg) ! msg (GroupRouterImpl.scala:114-146) */
@@ -223,6 +227,10 @@ enum agx_action_op {
 #define AGX_ASK_MAX_ACTORS 0x3FFFFFu /* an engine with ask has at most 2^22 - 1 actors: the ref carries the id */
 #define AGX_ROUTE_KEEP_SENDER 1u
 #define AGX_ROUTE_BY_INDEX 2u
+#define AGX_ROUTE_HASHED 4u
+#define AGX_ROUTE_RANDOM 8u
+#define AGX_MAX_VIRTUAL_NODES 64u
+#define AGX_MAX_RING_POINTS (1u << 24)
 #define AGX_MAX_SERVICE_KEYS 8u
 #define AGX_TAG_RECEIVE_TIMEOUT 0xFBu /* the message tag of a receive-timeout envelope: reserved on an engine with
                                          receive timeouts */
@@ -952,6 +960,32 @@ agx_status agx_listing_info(agx_engine* eng, uint64_t* subscribes, uint64_t* fin
                             uint64_t* notified);
 /* The `sub` and `pending` masks of actors [first, first + count) (either pointer may be NULL). */
 agx_status agx_read_subscriptions(agx_engine* eng, uint64_t first, uint64_t count, uint8_t* sub_out, uint8_t* pending_out);
+
+/* Consistent-hashing and random routing for group routers (Routers.group(key).withConsistentHashingRouting /
+ * withRandomRouting: TY/internal/routing/RoutingLogic.scala:77-112, akka-actor routing/ConsistentHash.scala:25-139,
+ * routing/MurmurHash.scala:115-129; pinned by RoutingLogicSpec.scala:146-221; DESIGN.md 2.12 has the contract), on
+ * top of the receptionist: call after agx_set_receptionist and before the first agx_run (AGX_ESTATE afterwards).
+ * AGX_EINVAL: no receptionist, topics set (agx_set_topics after this call is refused too), a bit of
+ * hashed_keys_mask at or above the receptionist's n_keys, a non-zero mask with virtual_nodes_factor outside
+ * 1..AGX_MAX_VIRTUAL_NODES or with n_actors x virtual_nodes_factor above AGX_MAX_RING_POINTS, a second call.  With
+ * hashed_keys_mask 0 (random routing only) virtual_nodes_factor is ignored.  A node is an actor id as an unsigned
+ * decimal string; ring point v (1..virtual_nodes_factor) of actor a is concatenateNodeHash(stringHash(str(a)), v).
+ * The ring of a hashed key k in force during tick t is the ring points of the actors whose bit k was set at the end
+ * of tick t - 1, ordered by (hash as a signed 32-bit integer, id).  AGX_A_ROUTE with AGX_ROUTE_HASHED sends to the
+ * id of the first ring entry with hash >= stringHash(str(x)) (signed), else to that of entry 0; an empty ring is an
+ * empty listing (a dead letter, no_routees).  AGX_ROUTE_RANDOM sends to listing[fanout_rand(seed, self,
+ * (c & 0xFFFFFF) | 0x02000000, 0) mod size], c the low 32 bits of state word `word`, which grows by one on a hit.
+ * Tables that use either flag on an engine without this call, AGX_ROUTE_HASHED on a key outside the mask, or two of
+ * BY_INDEX / HASHED / RANDOM on one action make agx_run return AGX_EINVAL. */
+agx_status agx_set_router_logics(agx_engine* eng, uint32_t hashed_keys_mask, uint32_t virtual_nodes_factor, uint64_t seed);
+/* Totals since agx_create: hashed / random (routes of that logic that found a routee; they are part of `routed`),
+ * ring_rebuilds (rings rewritten after a change of their key), and per key the size of the ring in force for the
+ * next tick in ring points.  Any pointer may be NULL; zeros on an engine without router logics. */
+agx_status agx_router_info(agx_engine* eng, uint64_t* hashed, uint64_t* random, uint64_t* ring_rebuilds, uint32_t ring_size[8]);
+/* The ring of hashed key `key` in force for the next tick, in ring order: up to `cap` hashes / ids into out_hash /
+ * out_id (either may be NULL), its size into out_n.  AGX_EINVAL without router logics or for a key outside the mask. */
+agx_status agx_read_hash_ring(agx_engine* eng, uint32_t key, uint32_t* out_hash, uint32_t* out_id, uint64_t cap,
+                              uint64_t* out_n);
 
 /* --- the reply path: actors that live on the host ------------------------------------------
  * Ids [first_host_id, first_host_id + n_host) -- outside the population (>= n_actors, < 2^31) --
