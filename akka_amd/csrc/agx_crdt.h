@@ -665,6 +665,7 @@ __device__ __forceinline__ uint32_t crdt_apply(const DevParams& P, const CrdtHea
         const uint32_t x = dl_record(P, s32, kind, self);
         const uint32_t vn = s32.ld(vb + node);
         s32.put(x + 1, (op == AGX_OP_ADD ? 1u : op == AGX_OP_REMOVE ? 2u : 3u) | (op == AGX_OP_CLEAR ? 0u : arg << 8));
+        if (op == AGX_OP_ADD && vn == 0xFFFFFFFFu) atomicOr(P.err, 2ull);  // kErrRange: the logged version would wrap
         s32.put(x + 2, op == AGX_OP_ADD ? vn + 1u : op == AGX_OP_REMOVE ? vn : 0u);
         s32.put(x + 3, 0u);
         if (op != AGX_OP_ADD)
@@ -681,7 +682,8 @@ __device__ __forceinline__ uint32_t crdt_apply(const DevParams& P, const CrdtHea
         uint64_t vv = st[vwi];
         const uint32_t sh = (node & 1u) * 32u;
         const uint32_t ver = (uint32_t)(vv >> sh) + 1u;
-        vv = (vv & ~(0xFFFFFFFFull << sh)) | ((uint64_t)ver << sh);
+        if (ver == 0u) atomicOr(P.err, 2ull);  // kErrRange: the reference's Long version would not wrap
+        vv =(vv & ~(0xFFFFFFFFull << sh)) | ((uint64_t)ver << sh);
         st[vwi] = vv;
         dots[node / 2] = (uint64_t)ver << sh;
       }
@@ -854,6 +856,7 @@ __device__ __forceinline__ void orset_merge_wave(const DevParams& P, const CrdtH
 #pragma unroll
         for (uint32_t n = 0; n < 8; ++n)
           if (n == node) ver = cur[n] = cur[n] + 1u;
+        if (ver == 0u && e == 0) atomicOr(P.err, 2ull);  // kErrRange: the reference's Long version would not wrap
       }
       if (c == kOrClear || arg == e) {
 #pragma unroll

@@ -2710,7 +2710,8 @@ agx_status read_counters(agx_engine* e, uint64_t* s) {
 // still fills its counters); destroy the engine and start over.
 agx_status error_status(const agx_engine* e, uint64_t err) {
   if (err & kErrRange)
-    return set_err(AGX_ERANGE, "a GCounter/PNCounter slot exceeded 2^64 - 1 (u64 slots; the reference uses BigInt)");
+    return set_err(AGX_ERANGE, "a GCounter/PNCounter slot exceeded 2^64 - 1 (u64 slots; the reference uses BigInt) or an "
+                   "ORSet replica's own version exceeded 2^32 - 1 (u32 versions; the reference uses Long)");
   if (err & kErrPrioTile)
     return set_err(AGX_ECAPACITY, "a bucket of %u actors that holds a priority-mailbox actor received more than one "
                    "tile of %d messages (backlog included): a prioritised actor's queue is ordered within one tile "

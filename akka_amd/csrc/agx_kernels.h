@@ -51,7 +51,7 @@ constexpr int kStagedChunks = 256;  // host-staged tells are split over this man
 enum { ST_DELIVERED = 0, ST_DEAD = 1, ST_UNHANDLED = 2, ST_EMITTED = 3, ST_STEPS = 4, ST_ERROR = 5, ST_ACTIVE = 6,
        ST_IDENT = 7, ST_N = 8 };
 constexpr uint64_t kErrCapacity = 1;
-constexpr uint64_t kErrRange = 2;  // a counter slot wrapped past 2^64 - 1 (AGX_ERANGE)
+constexpr uint64_t kErrRange = 2;  // a counter slot wrapped past 2^64 - 1 or an ORSet version past 2^32 - 1 (AGX_ERANGE)
 constexpr uint64_t kErrBarrier = 4;  // a persistent superstep launch's grid barrier timed out (AGX_EDEVICE)
 constexpr uint64_t kErrPrioTile = 8;  // a bucket with a priority-mailbox actor exceeded one LDS tile (AGX_ECAPACITY)
 constexpr uint64_t kErrStashTile = 16;  // a bucket with an actor of a stash class exceeded one LDS tile (AGX_ECAPACITY)

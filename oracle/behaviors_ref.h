@@ -35,7 +35,8 @@ typedef struct {
   uint32_t gossip_f;       /* CRDT gossip fan-out */
   uint64_t gossip_seed;
   uint32_t delta_max;      /* delta-CRDT mode: Replicator max-delta-size (0 = off) */
-  uint32_t error;          /* set on a delta-log overflow (engine: AGX_ECAPACITY) */
+  uint32_t error;          /* bit 0: a delta-log overflow (engine: AGX_ECAPACITY); bit 1: an ORSet version
+                              past 2^32 - 1 (engine: AGX_ERANGE) */
   const agx_case* bcase;   /* compiled behaviours (agx_set_behaviors) */
   const agx_act* bact;
   const uint32_t* bfirst;
@@ -133,7 +134,7 @@ static inline uint32_t* dref_record(ref_params* P, uint64_t* w, uint32_t kind, u
   if (s > AGX_DELTA_LOG) { /* the ring slot's previous seqNr must have reached every node */
     const uint32_t m = crdt_key_size(a, P->n), node = a % AGX_CRDT_NODES;
     for (uint32_t i = 0; i < m; ++i)
-      if (i != node && env[10 + i] < s - AGX_DELTA_LOG) P->error = 1;
+      if (i != node && env[10 + i] < s - AGX_DELTA_LOG) P->error |= 1u;
   }
   uint32_t* e = dref_entry(w, kind, s);
   memset(e, 0, AGX_DELTA_LOG_U32(kind == AGX_KIND_ORSET) * 4u);
@@ -354,7 +355,9 @@ static inline uint32_t ref_apply_crdt(ref_params* P, uint32_t kind, uint32_t a, 
         if (op != AGX_OP_ADD) memcpy(e + 4, orset_vv(w), AGX_CRDT_NODES * 4u);
         if (op == AGX_OP_CLEAR) e[2] = 0;
       }
-      if (op == AGX_OP_ADD) orset_add(w, node, arg);
+      if (op == AGX_OP_ADD) {
+        if (orset_add(w, node, arg)) P->error |= 2u; /* the version would wrap: refused */
+      }
       else if (op == AGX_OP_REMOVE) orset_remove(w, arg);
       else orset_clear(w);
       return AGX_RES_SAME;

@@ -181,6 +181,9 @@ typedef struct bsp_sim {
   /* census of queued DeltaPropagations (bsp_delta_backlog_census): per data type (payload >> 30:
    * GCounter, PNCounter, ORSet), the envelope-supersteps that delta rows spent waiting in a backlog */
   uint64_t delta_queued[4];
+  /* census of queued full-state ORSet gossips (bsp_orset_backlog_census): the envelope-supersteps that
+   * such rows spent waiting in a backlog -- [0] all of them, [1] those with all 512 dots live */
+  uint64_t orset_queued[2];
 } bsp_sim;
 
 bsp_sim* bsp_create(uint64_t n_actors, uint32_t throughput, uint32_t capacity, uint32_t n_words,
@@ -266,7 +269,8 @@ int bsp_register_range(bsp_sim* s, uint64_t first, uint64_t count, uint32_t kind
     uint64_t a = first + i;
     s->kind[a] = (uint8_t)kind;
     s->alive[a] = kind != AGX_KIND_NONE;
-    for (uint32_t w = 0; w < s->W; ++w) s->state[a * s->W + w] = init ? init[i * stride_words + w] : 0;
+    for (uint32_t w = 0; w < s->W; ++w) /* a row narrower than the state: the rest is zero */
+      s->state[a * s->W + w] = init && w < stride_words ? init[i * stride_words + w] : 0;
   }
   return 0;
 }
@@ -677,7 +681,8 @@ static int bsp_step(bsp_sim* s) {
   s->staged.n = 0;
   for (uint32_t t = 0; t < nt; ++t) {
     bsp_part* x = &parts[t];
-    if (x->error || x->P.error) s->P.error = 1;
+    if (x->error) s->P.error |= 1u;
+    s->P.error |= x->P.error;
     seg[t] = x->backlog;
     seg[nt + t] = x->emitted;
     s->st.delivered += x->st.delivered;
@@ -705,6 +710,13 @@ static int bsp_step(bsp_sim* s) {
     for (uint64_t i = 0; i < seg[t].n; ++i) {
       const env_t* m = &seg[t].v[i];
       if (ref_is_wide(m->src) && (m->payload & AGX_DELTA_ROW_BIT)) s->delta_queued[m->payload >> 30]++;
+      else if (ref_is_wide(m->src) && (m->payload >> 30) == AGX_KIND_ORSET - AGX_KIND_GCOUNTER && seg[t].rw >= AGX_ORSET_WORDS) {
+        const uint32_t* d = (const uint32_t*)(seg[t].rows + i * seg[t].rw);
+        uint32_t live = 0;
+        for (uint32_t k = 0; k < AGX_ORSET_ELEMS * AGX_CRDT_NODES; ++k) live += d[k] != 0u;
+        s->orset_queued[0]++;
+        if (live == AGX_ORSET_ELEMS * AGX_CRDT_NODES) s->orset_queued[1]++;
+      }
     }
   free(parts);
   s->st.supersteps++;
@@ -716,13 +728,20 @@ int bsp_run(bsp_sim* s, uint32_t max_steps, agx_stats* out) {
     if (!bsp_step(s)) break;
   s->st.in_flight = bsp_in_flight(s);
   if (out) *out = s->st;
-  return s->P.error ? AGX_ECAPACITY : 0;
+  return (s->P.error & 2u) ? AGX_ERANGE : s->P.error ? AGX_ECAPACITY : 0;
 }
 
 /* out[k]: envelope-supersteps that DeltaPropagations of data type k (0 GCounter, 1 PNCounter, 2 ORSet)
  * spent queued behind a throughput cap, summed over the supersteps since bsp_create */
 void bsp_delta_backlog_census(const bsp_sim* s, uint64_t* out) {
   for (int k = 0; k < 3; ++k) out[k] = s->delta_queued[k];
+}
+
+/* out[0]: envelope-supersteps that full-state ORSet gossip rows spent queued behind a throughput cap,
+ * out[1]: those of rows with all 512 dots live; summed over the supersteps since bsp_create */
+void bsp_orset_backlog_census(const bsp_sim* s, uint64_t* out) {
+  out[0] = s->orset_queued[0];
+  out[1] = s->orset_queued[1];
 }
 
 void bsp_read_state(bsp_sim* s, uint64_t first, uint64_t count, uint64_t* words, uint8_t* alive) {
@@ -750,11 +769,14 @@ uint64_t bsp_gcounter_value(const uint64_t* c, uint32_t r) {
 }
 /* ORSet restatement on the engine layout (crdt_ref.h), for the ORSetSpec KATs. */
 void bsp_orset_merge(uint64_t* self, const uint64_t* that) { orset_merge(self, that); }
-void bsp_orset_add(uint64_t* w, uint32_t node, uint32_t e) { orset_add(w, node, e); }
+int bsp_orset_add(uint64_t* w, uint32_t node, uint32_t e) { return orset_add(w, node, e); }
 void bsp_orset_remove(uint64_t* w, uint32_t e) { orset_remove(w, e); }
 void bsp_orset_subtract_dots(uint32_t* out, const uint32_t* dot, const uint32_t* vv) { orset_subtract_dots(out, dot, vv); }
 uint32_t bsp_crdt_peer(uint64_t seed, uint32_t self, uint32_t round, uint32_t j, uint64_t n) {
   return crdt_peer(seed, self, round, j, n);
+}
+uint32_t bsp_crdt_key_peer(uint64_t seed, uint32_t self, uint32_t round, uint32_t j, uint64_t n) {
+  return crdt_key_peer(seed, self, round, j, n);
 }
 
 /* PNCounter = (increments, decrements) GCounters; merge each (PNCounter.scala:178). */

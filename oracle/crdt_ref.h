@@ -71,13 +71,17 @@ static inline void orset_merge(uint64_t* self, const uint64_t* that) {
 /* ORSet.add (DD/ORSet.scala:339-351): vvector + node; the element's birth dot
  * becomes (node -> new version).  Versions come from a per-replica monotonic
  * counter (the reference draws them from the JVM-wide Timestamp.counter,
- * VersionVector.scala:76-80,277-281; merges only compare them per node). */
-static inline void orset_add(uint64_t* w, uint32_t node, uint32_t e) {
+ * VersionVector.scala:76-80,277-281; merges only compare them per node).  The reference's
+ * versions are Long and never wrap: at a u32 entry of 2^32 - 1 the add is refused (returns -1,
+ * nothing changed; the engine reports AGX_ERANGE). */
+static inline int orset_add(uint64_t* w, uint32_t node, uint32_t e) {
   uint32_t* d = orset_dots(w) + e * AGX_CRDT_NODES;
   uint32_t* vv = orset_vv(w);
+  if (vv[node] == 0xFFFFFFFFu) return -1;
   vv[node] += 1u;
   for (uint32_t n = 0; n < AGX_CRDT_NODES; ++n) d[n] = 0u;
   d[node] = vv[node];
+  return 0;
 }
 
 /* ORSet.remove (:380-387): drop the element, vvector unchanged. */

@@ -402,7 +402,8 @@ int fjp_register_range(void* h, uint64_t first, uint64_t count, uint32_t kind, c
     uint64_t a = first + i;
     s->actors[a].kind = kind;
     s->actors[a].status.store(kind == AGX_KIND_NONE ? kClosed : 0u);
-    for (uint32_t w = 0; w < s->W; ++w) s->state[a * s->W + w] = init ? init[i * stride_words + w] : 0;
+    for (uint32_t w = 0; w < s->W; ++w) /* a row narrower than the state: the rest is zero */
+      s->state[a * s->W + w] = init && w < stride_words ? init[i * stride_words + w] : 0;
   }
   return 0;
 }

@@ -73,10 +73,11 @@ def _load_bsp():
             "bsp_set_delta_crdt": (ctypes.c_int, [vp, u32]),
             "bsp_set_behaviors": (ctypes.c_int, [vp, vp, u32, vp, u32, P32, u32]),
             "bsp_orset_merge": (None, [P64, P64]),
-            "bsp_orset_add": (None, [P64, u32, u32]),
+            "bsp_orset_add": (ctypes.c_int, [P64, u32, u32]),
             "bsp_orset_remove": (None, [P64, u32]),
             "bsp_orset_subtract_dots": (None, [P32, P32, P32]),
             "bsp_crdt_peer": (u32, [u64, u32, u32, u32, u64]),
+            "bsp_crdt_key_peer": (u32, [u64, u32, u32, u32, u64]),
             "bsp_orset_delta_bytes": (u32, []),
             "bsp_orset_add_d": (None, [P64, vp, u32, u32, u32]),
             "bsp_orset_remove_d": (None, [P64, vp, u32, u32]),
@@ -91,6 +92,7 @@ def _load_bsp():
             "bsp_run": (ctypes.c_int, [vp, u32, ctypes.POINTER(Stats)]),
             "bsp_read_state": (None, [vp, u64, u64, P64, P8]),
             "bsp_delta_backlog_census": (None, [vp, P64]),
+            "bsp_orset_backlog_census": (None, [vp, P64]),
             "bsp_java_hash_decimal": (ctypes.c_int32, [u32]),
             "bsp_shard_id": (ctypes.c_int32, [u32, u32]),
             "bsp_owner": (u32, [u32, u32, u32]),
@@ -240,7 +242,7 @@ class BspOracle(_Base):
         st = Stats()
         rc = self.lib.bsp_run(self.h, min(int(max_supersteps), 0xFFFFFFFF), ctypes.byref(st))
         if rc:
-            raise OverflowError(f"bsp_run: status {rc} (delta log overflow)")
+            raise OverflowError(f"bsp_run: status {rc} " + ("(an ORSet version past 2^32 - 1)" if rc == 7 else "(delta log overflow)"))
         return st.as_dict()
 
     def read_state(self, first=0, count=None):
@@ -256,6 +258,15 @@ class BspOracle(_Base):
         that its reference run kept delta rows waiting in mailboxes."""
         c = np.zeros(3, np.uint64)
         self.lib.bsp_delta_backlog_census(self.h, _p(c, ctypes.c_uint64))
+        return tuple(int(x) for x in c)
+
+
+    def orset_backlog_census(self):
+        """(rows, full rows): the envelope-supersteps that full-state ORSet gossip rows -- all of them,
+        and those with all 512 dots live -- spent queued behind a throughput cap, over every superstep
+        run so far: a test's proof that its reference run kept full snapshot rows waiting in mailboxes."""
+        c = np.zeros(2, np.uint64)
+        self.lib.bsp_orset_backlog_census(self.h, _p(c, ctypes.c_uint64))
         return tuple(int(x) for x in c)
 
 
@@ -412,7 +423,8 @@ class orset:
     @staticmethod
     def add(a, node, e):
         out = np.ascontiguousarray(np.asarray(a, np.uint64)).copy()
-        _load_bsp().bsp_orset_add(_p(out, ctypes.c_uint64), node, e)
+        if _load_bsp().bsp_orset_add(_p(out, ctypes.c_uint64), node, e):
+            raise OverflowError("ORSet.add: the node's version would pass 2^32 - 1 (the reference's Long never wraps)")
         return out
 
     @staticmethod
@@ -436,6 +448,11 @@ class orset:
 
 def crdt_peer(seed: int, self_id: int, round_: int, j: int, n: int) -> int:
     return int(_load_bsp().bsp_crdt_peer(seed, self_id, round_, j, n))
+
+
+def crdt_key_peer(seed: int, self_id: int, round_: int, j: int, n: int) -> int:
+    """Delta-CRDT mode: the full-state gossip peer within the replica's key of 8 (crdt_ref.h crdt_key_peer)."""
+    return int(_load_bsp().bsp_crdt_key_peer(seed, self_id, round_, j, n))
 
 
 class OrsetDop(ctypes.Structure):

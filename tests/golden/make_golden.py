@@ -171,8 +171,63 @@ def orset_kats():
              "checks": [["elements", "a3", ["Z"]], ["elements", "b3", ["Z"]],
                         ["elements", "t1", []], ["elements", "t2", []], ["elements", "t3", []],
                         ["elements", "t4", []], ["elements", "t5", []], ["elements", "t6", []]]},
-        ],
+        ] + orset_must_scripts(),
     }
+
+
+def orset_must_scripts():
+    """The eight cases of ORSetSpec's "A ORSet must" block (:38-230), node1 / node2 -> 0 / 1, user1..4 ->
+    "u1".."u4".  The spec asserts `contain` / `not contain` for every user its case adds, so each check
+    here is the whole element set that those assertions fix.  A value the spec keeps (c3, c5, ...) is a
+    `copy` taken at that point."""
+    add4 = [["add", "c", 0, "u1"], ["add", "c", 0, "u2"], ["add", "c", 0, "u4"], ["add", "c", 0, "u3"]]
+    both = lambda a, b, x, y: [["merge", a, x, y], ["merge", b, y, x]]
+    return [
+        {"name": "be able to add user (:38-51)",
+         "ops": [["new", "c"]] + add4,
+         "checks": [["elements", "c", ["u1", "u2", "u3", "u4"]]]},
+        {"name": "be able to remove added user (:53-72)",
+         "ops": [["new", "c3"], ["add", "c3", 0, "u1"], ["add", "c3", 0, "u2"], ["copy", "c5", "c3"],
+                 ["remove", "c5", "u2"], ["remove", "c5", "u1"]] + both("c6", "c7", "c3", "c5"),
+         "checks": [["elements", "c5", []], ["elements", "c6", []], ["elements", "c7", []]]},
+        {"name": "be able to add removed (:74-83)",
+         "ops": [["new", "c"], ["remove", "c", "u1"], ["add", "c", 0, "u1"], ["copy", "c3", "c"],
+                 ["remove", "c", "u1"], ["copy", "c4", "c"], ["add", "c", 0, "u1"]],
+         "checks": [["elements", "c3", ["u1"]], ["elements", "c4", []], ["elements", "c", ["u1"]]]},
+        {"name": "be able to remove and add several times (:85-104)",
+         "ops": [["new", "c"], ["add", "c", 0, "u1"], ["add", "c", 0, "u2"], ["remove", "c", "u1"], ["copy", "c4", "c"],
+                 ["add", "c", 0, "u1"], ["add", "c", 0, "u2"], ["copy", "c6", "c"],
+                 ["remove", "c", "u1"], ["add", "c", 0, "u2"], ["remove", "c", "u1"]],
+         "checks": [["elements", "c4", ["u2"]], ["elements", "c6", ["u1", "u2"]], ["elements", "c", ["u2"]]]},
+        {"name": "merged with another ORSet with unique user sets (:106-130)",
+         "ops": [["new", "c1"], ["add", "c1", 0, "u1"], ["add", "c1", 0, "u2"],
+                 ["new", "c2"], ["add", "c2", 1, "u3"], ["add", "c2", 1, "u4"], ["remove", "c2", "u3"]] +
+                both("m1", "m2", "c1", "c2"),
+         "checks": [["elements", "c1", ["u1", "u2"]], ["elements", "c2", ["u4"]],
+                    ["elements", "m1", ["u1", "u2", "u4"]], ["elements", "m2", ["u1", "u2", "u4"]]]},
+        {"name": "merged with another ORSet with overlapping user sets (:132-160)",
+         "ops": [["new", "c1"], ["add", "c1", 0, "u1"], ["add", "c1", 0, "u2"], ["add", "c1", 0, "u3"],
+                 ["remove", "c1", "u1"], ["remove", "c1", "u3"],
+                 ["new", "c2"], ["add", "c2", 1, "u1"], ["add", "c2", 1, "u2"], ["add", "c2", 1, "u3"],
+                 ["add", "c2", 1, "u4"], ["remove", "c2", "u3"]] + both("m1", "m2", "c1", "c2"),
+         "checks": [["elements", "c1", ["u2"]], ["elements", "c2", ["u1", "u2", "u4"]],
+                    ["elements", "m1", ["u1", "u2", "u4"]], ["elements", "m2", ["u1", "u2", "u4"]]]},
+        {"name": "merged for concurrent updates (:162-200)",
+         "ops": [["new", "c1"], ["add", "c1", 0, "u1"], ["add", "c1", 0, "u2"], ["add", "c1", 0, "u3"],
+                 ["copy", "c2", "c1"], ["add", "c2", 1, "u1"], ["remove", "c2", "u2"], ["remove", "c2", "u3"]] +
+                both("m1", "m2", "c1", "c2") +
+                [["copy", "c3", "c1"], ["add", "c3", 0, "u4"], ["remove", "c3", "u3"], ["add", "c3", 0, "u2"]] +
+                both("m3", "m4", "c2", "c3"),
+         "checks": [["elements", "c1", ["u1", "u2", "u3"]], ["elements", "c2", ["u1"]],
+                    ["elements", "m1", ["u1"]], ["elements", "m2", ["u1"]],
+                    ["elements", "m3", ["u1", "u2", "u4"]], ["elements", "m4", ["u1", "u2", "u4"]]]},
+        {"name": "merged after remove (:202-227)",
+         "ops": [["new", "c1"], ["add", "c1", 0, "u1"], ["add", "c1", 0, "u2"], ["copy", "c2", "c1"],
+                 ["remove", "c2", "u2"]] + both("m1", "m2", "c1", "c2") +
+                [["copy", "c3", "c1"], ["add", "c3", 0, "u3"]] + both("m3", "m4", "c3", "c2"),
+         "checks": [["elements", "m1", ["u1"]], ["elements", "m2", ["u1"]],
+                    ["elements", "m3", ["u1", "u3"]], ["elements", "m4", ["u1", "u3"]]]},
+    ]
 
 
 def versionvector_kats():
