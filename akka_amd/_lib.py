@@ -96,6 +96,9 @@ SIGNATURES = {
                                                    ctypes.c_uint32]),
     "agx_receive_timeout_info": (ctypes.c_int32, [ctypes.c_void_p, c_u64p, c_u64p, c_u64p, c_u64p]),
     "agx_read_receive_timeout": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_u32p, c_u32p, c_u32p]),
+    "agx_set_sharding": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "agx_sharding_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 7),
+    "agx_read_entities": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_u32p, c_u32p, c_u32p]),
     "agx_set_ask": (ctypes.c_int32, [ctypes.c_void_p]),
     "agx_ask_info": (ctypes.c_int32, [ctypes.c_void_p, c_u64p, c_u64p, c_u64p, c_u64p]),
     "agx_read_asks": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, c_u32p, c_u32p]),
@@ -172,7 +175,8 @@ SIGNATURES = {
 
 # entry points newer than some A/B diagnostic builds (tools/build_variant.sh of an older checkout)
 OPTIONAL = {"agx_tell", "agx_pump_idle", "agx_pump_cancel", "agx_exchange_info", "agx_run_timed", "agx_build_hash",
-            "agx_persist_info", "agx_set_router_logics", "agx_router_info", "agx_read_hash_ring"}
+            "agx_persist_info", "agx_set_router_logics", "agx_router_info", "agx_read_hash_ring", "agx_set_sharding",
+            "agx_sharding_info", "agx_read_entities"}
 
 
 def load():

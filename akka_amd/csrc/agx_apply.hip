@@ -89,6 +89,8 @@ hipError_t feature_dispatch(uint32_t vid, uint32_t mode, uint32_t km_flags, bool
         case kStashKM: return launch_feature<V_ALL_COMPILED, kStashKM, false>(mode, g, s, ba);
         case kTimersKM: return launch_feature<V_ALL_COMPILED, kTimersKM, false>(mode, g, s, ba);
         case kTimersKM | kIdleKM: return launch_feature<V_ALL_COMPILED, kTimersKM | kIdleKM, false>(mode, g, s, ba);
+        case kTimersKM | kIdleKM | kShardKM:
+          return launch_feature<V_ALL_COMPILED, kTimersKM | kIdleKM | kShardKM, false>(mode, g, s, ba);
         case kTimersKM | kAskKM: return launch_feature<V_ALL_COMPILED, kTimersKM | kAskKM, false>(mode, g, s, ba);
         case kWatchKM: return launch_feature<V_ALL_COMPILED, kWatchKM, false>(mode, g, s, ba);
         case kWatchKM | kChildKM: return launch_feature<V_ALL_COMPILED, kWatchKM | kChildKM, false>(mode, g, s, ba);

@@ -287,6 +287,63 @@ __device__ __forceinline__ bool rt_transparent(const uint32_t (&m)[8], uint32_t 
   return (x >> (tag & 31u)) & 1u;
 }
 
+// ---- sharded entities (agx_set_sharding; akka-cluster-sharding Shard.scala:388-516), on top of the
+// receive timeouts.  The storage is an allocation of its own whose address stands in the timer storage's header
+// words [12..13] (free on an engine with receive timeouts), u32 units:
+//   [0]       n_types (1..AGX_MAX_ENTITY_TYPES)
+//   [4..15]   six u64 counters (kSc*)
+//   [kShTypeOff + kShTypeWords * t]  type t: first_id, count, kind, flags (kShWord1Id), word-0 base lo / hi,
+//                                    word 1 lo / hi, stop payload, idle delay, idle payload
+//   [kShRowOff ..]  three [actor]-indexed rows of np = nb << bb words:
+//     st[np]    the id's incarnation count | kShPassivating
+//     pst[np]   the tick of the entity's last stop while passivating (0: none): a start in the tick after it is a restart
+//     held[np]  what the entity's last stop left for the next formation to read, then 0:
+//               kShHeld | c  stopped while passivating after c messages of its window: the rest of its admitted
+//                            inbox stays queued (shard_requeue, this tick)
+//               d            a plain stop left d queued messages behind: the old mailbox's, dead at the next formation
+constexpr uint32_t kTmShardPtr = 12;
+constexpr uint32_t kShCtr = 4, kShTypeOff = 16, kShTypeWords = 12, kShRowOff = kShTypeOff + kShTypeWords * AGX_MAX_ENTITY_TYPES;
+constexpr uint32_t kShPassivating = 0x80000000u, kShHeld = 0x80000000u, kShWord1Id = AGX_ENTITY_WORD1_ID;
+enum : uint32_t { kScStarted, kScRestarted, kScPassivations, kScPassivated, kScIgnored, kScUnknown, kScN };
+struct ShardDev {
+  uint32_t* base;
+  uint32_t *st, *pst, *held;
+  uint32_t nt;
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kShCtr) + i;
+  }
+  __device__ __forceinline__ const uint32_t* type(uint32_t t) const { return base + kShTypeOff + kShTypeWords * t; }
+  // the entity type of id l, nt for an id in no range (at most 8 uniform rows: no search structure)
+  __device__ __forceinline__ uint32_t type_of(uint32_t l) const {
+    uint32_t r = nt;
+    for (uint32_t t = 0; t < nt; ++t) {
+      const uint32_t* T = type(t);
+      if (l - T[0] < T[1]) r = t;
+    }
+    return r;
+  }
+  // does [a0, a0 + na) meet an entity range?
+  __device__ __forceinline__ bool meets(uint32_t a0, uint32_t na) const {
+    bool m = false;
+    for (uint32_t t = 0; t < nt; ++t) {
+      const uint32_t* T = type(t);
+      m |= a0 < T[0] + T[1] && T[0] < a0 + na;
+    }
+    return m;
+  }
+};
+__device__ __forceinline__ ShardDev shard_dev(const TimerDev& TD) {
+  ShardDev s;
+  s.base = reinterpret_cast<uint32_t*>(*reinterpret_cast<const unsigned long long*>(TD.base + kTmShardPtr));
+  s.nt = s.base[0];
+  s.st = s.base + kShRowOff;
+  s.pst = s.st + TD.np;
+  s.held = s.pst + TD.np;
+  return s;
+}
+// what the drain of one message hands back beside RtRegs: the case ran AGX_A_PASSIVATE
+constexpr uint32_t kRtPassivate = 4u;
+
 // ---- ask (agx_set_ask; TY/internal/ActorContextImpl.scala:203-218, TY/scaladsl/AskPattern.scala:
 // 109-162), on top of the timers: an outstanding ask is a single timer slot with one more fact about it, the
 // timeout is the slot's TimerMsg.  The timer storage of such an engine is longer: after agen[np] comes
@@ -740,6 +797,9 @@ constexpr uint32_t kListKM = 1u << 21;
 // KM flag (not a kind): the variant knows consistent-hashing and random routing (agx_set_router_logics); only ever
 // combined with kRecepKM.
 constexpr uint32_t kHashKM = 1u << 20;
+// KM flag (not a kind): the variant knows sharded entities (agx_set_sharding); only ever combined as
+// kTimersKM | kIdleKM | kShardKM.
+constexpr uint32_t kShardKM = 1u << 19;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -836,7 +896,9 @@ __device__ __forceinline__ uint64_t tm_operand(const TimerDev& TD, uint32_t l, u
 // (kAsk: the ask instantiations, DESIGN.md §2.9 -- AGX_A_ASK_ARM starts the key as a single timer marked as an ask
 // and leaves the ask ref in `ar`, AGX_A_ASK_SEND emits the case's one envelope with that ref as its sender; a plain
 // timer start clears the mark.  `emit` is then an AskEmit)
-template <bool kIdle = false, bool kAsk = false, typename Emit>
+// (kShard: the sharding instantiations, DESIGN.md §2.13 -- AGX_A_PASSIVATE only raises kRtPassivate in `rt`: the
+// caller, which knows the entity's type and mark, sends the stop payload through the case's tell slot)
+template <bool kIdle = false, bool kAsk = false, bool kShard = false, typename Emit>
 __device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const TimerDev& TD, uint32_t l, uint32_t bkt,
                                                       uint32_t now, uint32_t& kind, uint32_t self, uint64_t* w,
                                                       uint32_t src, uint32_t pay, Emit& emit, RtRegs* rt = nullptr,
@@ -896,6 +958,9 @@ __device__ __forceinline__ uint32_t compiled_apply_tm(const DevParams& P, const 
               rt->flags |= kRtChanged | (rt->delay ? kRtWasOff : 0u);
               rt->delay = 0u;
             }
+          }
+          if constexpr (kShard) {
+            if (A.op == AGX_A_PASSIVATE) rt->flags |= kRtPassivate;
           }
           if constexpr (kAsk) {
             const uint32_t msg = A.or_mask ? ((uint32_t)v & 0xFFFFFFu) | A.or_mask : (uint32_t)v;

@@ -162,6 +162,11 @@ struct agx_engine {
     uint32_t delay, payload;
   };
   std::vector<RtStart> rt_starts;  // agx_start_receive_timeout calls not yet applied on the device (prepare_run)
+  // sharded entities (agx_set_sharding), on top of receive timeouts: the entity types and the storage (agx_device.h
+  // ShardDev), whose address stands in the timer storage
+  std::vector<agx_entity_type> sh_types;
+  uint32_t* d_shard = nullptr;
+  bool beh_passivate = false;  // the compiled tables hold AGX_A_PASSIVATE
   // the ask pattern (agx_set_ask), on top of the timers: one [key][actor] row appended to the timer storage.  Such an
   // engine launches the kTimers | kAsk instantiation
   bool ask_on = false;
@@ -473,7 +478,7 @@ namespace {
 // of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
 // the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
 // apply_variant, launch_apply and make_params.
-enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_IDLE, F_RECEP, F_ASK, F_LIST, F_TOPIC, F_HASH, F_N, F_NONE = F_N };
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_SHARD, F_IDLE, F_RECEP, F_ASK, F_LIST, F_TOPIC, F_HASH, F_N, F_NONE = F_N };
 
 struct FeatureRow {
   bool (*on)(const agx_engine*);
@@ -516,6 +521,10 @@ const FeatureRow kFeatures[F_N] = {
     // theirs: the row only selects the launch
     {[](const agx_engine* e) { return e->d_child != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      nullptr, kWatchKM | kChildKM, false, F_WATCH},
+    // sharded entities (agx_set_sharding) come on top of receive timeouts, which come on top of the timers: the row
+    // stands before theirs, so launched_feature (the first row that is on) selects the sharding instantiation
+    {[](const agx_engine* e) { return e->d_shard != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+     nullptr, kTimersKM | kIdleKM | kShardKM, false, F_TIMERS},
     // receive timeouts (agx_set_receive_timeout) come on top of the timers in the same way
     {[](const agx_engine* e) { return e->rt_on; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      kTimersKM | kIdleKM, false, F_TIMERS},
@@ -2408,6 +2417,12 @@ agx_status prepare_run(agx_engine* e) {
   if (e->rt_on && e->beh_rt_tag)
     return set_err(AGX_EINVAL, "the compiled behaviours name message tag 0xFB, reserved for receive-timeout envelopes on an "
                    "engine with receive timeouts");
+  if (e->beh_passivate && !e->d_shard)  // (only the sharding variant interprets those: loud, never wrong)
+    return set_err(AGX_EINVAL, "the compiled behaviours passivate, but the engine has no sharding (agx_set_sharding)");
+  for (const auto& t : e->sh_types)
+    if (t.kind - AGX_KIND_COMPILED >= e->n_beh)
+      return set_err(AGX_EINVAL, "sharding: an entity type's kind %u is no compiled behaviour of the tables (%u behaviours)",
+                     t.kind, e->n_beh);
   if (e->beh_ask_keys && !e->ask_on)  // (only the ask variant interprets those: loud, never wrong)
     return set_err(AGX_EINVAL, "the compiled behaviours ask, but the engine has no ask pattern (agx_set_ask)");
   if (e->beh_ask_unpaired >= 0)
@@ -3993,6 +4008,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_timers);
   hipFree(e->d_watch);
   hipFree(e->d_child);
+  hipFree(e->d_shard);
   hipFree(e->d_super);
   hipFree(e->d_recep);
   hipFree(e->d_topic);
@@ -4033,6 +4049,13 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
     if (count && first_id < c1 && c0 < first_id + count)
       return set_err(AGX_EINVAL, "register_range [%llu, %llu) overlaps the child block [%llu, %llu) (agx_set_children): "
                      "its actors are created by their parents", (unsigned long long)first_id,
+                     (unsigned long long)(first_id + count), (unsigned long long)c0, (unsigned long long)c1);
+  }
+  for (const auto& t : e->sh_types) {  // (sharding: the ids of an entity range belong to the engine)
+    const uint64_t c0 = t.first_id, c1 = c0 + t.count;
+    if (count && first_id < c1 && c0 < first_id + count)
+      return set_err(AGX_EINVAL, "register_range [%llu, %llu) overlaps the entity range [%llu, %llu) (agx_set_sharding): "
+                     "its entities are started by their first message", (unsigned long long)first_id,
                      (unsigned long long)(first_id + count), (unsigned long long)c0, (unsigned long long)c1);
   }
   if (kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET) AGX_TRY(enable_crdt(e, kind));
@@ -4399,6 +4422,109 @@ agx_status agx_read_receive_timeout(agx_engine* e, uint64_t first_id, uint64_t c
   if (payload) AGX_TRY(copy_sync(e, payload, e->d_timers + rt_row_off(e) + 2ull * npad + first_id, count * 4ull, hipMemcpyDeviceToHost));
   if (remaining)
     for (uint64_t i = 0; i < count; ++i) remaining[i] = nx[i] == kTmNone ? 0xFFFFFFFFu : nx[i] - clk;
+  return AGX_OK;
+}
+
+// akka-cluster-sharding Shard.scala:388-516
+agx_status agx_set_sharding(agx_engine* e, const agx_entity_type* types, uint32_t n_types) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->rt_on)
+    return set_err(AGX_EINVAL, "sharding needs an engine with receive timeouts (agx_set_timers, then agx_set_receive_timeout "
+                   "first)");
+  if (e->started) return set_err(AGX_ESTATE, "set sharding before the first agx_run");
+  if (e->d_shard) return set_err(AGX_EINVAL, "sharding is set already (agx_set_sharding is called once)");
+  if (n_types < 1u || n_types > AGX_MAX_ENTITY_TYPES || !types)
+    return set_err(AGX_EINVAL, "sharding: %u entity types (1..%u)", n_types, AGX_MAX_ENTITY_TYPES);
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(sync_mirrors(e));
+  const uint64_t n = e->n_global;
+  for (uint32_t i = 0; i < n_types; ++i) {
+    const agx_entity_type& t = types[i];
+    const uint64_t c0 = t.first_id, c1 = c0 + t.count;
+    if (!t.count || c1 > n) return set_err(AGX_EINVAL, "sharding: entity type %u is empty or leaves [0, n_actors)", i);
+    for (uint32_t j = 0; j < i; ++j) {
+      const uint64_t d0 = types[j].first_id, d1 = d0 + types[j].count;
+      if (c0 < d1 && d0 < c1) return set_err(AGX_EINVAL, "sharding: the ranges of entity types %u and %u overlap", j, i);
+    }
+    if (t.kind < AGX_KIND_COMPILED || t.kind >= AGX_KIND_COMPILED + AGX_MAX_BEHAVIORS || (t.flags & ~AGX_ENTITY_WORD1_ID) ||
+        t.reserved)
+      return set_err(AGX_EINVAL, "sharding: entity type %u: kind %u is no compiled behaviour kind, or unknown flags", i, t.kind);
+    const uint32_t st = t.stop_payload >> 24, it = t.idle_payload >> 24;
+    if (st == AGX_TAG_TIMER || st == AGX_TAG_RECEIVE_TIMEOUT || (t.idle_delay && (it == AGX_TAG_TIMER || it == AGX_TAG_RECEIVE_TIMEOUT)))
+      return set_err(AGX_EINVAL, "sharding: entity type %u: a stop or idle message carries a reserved tag (0xFF, 0xFB)", i);
+    for (uint64_t x = c0; x < c1; ++x)
+      if (e->h_alive[x] & 1u)
+        return set_err(AGX_EINVAL, "sharding: id %llu of entity type %u's range is registered", (unsigned long long)x, i);
+  }
+  AGX_TRY(alloc_timers(e));
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  const size_t total = kShRowOff + 3ull * npad;
+  if (hipMalloc((void**)&e->d_shard, total * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->d_shard = nullptr;
+    return set_err(AGX_ENOMEM, "the entity storage of %llu actors does not fit on the device", (unsigned long long)n);
+  }
+  std::vector<uint32_t> h(kShRowOff, 0u);
+  h[0] = n_types;
+  for (uint32_t i = 0; i < n_types; ++i) {
+    uint32_t* T = &h[kShTypeOff + kShTypeWords * i];
+    T[0] = types[i].first_id;
+    T[1] = types[i].count;
+    T[2] = types[i].kind;
+    T[3] = types[i].flags;
+    T[4] = (uint32_t)types[i].base0;
+    T[5] = (uint32_t)(types[i].base0 >> 32);
+    T[6] = (uint32_t)types[i].word1;
+    T[7] = (uint32_t)(types[i].word1 >> 32);
+    T[8] = types[i].stop_payload;
+    T[9] = std::min(types[i].idle_delay, kTmMaxDelay);
+    T[10] = types[i].idle_payload;
+  }
+  HIP_TRY(hipMemsetAsync(e->d_shard, 0, total * 4ull, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_shard, h.data(), h.size() * 4ull, hipMemcpyHostToDevice, e->stream));
+  const unsigned long long addr = (unsigned long long)(uintptr_t)e->d_shard;
+  HIP_TRY(hipMemcpyAsync(e->d_timers + kTmShardPtr, &addr, 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->sh_types.assign(types, types + n_types);
+  if (!(e->kinds_mask & kb(AGX_KIND_COMPILED))) e->kinds_mask |= kb(AGX_KIND_COMPILED);  // (the entities' kinds)
+  drop_graphs(e);  // the variant is captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_sharding_info(agx_engine* e, uint64_t* started, uint64_t* restarted, uint64_t* passivations, uint64_t* passivated,
+                             uint64_t* passivate_ignored, uint64_t* passivate_unknown, uint64_t* alive) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[kScN] = {0, 0, 0, 0, 0, 0}, na = 0;
+  if (e->d_shard) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(copy_sync(e, c, e->d_shard + kShCtr, sizeof(c), hipMemcpyDeviceToHost));
+    AGX_TRY(sync_mirrors(e));  // (the flags of the device are the newer ones after a run)
+    for (const auto& t : e->sh_types)
+      for (uint64_t x = t.first_id; x < (uint64_t)t.first_id + t.count; ++x) na += e->h_alive[x] & 1u;
+  }
+  if (started) *started = c[kScStarted];
+  if (restarted) *restarted = c[kScRestarted];
+  if (passivations) *passivations = c[kScPassivations];
+  if (passivated) *passivated = c[kScPassivated];
+  if (passivate_ignored) *passivate_ignored = c[kScIgnored];
+  if (passivate_unknown) *passivate_unknown = c[kScUnknown];
+  if (alive) *alive = na;
+  return AGX_OK;
+}
+
+agx_status agx_read_entities(agx_engine* e, uint64_t first_id, uint64_t count, uint32_t* alive, uint32_t* incarnations,
+                             uint32_t* passivating) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (first_id + count > e->n_global || first_id + count < first_id) return set_err(AGX_EINVAL, "bad actor range");
+  AGX_TRY(ensure_dev(e));
+  AGX_TRY(sync_mirrors(e));
+  std::vector<uint32_t> st(count, 0u);
+  if (e->d_shard && count) AGX_TRY(copy_sync(e, st.data(), e->d_shard + kShRowOff + first_id, count * 4ull, hipMemcpyDeviceToHost));
+  for (uint64_t i = 0; i < count; ++i) {
+    if (alive) alive[i] = e->h_alive[first_id + i] & 1u;
+    if (incarnations) incarnations[i] = st[i] & ~kShPassivating;
+    if (passivating) passivating[i] = (st[i] & kShPassivating) ? 1u : 0u;
+  }
   return AGX_OK;
 }
 
@@ -5253,7 +5379,7 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
     if (rcop && (A.pad1 >= AGX_MAX_SERVICE_KEYS || A.pad0 > (A.op == AGX_A_ROUTE ? kRouteFlags : 0u) ||
                  (A.op == AGX_A_ROUTE && (A.pad0 & AGX_ROUTE_BY_INDEX) && !opnd_ok(A.dsrc, A.dword))))
       return set_err(AGX_EINVAL, "compiled behaviours: bad action %u (service keys 0..7, route flags 0..3)", i);
-    if (A.op < AGX_A_SET || A.op > AGX_A_FIND || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
+    if (A.op < AGX_A_SET || A.op > AGX_A_PASSIVATE || A.word > (tmop ? AGX_MAX_TIMER_KEYS - 1u : 1u) ||
         !opnd_ok(A.src, A.sword) ||
         ((A.op == AGX_A_TELL || A.op == AGX_A_TIMER_SINGLE || A.op == AGX_A_TIMER_PERIODIC || wdop || A.op == AGX_A_STOP_CHILD ||
           A.op == AGX_A_SET_RECEIVE_TIMEOUT || askop) &&
@@ -5318,6 +5444,18 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   if (e->d_child && ctl_tags)
     return set_err(AGX_EINVAL, "compiled behaviours: message tags 0xFD and 0xFC are reserved for Create and Stop envelopes on "
                    "an engine with children");
+  // sharding: a Passivate sends the entity's stop message through the case's tell slot
+  for (uint32_t c = 0; c < n_cases; ++c) {
+    uint32_t sends = 0;
+    bool pas = false;
+    for (uint32_t i = cases[c].act_first; i < (uint32_t)cases[c].act_first + cases[c].act_count; ++i) {
+      sends += acts[i].op == AGX_A_TELL || acts[i].op == AGX_A_PASSIVATE;
+      pas |= acts[i].op == AGX_A_PASSIVATE;
+    }
+    if (pas && sends > 1u)
+      return set_err(AGX_EINVAL, "compiled behaviours: case %u holds %u of tell and passivate; an engine with sharding has "
+                     "max_emit 1", c, sends);
+  }
   // the receptionist: a route sends one envelope through the case's tell slot; the service keys the tables use
   bool uses_recep = false, uses_publish = false, uses_listing = false;
   uint32_t rc_keys_used = 0;
@@ -5422,6 +5560,8 @@ agx_status agx_set_behaviors(agx_engine* e, const agx_case* cases, uint32_t n_ca
   for (uint32_t i = 0; i < n_acts; ++i)
     e->beh_rt |= acts[i].op == AGX_A_SET_RECEIVE_TIMEOUT || acts[i].op == AGX_A_CANCEL_RECEIVE_TIMEOUT;
   e->beh_rt_tag = rt_tag;
+  e->beh_passivate = false;  // (checked against agx_set_sharding at agx_run)
+  for (uint32_t i = 0; i < n_acts; ++i) e->beh_passivate |= acts[i].op == AGX_A_PASSIVATE;
   e->beh_recep = uses_recep;  // (checked against agx_set_receptionist at agx_run)
   e->beh_rc_keys = rc_keys_used;
   e->beh_publish = uses_publish;  // (checked against agx_set_topics at agx_run)

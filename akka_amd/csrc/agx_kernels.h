@@ -1633,6 +1633,176 @@ __device__ __forceinline__ void child_tick_end(const BucketArgs& a, const Bucket
   }
 }
 
+// ---- sharded entities (agx_set_sharding): the starts of tick `now` in bucket b, before admission
+// (Shard.getOrCreateEntity, Shard.scala:504-516).  Actor-parallel: a thread looks at its four actors; a bucket that
+// meets no entity range, or holds no dead entity with mail, pays the range test (uniform loads), one LDS read per
+// actor and one block scan.  Else the thread of such an entity walks its segment: the messages its last plain stop
+// left queued (`held`) and those it sent itself (a self-tell, a TimerMsg, a receive-timeout envelope: they bypass
+// the shard) are dead letters; if anything stays the entity is alive again with its type's kind and state -- written
+// to memory, the prefetch after the barrier reads them -- and its receive timeout set at `now`.  The dead items leave
+// the inbox: the rest keeps its order, the segment starts move, `cnt` shrinks.
+__device__ __forceinline__ void shard_classify(const BucketArgs& a, const BucketLds& L, const ShardDev& SH, const TimerDev& TD,
+                                               uint32_t b, uint32_t a0, uint32_t na, uint32_t now, uint32_t& cnt,
+                                               uint32_t& ndead) {
+  const DevParams& P = a.P;
+  const int tid = threadIdx.x;
+  uint32_t cand = 0;  // bit j: actor tid * 4 + j is a dead entity with mail
+  if (SH.meets(a0, na)) {  // (block-uniform)
+#pragma unroll
+    for (int j = 0; j < kBAct; ++j) {
+      const uint32_t la = tid * kBAct + j;
+      if (la < na && L.seg[la + 1] != L.seg[la] && !(L.alive[la] & 1u) && SH.type_of(a0 + la) < SH.nt) cand |= 1u << j;
+    }
+  }
+  uint32_t tot;
+  block_excl_sum<kBThreads>(cand ? 1u : 0u, L.scratch, &tot);
+  if (!tot) return;  // (block-uniform)
+  uint32_t* const pre = reinterpret_cast<uint32_t*>(L.U);  // [kBucket + 1] 1: the item stays; then: the items that stay before q
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) pre[tid * kBIpt + r] = 1u;
+  __syncthreads();
+  uint32_t nrm = 0, nst = 0, nrs = 0, emin = kTmNone;
+#pragma unroll 1
+  for (int j = 0; j < kBAct; ++j) {
+    if (!((cand >> j) & 1u)) continue;
+    const uint32_t la = tid * kBAct + j, l = a0 + la, s0 = L.seg[la], s1 = L.seg[la + 1];
+    const uint32_t hv = SH.held[l], old = (hv & kShHeld) ? 0u : hv;
+    if (hv) SH.held[l] = 0u;
+    uint32_t stay = 0;
+    for (uint32_t q = s0; q < s1; ++q) {
+      if (q - s0 < old || L.src[q] == l) {
+        pre[q] = 0u;
+        ++nrm;
+      } else {
+        ++stay;
+      }
+    }
+    if (!stay) continue;
+    const uint32_t* T = SH.type(SH.type_of(l));
+    const uint8_t ab = L.alive[la] | 1u;
+    L.alive[la] = ab;
+    P.alive[l] = ab;
+    P.kind[l] = (uint8_t)T[2];
+    stg64(P.state, sidx(P, l, 0), ((uint64_t)T[5] << 32) | T[4]);
+    if (P.W > 1) stg64(P.state, sidx(P, l, 1), (T[3] & kShWord1Id) ? (uint64_t)l : (((uint64_t)T[7] << 32) | T[6]));
+    for (uint32_t k = 2; k < P.W; ++k) stg64(P.state, sidx(P, l, k), 0ull);
+    if (T[9]) {  // the idle type: the receive timeout (delay, payload) set at this tick
+      const IdleDev ID = idle_dev(TD);
+      ID.delay[l] = T[9];
+      ID.pay[l] = T[10];
+      ID.next[l] = now + T[9];
+      emin = min(emin, now + T[9]);
+    }
+    SH.st[l] = SH.st[l] + 1u;  // (not passivating: any stop cleared the mark)
+    ++nst;
+    nrs += (SH.pst[l] != 0u && SH.pst[l] == now - 1u) ? 1u : 0u;  // (ticks count from 1)
+  }
+  if (emin != kTmNone) atomicMin(&TD.earliest(b), emin);
+  ndead += nrm;
+  __syncthreads();  // (the flags; L.alive)
+  const uint4 k4 = reinterpret_cast<const uint4*>(L.key)[tid], s4 = reinterpret_cast<const uint4*>(L.src)[tid],
+              p4 = reinterpret_cast<const uint4*>(L.pay)[tid];
+  const uint32_t kk[kBIpt] = {k4.x, k4.y, k4.z, k4.w}, ss[kBIpt] = {s4.x, s4.y, s4.z, s4.w},
+                 pp[kBIpt] = {p4.x, p4.y, p4.z, p4.w};
+  uint32_t fl[kBIpt], nkeep = 0;
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) {
+    fl[r] = pre[tid * kBIpt + r];
+    nkeep += fl[r];
+  }
+  uint32_t tk, t1, t2;
+  uint32_t run = block_excl_sum<kBThreads>(nkeep, L.scratch, &tk);  // (syncs: every flag is in registers)
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) {
+    pre[tid * kBIpt + r] = run;
+    run += fl[r];
+  }
+  if (tid == kBThreads - 1) pre[kBucket] = run;
+  block_excl_sum2<kBThreads>(nst, nrs, L.scratch, &t1, &t2);  // (syncs: `pre` is whole, the items are in registers)
+#pragma unroll
+  for (int r = 0; r < kBIpt; ++r) {
+    const uint32_t q = tid * kBIpt + r;
+    if (q < cnt && fl[r]) {
+      const uint32_t to = pre[q];  // (<= q: only items already in registers are overwritten)
+      L.key[to] = kk[r];
+      L.src[to] = ss[r];
+      L.pay[to] = pp[r];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) L.seg[tid * kBAct + j] = pre[L.seg[tid * kBAct + j]];
+  if (tid == 0) {
+    L.seg[kBucket] = pre[L.seg[kBucket]];
+    if (t1) atomicAdd(SH.ctr(kScStarted), (unsigned long long)t1);
+    if (t2) atomicAdd(SH.ctr(kScRestarted), (unsigned long long)t2);
+  }
+  cnt = tk - ((uint32_t)kBucket - cnt);  // (the flags past cnt are 1)
+  __syncthreads();
+}
+
+// The end of a tick in which an entity of bucket b stopped while passivating (Shard.passivateCompleted, Shard.scala:
+// 453-466): what was queued behind the stop -- the rest of its window and its backlog -- stays queued for the start
+// of the next tick.  The block writes the bucket's backlog again, from the LDS inbox: every other actor's as the
+// classification did, such an entity's from the message after the stop.  A slot a tell was staged over belongs to a
+// consumed message (tell e of an actor comes from a message of index >= e): its key is not trusted, the segment
+// bounds decide.  Block-uniform call, after the barrier that follows the drains; U is free.  Returns the new count.
+template <bool kGather>
+__device__ __forceinline__ uint32_t shard_requeue(const BucketArgs& a, const BucketLds& L, const ShardDev& SH, uint32_t b,
+                                                  uint32_t lo, uint32_t cnt, uint32_t a0, uint32_t na, uint32_t w) {
+  const DevParams& P = a.P;
+  const int tid = threadIdx.x;
+  uint32_t* const blpre = reinterpret_cast<uint32_t*>(L.U);  // [kBucket] the actor's place in the bucket's backlog
+  uint32_t* const from = blpre + kBucket;                    // [kBucket] the first position of its segment that is queued
+  uint32_t qn[kBAct], f[kBAct], nq = 0;
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) {
+    const uint32_t la = tid * kBAct + j, len = L.seg[la + 1] - L.seg[la];
+    qn[j] = 0;
+    f[j] = len;
+    if (la < na && len && (L.alive[la] & 1u)) {  // (L.alive: the flags of the tick's entry, the classification's)
+      uint32_t C, T;
+      mbox_limits(P, L.alive[la], C, T);
+      const uint32_t keep = (C == 0 || len < C) ? len : C;
+      const uint32_t hv = SH.held[a0 + la];
+      f[j] = (hv & kShHeld) ? min(hv & ~kShHeld, keep) : min(T, keep);
+      qn[j] = keep - f[j];
+      if (hv & kShHeld) SH.held[a0 + la] = 0u;
+    }
+    nq += qn[j];
+  }
+  uint32_t bltot;
+  uint32_t ex = block_excl_sum<kBThreads>(nq, L.scratch, &bltot);
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) {
+    blpre[tid * kBAct + j] = ex;
+    from[tid * kBAct + j] = f[j];
+    ex += qn[j];
+  }
+  __syncthreads();
+  const Msgs blw = a.g.bl[w];
+  const uint32_t amask = (1u << a.bb) - 1u;
+  for (uint32_t q = tid; q < cnt; q += kBThreads) {
+    const uint32_t key = L.key[q], la = key & amask;
+    const uint32_t s0 = L.seg[la], len = L.seg[la + 1] - s0, p = q - s0;
+    if (p >= len) continue;  // (q lies outside la's segment: a staged tell's key)
+    const uint32_t ab = L.alive[la];
+    uint32_t C, T;
+    mbox_limits(P, ab, C, T);
+    const uint32_t keep = (C == 0 || len < C) ? len : C;
+    if (!(ab & 1u) || p < from[la] || p >= keep) continue;
+    const uint32_t o = lo + blpre[la] + (p - from[la]);
+    blw.key[o] = key;
+    blw.src[o] = L.src[q];
+    blw.pay[o] = L.pay[q];
+  }
+  if (tid == 0) {
+    if constexpr (kGather) a.g.blc[w][b] = bltot;
+    else a.chunk_cnt[b] = bltot;
+  }
+  __syncthreads();
+  return bltot;
+}
+
 // ---- the receptionist (agx_set_receptionist): what a thread's drains changed reaches the storage
 // once per wave -- the changed key bits as one atomic OR on the global dirty word (and the block's own "recount"
 // word in LDS), each counter as one atomic add.  A wave without a change or a route (the common case) does nothing.
@@ -1941,6 +2111,19 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     pre0 = pre1 = nullptr;  // (a born actor's state words are written to memory: the prefetch reads them there)
     child_classify<kGather>(a, L, CD, WD, b, a0, na, tnow, cnt, acc[0]);
   }
+  // kSh: sharded entities (agx_set_sharding), on top of the receive timeouts.  A dead entity with
+  // mail starts here, before admission; compiled cases passivate; an entity that stops while passivating keeps what
+  // was queued behind the stop (shard_requeue, after the drains).
+  constexpr bool kSh = (KM & kShardKM) != 0;
+  static_assert(!kSh || kIdle, "sharded entities: on the receive-timeout instantiations only");
+  ShardDev SH{};
+  uint32_t shdead = 0;  // kSh: the dead letters of the starts' formation (this thread's entities')
+  bool shheld = false;  // kSh: an entity of this thread stopped while passivating in this tick
+  if constexpr (kSh) {
+    SH = shard_dev(TD);
+    pre0 = pre1 = nullptr;  // (a started entity's state words are written to memory: the prefetch reads them there)
+    shard_classify(a, L, SH, TD, b, a0, na, tnow, cnt, shdead);
+  }
   // kRc: the receptionist (agx_set_receptionist).  The inbox is the plain one; the drain keeps an
   // actor's key mask in a register across its window, compiled cases register, deregister, find and route against
   // the listings in force, and a block in which a mask changed recounts its bucket's members (L.rowtop is that
@@ -1994,6 +2177,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
   AGX_STAMP(a, 3);
   // ---- classification per actor (blocked): drained / queued (backlog) / dead letters
   uint32_t nbl_t = 0, ndead = ndead0, blc[kBAct];  // ndead0: this thread's actors' arrivals dropped before the sort
+  if constexpr (kSh) ndead += shdead;
 #pragma unroll
   for (int j = 0; j < kBAct; ++j) {
     const uint32_t la = tid * kBAct + j;
@@ -2577,8 +2761,24 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
             pv = rp;
           }
           RtRegs rt{rd, rp, 0u};
-          const uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_tm<true>(P, TD, l, b, tnow, kcur, self, wv, sv, pv, em, &rt)
+          const uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_tm<true, false, kSh>(P, TD, l, b, tnow, kcur, self, wv, sv, pv, em, &rt)
                                                        : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          if constexpr (kSh) {
+            // context.passivate() is shard ! Passivate(self) (Shard.passivate, Shard.scala:405-417): an entity that is
+            // not passivating is marked and gets its type's stop message through the case's tell slot
+            if (rt.flags & kRtPassivate) {
+              const uint32_t ty = SH.type_of(l), s = SH.st[l];
+              if (ty >= SH.nt) {
+                atomicAdd(SH.ctr(kScUnknown), 1ull);
+              } else if (s & kShPassivating) {
+                atomicAdd(SH.ctr(kScIgnored), 1ull);
+              } else {
+                SH.st[l] = s | kShPassivating;
+                em(self, SH.type(ty)[8]);
+                atomicAdd(SH.ctr(kScPassivations), 1ull);
+              }
+            }
+          }
           if (rt.flags & kRtChanged) {
             if (rt.delay) {
               rp = rt.pay;
@@ -2591,6 +2791,22 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           if (r == AGX_RES_STOPPED) {
             if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
             else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            if constexpr (kSh) {
+              // an entity that stops while passivating keeps what is queued behind the stop (shard_requeue); a plain
+              // stop leaves its queued mail to die at the next formation, which has to tell it from later arrivals
+              const uint32_t s = SH.st[l];
+              if (s & kShPassivating) {
+                SH.st[l] = s & ~kShPassivating;
+                SH.pst[l] = tnow;
+                SH.held[l] = kShHeld | (q + 1u);
+                atomicAdd(SH.ctr(kScPassivated), 1ull);
+                shheld = true;
+              } else {
+                ndead += nd - q - 1;
+                const uint32_t keep = (Ca == 0 || len < Ca) ? len : Ca;
+                if (keep > nd && SH.type_of(l) < SH.nt) SH.held[l] = keep - nd;
+              }
+            } else
             ndead += nd - q - 1;  // drained-but-unprocessed after the stop
             for (uint32_t k = 0; k < TD.nk; ++k) TD.cancel(k, l, b);  // cancelAll on PostStop
             was_off |= rd != 0u;  // any stop turns the timeout off
@@ -2653,7 +2869,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
             if (aw & kAskHasTag) pv = (pv & 0xFFFFFFu) | (aw << 24);
           }
           const uint32_t r = kcur >= AGX_KIND_COMPILED
-                                 ? compiled_apply_tm<false, true>(P, TD, l, b, tnow, kcur, self, wv, sv, pv, aem, nullptr, &ar)
+                                 ? compiled_apply_tm<false, true, false>(P, TD, l, b, tnow, kcur, self, wv, sv, pv, aem, nullptr, &ar)
                                  : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, aem);
           if (r == AGX_RES_UNHANDLED) ++nunh;
           if (r == AGX_RES_STOPPED) {
@@ -2985,6 +3201,8 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     if constexpr (kLs) listing_commit(LD, lsc, L.rowtop);
     if constexpr (kHr) hash_commit(HD, hcc);
     __syncthreads();
+    if constexpr (kSh)  // (block-uniform; U is free: the state words were written back)
+      if (__syncthreads_or(shheld ? 1 : 0)) bltot = shard_requeue<kGather>(a, L, SH, b, lo, cnt, a0, na, w);
     if constexpr (kLs) {  // (block-uniform; bit 0: a key mask changed, bit 1: a sub or pending byte)
       if (*L.rowtop & 1u) recep_recount(RD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));
       if (*L.rowtop & 2u) listing_recount(LD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));

@@ -50,7 +50,7 @@ hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 grid, h
 // launch a feature's fast launch k_bucket_apply<variant vid, mode, no skew, KM | km_flags, kPrio = prio> (agx_engine.hip
 // kFeatures: km_flags = the feature's KM flag bits, or none and `prio` for priority mailboxes).  Instantiated in the
 // modes M_FUSED / M_BYPASS: kPrio for the catch-all plain variants V_ALL / V_ALL_COMPILED, the flag combinations
-// kStashKM, kTimersKM, kTimersKM | kIdleKM, kTimersKM | kAskKM, kWatchKM, kWatchKM | kChildKM, kSuperKM, kRecepKM,
+// kStashKM, kTimersKM, kTimersKM | kIdleKM, kTimersKM | kIdleKM | kShardKM, kTimersKM | kAskKM, kWatchKM, kWatchKM | kChildKM, kSuperKM, kRecepKM,
 // kRecepKM | kHashKM, kRecepKM | kTopicKM, kRecepKM | kTopicKM | kListKM for V_ALL_COMPILED
 // (hipErrorInvalidValue otherwise)
 hipError_t agx_launch_apply_feature(uint32_t vid, uint32_t mode, uint32_t km_flags, bool prio, dim3 grid, hipStream_t s,

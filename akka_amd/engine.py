@@ -282,6 +282,38 @@ class GpuEngine:
         check(self.lib.agx_read_receive_timeout(self._h, first, count, *(_ptr(x, ctypes.c_uint32) for x in a)))
         return dict(zip(("delay", "remaining", "payload"), a))
 
+    ENTITY_TYPE = np.dtype([("first_id", "<u4"), ("count", "<u4"), ("kind", "<u4"), ("flags", "<u4"), ("base0", "<u8"),
+                            ("word1", "<u8"), ("stop_payload", "<u4"), ("idle_delay", "<u4"), ("idle_payload", "<u4"),
+                            ("reserved", "<u4")])
+
+    def set_sharding(self, types) -> None:
+        """Sharded entities (agx_set_sharding; akka-cluster-sharding Shard.scala:388-516) on top of
+        receive timeouts -- call set_timers and set_receive_timeout first.  `types` are (first_id, count, kind, word-0
+        base, word-1 constant or None for the entity's id, stop payload, idle delay, idle payload),
+        typed.Tables.entity_types has them: the ids of a range are unregistered, an entity starts on its first
+        message, and compiled behaviours may context.passivate()."""
+        t = np.zeros(max(len(types), 1), self.ENTITY_TYPE)
+        for i, (first, count, kind, base, w1, stop, delay, idle) in enumerate(types):
+            t[i] = (int(first), int(count), int(kind), 1 if w1 is None else 0, int(base), 0 if w1 is None else int(w1),
+                    int(stop) & 0xFFFFFFFF, int(delay), int(idle) & 0xFFFFFFFF, 0)
+        check(self.lib.agx_set_sharding(self._h, t.ctypes.data_as(ctypes.c_void_p), len(types)))
+
+    SHARDING_INFO = ("started", "restarted", "passivations", "passivated", "passivate_ignored", "passivate_unknown", "alive")
+
+    def sharding_info(self) -> dict:
+        """agx_sharding_info: totals started / restarted / passivations / passivated / passivate_ignored /
+        passivate_unknown, and the entities alive now."""
+        v = [ctypes.c_uint64() for _ in range(7)]
+        check(self.lib.agx_sharding_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(self.SHARDING_INFO, (int(x.value) for x in v)))
+
+    def read_entities(self, first: int = 0, count: int | None = None) -> dict:
+        """agx_read_entities: alive, incarnations and passivating of the ids [first, first + count)."""
+        count = self.cfg.n_actors - first if count is None else count
+        a = [np.zeros(count, np.uint32) for _ in range(3)]
+        check(self.lib.agx_read_entities(self._h, first, count, *(_ptr(x, ctypes.c_uint32) for x in a)))
+        return dict(zip(("alive", "incarnations", "passivating"), a))
+
     def set_ask(self) -> None:
         """The ask pattern for every actor (agx_set_ask): context.ask -- request-response with a timeout
         (TY/internal/ActorContextImpl.scala:203-218, TY/scaladsl/AskPattern.scala:109-162) on top of

@@ -56,6 +56,11 @@ What lowers:
     §2.12): ``A_ROUTE`` with ``ROUTE_HASHED`` / ``ROUTE_RANDOM``; ``Tables.uses_router_logics`` ->
     engine.set_router_logics(tables.hashed_keys_mask, tables.virtual_nodes_factor, seed), after
     engine.set_receptionist; not together with topics or listings;
+  * ``EntityTypeKey(name)``, ``Entity(key, behavior, first_id, count, word0=.., word1=.. | Entity.ID)
+    .with_stop_message(msg).with_receive_timeout(delay, msg)`` and ``context.passivate()`` (sharded entities on the
+    receive-timeout engine): ``compile_behaviors(..., entities=[...])`` lowers the entities'
+    behaviours with the roots, ``Tables.entity_types`` goes to engine.set_sharding after engine.set_receive_timeout,
+    refs to entities are ordinary ids, and a case holds at most one of tell and passivate;
   * a handler returns a list of effects -- ``field.set/add/inc/max/min(v)``, ``ref.tell(v)`` --
     followed by the next behaviour; ``test=`` (a message predicate, like ReceiveBuilder's
     ``JPredicate``) and ``when=`` (a state guard: the lowering of an ``if`` inside a handler into
@@ -118,6 +123,8 @@ A_SUBSCRIBE_LISTING, A_FIND = 23, 24               # context.receptionist_subscr
 ASK_REF_BIT, ASK_REF_KEY_SHIFT, ASK_REF_GEN_SHIFT, ASK_REF_GEN_MASK, ASK_REF_ID_MASK = 1 << 31, 29, 22, 0x7F, (1 << 22) - 1
 ASK_MAX_ACTORS = (1 << 22) - 1
 MAX_SERVICE_KEYS = 8
+A_PASSIVATE = 25                                   # context.passivate: shard ! Passivate(self)
+MAX_ENTITY_TYPES = 8
 
 
 class AgxCase(ctypes.Structure):
@@ -312,6 +319,62 @@ class ServiceKey:
     """ServiceKey[T](id) (TY/receptionist/Receptionist.scala): names a service; keys with the same name are the
     same key.  The lowering numbers the keys in use, at most MAX_SERVICE_KEYS, in order of first appearance."""
     name: str
+
+
+@dataclass(frozen=True)
+class EntityTypeKey:
+    """EntityTypeKey[T](name) (akka-cluster-sharding-typed EntityTypeKey): names an entity type."""
+    name: str
+
+
+class _EntityId:
+    def __repr__(self):
+        return "Entity.ID"
+
+
+class Entity:
+    """Entity(typeKey)(createBehavior) (akka-cluster-sharding-typed Entity): the ids [first_id, first_id + count) are
+    the type's entities.  They are not registered: an entity starts in `behavior` on its first message with state word
+    0 = `word0` and word 1 = `word1` (a constant, or Entity.ID: the entity's id).  ``with_stop_message(msg)`` is the
+    message context.passivate() makes the shard send (required); ``with_receive_timeout(delay, msg)`` sets the
+    receive timeout of every start."""
+    ID = _EntityId()
+
+    def __init__(self, key, behavior, first_id: int, count: int, word0: int = 0, word1=0):
+        if not isinstance(key, EntityTypeKey):
+            raise CompileError(f"Entity takes an EntityTypeKey, not {key!r}")
+        if not isinstance(behavior, Behavior):
+            raise CompileError(f"Entity takes a Behavior, not {behavior!r}")
+        if not isinstance(first_id, (int, np.integer)) or not isinstance(count, (int, np.integer)) or first_id < 0 or count < 1:
+            raise CompileError(f"an entity range is [first_id, first_id + count) with count >= 1, not ({first_id!r}, {count!r})")
+        if not isinstance(word0, (int, np.integer)) or not 0 <= int(word0) < (1 << 64):
+            raise CompileError(f"an entity's word 0 is a u64 constant, not {word0!r}")
+        if word1 is not self.ID and (not isinstance(word1, (int, np.integer)) or not 0 <= int(word1) < (1 << 64)):
+            raise CompileError(f"an entity's word 1 is a u64 constant or Entity.ID, not {word1!r}")
+        self.key, self.behavior, self.first_id, self.count = key, behavior, int(first_id), int(count)
+        self.word0, self.word1 = int(word0), None if word1 is self.ID else int(word1)
+        self.stop_payload = None
+        self.idle = (0, 0)
+
+    @staticmethod
+    def _payload(msg, what) -> int:
+        if isinstance(msg, Message):
+            if msg.arg.src != V_CONST:
+                raise CompileError(f"{what} is a constant message")
+            return ((msg.arg.k & 0xFFFFFF) | msg.or_mask) & 0xFFFFFFFF
+        if isinstance(msg, (int, np.integer)):
+            return int(msg) & 0xFFFFFFFF
+        raise CompileError(f"{what} is a MessageType application or a u32 payload, not {msg!r}")
+
+    def with_stop_message(self, msg) -> "Entity":
+        self.stop_payload = self._payload(msg, "an entity's stop message")
+        return self
+
+    def with_receive_timeout(self, delay: int, msg) -> "Entity":
+        if not isinstance(delay, (int, np.integer)) or not 1 <= int(delay) <= MAX_TIMER_DELAY:
+            raise CompileError(f"an entity's receive timeout is 1..{MAX_TIMER_DELAY} ticks, not {delay!r}")
+        self.idle = (int(delay), self._payload(msg, "an entity's receive-timeout message"))
+        return self
 
 
 @dataclass(frozen=True)
@@ -577,6 +640,13 @@ class ActorContext:
     def cancel_receive_timeout(self) -> "Action":
         """context.cancelReceiveTimeout(): an envelope already enqueued stays in the mailbox and is discarded."""
         return Action(A_CANCEL_RECEIVE_TIMEOUT, 0)
+
+    # sharded entities (engine.set_sharding on top of engine.set_receive_timeout; akka-cluster-sharding Shard.scala:405-417)
+    def passivate(self) -> "Action":
+        """context.parent ! Passivate(stopMessage): the shard marks the entity as passivating and sends it its type's
+        stop message; what arrives behind that message is buffered and starts the entity again.  It is the case's one
+        envelope.  Run by an actor that is no entity it does nothing (counted)."""
+        return Action(A_PASSIVATE, 0)
 
     # the ask pattern (engine.set_ask on top of engine.set_timers; TY/internal/ActorContextImpl.scala:203-218,
     # TY/scaladsl/AskPattern.scala:109-162; DESIGN.md §2.9)
@@ -1120,6 +1190,8 @@ class Tables:
     listing_types: dict = field(default_factory=dict)  # key number -> the MessageType of its Listing -> engine.set_listings
     hashed_keys: list = field(default_factory=list)  # the key numbers routed through by consistent hashing -> engine.set_router_logics
     virtual_nodes_factor: int = 0  # the hashed routers' virtualNodesFactor (0: none named one) -> engine.set_router_logics
+    # (first_id, count, kind, word 0, word 1 or None: the entity's id, stop payload, idle delay, idle payload) -> engine.set_sharding
+    entity_types: list = field(default_factory=list)
 
     @property
     def uses_supervision(self) -> bool:
@@ -1207,6 +1279,12 @@ class Tables:
         return any(a.op in (A_SET_RECEIVE_TIMEOUT, A_CANCEL_RECEIVE_TIMEOUT) for a in self.acts[:self.n_acts])
 
     @property
+    def uses_sharding(self) -> bool:
+        """The behaviours passivate or entity types are declared: the engine needs engine.set_sharding(
+        tables.entity_types) on top of engine.set_receive_timeout."""
+        return bool(self.entity_types) or any(a.op == A_PASSIVATE for a in self.acts[:self.n_acts])
+
+    @property
     def uses_watch(self) -> bool:
         """The behaviours watch, unwatch or hold a signal case: the engine needs engine.set_death_watch(n)."""
         return any(c.signal and not c.sig_code for b in self.behaviors for c in b.cases) or \
@@ -1250,11 +1328,26 @@ def _reachable(roots) -> list:
     return order
 
 
-def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tables:
+def compile_behaviors(roots, max_emit: int | None = None, transparent=(), entities=()) -> Tables:
     """Lower `roots` and every behaviour they become into the engine's tables.  With `max_emit`
     (the engine's agx_cfg.max_emit), a case that tells more often than that is a CompileError:
     the apply kernels reserve max_emit tell slots per message.  `transparent`: the MessageTypes that are
-    NotInfluenceReceiveTimeout for behaviours with a receive timeout (Tables.transparent_tags)."""
+    NotInfluenceReceiveTimeout for behaviours with a receive timeout (Tables.transparent_tags).  `entities`: the
+    Entity declarations of an engine with sharding (Tables.entity_types); their behaviours are lowered too."""
+    entities = list(entities)
+    for en in entities:
+        if not isinstance(en, Entity):
+            raise CompileError(f"entities= takes Entity declarations, not {en!r}")
+        if en.stop_payload is None:
+            raise CompileError(f"entity type {en.key.name!r} has no stop message (with_stop_message): context.passivate() "
+                               "has nothing to send")
+    if len(entities) > MAX_ENTITY_TYPES:
+        raise CompileError(f"more than {MAX_ENTITY_TYPES} entity types")
+    for i, en in enumerate(entities):
+        for o in entities[:i]:
+            if en.first_id < o.first_id + o.count and o.first_id < en.first_id + en.count:
+                raise CompileError(f"the ranges of entity types {o.key.name!r} and {en.key.name!r} overlap")
+    roots = list(roots) + [en.behavior for en in entities if not any(en.behavior is r for r in roots)]
     for mt in transparent:
         if not isinstance(mt, MessageType):
             raise CompileError(f"transparent= takes MessageTypes, not {mt!r}")
@@ -1361,6 +1454,8 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
     t.listing_types = ltypes
     t.hashed_keys = sorted(hkeys)
     t.virtual_nodes_factor = vnfs[0] if vnfs else 0
+    t.entity_types = [(en.first_id, en.count, KIND_COMPILED + index[id(en.behavior)], en.word0, en.word1, en.stop_payload,
+                       en.idle[0], en.idle[1]) for en in entities]
     for b in behs:  # a supervisor of a class catches it and its descendants: the hierarchy as masks
         row = []
         for sv in b.supervisors:
@@ -1422,6 +1517,24 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=()) -> Tab
         if named:
             raise CompileError("message tag 0xFB is reserved for the receive-timeout envelope in behaviours that use a "
                                "receive timeout")
+    if t.uses_sharding:  # on the receive-timeout engine: max_emit 1, a Passivate is the case's one envelope
+        for c in cases:
+            ops = [acts[j].op for j in range(c.act_first, c.act_first + c.act_count)]
+            n = sum(1 for o in ops if o in (A_TELL, A_PASSIVATE, A_SPAWN, A_ASK_SEND))
+            if A_PASSIVATE in ops and n > 1:
+                raise CompileError(f"a case holds {n} of tell, spawn, ask and passivate: a Passivate sends the entity's stop "
+                                   "message through the case's one envelope, and an engine with sharding has max_emit 1")
+        if t.stash_capacity or t.uses_watch or t.uses_children or t.uses_supervision or t.uses_ask or t.uses_receptionist or \
+                any(V_STASH in (a.src, a.dsrc) for a in acts) or any(V_STASH in (c.src1, c.src2, c.src3, c.src4) for c in cases):
+            raise CompileError("sharding lives on the receive-timeout engine, which shares an engine with neither a stash, "
+                               "death watch, children, supervision, ask nor the receptionist: the behaviours use sharding "
+                               "and one of them")
+        if max_emit is not None and max_emit > 1:
+            raise CompileError(f"sharding needs max_emit = 1, not {max_emit}")
+        for en in entities:
+            for pay, what in ((en.stop_payload, "stop"), (en.idle[1] if en.idle[0] else 0, "receive-timeout")):
+                if pay >> 24 in (TAG_TIMER, TAG_RECEIVE_TIMEOUT):
+                    raise CompileError(f"entity type {en.key.name!r}: its {what} message carries a reserved tag (0xFF, 0xFB)")
     if t.timer_keys or t.uses_receive_timeout:  # tag 0xFF is the TimerMsg's: no message type of these behaviours may carry it
         for a in acts:
             if a.or_mask >> 24 == TAG_TIMER:

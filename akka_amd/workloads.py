@@ -53,7 +53,8 @@ class Workload:
     # delays or None, payload)], "receive_timeout": {"transparent": message tags, "starts": [(first, count, delay,
     # payload)]}} -- empty: no timers; without "receive_timeout": no receive timeouts (agx_set_receive_timeout /
     # agx_start_receive_timeout, on top of the timers: behaviours that use only a receive timeout pass n_keys 1);
-    # "ask": True -- the ask pattern (agx_set_ask, on top of the timers; not together with "receive_timeout")
+    # "ask": True -- the ask pattern (agx_set_ask, on top of the timers; not together with "receive_timeout");
+    # "receive_timeout" may hold "sharding": the entity types (agx_set_sharding, typed.Tables.entity_types)
     timers: dict = field(default_factory=dict)
     # death watch (agx_set_death_watch / agx_start_watch): {"n_slots": k, "starts": [(first, count, watchees or
     # None, offset, message or None)]} -- empty: no death watch
@@ -134,6 +135,8 @@ class Workload:
                 target.set_receive_timeout(rt.get("transparent", ()))
                 for first, count, delay, payload in rt.get("starts", ()):
                     target.start_receive_timeout(first, count, delay, payload)
+                if rt.get("sharding"):  # (sharded entities, on top of the receive timeouts: agx_set_sharding)
+                    target.set_sharding(rt["sharding"])
         if self.watch:  # (empty: targets without the calls are unaffected)
             target.set_death_watch(self.watch["n_slots"])
             if self.children:  # (before the setup watches: a child block's ids are "not created yet", not "dead")
@@ -833,6 +836,95 @@ def passivating_entities(n: int = 1 << 20, n_shards: int = 4096, idle: int = 8, 
                     [(0, n, tb.kind_of(entity), init), (n, n_shards, tb.kind_of(shard), None)], behaviors=tb,
                     bucket_actors=bucket_actors, schedule=schedule,
                     timers={"n_keys": max(tb.timer_keys, 1), "receive_timeout": rt})
+
+
+# ------------------------------------------------------------------ sharded entities: start on demand, Passivate, restart
+SE_JOB, SE_IDLE, SE_BYE, SE_PASSIVATE, SE_STOP = 1, 2, 3, 4, 5
+
+
+def sharded_entity():
+    """An entity of a shard (akka-cluster-sharding Shard.scala:388-516) and a plain actor beside it: the entity counts
+    the jobs of its incarnation (state word 0; word 1 is its id); Idle -- its receive timeout -- and a host's
+    Passivate make it context.passivate(); Bye is its stop message; Stop is a crash-like plain stop."""
+    from . import typed
+    B = typed.Behaviors
+    job, idle, bye, passivate, stop = (typed.MessageType(n, t) for n, t in
+                                       (("Job", SE_JOB), ("Idle", SE_IDLE), ("Bye", SE_BYE), ("Passivate", SE_PASSIVATE),
+                                        ("Stop", SE_STOP)))
+    es = typed.State("jobs", "id")
+    entity = (typed.ReceiveBuilder.create(es)
+              .on_message(job, lambda m, s: [s.jobs.inc(), B.same])
+              .on_message(idle, lambda m, s: [typed.context.passivate(), B.same])
+              .on_message(passivate, lambda m, s: [typed.context.passivate(), B.same])
+              .on_message(bye, lambda m, s: [B.stopped])
+              .on_message(stop, lambda m, s: [B.stopped])
+              .on_any_message(lambda m, s: [B.unhandled])
+              .build("sharded_entity"))
+    ps = typed.State("jobs", "unused")
+    plain = (typed.ReceiveBuilder.create(ps)
+             .on_message(job, lambda m, s: [s.jobs.inc(), B.same])
+             .on_any_message(lambda m, s: [B.unhandled])
+             .build("plain"))
+    return entity, plain, bye, idle
+
+
+def _sharded(name, n, n_plain, idle, throughput, bucket_actors, schedule, capacity=0) -> Workload:
+    from . import typed
+    entity, plain, bye, idle_msg = sharded_entity()
+    ent = typed.Entity(typed.EntityTypeKey("job-counter"), entity, n_plain, n, word1=typed.Entity.ID).with_stop_message(bye())
+    if idle:
+        ent = ent.with_receive_timeout(idle, idle_msg())
+    tb = typed.compile_behaviors([plain], max_emit=1, entities=[ent])
+    rt = {"transparent": (), "starts": [], "sharding": tb.entity_types}
+    return Workload(name, n_plain + n, 2, 1, throughput, capacity, [(0, n_plain, tb.kind_of(plain), None)] if n_plain else [],
+                    behaviors=tb, bucket_actors=bucket_actors, schedule=schedule,
+                    timers={"n_keys": max(tb.timer_keys, 1), "receive_timeout": rt})
+
+
+def sharded_entities(n: int = 1 << 20, idle: int = 4, ticks: int = 64, seed: int = 1, throughput: int = 16,
+                     bucket_actors: int = 256, n_plain: int = 8, p_passivate: float = 0.01, p_stop: float = 0.005) -> Workload:
+    """`n` entities (ids n_plain .. n_plain + n - 1, none registered) beside `n_plain` registered plain actors.  Entity
+    i gets a job every period_i ticks for `ticks` ticks (Workload.schedule, run_schedule), period_i drawn from 1, 2,
+    idle, idle + 1, idle + 2 and 2 * idle + 3: the first two keep an entity busy, the last lets it passivate between
+    two jobs, the ones between land in the ticks of the Idle, of the stop message and right after it.  An entity
+    starts on its first job with the receive timeout `idle`; idle it receives Idle, passivates, stops on Bye, and its
+    next job starts it again: state word 0 counts the jobs of the current incarnation.  With probability
+    `p_passivate` / `p_stop` per entity and tick the host also sends Passivate (ignored while one is under way) or
+    Stop (a plain stop: the mail queued behind it is dead letters).  The run goes quiescent once every entity has
+    passivated after the last tick."""
+    rng = np.random.default_rng(seed)
+    periods = np.asarray([1, 2, idle, idle + 1, idle + 2, 2 * idle + 3], np.int64)
+    per = periods[rng.integers(0, len(periods), n)]
+    phase = rng.integers(0, 1 << 30, n) % per
+    ids = (np.arange(n, dtype=np.uint32) + np.uint32(n_plain))
+    schedule = []
+    for t in range(ticks):
+        ctl = rng.random(n)
+        pas, stp = ids[ctl < p_passivate], ids[(ctl >= p_passivate) & (ctl < p_passivate + p_stop)]
+        job = ids[(t % per) == phase]
+        dst = np.concatenate([pas, stp, job, np.arange(n_plain, dtype=np.uint32)[: 1 if n_plain else 0]])
+        pay = np.concatenate([np.full(pas.size, SE_PASSIVATE << 24, np.uint32), np.full(stp.size, SE_STOP << 24, np.uint32),
+                              np.full(dst.size - pas.size - stp.size, SE_JOB << 24, np.uint32)])
+        schedule.append((dst, np.full(dst.size, NO_SENDER, np.uint32), pay))
+    return _sharded("sharded_entities", n, n_plain, idle, throughput, bucket_actors, schedule)
+
+
+def passivation_race(n: int = 1 << 16, idle: int = 2, throughput: int = 16, bucket_actors: int = 256, n_plain: int = 8,
+                     capacity: int = 0) -> Workload:
+    """Jobs timed against the stop message.  Every entity starts on a job at tick 1, receives Idle at tick 1 + idle and
+    passivates; its stop message arrives at tick S = 2 + idle.  By i mod 4 the host sends entity i a job for tick S
+    (behind the stop message: buffered, the entity restarts), for tick S + 1 (the entity is gone: a fresh start), for
+    both, or three jobs for tick S - 1, ahead of the Idle envelope -- at throughput 1 the envelope, and later the stop
+    message, then wait behind them.  Run at throughput 1 and 16."""
+    ids = (np.arange(n, dtype=np.uint32) + np.uint32(n_plain))
+    c = np.arange(n) % 4
+    S = 2 + idle
+    at = {1: [ids], S - 1: [ids[c == 3]] * 3, S: [ids[(c == 0) | (c == 2)]], S + 1: [ids[(c == 1) | (c == 2)]]}
+    schedule = []
+    for t in range(1, S + 2):
+        dst = np.concatenate(at.get(t, []) + [np.zeros(0, np.uint32)]).astype(np.uint32)
+        schedule.append((dst, np.full(dst.size, NO_SENDER, np.uint32), np.full(dst.size, SE_JOB << 24, np.uint32)))
+    return _sharded("passivation_race", n, n_plain, idle, throughput, bucket_actors, schedule, capacity)
 
 
 # ------------------------------------------------------------------ the ask pattern: clients that bound their wait

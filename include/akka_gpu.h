@@ -218,7 +218,12 @@ enum agx_action_op {
    * key, pad0 must be 0; an actor subscribes or asks for itself only.  Neither is an envelope of the case: a case may
    * hold them beside its one TELL, ROUTE or PUBLISH. */
   AGX_A_SUBSCRIBE_LISTING = 23, /* receptionist ! Subscribe(key, self) (LocalReceptionist.scala:213-220) */
-  AGX_A_FIND = 24               /* receptionist ! Find(key, self)      (LocalReceptionist.scala:209-211) */
+  AGX_A_FIND = 24,              /* receptionist ! Find(key, self)      (LocalReceptionist.scala:209-211) */
+  /* Sharded entities (engines with sharding, agx_set_sharding).  PASSIVATE is shard !
+   * Passivate(context.self): the entity is marked passivating and its type's stop message goes to the entity itself
+   * through the case's tell slot (sender = the entity); no operand is read.  A case holds at most one of TELL and
+   * PASSIVATE. */
+  AGX_A_PASSIVATE = 25          /* context.passivate(): shard ! Passivate(self) (Shard.scala:405-417) */
 };
 /* The ask ref: AGX_ASK_REF_BIT | key << 29 | (generation mod 2^7) << 22 | the asker's id. */
 #define AGX_ASK_REF_BIT 0x80000000u
@@ -239,6 +244,8 @@ enum agx_action_op {
 #define AGX_TAG_CREATE 0xFDu    /* the message tag of a Create envelope: reserved on an engine with children */
 #define AGX_TAG_STOP 0xFCu      /* the message tag of a Stop envelope: reserved on an engine with children */
 #define AGX_MAX_CHILD_REGIONS 8u
+#define AGX_MAX_ENTITY_TYPES 8u
+#define AGX_ENTITY_WORD1_ID 1u  /* agx_entity_type.flags: state word 1 starts as the entity's id, not as `word1` */
 #define AGX_MAX_SPAWN_SITES 64u
 #define AGX_SPAWN_ARG_BITS 18u  /* a Create's payload: AGX_TAG_CREATE << 24 | site << 18 | argument */
 #define AGX_SPAWN_ARG_MASK 0x3FFFFu
@@ -665,6 +672,56 @@ agx_status agx_receive_timeout_info(agx_engine* eng, uint64_t* fired, uint64_t* 
  * 0xFFFFFFFF when none is to come.  Any pointer may be NULL. */
 agx_status agx_read_receive_timeout(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t* delay, uint32_t* remaining,
                                     uint32_t* payload);
+
+/* Sharded entities (akka-cluster-sharding Shard.scala: getOrCreateEntity :504-516, passivate :405-417, deliverMessage /
+ * appendToMessageBuffer :469-496, entityTerminated / passivateCompleted / sendMsgBuffer :388-400, :437-466; DESIGN.md
+ * 2.13 has the contract).  On top of receive timeouts: call agx_set_timers and agx_set_receive_timeout first; time is
+ * the timers' logical time.  An entity type is a range of unregistered ids [first_id, first_id + count) in [0,
+ * n_actors), pairwise disjoint, with a compiled behaviour `kind`, the state a start gives (word 0 = base0, word 1 =
+ * `word1` or, with AGX_ENTITY_WORD1_ID, the entity's id; other words 0), the stop message payload, and the receive
+ * timeout (idle_delay ticks, idle_payload) a start sets -- idle_delay 0: none.
+ * Start: at the inbox formation of tick t a not-alive entity with at least one starting item -- an item whose sender
+ * is not the entity itself -- becomes alive before admission with its type's kind and state and, with an idle delay,
+ * the receive timeout set at tick t; `started` and the id's incarnation count grow; the tick's mail is admitted as for
+ * any live actor.  Items the entity sent itself (a self-tell, a TimerMsg, a receive-timeout envelope) never start it:
+ * to a stopped entity they are dead letters at that formation.
+ * A stop without Passivate is today's stop: timers and timeout off, the rest of the window and the queued mail are
+ * dead letters (the queued mail at the next formation); mail of a later tick starts a new incarnation.
+ * AGX_A_PASSIVATE run at tick s by an entity that is not passivating marks it, sends the type's stop payload to the
+ * entity itself (sender = the entity; `emitted`; it arrives with tick s + 1's arrivals) and counts `passivations`; run
+ * by a passivating entity nothing is sent (`passivate_ignored`), by an actor in no entity range the same
+ * (`passivate_unknown`).  A stop while passivating counts `passivated`: everything queued behind the stop -- the rest
+ * of the tick's admitted inbox, later arrivals -- stays queued and is no dead letter, except what the entity sent
+ * itself, which dies at the next formation.  If anything stays the entity starts again at the formation of the next
+ * tick (`restarted` as well as `started`) and receives that mail in order.  Any stop clears the mark.
+ * Bounded differences: an entity that handles its stop message without stopping goes on receiving; the buffer's bound
+ * is the entity's mailbox capacity with tail-drop; a stale receive-timeout envelope can reach a new incarnation.
+ * Conservation is that of receive timeouts.  A passivating entity with queued mail keeps the engine non-quiescent.
+ * AGX_EINVAL: without receive timeouts ("sharding needs an engine with receive timeouts"), on a second call, with the
+ * ask pattern, for n_types outside 1..AGX_MAX_ENTITY_TYPES, a type that is empty, leaves [0, n_actors), overlaps
+ * another, holds a registered id, names a kind that is no compiled behaviour kind, unknown flags, or a stop or idle
+ * payload with a reserved tag (0xFF, 0xFB); AGX_ESTATE after the first run; AGX_ENOMEM.  agx_register_range into an
+ * entity range is AGX_EINVAL in either call order.  Tables that hold AGX_A_PASSIVATE on an engine without sharding
+ * make agx_run return AGX_EINVAL; a case with PASSIVATE beside a TELL is refused by agx_set_behaviors. */
+typedef struct agx_entity_type {
+  uint32_t first_id, count;
+  uint32_t kind;          /* AGX_KIND_COMPILED + b */
+  uint32_t flags;         /* AGX_ENTITY_WORD1_ID or 0 */
+  uint64_t base0, word1;  /* state words 0 and 1 of a start */
+  uint32_t stop_payload;  /* the stop message AGX_A_PASSIVATE sends */
+  uint32_t idle_delay, idle_payload;  /* the receive timeout a start sets (idle_delay 0: none) */
+  uint32_t reserved;      /* 0 */
+} agx_entity_type;
+agx_status agx_set_sharding(agx_engine* eng, const agx_entity_type* types, uint32_t n_types);
+/* Totals since agx_create: started, restarted, passivations, passivated, passivate_ignored, passivate_unknown; right
+ * now: the entities alive.  Any pointer may be NULL. */
+agx_status agx_sharding_info(agx_engine* eng, uint64_t* started, uint64_t* restarted, uint64_t* passivations,
+                             uint64_t* passivated, uint64_t* passivate_ignored, uint64_t* passivate_unknown,
+                             uint64_t* alive);
+/* The ids [first_id, first_id + count) (for tests and tools): alive, the incarnation count, passivating.  Ids in no
+ * entity range read 0 incarnations.  Any pointer may be NULL. */
+agx_status agx_read_entities(agx_engine* eng, uint64_t first_id, uint64_t count, uint32_t* alive, uint32_t* incarnations,
+                             uint32_t* passivating);
 
 /* The ask pattern: request-response with a timeout (ActorContext.ask: TY/internal/ActorContextImpl.scala:203-218;
  * AskPattern.ask: TY/scaladsl/AskPattern.scala:109-162; pinned by ActorContextAskSpec.scala:41-189 and AskSpec.scala:
