@@ -110,6 +110,9 @@ SIGNATURES = {
     "agx_set_supervision": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
     "agx_supervision_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 5),
     "agx_read_supervision": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, c_u32p, c_u32p, c_u32p]),
+    "agx_set_backoff": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
+    "agx_backoff_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 5),
+    "agx_read_backoff": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, c_u32p, c_u32p]),
     "agx_set_children": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),
     "agx_spawn_children": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
     "agx_children_info": (ctypes.c_int32, [ctypes.c_void_p] + [c_u64p] * 8),
@@ -176,7 +179,7 @@ SIGNATURES = {
 # entry points newer than some A/B diagnostic builds (tools/build_variant.sh of an older checkout)
 OPTIONAL = {"agx_tell", "agx_pump_idle", "agx_pump_cancel", "agx_exchange_info", "agx_run_timed", "agx_build_hash",
             "agx_persist_info", "agx_set_router_logics", "agx_router_info", "agx_read_hash_ring", "agx_set_sharding",
-            "agx_sharding_info", "agx_read_entities"}
+            "agx_sharding_info", "agx_read_entities", "agx_set_backoff", "agx_backoff_info", "agx_read_backoff"}
 
 
 def load():

@@ -24,8 +24,8 @@ struct GroupLaunch {
   hipError_t (*ring)(uint32_t vid, bool tiny, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
   hipError_t (*persist_occupancy)(uint32_t vid, int*);
 };
-#define AGX_GROUPS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
-static_assert(kVGroups == 8, "AGX_GROUPS names every group");
+#define AGX_GROUPS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+static_assert(kVGroups == 9, "AGX_GROUPS names every group");
 #define AGX_GROUP_DECL(g) const GroupLaunch& agx_group_##g();
 AGX_GROUPS(AGX_GROUP_DECL)
 
@@ -103,6 +103,10 @@ hipError_t feature_dispatch(uint32_t vid, uint32_t mode, uint32_t km_flags, bool
       }
     }
   }
+  // restartWithBackoff: a unit of its own (kBackoffGroup), so that V_ALL_COMPILED's unit compiles what it compiled before
+  if constexpr (G == kBackoffGroup)
+    if (vid == V_ALL_COMPILED && !prio && km_flags == (kSuperKM | kBackoffKM))
+      return launch_feature<V_ALL_COMPILED, kSuperKM | kBackoffKM, false>(mode, g, s, ba);
   return hipErrorInvalidValue;
 }
 
@@ -197,6 +201,7 @@ hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 g, hipS
 hipError_t agx_launch_apply_feature(uint32_t vid, uint32_t mode, uint32_t km_flags, bool prio, dim3 g, hipStream_t s,
                                     const BucketArgs& ba) {
   if (vid >= V_N) return hipErrorInvalidValue;
+  if (km_flags == (kSuperKM | kBackoffKM)) return kGroups[kBackoffGroup]().feature(vid, mode, km_flags, prio, g, s, ba);
   return group_of(vid).feature(vid, mode, km_flags, prio, g, s, ba);
 }
 

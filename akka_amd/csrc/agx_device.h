@@ -800,6 +800,9 @@ constexpr uint32_t kHashKM = 1u << 20;
 // KM flag (not a kind): the variant knows sharded entities (agx_set_sharding); only ever combined as
 // kTimersKM | kIdleKM | kShardKM.
 constexpr uint32_t kShardKM = 1u << 19;
+// KM flag (not a kind): the variant knows restartWithBackoff (agx_set_backoff); only ever combined as
+// kSuperKM | kBackoffKM.
+constexpr uint32_t kBackoffKM = 1u << 18;
 constexpr uint32_t KM_ALL = kb(AGX_KIND_COUNTER) | kb(AGX_KIND_RING) | kb(AGX_KIND_FANOUT) | kb(AGX_KIND_FORWARD_RR) |
                             kb(AGX_KIND_STOP_AFTER) | kb(AGX_KIND_PINGPONG) | kb(AGX_KIND_EVEN);
 
@@ -1278,6 +1281,128 @@ __device__ __noinline__ uint32_t sv_failed(const DevParams& P, uint32_t nb, uint
         if (E[lev].reset_mask & 2u) w[1] = E[lev].reset[1];
         atomicAdd(SV.ctr(kScRestarts), 1ull);
         return AGX_RES_SAME;
+      }
+    }
+  }
+  if (kind >= AGX_KIND_COMPILED) compiled_apply_s(P, kind, self, w, self, AGX_SIGNAL_POSTSTOP, true, none, emit);
+  atomicAdd(SV.ctr(kScStops), 1ull);
+  return AGX_RES_STOPPED;
+}
+
+// ---- restartWithBackoff (agx_set_backoff; TY/internal/Supervision.scala:163-406), on top of
+// supervision.  An allocation of its own, reached from words kSvBackoff, kSvBackoff + 1 of the SuperDev header
+// (its address), u32 units:
+//   [0]      n_levels (agx_set_supervision's)
+//   [4..9]   three u64 counters: backoffs, dropped, limit_stops
+//   [kBoBucketOff + b]  bound: the largest `until` any actor of bucket b was given (atomicMax at the failure): a
+//            bucket whose bound is at or before the tick holds no suspended actor
+//   then, 16-byte aligned: the rows, AGX_MAX_SUPERVISORS per behaviour, kBoRowWords words each (agx_backoff first),
+//   then until[np] (the first tick at which the actor drains again; 0: never suspended), cap[np] (the stash bound of
+//   its suspension, kBoNoBound: none of its own) and cut[np] (kBoCut | the index of the first message held, written
+//   by the drain at the failure and cleared by bo_requeue in the same tick).
+// A backoff entry keeps its reset-due in the entry's deadline word (SuperDev), which it does not use otherwise.
+// Only an actor's own lane writes its words, and only on the cold path.
+constexpr uint32_t kSvBackoff = 12;
+constexpr uint32_t kBoCtr = 4, kBoBucketOff = 16, kBoRowWords = 8;
+constexpr uint32_t kBcBackoffs = 0, kBcDropped = 1, kBcLimitStops = 2;
+constexpr uint32_t kBoCut = 0x80000000u, kBoNoBound = 0xFFFFFFFFu;
+constexpr uint32_t kBoSuspended = 0x100u;  // bo_failed's third answer: restarted, and suspended from the next message on
+constexpr uint32_t kBoAlive = 0x80u;       // LDS alive byte, bit 7: the actor is suspended in this tick (bo_classify)
+__host__ __device__ __forceinline__ size_t bo_row_off(uint32_t nb) {
+  return ((size_t)kBoBucketOff + (size_t)nb + 3u) & ~(size_t)3;
+}
+__host__ __device__ __forceinline__ size_t bo_until_off(uint32_t nb) {
+  return bo_row_off(nb) + (size_t)AGX_MAX_BEHAVIORS * AGX_MAX_SUPERVISORS * kBoRowWords;
+}
+struct BackoffDev {
+  uint32_t* base;
+  uint32_t nb, np;
+  __device__ __forceinline__ uint32_t* bound(uint32_t b) const { return base + kBoBucketOff + b; }
+  __device__ __forceinline__ unsigned long long* ctr(uint32_t i) const {
+    return reinterpret_cast<unsigned long long*>(base + kBoCtr) + i;
+  }
+  __device__ __forceinline__ const agx_backoff* row(uint32_t beh, uint32_t lev) const {
+    return reinterpret_cast<const agx_backoff*>(base + bo_row_off(nb) + ((size_t)beh * AGX_MAX_SUPERVISORS + lev) * kBoRowWords);
+  }
+  __device__ __forceinline__ uint32_t* until(uint32_t l) const { return base + bo_until_off(nb) + l; }
+  __device__ __forceinline__ uint32_t* cap(uint32_t l) const { return until(l) + np; }
+  __device__ __forceinline__ uint32_t* cut(uint32_t l) const { return until(l) + 2u * (size_t)np; }
+};
+__device__ __forceinline__ BackoffDev backoff_dev(const uint32_t* super, uint32_t nb, uint32_t bb) {
+  const uint64_t p = (uint64_t)super[kSvBackoff] | ((uint64_t)super[kSvBackoff + 1u] << 32);
+  return BackoffDev{reinterpret_cast<uint32_t*>(p), nb, nb << bb};
+}
+
+// sv_failed of the backoff instantiations: the same catch clause, with the entries that carry a backoff row (rules
+// 1-5 of §2.14).  Returns AGX_RES_SAME, AGX_RES_STOPPED or kBoSuspended (restarted: `kind` and `w` are the re-created
+// behaviour and state; the drain's window ends at this message and `until`, the stash bound and the bucket's bound
+// are written).  A function of its own: the supervision instantiations compile sv_failed as before.  Not inlined.
+template <typename Emit>
+__device__ __noinline__ uint32_t bo_failed(const DevParams& P, uint32_t nb, uint32_t bb, uint32_t l, uint32_t b,
+                                           uint32_t& kind, uint32_t self, uint64_t* w, uint32_t res, uint32_t cls,
+                                           Emit& emit) {
+  const SuperDev SV = super_dev(P.super, nb, bb);
+  const BackoffDev BD = backoff_dev(P.super, nb, bb);
+  uint32_t none = 0;
+  if (res == AGX_RES_FAIL) {
+    atomicAdd(SV.ctr(kScFailures), 1ull);
+    const uint32_t ik = SV.init_kind(l), ib = ik - AGX_KIND_COMPILED, nl = SV.base[kSvLevels];
+    if (ik >= AGX_KIND_COMPILED && ib < SV.base[kSvBeh]) {
+      const agx_supervisor* const E = SV.entries(ib);
+      const uint32_t t = SV.tick(b);
+      for (uint32_t lev = 0; lev < nl; ++lev) {  // inner first
+        if (!((E[lev].class_mask >> (cls & 31u)) & 1u)) continue;
+        const uint32_t strat = E[lev].strategy;
+        if (strat == AGX_SUP_RESUME) {
+          atomicAdd(SV.ctr(kScResumes), 1ull);
+          return AGX_RES_SAME;
+        }
+        if (strat != AGX_SUP_RESTART) break;  // STOP
+        const agx_backoff R = *BD.row(ib, lev);
+        uint32_t c = *SV.count(lev, l), d = *SV.deadline(lev, l);
+        const int32_t mx = E[lev].max_restarts;
+        if (R.min_backoff == 0u) {  // a plain restart: sv_failed's rule
+          const bool left = d == 0u || t <= d;
+          if (mx != -1 && c >= (uint32_t)mx && left) continue;  // rethrown: the next outer entry that catches it
+          if (kind >= AGX_KIND_COMPILED) compiled_apply_s(P, kind, self, w, self, AGX_SIGNAL_PRERESTART, true, none, emit);
+          *SV.count(lev, l) = left ? c + 1u : 1u;
+          *SV.deadline(lev, l) = (d != 0u && left) ? d : t + E[lev].within;
+        } else {
+          if (d != 0u && t >= d) {  // ResetRestartCount(current), lazily: the reset-due has passed
+            c = d = 0u;
+            *SV.count(lev, l) = 0u;
+            *SV.deadline(lev, l) = 0u;
+          }
+          if (mx != -1 && c >= (uint32_t)mx) {  // BehaviorImpl.failed (:314-320): not rethrown
+            atomicAdd(BD.ctr(kBcLimitStops), 1ull);
+            break;
+          }
+          if (kind >= AGX_KIND_COMPILED) compiled_apply_s(P, kind, self, w, self, AGX_SIGNAL_PRERESTART, true, none, emit);
+          *SV.count(lev, l) = c + 1u;
+          // calculateDelay (:163-173) in 64-bit integers: delay < 2^31, the factors < 2^17 and 2^16
+          uint64_t delay = (uint64_t)R.min_backoff << (c >= 30u ? 0u : c);
+          if (c >= 30u || delay > (uint64_t)R.max_backoff) delay = R.max_backoff;
+          const uint64_t r16 = fanout_rand(P.fan_seed, self, t, 0u) >> 48;
+          delay += (delay * (uint64_t)R.random_factor_q16 * r16) >> 32;
+          const uint64_t until = (uint64_t)t + delay > 0xFFFFFFFFull ? 0xFFFFFFFFull : (uint64_t)t + delay;
+          const uint64_t due = until + (uint64_t)R.reset_after > 0xFFFFFFFFull ? 0xFFFFFFFFull : until + (uint64_t)R.reset_after;
+          *BD.until(l) = (uint32_t)until;
+          *SV.deadline(lev, l) = (uint32_t)due;
+          uint32_t C, T;
+          mbox_limits(P, P.alive[l], C, T);
+          *BD.cap(l) = R.stash_capacity >= 0 ? (uint32_t)R.stash_capacity : (C ? C : kBoNoBound);
+          atomicMax(BD.bound(b), (uint32_t)until);
+          atomicAdd(BD.ctr(kBcBackoffs), 1ull);
+        }
+        for (uint32_t in = 0; in < lev; ++in) {  // a restart re-creates the inner interceptors
+          *SV.count(in, l) = 0u;
+          *SV.deadline(in, l) = 0u;
+        }
+        kind = ik;
+        if (E[lev].reset_mask & 1u) w[0] = E[lev].reset[0];
+        if (E[lev].reset_mask & 2u) w[1] = E[lev].reset[1];
+        atomicAdd(SV.ctr(kScRestarts), 1ull);
+        return R.min_backoff == 0u ? AGX_RES_SAME : kBoSuspended;
       }
     }
   }

@@ -215,6 +215,11 @@ struct agx_engine {
   uint32_t beh_sv_tells = 0;           // the most tells a failing or stopping case and a supervision signal case of one behaviour make together
   uint64_t sv_ticks = 0;               // supersteps with mail so far (= agx_stats.supersteps)
   uint32_t sv_clock = 0;               // the device clock after the last run (every bucket's launch count)
+  // restartWithBackoff (agx_set_backoff), on top of supervision: such an engine launches the backoff instantiation
+  uint32_t* d_backoff = nullptr;       // agx_device.h BackoffDev (its address stands in d_super's header)
+  std::vector<agx_backoff> bo_tab;     // [behaviour][AGX_MAX_SUPERVISORS]
+  std::vector<agx_supervisor> bo_sv;   // the supervision table the rows were checked against (sv_tab then)
+  uint32_t bo_levels = 0, bo_beh = 0;
   // the receptionist (agx_set_receptionist): service keys, per-actor key masks, listings.  Such an engine launches
   // the receptionist instantiation of the compiled catch-all variant, then the rebuild kernels, every superstep
   uint32_t* d_recep = nullptr;   // DevParams.recep (agx_device.h RecepDev)
@@ -478,7 +483,7 @@ namespace {
 // of a catch-all k_bucket_apply (agx_launch_apply_feature) and no wave / ring / dense / persistent launch.  What is
 // the same for every feature reads this table: the setters' common refusals (refuse_feature), enable_crdt's,
 // apply_variant, launch_apply and make_params.
-enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_SHARD, F_IDLE, F_RECEP, F_ASK, F_LIST, F_TOPIC, F_HASH, F_N, F_NONE = F_N };
+enum Feature : uint32_t { F_PRIO, F_STASH, F_TIMERS, F_WATCH, F_SUPER, F_CHILD, F_SHARD, F_IDLE, F_RECEP, F_ASK, F_LIST, F_TOPIC, F_HASH, F_BACKOFF, F_N, F_NONE = F_N };
 
 struct FeatureRow {
   bool (*on)(const agx_engine*);
@@ -546,6 +551,10 @@ const FeatureRow kFeatures[F_N] = {
     // topics exclude one another
     {[](const agx_engine* e) { return e->d_hash != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
      nullptr, kRecepKM | kHashKM, false, F_RECEP},
+    // restartWithBackoff (agx_set_backoff) comes on top of supervision, the only row there: launched_feature selects
+    // the backoff instantiation for such an engine, and an engine that never calls agx_set_backoff launches what it did
+    {[](const agx_engine* e) { return e->d_backoff != nullptr; }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+     nullptr, kSuperKM | kBackoffKM, false, F_SUPER},
 };
 #undef AGX_ONCE
 
@@ -2211,6 +2220,15 @@ size_t super_words(const agx_engine* e) {
 // The supervision storage (agx_device.h SuperDev) -- sized by n_local: everything zero (no restart counted, no
 // deadline), then the levels and the entries
 agx_status alloc_super(agx_engine* e) {
+  // (the backoff rows belong to the entries they were checked against: another table drops them)
+  if (e->d_backoff && (e->bo_levels != e->sv_levels || e->bo_beh != e->sv_beh ||
+                       memcmp(e->bo_sv.data(), e->sv_tab.data(), e->sv_tab.size() * sizeof(agx_supervisor)) != 0)) {
+    hipFree(e->d_backoff);
+    e->d_backoff = nullptr;
+    e->bo_tab.clear();
+    if (e->d_super) HIP_TRY(hipMemsetAsync(e->d_super + kSvBackoff, 0, 8, e->stream));
+    drop_graphs(e);  // (the launched instantiation is the supervision one again)
+  }
   if (!e->d_super) {
     const size_t total = super_words(e);
     if (hipMalloc((void**)&e->d_super, total * 4ull) != hipSuccess) {
@@ -4010,6 +4028,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_child);
   hipFree(e->d_shard);
   hipFree(e->d_super);
+  hipFree(e->d_backoff);
   hipFree(e->d_recep);
   hipFree(e->d_topic);
   hipFree(e->d_list);
@@ -4763,6 +4782,97 @@ agx_status agx_read_supervision(agx_engine* e, uint64_t actor_id, uint32_t* init
     if (count) count[k] = col[k];
     if (remaining) remaining[k] = d == 0u ? 0xFFFFFFFFu : (uint64_t)d > e->sv_ticks ? (uint32_t)(d - e->sv_ticks) : 0u;
   }
+  return AGX_OK;
+}
+
+// TY/internal/Supervision.scala:163-406
+agx_status agx_set_backoff(agx_engine* e, const agx_backoff* table, uint32_t n_behaviors, uint32_t n_levels) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!e->sv_on) return set_err(AGX_EINVAL, "backoff needs an engine with supervision (agx_set_supervision first)");
+  if (e->d_backoff) return set_err(AGX_EINVAL, "backoff is set once (agx_set_supervision with another table drops the rows)");
+  if (!table || n_behaviors != e->sv_beh || n_levels != e->sv_levels)
+    return set_err(AGX_EINVAL, "backoff: %u levels for %u behaviours; agx_set_supervision had %u levels for %u behaviours",
+                   n_levels, n_behaviors, e->sv_levels, e->sv_beh);
+  for (uint32_t i = 0; i < n_behaviors * n_levels; ++i) {
+    const agx_backoff& R = table[i];
+    if (!R.min_backoff) continue;  // (the entry stays a plain restart)
+    if (R.min_backoff > R.max_backoff || R.max_backoff > 0x7FFFFFFFu || R.random_factor_q16 > 65536u || R.reset_after < 1u ||
+        R.stash_capacity < -1)
+      return set_err(AGX_EINVAL, "backoff: bad row %u of behaviour %u (1 <= min_backoff <= max_backoff <= 2^31 - 1 ticks, "
+                     "random_factor_q16 <= 65536, reset_after >= 1 tick, stash_capacity >= -1)", i % n_levels, i / n_levels);
+    const agx_supervisor& S = e->sv_tab[(size_t)(i / n_levels) * AGX_MAX_SUPERVISORS + i % n_levels];
+    if (!S.class_mask || S.strategy != AGX_SUP_RESTART)
+      return set_err(AGX_EINVAL, "backoff: row %u of behaviour %u stands on an entry that is not AGX_SUP_RESTART", i % n_levels,
+                     i / n_levels);
+  }
+  if (e->started) return set_err(AGX_ESTATE, "set backoff before the first agx_run");
+  AGX_TRY(ensure_dev(e));
+  e->bo_tab.assign((size_t)AGX_MAX_BEHAVIORS * AGX_MAX_SUPERVISORS, agx_backoff{});
+  for (uint32_t b = 0; b < n_behaviors; ++b)
+    for (uint32_t k = 0; k < n_levels; ++k) e->bo_tab[(size_t)b * AGX_MAX_SUPERVISORS + k] = table[(size_t)b * n_levels + k];
+  const uint64_t npad = (uint64_t)e->nb << e->bb;
+  const size_t total = bo_until_off(e->nb) + 3ull * npad;
+  // (the engine names the storage only when it is whole and the SuperDev header points to it: a call that fails on the
+  // way leaves an engine without backoff, which launches the supervision instantiation)
+  uint32_t* d = nullptr;
+  if (hipMalloc((void**)&d, total * 4ull) != hipSuccess) {
+    (void)hipGetLastError();
+    e->bo_tab.clear();
+    return set_err(AGX_ENOMEM, "the backoff state of %llu actors (%llu MB) does not fit on the device",
+                   (unsigned long long)npad, (unsigned long long)(total >> 18));
+  }
+  std::vector<uint32_t> rows((size_t)AGX_MAX_BEHAVIORS * AGX_MAX_SUPERVISORS * kBoRowWords, 0u);
+  for (size_t i = 0; i < e->bo_tab.size(); ++i) memcpy(&rows[i * kBoRowWords], &e->bo_tab[i], sizeof(agx_backoff));
+  const uint64_t addr = (uint64_t)(uintptr_t)d;
+  hipError_t he = hipMemsetAsync(d, 0, total * 4ull, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(d, &e->sv_levels, 4, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(d + bo_row_off(e->nb), rows.data(), rows.size() * 4ull, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(e->d_super + kSvBackoff, &addr, 8, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) {
+    hipFree(d);
+    e->bo_tab.clear();
+    HIP_TRY(he);
+  }
+  e->d_backoff = d;
+  e->bo_sv = e->sv_tab;
+  e->bo_levels = e->sv_levels;
+  e->bo_beh = e->sv_beh;
+  drop_graphs(e);  // the instantiation is captured in the superstep graphs
+  return AGX_OK;
+}
+
+agx_status agx_backoff_info(agx_engine* e, uint64_t* backoffs, uint64_t* resumed, uint64_t* dropped, uint64_t* limit_stops,
+                            uint64_t* suspended) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  uint64_t c[3] = {0, 0, 0}, susp = 0;
+  if (e->d_backoff) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(copy_sync(e, c, e->d_backoff + kBoCtr, sizeof(c), hipMemcpyDeviceToHost));
+    // suspended now: the actors that will not drain in the next tick (until > ticks + 1); `resumed` is derived
+    std::vector<uint32_t> until(e->n_local);
+    AGX_TRY(copy_sync(e, until.data(), e->d_backoff + bo_until_off(e->nb), (size_t)e->n_local * 4ull, hipMemcpyDeviceToHost));
+    for (uint32_t u : until) susp += (uint64_t)u > e->sv_ticks + 1ull ? 1u : 0u;
+  }
+  if (backoffs) *backoffs = c[kBcBackoffs];
+  if (resumed) *resumed = c[kBcBackoffs] - susp;
+  if (dropped) *dropped = c[kBcDropped];
+  if (limit_stops) *limit_stops = c[kBcLimitStops];
+  if (suspended) *suspended = susp;
+  return AGX_OK;
+}
+
+agx_status agx_read_backoff(agx_engine* e, uint64_t actor_id, uint32_t* suspended_for, uint32_t* until) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (actor_id >= e->n_global) return set_err(AGX_EINVAL, "bad actor id");
+  uint32_t u = 0;
+  if (e->d_backoff) {
+    AGX_TRY(ensure_dev(e));
+    AGX_TRY(copy_sync(e, &u, e->d_backoff + bo_until_off(e->nb) + actor_id, 4, hipMemcpyDeviceToHost));
+  }
+  if (suspended_for) *suspended_for = (uint64_t)u > e->sv_ticks + 1ull ? (uint32_t)(u - 1ull - e->sv_ticks) : 0u;
+  if (until) *until = u;
   return AGX_OK;
 }
 

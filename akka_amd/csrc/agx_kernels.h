@@ -1803,6 +1803,109 @@ __device__ __forceinline__ uint32_t shard_requeue(const BucketArgs& a, const Buc
   return bltot;
 }
 
+// ---- restartWithBackoff (agx_set_backoff): the suspended actors of bucket b at tick t, before
+// admission.  A bucket whose bound is at or before the tick pays one uniform compare.  Else the thread of an actor
+// with mail loads its `until`; a suspended actor is marked in its LDS alive byte (kBoAlive): its drain window is 0
+// and its admission bound is the stash bound, so its segment goes to the backlog whole.
+__device__ __forceinline__ void bo_classify(const BucketArgs& a, const BucketLds& L, const BackoffDev& BD, uint32_t b,
+                                            uint32_t a0, uint32_t na) {
+  const uint32_t t = super_dev(a.P.super, a.nb, a.bb).tick(b);
+  if (*BD.bound(b) <= t) return;  // (block-uniform)
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) {
+    const uint32_t la = threadIdx.x * kBAct + j;
+    if (la < na && L.seg[la + 1] != L.seg[la] && (L.alive[la] & 1u) && *BD.until(a0 + la) > t) L.alive[la] |= (uint8_t)kBoAlive;
+  }
+  __syncthreads();
+}
+
+// The end of a tick in which an actor of bucket b failed into a backoff (RestartSupervisor's StashBuffer, Supervision.
+// scala:186-206,350-352): what was queued behind the failing message -- the rest of its window and its backlog --
+// stays queued, cut to the stash capacity.  shard_requeue's rewrite of the bucket's backlog from the LDS inbox: every
+// other actor's as the classification did (an actor suspended at the entry: whole, up to its bound), such an actor's
+// from the message after the failing one.  A slot a tell was staged over belongs to a consumed message: its key is
+// not trusted, the segment bounds decide.  What the cut drops joins this thread's dead letters and `dropped`.
+// Block-uniform call, after the barrier that follows the drains; U is free.  Returns the new count.  (Inlined: out of
+// line, called with copies of the arguments, it more than doubled the kernel's scratch frame: DESIGN.md §8 round 24.)
+template <bool kGather>
+__device__ __forceinline__ uint32_t bo_requeue(const BucketArgs& a, const BucketLds& L, const BackoffDev& BD, uint32_t b,
+                                               uint32_t lo, uint32_t cnt, uint32_t a0, uint32_t na, uint32_t w,
+                                               uint32_t& ndead, uint32_t& ndrop) {
+  const DevParams& P = a.P;
+  const int tid = threadIdx.x;
+  uint32_t* const blpre = reinterpret_cast<uint32_t*>(L.U);  // [kBucket] the actor's place in the bucket's backlog
+  uint32_t* const from = blpre + kBucket;                    // [kBucket] the first position of its segment that is queued
+  uint32_t* const upto = from + kBucket;                     // [kBucket] one past the last
+  uint32_t qn[kBAct], f[kBAct], nq = 0;
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) {
+    const uint32_t la = tid * kBAct + j, len = L.seg[la + 1] - L.seg[la];
+    qn[j] = 0;
+    f[j] = len;
+    if (la < na && len && (L.alive[la] & 1u)) {  // (L.alive: the flags of the tick's entry, the classification's)
+      const uint32_t ab = L.alive[la];
+      uint32_t C, T;
+      mbox_limits(P, ab, C, T);
+      uint32_t keep = (C == 0 || len < C) ? len : C;
+      if (ab & kBoAlive) {  // suspended at the entry: as the classification queued it
+        keep = min(keep, *BD.cap(a0 + la));
+        T = 0u;
+      }
+      const uint32_t cv = *BD.cut(a0 + la);
+      if (cv & kBoCut) {
+        f[j] = min(cv & ~kBoCut, keep);
+        qn[j] = min(keep - f[j], *BD.cap(a0 + la));
+        ndead += keep - f[j] - qn[j];
+        ndrop += keep - f[j] - qn[j];
+        *BD.cut(a0 + la) = 0u;
+      } else {
+        f[j] = min(T, keep);
+        qn[j] = keep - f[j];
+      }
+    }
+    nq += qn[j];
+  }
+  uint32_t bltot;
+  uint32_t ex = block_excl_sum<kBThreads>(nq, L.scratch, &bltot);
+#pragma unroll
+  for (int j = 0; j < kBAct; ++j) {
+    blpre[tid * kBAct + j] = ex;
+    from[tid * kBAct + j] = f[j];
+    upto[tid * kBAct + j] = f[j] + qn[j];
+    ex += qn[j];
+  }
+  __syncthreads();
+  const Msgs blw = a.g.bl[w];
+  const uint32_t amask = (1u << a.bb) - 1u;
+  for (uint32_t q = tid; q < cnt; q += kBThreads) {
+    const uint32_t key = L.key[q], la = key & amask;
+    const uint32_t s0 = L.seg[la], len = L.seg[la + 1] - s0, p = q - s0;
+    if (p >= len) continue;  // (q lies outside la's segment: a staged tell's key)
+    if (p < from[la] || p >= upto[la]) continue;
+    const uint32_t o = lo + blpre[la] + (p - from[la]);
+    blw.key[o] = key;
+    blw.src[o] = L.src[q];
+    blw.pay[o] = L.pay[q];
+  }
+  if (tid == 0) {
+    if constexpr (kGather) a.g.blc[w][b] = bltot;
+    else a.chunk_cnt[b] = bltot;
+  }
+  __syncthreads();
+  return bltot;
+}
+
+// what bucket_finish keeps of a bucket's backoff: declared through a template, so the instantiations without the
+// flag declare nothing
+template <bool kBo>
+struct BoLocals {};
+template <>
+struct BoLocals<true> {
+  BackoffDev BD;
+  bool held;      // an actor of this thread was suspended in this tick
+  uint32_t drop;  // the messages a stash bound cut or refused (this thread's actors')
+};
+
 // ---- the receptionist (agx_set_receptionist): what a thread's drains changed reaches the storage
 // once per wave -- the changed key bits as one atomic OR on the global dirty word (and the block's own "recount"
 // word in LDS), each counter as one atomic add.  A wave without a change or a route (the common case) does nothing.
@@ -2099,6 +2202,16 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
   // PostStop signals; a message that neither fails nor stops touches none of the supervision storage.
   constexpr bool kSv = (KM & kSuperKM) != 0;
   static_assert(!kSv || (kLds && !kWide && !kOwner && !kStash && !kTm && !kWd), "supervision: single-rank fast launches, plain behaviours");
+  // kBo: restartWithBackoff (agx_set_backoff), on top of supervision.  The suspended actors are
+  // marked here, before admission; a failure caught by a backoff entry ends the actor's window and suspends it
+  // (bo_failed), and keeps what was queued behind it, cut to the stash capacity (bo_requeue, after the drains).
+  constexpr bool kBo = (KM & kBackoffKM) != 0;
+  static_assert(!kBo || kSv, "backoff: on the supervision instantiations only");
+  BoLocals<kBo> bo{};  // (empty in every other instantiation: they declare nothing new)
+  if constexpr (kBo) {
+    bo.BD = backoff_dev(P.super, a.nb, a.bb);
+    bo_classify(a, L, bo.BD, b, a0, na);
+  }
   // kCh: children (agx_set_children), on top of death watch.  The tick's Create and Stop envelopes
   // are consumed here, before admission: the classification below sees the inbox without them and the actors
   // they gave birth to or stopped; compiled cases spawn and stop children; the end of the tick stops the
@@ -2202,6 +2315,25 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       }
       winl[la] = win;
     } else
+    if constexpr (kBo) {  // a suspended actor: drain window 0, admitted while the held length is below the stash bound
+      if (len) {
+        const uint32_t ab = L.alive[la];
+        if (!(ab & 1u)) {
+          ndead += len;
+        } else {
+          uint32_t C, T;
+          mbox_limits(P, ab, C, T);
+          uint32_t keep = (C == 0 || len < C) ? len : C;
+          if (ab & kBoAlive) {
+            keep = min(keep, *bo.BD.cap(a0 + la));
+            T = 0u;
+            bo.drop += len - keep;
+          }
+          ndead += len - keep;
+          q = keep > T ? keep - T : 0u;
+        }
+      }
+    } else
     if (len) {
       const uint32_t ab = L.alive[la];
       if (!(ab & 1u)) {
@@ -2266,6 +2398,13 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         keep = (C == 0 || mail < C) ? mail : C;
         queued = valid && (ab & 1u) && p >= win && pm < keep && (win != 0u || pm >= T);
         qoff = win ? pm : pm - T;
+      }
+      if constexpr (kBo) {
+        if (ab & kBoAlive) {  // held whole, up to the stash bound
+          keep = min(keep, *bo.BD.cap(a0 + la));
+          queued = valid && (ab & 1u) && p < keep;
+          qoff = p;
+        }
       }
       const uint32_t sv = valid ? isrc(q) : 0u;
       uint32_t pv = valid ? ipay(q) : 0u;
@@ -2592,6 +2731,8 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       if (kCompact && la == kNone) return;
       const uint32_t s0 = L.seg[la], len = L.seg[la + 1] - s0;
       if (la >= na || !len || !(L.alive[la] & 1u)) return;
+      if constexpr (kBo)
+        if (L.alive[la] & kBoAlive) return;  // suspended: nothing is processed, the segment is queued whole
       const uint32_t l = a0 + la;
       const uint32_t self = P.R > 1 ? P.gid[l] : l;
       EmitterLds em{&P, stk, sts, stp, s0, self, 0, 0, L.nh, a.nx_shift, nhmask};
@@ -2999,6 +3140,42 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           }
         }
         if (ndisc) atomicAdd(WD.ctr(kWcDiscarded), (unsigned long long)ndisc);
+      } else if constexpr (kBo) {
+        // the supervised drain below with bo_failed: a failure caught by a backoff entry restarts the actor and ends
+        // its window -- the index of the first message held goes to its cut word, for bo_requeue after the drains
+        for (uint32_t q = 0; q < nd; ++q) {
+          const uint32_t sv = sts[s0 + q], pv = stp[s0 + q];
+          uint32_t cls = 0;
+          uint32_t r = kcur >= AGX_KIND_COMPILED ? compiled_apply_s(P, kcur, self, wv, sv, pv, false, cls, em)
+                                                 : apply_msg<KM>(P, kcur, self, l, wv, sv, pv, em);
+          ++ndel;
+          if (r == AGX_RES_UNHANDLED) ++nunh;
+          if (__builtin_expect(r == AGX_RES_FAIL || r == AGX_RES_STOPPED, 0)) {
+            // (copies: what the call takes by address lives in memory, and the drain's own state must stay in registers)
+            DevParams Pl = P;  // (the kernel's own arguments included: their copy is made here, on the cold path only)
+            EmitterLds em2 = em;
+            em2.P = &Pl;
+            uint64_t w2[2] = {wv[0], wv[1]};
+            uint32_t k2 = kcur;
+            r = bo_failed(Pl, a.nb, a.bb, l, b, k2, self, w2, r, cls, em2);
+            em = em2;
+            em.P = &P;
+            wv[0] = w2[0];
+            wv[1] = w2[1];
+            kcur = k2;
+            if (r == kBoSuspended) {
+              *bo.BD.cut(l) = kBoCut | (q + 1u);
+              bo.held = true;
+              break;
+            }
+          }
+          if (r == AGX_RES_STOPPED) {
+            if constexpr (kGather) P.alive[l] = L.alive[la] & 0xFEu;
+            else P.stopq[atomicAdd(P.nstop, 1u)] = l;
+            ndead += nd - q - 1;  // drained-but-unprocessed after the stop
+            break;
+          }
+        }
       } else if constexpr (kSv) {
         // the drain under the supervisor (Supervision.scala:122-126): a failure or a stop takes the cold path,
         // which resumes, restarts (the drain goes on under the restarted behaviour: the mailbox survives) or
@@ -3203,6 +3380,10 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     __syncthreads();
     if constexpr (kSh)  // (block-uniform; U is free: the state words were written back)
       if (__syncthreads_or(shheld ? 1 : 0)) bltot = shard_requeue<kGather>(a, L, SH, b, lo, cnt, a0, na, w);
+    if constexpr (kBo) {  // (block-uniform; U is free: the state words were written back)
+      if (__syncthreads_or(bo.held ? 1 : 0)) bltot = bo_requeue<kGather>(a, L, bo.BD, b, lo, cnt, a0, na, w, ndead, bo.drop);
+      if (bo.drop) atomicAdd(bo.BD.ctr(kBcDropped), (unsigned long long)bo.drop);
+    }
     if constexpr (kLs) {  // (block-uniform; bit 0: a key mask changed, bit 1: a sub or pending byte)
       if (*L.rowtop & 1u) recep_recount(RD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));
       if (*L.rowtop & 2u) listing_recount(LD, b, a0, na, reinterpret_cast<uint32_t*>(L.U));

@@ -41,7 +41,9 @@ enum : uint32_t { M_FUSED = 0, M_OWNER = 1, M_BYPASS = 2, M_PERSIST = 3 /* dense
 
 // variant groups = translation units (agx_apply.hip built with -DAGX_VGROUP=0..kVGroups-1);
 // the heavy CRDT variants are spread so the units take similar time
-constexpr uint32_t kVGroups = 8;
+constexpr uint32_t kVGroups = 9;
+// the last group holds no variant of the table: it is the unit of the kSuperKM | kBackoffKM feature launches alone
+constexpr uint32_t kBackoffGroup = 8;
 constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7};
 
 // launch k_bucket_apply<variant vid, mode, skew> with `grid` x kBThreads threads on `s`
@@ -51,7 +53,8 @@ hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 grid, h
 // kFeatures: km_flags = the feature's KM flag bits, or none and `prio` for priority mailboxes).  Instantiated in the
 // modes M_FUSED / M_BYPASS: kPrio for the catch-all plain variants V_ALL / V_ALL_COMPILED, the flag combinations
 // kStashKM, kTimersKM, kTimersKM | kIdleKM, kTimersKM | kIdleKM | kShardKM, kTimersKM | kAskKM, kWatchKM, kWatchKM | kChildKM, kSuperKM, kRecepKM,
-// kRecepKM | kHashKM, kRecepKM | kTopicKM, kRecepKM | kTopicKM | kListKM for V_ALL_COMPILED
+// kRecepKM | kHashKM, kRecepKM | kTopicKM, kRecepKM | kTopicKM | kListKM for V_ALL_COMPILED, all in
+// V_ALL_COMPILED's group, and kSuperKM | kBackoffKM for V_ALL_COMPILED in kBackoffGroup
 // (hipErrorInvalidValue otherwise)
 hipError_t agx_launch_apply_feature(uint32_t vid, uint32_t mode, uint32_t km_flags, bool prio, dim3 grid, hipStream_t s,
                                     const BucketArgs& ba);

@@ -396,6 +396,35 @@ class GpuEngine:
         check(self.lib.agx_read_supervision(self._h, actor_id, ctypes.byref(kind), *(_ptr(x, ctypes.c_uint32) for x in a)))
         return dict(initial_kind=int(kind.value), count=a[0], remaining=a[1])
 
+    def set_backoff(self, rows) -> None:
+        """agx_set_backoff, after set_supervision: `rows[b]` are compiled behaviour b's backoff rows (typed.AgxBackoff,
+        one per supervisor entry, inner first; typed.Tables.backoff has them).  A row with min_backoff != 0 turns
+        the restart entry of the same place into SupervisorStrategy.restartWithBackoff (TY/internal/Supervision.
+        scala:163-406); the others leave theirs a plain restart."""
+        from .typed import AgxBackoff
+        rows = [list(r) for r in rows]
+        n_levels = max([len(r) for r in rows] + [1])
+        arr = (AgxBackoff * max(len(rows) * n_levels, 1))()
+        for b, r in enumerate(rows):
+            for k, s in enumerate(r):
+                arr[b * n_levels + k] = s
+        check(self.lib.agx_set_backoff(self._h, ctypes.cast(arr, ctypes.c_void_p), len(rows), n_levels))
+
+    BACKOFF_INFO = ("backoffs", "resumed", "dropped", "limit_stops", "suspended")
+
+    def backoff_info(self) -> dict:
+        """agx_backoff_info: totals backoffs / resumed / dropped / limit_stops, and the actors suspended now."""
+        v = [ctypes.c_uint64() for _ in range(5)]
+        check(self.lib.agx_backoff_info(self._h, *(ctypes.byref(x) for x in v)))
+        return dict(zip(self.BACKOFF_INFO, (int(x.value) for x in v)))
+
+    def read_backoff(self, actor_id: int) -> dict:
+        """agx_read_backoff: the coming ticks during which the actor stays suspended (0: it drains in the next tick)
+        and the tick at which it drains again (0: never suspended)."""
+        v = [ctypes.c_uint32() for _ in range(2)]
+        check(self.lib.agx_read_backoff(self._h, actor_id, *(ctypes.byref(x) for x in v)))
+        return dict(suspended_for=int(v[0].value), until=int(v[1].value))
+
     def set_children(self, regions, sites) -> None:
         """agx_set_children (an engine with death watch, before the first run): `regions` are (first_parent,
         n_parents, first_child, max_children) -- the k-th spawn of parent p creates id first_child + (p -

@@ -25,6 +25,10 @@ What lowers:
     restart.with_limit(n, within)``; a case may end in ``Behaviors.throw(exc)``, ``ExceptionType(name, parent)``
     declares the classes, and ``on_signal(PreRestart | PostStop, ...)`` handles the two signals
     (``Tables.supervisors`` -> engine.set_supervision);
+  * ``SupervisorStrategy.restart_with_backoff(min_backoff, max_backoff, random_factor)`` with
+    ``.with_max_restarts(n)``, ``.with_reset_backoff_after(ticks)`` and ``.with_stash_capacity(n)`` (TY/internal/
+    Supervision.scala:163-406): times are ticks (``Tables.backoff`` -> engine.set_backoff, after
+    engine.set_supervision; ``Tables.uses_backoff``);
   * ``context.spawn(behavior, arg, word1=<const> | context.PARENT, into=field)``, ``context.stop(child)``,
     ``context.child_at(x)`` and ``context.spawned`` (children on the death-watch engine): the
     spawned behaviours are lowered with their parents, ``Tables.spawn_sites`` goes to engine.set_children, and a
@@ -75,7 +79,7 @@ What lowers:
 from __future__ import annotations
 
 import ctypes
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -150,7 +154,14 @@ class AgxSupervisor(ctypes.Structure):
                 ("within", ctypes.c_uint32), ("reset", ctypes.c_uint64 * 2)]
 
 
+class AgxBackoff(ctypes.Structure):
+    """include/akka_gpu.h agx_backoff (20 B)."""
+    _fields_ = [("min_backoff", ctypes.c_uint32), ("max_backoff", ctypes.c_uint32), ("random_factor_q16", ctypes.c_uint32),
+                ("reset_after", ctypes.c_uint32), ("stash_capacity", ctypes.c_int32)]
+
+
 assert ctypes.sizeof(AgxCase) == 48 and ctypes.sizeof(AgxAct) == 32 and ctypes.sizeof(AgxSupervisor) == 32
+assert ctypes.sizeof(AgxBackoff) == 20
 
 
 class CompileError(ValueError):
@@ -931,12 +942,60 @@ class _Restart(_Strategy):
         return _Strategy(SUP_RESTART, max_restarts, within)
 
 
+@dataclass(frozen=True)
+class _Backoff(_Strategy):
+    """restartWithBackoff(min, max, randomFactor) (TY/SupervisorStrategy.scala): a restart entry with a backoff row
+    (engine.set_backoff(tables.backoff)).  Times are ticks; the defaults are the reference's: no limit, the count
+    resets min_backoff after the restart, the stash capacity is the actor's mailbox capacity (-1; the reference's
+    configured default is 1000)."""
+    min_backoff: int = 1
+    max_backoff: int = 1
+    random_factor_q16: int = 0
+    reset_after: int = 1
+    stash_capacity: int = -1
+
+    def with_max_restarts(self, n: int) -> "_Backoff":
+        """withMaxRestarts(n): the (n + 1)-th failure stops the actor (-1: no limit)."""
+        if not isinstance(n, (int, np.integer)) or isinstance(n, bool) or int(n) < -1 or int(n) > 0x7FFFFFFF:
+            raise CompileError(f"with_max_restarts: an integer >= -1, not {n!r}")
+        return replace(self, max_restarts=int(n))
+
+    def with_reset_backoff_after(self, ticks: int) -> "_Backoff":
+        """withResetBackoffAfter(ticks): the count resets this many ticks after the delayed restart, >= 1."""
+        if not isinstance(ticks, (int, np.integer)) or isinstance(ticks, bool) or not 1 <= int(ticks) <= MAX_TIMER_DELAY:
+            raise CompileError(f"with_reset_backoff_after: a number of ticks in 1..{MAX_TIMER_DELAY}, not {ticks!r}")
+        return replace(self, reset_after=int(ticks))
+
+    def with_stash_capacity(self, n: int) -> "_Backoff":
+        """withStashCapacity(n): the messages held while the actor backs off (-1: the mailbox capacity; 0: none)."""
+        if not isinstance(n, (int, np.integer)) or isinstance(n, bool) or int(n) < -1 or int(n) > 0x7FFFFFFF:
+            raise CompileError(f"with_stash_capacity: an integer >= -1, not {n!r}")
+        return replace(self, stash_capacity=int(n))
+
+
 class SupervisorStrategy:
-    """SupervisorStrategy.resume / stop / restart / restart.with_limit(n, within).  restartWithBackoff is left out
-    (it needs a stash and a timer), and so are children (stopChildren) and logging."""
+    """SupervisorStrategy.resume / stop / restart / restart.with_limit(n, within) / restart_with_backoff(min, max,
+    random_factor).  Children (stopChildren) and logging are left out."""
     resume = _Strategy(SUP_RESUME)
     stop = _Strategy(SUP_STOP)
     restart = _Restart(SUP_RESTART)
+
+    @staticmethod
+    def restart_with_backoff(min_backoff: int, max_backoff: int, random_factor: float) -> _Backoff:
+        """restartWithBackoff(minBackoff, maxBackoff, randomFactor): after failure c + 1 the actor restarts and stays
+        suspended for min(max_backoff, min_backoff * 2^c) ticks (max_backoff from c = 30 on), plus up to
+        random_factor times that as jitter; what arrives meanwhile is held up to the stash capacity.  Chain
+        with_max_restarts / with_reset_backoff_after / with_stash_capacity."""
+        for name, v in (("min_backoff", min_backoff), ("max_backoff", max_backoff)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= int(v) <= MAX_TIMER_DELAY:
+                raise CompileError(f"restart_with_backoff: {name} is a number of ticks in 1..{MAX_TIMER_DELAY}, not {v!r}")
+        if int(min_backoff) > int(max_backoff):
+            raise CompileError(f"restart_with_backoff: min_backoff {min_backoff} exceeds max_backoff {max_backoff}")
+        if not isinstance(random_factor, (int, float, np.integer, np.floating)) or isinstance(random_factor, bool) or \
+                not 0.0 <= float(random_factor) <= 1.0:
+            raise CompileError(f"restart_with_backoff: random_factor lies in 0.0..1.0, not {random_factor!r}")
+        return _Backoff(SUP_RESTART, -1, 1, int(min_backoff), int(max_backoff), int(round(float(random_factor) * 65536)),
+                        int(min_backoff), -1)
 
 
 @dataclass(eq=False)
@@ -1183,6 +1242,7 @@ class Tables:
     first: np.ndarray
     n_acts: int = 0
     supervisors: list = field(default_factory=list)  # per behaviour: its AgxSupervisor entries, inner first
+    backoff: list = field(default_factory=list)  # per behaviour: an AgxBackoff row per entry (min_backoff 0: a plain one) -> engine.set_backoff
     exception_classes: list = field(default_factory=list)  # the ExceptionTypes in use; the index is the class number
     spawn_sites: list = field(default_factory=list)  # (kind, word-0 base, word 1 or None: the parent's id) -> engine.set_children
     transparent_tags: tuple = ()  # the tags of the NotInfluenceReceiveTimeout message types -> engine.set_receive_timeout
@@ -1198,6 +1258,12 @@ class Tables:
         """A behaviour is supervised, throws or holds a PreRestart / PostStop case: the engine needs
         engine.set_supervision(tables.supervisors)."""
         return any(self.supervisors) or any(c.sig_code or isinstance(c.result, _Throw) for b in self.behaviors for c in b.cases)
+
+    @property
+    def uses_backoff(self) -> bool:
+        """A supervisor restarts with backoff: the engine needs engine.set_backoff(tables.backoff) after
+        engine.set_supervision(tables.supervisors)."""
+        return any(r.min_backoff for row in self.backoff for r in row)
 
     @property
     def n_behaviors(self) -> int:
@@ -1468,6 +1534,11 @@ def compile_behaviors(roots, max_emit: int | None = None, transparent=(), entiti
                     e.reset[w] = v
             row.append(e)
         t.supervisors.append(row)
+        t.backoff.append([AgxBackoff(s.min_backoff, s.max_backoff, s.random_factor_q16, s.reset_after, s.stash_capacity)
+                          if isinstance(s, _Backoff) else AgxBackoff() for s in (sv.strategy for sv in b.supervisors)])
+    if t.uses_backoff and (t.uses_watch or t.timer_keys or t.stash_capacity):
+        raise CompileError("restart_with_backoff lives on the supervision engine, which shares an engine with neither death "
+                           "watch, timers nor a stash: the behaviours back off and use one of them")
     if t.uses_ask:  # on the timer engine: max_emit 1, the request is the case's one envelope
         if t.stash_capacity or t.uses_watch or t.uses_children or t.uses_supervision or t.uses_receptionist or \
                 t.uses_receive_timeout or any(V_STASH in (a.src, a.dsrc) for a in acts) or \

@@ -60,7 +60,8 @@ class Workload:
     # None, offset, message or None)]} -- empty: no death watch
     watch: dict = field(default_factory=dict)
     # supervision (agx_set_supervision): {"rows": per compiled behaviour its supervisor entries, inner first
-    # (typed.Tables.supervisors)} -- empty: no supervision
+    # (typed.Tables.supervisors), "backoff": per compiled behaviour a backoff row per entry (agx_set_backoff, on top;
+    # typed.Tables.backoff; absent or empty: plain restarts)} -- empty: no supervision
     supervision: dict = field(default_factory=dict)
     # children (agx_set_children / agx_spawn_children, on top of `watch`): {"regions": [(first_parent, n_parents,
     # first_child, max_children)], "sites": typed.Tables.spawn_sites, "spawns": [(first, count, site, arg)]} --
@@ -145,6 +146,8 @@ class Workload:
                 target.start_watch(first, count, watchees, offset=offset, message=message)
         if self.supervision:  # (empty: targets without the call are unaffected)
             target.set_supervision(self.supervision["rows"])
+            if self.supervision.get("backoff"):  # (restartWithBackoff, on top of supervision: agx_set_backoff)
+                target.set_backoff(self.supervision["backoff"])
         if self.children:  # (empty: targets without the calls are unaffected; set_children: with the watch above)
             for first, count, site, arg in self.children.get("spawns", ()):
                 target.spawn_children(first, count, site, arg)
@@ -1122,6 +1125,110 @@ def flaky_workers(n: int = 1 << 20, hops: int = 8, poison_every: int = 16, max_p
     return Workload("flaky_workers", n, 2, 1, throughput, 0, [(0, n, tb.kind_of(b), init)], behaviors=tb,
                     tells=(dst, np.full(dst.size, NO_SENDER, np.uint32), pay), outbound=(n, max(n_host, 1)),
                     bucket_actors=bucket_actors, supervision={"rows": tb.supervisors})
+
+
+# ------------------------------------------------------------------ restartWithBackoff
+BW_JOB, BW_RESTARTED, BW_STOPPED = 1, 3, 4
+
+
+def backoff_workers(n: int = 1 << 20, jobs: int = 8, hops: int = 6, away_every: int = 8, max_away: int = 6,
+                    min_backoff: int = 1, max_backoff: int = 16, random_factor: float = 0.2, reset_after: int = 4,
+                    max_restarts: int = -1, stash_capacity: int = -1, seed: int = 1, throughput: int = 3,
+                    bucket_actors: int = 128, churn: int = 0) -> Workload:
+    """Flaky clients of a resource that is away for a stretch, under restart_with_backoff (TY/internal/Supervision.
+    scala:163-406).  Every client gets `jobs` Job(hops) messages, counts each and passes it on with one hop less.
+    One client in `away_every` finds its resource away for its next 1..max_away jobs (word 1, seeded; a constructor
+    argument, so a restart keeps what is left of it): on each of them it throws ResourceAway, restarts and backs
+    off -- 1, 2, 4, ... ticks with jitter, so with max_away > 3 the counts pass 3 -- while its other jobs and its
+    neighbour's wait in the stash; once the resource is back it works them off in order.  (The resource is each
+    client's own countdown and no actor of its own: a client that waits for a reply needs an ask timeout, and timers
+    share no engine with supervision.)  PreRestart reports the jobs done since the last restart (word 0, which the
+    restart resets) to the monitor, a host-side actor; PostStop reports a client that ran out of restarts.
+    `churn` > 0 keeps the failures coming for as long as jobs circulate: every client also throws on the job after
+    its `churn`-th since the last restart, passing that job on first."""
+    from . import typed
+    st = typed.State("since", "away")
+    B = typed.Behaviors
+    job = typed.MessageType("Job", BW_JOB)
+    away = typed.ExceptionType("ResourceAway")
+    monitor = typed.actor_ref(n)
+    rb = typed.ReceiveBuilder.create(st)
+    rb.on_message(job, lambda m, s: [s.away.add(-1), B.throw(away)], when=lambda m, s: s.away > 0)
+    rb.on_message(job, lambda m, s: [s.since.inc(), B.same], test=lambda m: m.arg == 0)
+    if churn:  # steady churn: the resource is away again for every `churn`-th job; that job is passed on before the throw
+        rb.on_message(job, lambda m, s: [typed.self_ref(1).tell(job(m.arg - 1)), B.throw(away)], when=lambda m, s: s.since >= churn)
+    rb.on_message(job, lambda m, s: [s.since.inc(), typed.self_ref(1).tell(job(m.arg - 1)), B.same])
+    rb.on_any_message(lambda m, s: [B.unhandled])
+    if not churn:  # (the passing-on throw takes the message's one tell: no reports then)
+        rb.on_signal(typed.PreRestart, lambda sig, s: [monitor.tell(s.since, tag=BW_RESTARTED), B.same])
+        rb.on_signal(typed.PostStop, lambda sig, s: [monitor.tell(s.since, tag=BW_STOPPED), B.same])
+    b = rb.build("backoff_worker")
+    strat = (typed.SupervisorStrategy.restart_with_backoff(min_backoff, max_backoff, random_factor)
+             .with_max_restarts(max_restarts).with_reset_backoff_after(reset_after).with_stash_capacity(stash_capacity))
+    b = B.supervise(b, reset={st.since: 0}).on_failure(strat, exc=away)
+    tb = typed.compile_behaviors([b], max_emit=1)
+    rng = np.random.default_rng(seed)
+    init = np.zeros((n, 2), np.uint64)
+    sick = np.flatnonzero(rng.random(n) < 1.0 / away_every)
+    init[sick, 1] = rng.integers(1, max_away + 1, sick.size)
+    dst = np.tile(np.arange(n, dtype=np.uint32), jobs)  # (round-robin: job j of every client before job j + 1 of any)
+    pay = np.full(dst.size, job.payload(hops), np.uint32)
+    return Workload("backoff_workers", n, 2, 1, throughput, 0, [(0, n, tb.kind_of(b), init)], behaviors=tb,
+                    tells=(dst, np.full(dst.size, NO_SENDER, np.uint32), pay), outbound=(n, 1),
+                    bucket_actors=bucket_actors, supervision={"rows": tb.supervisors, "backoff": tb.backoff})
+
+
+BS_TICK, BS_DATA, BS_RESTARTED = 1, 2, 3
+
+
+def backoff_stash_pressure(n: int = 1 << 12, ticks: int = 24, poison_every: int = 6, capacities=(0, 1, 2, -1),
+                           mailbox_capacity: int = 4, min_backoff: int = 2, max_backoff: int = 8, reset_after: int = 3,
+                           seed: int = 1, bucket_actors: int = 64) -> Workload:
+    """Steady senders against suspended actors with small stash capacities.  The first half of the actors are
+    senders, the second half their targets (word 1 of a sender: a constructor argument).  Every sender starts with
+    `ticks` Tick messages and drains one per tick (throughput 1), sending its target a Data message each time; one
+    Data in `poison_every` (seeded) is poison, on which the target throws and backs off for 2, 4, 8 ticks.  While
+    it is suspended a message a tick presses on a stash of capacities[k] (the targets take the capacities block by
+    block; -1: the bounded mailbox's `mailbox_capacity`): what does not fit is dropped.  PreRestart reports the
+    Data a target had counted (word 0, which the restart resets) to the monitor, a host-side actor."""
+    from . import typed
+    assert n % (2 * len(capacities)) == 0 and n >= 2 * len(capacities)
+    assert ticks * bucket_actors <= 2048, "the start-up Ticks of a bucket stay within one tile"
+    B = typed.Behaviors
+    tick = typed.MessageType("Tick", BS_TICK)
+    bad = typed.ExceptionType("PoisonedData")
+    monitor = typed.actor_ref(n)
+    sst = typed.State("sent", "target")
+    sender = (typed.ReceiveBuilder.create(sst)
+              .on_message(tick, lambda m, s: [s.sent.inc(), s.target.ref.tell(m.arg, tag=BS_DATA), B.same])
+              .on_any_message(lambda m, s: [B.unhandled])
+              .build("pressure_sender"))
+    behs = [sender]
+    for k, cap in enumerate(capacities):
+        tst = typed.State("got", "unused")
+        t = (typed.ReceiveBuilder.create(tst)
+             .on_any_message(lambda m, s: [B.throw(bad)], test=lambda m: m.tag == BS_DATA, when=lambda m, s: m.arg == 1)
+             .on_any_message(lambda m, s: [s.got.inc(), B.same], test=lambda m: m.tag == BS_DATA)
+             .on_any_message(lambda m, s: [B.unhandled])
+             .on_signal(typed.PreRestart, lambda sig, s: [monitor.tell(s.got, tag=BS_RESTARTED), B.same])
+             .build(f"pressure_target_{k}"))
+        strat = (typed.SupervisorStrategy.restart_with_backoff(min_backoff, max_backoff, 0.0)
+                 .with_reset_backoff_after(reset_after).with_stash_capacity(cap))
+        behs.append(B.supervise(t, reset={tst.got: 0}).on_failure(strat, exc=bad))
+    tb = typed.compile_behaviors(behs, max_emit=1)
+    h, blk = n // 2, n // 2 // len(capacities)
+    init = np.zeros((h, 2), np.uint64)
+    init[:, 1] = h + np.arange(h, dtype=np.uint64)
+    ranges = [(0, h, tb.kind_of(sender), init)]
+    ranges += [(h + k * blk, blk, tb.kind_of(behs[1 + k]), None) for k in range(len(capacities))]
+    rng = np.random.default_rng(seed)
+    dst = np.tile(np.arange(h, dtype=np.uint32), ticks)
+    pay = ((BS_TICK << 24) | (rng.random(dst.size) < 1.0 / poison_every)).astype(np.uint32)
+    # (the targets' bounded mailbox is class 1; the senders' start-up Ticks need the unbounded default)
+    return Workload("backoff_stash_pressure", n, 2, 1, 1, 0, ranges, behaviors=tb,
+                    tells=(dst, np.full(dst.size, NO_SENDER, np.uint32), pay), outbound=(n, 1),
+                    bucket_actors=bucket_actors, mailbox_classes={1: mailbox_capacity}, mailboxes=[(h, h, 1)],
+                    supervision={"rows": tb.supervisors, "backoff": tb.backoff})
 
 
 # ------------------------------------------------------------------ children (DESIGN.md §2.6)

@@ -843,8 +843,8 @@ agx_status agx_read_watch(agx_engine* eng, uint64_t actor_id, uint32_t watchee[4
  * engine uses no wave, ring, dense or persistent launch, and a bucket whose inbox exceeds one 2048-message
  * tile makes agx_run return AGX_ECAPACITY (sticky).  Tables with AGX_RES_FAIL or a supervision signal case on
  * an engine without supervision, and tables with watch, timer or stash content on an engine with it, make
- * agx_run return AGX_EINVAL.  Left out: restartWithBackoff, children, supervise around a behaviour reached by
- * become, logging. */
+ * agx_run return AGX_EINVAL.  restartWithBackoff comes on top (agx_set_backoff below).  Left out: children,
+ * supervise around a behaviour reached by become, logging. */
 #define AGX_MAX_SUPERVISORS 4u
 #define AGX_SUP_RESUME 1u
 #define AGX_SUP_RESTART 2u
@@ -868,6 +868,47 @@ agx_status agx_supervision_info(agx_engine* eng, uint64_t* failures, uint64_t* r
  * deadline).  Levels past n_levels read as 0 / 0xFFFFFFFF.  Any pointer may be NULL. */
 agx_status agx_read_supervision(agx_engine* eng, uint64_t actor_id, uint32_t* initial_kind, uint32_t count[4],
                                 uint32_t remaining[4]);
+
+/* restartWithBackoff (SupervisorStrategy.restartWithBackoff(min, max, randomFactor) with withMaxRestarts,
+ * withResetBackoffAfter and withStashCapacity: TY/internal/Supervision.scala:163-406, pinned by SupervisionSpec.scala:
+ * 370-422,774-924; DESIGN.md 2.14 has the contract).  Backoff sits on top of supervision: agx_set_backoff comes after
+ * agx_set_supervision, with the same n_behaviors and n_levels, before the first run, once.  Row table[b * n_levels +
+ * k] turns the AGX_SUP_RESTART entry of the same place into a backoff entry; a row with min_backoff == 0 leaves the
+ * entry a plain restart.  The entry's max_restarts is withMaxRestarts, its `within` is ignored.
+ * A failure caught by a backoff entry at tick t, the entry having the count c and a reset-due r (none at first):
+ * r exists and t >= r: c = 0, r = none.  Then, if max_restarts != -1 and c >= max_restarts, the actor stops
+ * (PostStop); unlike a plain restart the failure does not pass to an outer entry.  Otherwise PreRestart runs, c
+ * becomes c + 1, the inner entries are cleared, kind and reset words are re-created as by a restart, and the actor is
+ * suspended: delay = c >= 30 ? max_backoff : min(max_backoff, min_backoff << c), plus (delay * random_factor_q16 *
+ * r16) >> 32 with r16 the top 16 bits of the counter RNG (the seed of agx_set_fanout / agx_set_gossip, 0 without;
+ * the actor's id; t); until = t + delay, r = until + reset_after (both saturate at 2^32 - 1).
+ * The failing message counts as delivered and the drain window ends there.  While t < until nothing addressed to
+ * the actor is processed: the queue behind the failing message is cut to its first stash_capacity items and stays
+ * queued, in order; in later ticks an arrival is admitted while the held length is below min(mailbox capacity,
+ * stash_capacity).  What is cut or refused is a dead letter and counts as `dropped`.  stash_capacity -1 is the
+ * mailbox capacity (none of its own on an unbounded mailbox; the reference's configured default is 1000).  Held
+ * mail is in flight: a run to quiescence lets the delay pass.  From tick `until` on the actor drains as always.
+ * AGX_EINVAL, each with its own message: before agx_set_supervision, a second call, other dimensions than
+ * agx_set_supervision's, a bad row (1 <= min_backoff <= max_backoff <= 2^31 - 1, random_factor_q16 <= 65536,
+ * reset_after >= 1, stash_capacity >= -1), a row on a level whose entry is not AGX_SUP_RESTART.  AGX_ESTATE after
+ * the first run.  agx_set_supervision with another table drops the rows.  Every refusal of the supervision engine is
+ * inherited.  Left out: stopChildren, stashing of signals, withLoggingEnabled. */
+typedef struct agx_backoff {
+  uint32_t min_backoff, max_backoff; /* ticks; min_backoff 0: the entry stays a plain restart                     */
+  uint32_t random_factor_q16;        /* 0..65536: the jitter's factor in 1/65536                                  */
+  uint32_t reset_after;              /* ticks after `until` at which the count resets, >= 1                       */
+  int32_t stash_capacity;            /* >= -1; -1: the mailbox capacity                                           */
+} agx_backoff; /* 20 bytes */
+agx_status agx_set_backoff(agx_engine* eng, const agx_backoff* table, uint32_t n_behaviors, uint32_t n_levels);
+/* Totals since agx_create: backoffs (suspensions), resumed (suspensions that have ended: backoffs - suspended),
+ * dropped (messages cut or refused by a stash bound), limit_stops (stops by withMaxRestarts), and the actors
+ * suspended now (those that will not drain in the next tick).  Any pointer may be NULL. */
+agx_status agx_backoff_info(agx_engine* eng, uint64_t* backoffs, uint64_t* resumed, uint64_t* dropped,
+                            uint64_t* limit_stops, uint64_t* suspended);
+/* One actor: the coming ticks during which it stays suspended (0: it drains in the next tick) and the tick at which
+ * it drains again (0: never suspended).  For a backoff level agx_read_supervision's `remaining` is the ticks until
+ * the count resets.  Any pointer may be NULL. */
+agx_status agx_read_backoff(agx_engine* eng, uint64_t actor_id, uint32_t* suspended_for, uint32_t* until);
 
 /* Child actors (context.spawn / context.stop(child) and the parent's stop taking its children: AA/dungeon/
  * Children.scala, TY/internal/adapter/ActorContextAdapter.scala:79-106, pinned by ActorContextSpec.scala:214-240,
