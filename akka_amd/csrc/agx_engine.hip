@@ -396,6 +396,11 @@ struct agx_engine {
   uint4* d_orw = nullptr;
   uint2* d_orm = nullptr;
   uint32_t* d_orw_n = nullptr;
+  // LWWMap engines (agx_set_lwwmap): the LWWRegister clock; d_lww_step0 = the supersteps with mail that ran
+  // before the replay being launched (k_lwwmap_merge's logical time; written stream-ordered, run_single)
+  uint32_t lww_clock = AGX_LWW_CLOCK_DEFAULT;
+  uint64_t lww_base = 0;
+  uint32_t* d_lww_step0 = nullptr;
   unsigned long long* d_ring_total = nullptr;
   uint32_t tstride = 4, region = 0;
   uint64_t acap = 0;  // arena capacity (fused: regions + overflow area)
@@ -887,6 +892,7 @@ uint32_t apply_variant(const agx_engine* e) {
     if (km == kb(AGX_KIND_GCOUNTER)) return V_GC;
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN;
     if (km == kb(AGX_KIND_ORSET)) return V_OR;
+    if (km == kb(AGX_KIND_LWWMAP)) return V_LWWMAP;  // (an LWWMap engine holds nothing else: agx_register_range)
     if ((km & ~kCrdtKM) == 0) return V_CRDT;  // CRDT kinds only: no plain-behaviour code
     return V_ALL_WIDE;
   }
@@ -1515,9 +1521,10 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
   }
   {
     const uint32_t vid = apply_variant(e);
-    const bool orm = vid == V_OR;  // ORSet-only full state: state effects in k_orset_merge
+    const bool lwm = vid == V_LWWMAP;       // LWWMap-only: state effects in k_lwwmap_merge
+    const bool orm = vid == V_OR || lwm;  // ORSet-only full state: state effects in k_orset_merge
     if (orm) {
-      if (!e->d_orw) return set_err(AGX_ESTATE, "ORSet work list not allocated (setup_orset)");
+      if (!e->d_orw || (lwm && !e->d_lww_step0)) return set_err(AGX_ESTATE, "ORSet work list not allocated (setup_orset)");
       ba.orw = e->d_orw;
       ba.orm = e->d_orm;
       ba.orw_n = e->d_orw_n;
@@ -1607,7 +1614,12 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       Scope s(e, K_SKEW);
       HIP_TRY(agx_launch_apply(vid, mode, true, gs, e->stream, ba));
     }
-    if (orm) {
+    if (lwm) {
+      Scope s(e, K_APPLY);
+      HIP_TRY(agx_launch_lwwmap_merge(dim3(grid_for(e->n_local / 4 + 1, 4096)), e->stream, ba.P, (const uint4*)e->d_orw,
+                                      (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n, e->d_lww_step0, e->cur_slot,
+                                      e->lww_clock, (int64_t)e->lww_base));
+    } else if (orm) {
       Scope s(e, K_APPLY);
       hipLaunchKernelGGL(k_orset_merge, dim3(grid_for(e->n_local / 4 + 1, 4096)), dim3(kThreads), 0, e->stream, ba.P,
                          (const uint4*)e->d_orw, (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n);
@@ -1736,7 +1748,12 @@ agx_status setup_ring_apply(agx_engine* e) {
 
 // ORSet-only full-state populations: k_orset_merge's work list (before any graph capture)
 agx_status setup_orset(agx_engine* e) {
-  if (e->d_orw || apply_variant(e) != V_OR) return AGX_OK;
+  const uint32_t vid = apply_variant(e);
+  if (e->d_orw || (vid != V_OR && vid != V_LWWMAP)) return AGX_OK;
+  if (vid == V_LWWMAP) {
+    AGX_TRY(dalloc(&e->d_lww_step0, 1));
+    HIP_TRY(hipMemset(e->d_lww_step0, 0, 4));
+  }
   AGX_TRY(dalloc(&e->d_orw, e->n_local));
   AGX_TRY(dalloc(&e->d_orm, e->acap));
   AGX_TRY(dalloc(&e->d_orw_n, 2));
@@ -2467,7 +2484,7 @@ agx_status prepare_run(agx_engine* e) {
     // 3.93e9 word-major; ORSet delta 1.29e9 actor-major vs 1.17e9 word-major, its element rows
     // are read whole).  AGX_CRDT_LAYOUT=actor|word overrides.
     const char* lay = getenv("AGX_CRDT_LAYOUT");
-    const bool word_major = apply_variant(e) != V_OR &&  // (k_orset_merge walks actor-major rows)
+    const bool word_major = apply_variant(e) != V_OR && apply_variant(e) != V_LWWMAP &&  // (k_orset_merge / k_lwwmap_merge walk actor-major rows)
                             (lay ? lay[0] == 'w' : (e->delta_max && !(e->kinds_mask & kb(AGX_KIND_ORSET))));
     if (e->pw && !e->pitch && !word_major) {
       const uint32_t pitch = e->W <= 16 ? (e->W + 1u) & ~1u : (e->W + 15u) & ~15u;
@@ -2744,7 +2761,8 @@ agx_status read_counters(agx_engine* e, uint64_t* s) {
 agx_status error_status(const agx_engine* e, uint64_t err) {
   if (err & kErrRange)
     return set_err(AGX_ERANGE, "a GCounter/PNCounter slot exceeded 2^64 - 1 (u64 slots; the reference uses BigInt) or an "
-                   "ORSet replica's own version exceeded 2^32 - 1 (u32 versions; the reference uses Long)");
+                   "ORSet / LWWMap replica's own version exceeded 2^32 - 1 (u32 versions; the reference uses Long) or an LWWMap "
+                   "timestamp would pass the int64 range (the reference's Long would wrap)");
   if (err & kErrPrioTile)
     return set_err(AGX_ECAPACITY, "a bucket of %u actors that holds a priority-mailbox actor received more than one "
                    "tile of %d messages (backlog included): a prioritised actor's queue is ordered within one tile "
@@ -2829,6 +2847,7 @@ agx_status collect_stats(agx_engine* e, agx_stats* out, bool check) {
   if (km & kb(AGX_KIND_GCOUNTER)) sw = std::max<uint64_t>(sw, AGX_GCOUNTER_WORDS);
   if (km & kb(AGX_KIND_PNCOUNTER)) sw = std::max<uint64_t>(sw, AGX_PNCOUNTER_WORDS);
   if (km & kb(AGX_KIND_ORSET)) sw = std::max<uint64_t>(sw, e->delta_max ? AGX_DELTA_ENV_WORDS + 4 : AGX_ORSET_WORDS);
+  if (km & kb(AGX_KIND_LWWMAP)) sw = std::max<uint64_t>(sw, AGX_LWWMAP_WORDS);
   st.bytes_alg = 12ull * st.delivered + 12ull * st.emitted + (16ull * std::min<uint64_t>(sw, e->W) + 2ull) * bs[4];
   if (out) *out = st;
   return est;
@@ -2916,6 +2935,19 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
   hipEvent_t* ev = e->lag_ev;
   agx_status st = AGX_OK;
   uint32_t left = max_steps;
+  // LWWMap engines: k_lwwmap_merge's logical time is the superstep's number among the supersteps with mail.  Those
+  // are the first supersteps of a run, so the supersteps launched below have the numbers lww_next + 1, ..., from the
+  // count so far; every launch is preceded, in stream order, by the number its first superstep follows (the empty
+  // supersteps a replay runs after quiescence draw no timestamp)
+  uint32_t lww_next = 0;
+  if (e->d_lww_step0 && left) {
+    uint64_t dsteps = 0;
+    AGX_TRY(copy_sync(e, &dsteps, e->d_stats + ST_STEPS, 8, hipMemcpyDeviceToHost));
+    lww_next = (uint32_t)(dsteps + e->host_steps);
+  }
+  auto lww_mark = [&](uint32_t after) {
+    if (e->d_lww_step0) hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, e->stream, e->d_lww_step0, after);
+  };
   // fused with dense-alone strict replays: the superstep that consumes host-staged tells runs eagerly
   // (block launch beside the dense launch): every bucket with staged tells would otherwise leave the
   // dense launch and void the replay
@@ -2928,6 +2960,7 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
     e->hd_pay.clear();
   }
   if (left && e->n_staged_dev) {
+    lww_mark(lww_next++);
     st = launch_step_single(e);
     --left;
   }
@@ -2981,6 +3014,7 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
   const uint32_t left0 = left;
   uint32_t launched_steps = 0;
   bool recovered = false;
+  const uint32_t lww_run0 = lww_next;  // (the number the first superstep counted by launched_steps follows)
   int last_ring = -1;  // ring slot of the last fused replay launched (-1: eager work came last)
   auto fused_poll = [&](uint32_t slot) -> bool {
     const uint32_t* h = e->h_cntb + rep_ring[slot] * ring_row;
@@ -3031,6 +3065,8 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
     e->skew_only = !dense;
     e->recover_dense = dense;
     last_ring = -1;  // (eager launches after the replays: the error word is copied back)
+    lww_mark(lww_run0 + rep_start[slot]);  // (superstep k of that replay again: cur_slot = k)
+    lww_next = lww_run0 + rep_start[slot] + k + 1u;
     agx_status s2 = launch_apply(e, e->A);  // (advances e->par past superstep k)
     e->skew_only = false;
     e->recover_dense = false;
@@ -3103,6 +3139,7 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
     const uint32_t par0 = e->par;
     const bool eager_now = eager_first;
     eager_first = false;
+    lww_mark(lww_next);
     if (use_graph && eager_now) {  // one eager superstep, reported through the replay ring like a replay of 1
       cnt = 1;
       st = launch_step_single(e);
@@ -3130,6 +3167,7 @@ agx_status run_single(agx_engine* e, uint32_t max_steps) {
       st = launch_step_single(e);
     }
     left -= cnt;
+    lww_next += cnt;
     ++launched;
     if (e->fused) {  // per-superstep inbox sizes of this replay
       rep_steps[slot] = cnt;
@@ -3592,8 +3630,14 @@ void drop_graphs(agx_engine* e) {
 // First CRDT kind (or a wider one): size the snapshot heap for `kind`'s rows (full state, plus
 // deltaVersions and DeltaPropagation rows in delta-CRDT mode; include/akka_gpu.h).
 agx_status enable_crdt(agx_engine* e, uint32_t kind) {
+  static_assert((2 * AGX_LWWMAP_WORDS + kRowAlign - 1) / kRowAlign * kRowAlign >= kLwRowMax,
+                "the row pitch of an LWWMap engine holds the widest LWWMap snapshot row (agx_lwwmap.h)");
+  if (kind == AGX_KIND_LWWMAP && e->delta_max)
+    return set_err(AGX_EINVAL, "LWWMap replicas gossip their full state: not on an engine with delta-CRDT replication "
+                   "(agx_set_delta_crdt; ORMap delta ops are left out)");
   const uint32_t words = kind == AGX_KIND_GCOUNTER ? AGX_GCOUNTER_WORDS
-                         : kind == AGX_KIND_PNCOUNTER ? AGX_PNCOUNTER_WORDS : AGX_ORSET_WORDS;
+                         : kind == AGX_KIND_PNCOUNTER ? AGX_PNCOUNTER_WORDS
+                         : kind == AGX_KIND_LWWMAP ? AGX_LWWMAP_WORDS : AGX_ORSET_WORDS;
   const uint32_t need = !e->delta_max ? words
                         : kind == AGX_KIND_GCOUNTER ? AGX_GCOUNTER_DELTA_WORDS
                         : kind == AGX_KIND_PNCOUNTER ? AGX_PNCOUNTER_DELTA_WORDS : AGX_ORSET_DELTA_WORDS;
@@ -4020,7 +4064,7 @@ agx_status agx_destroy(agx_engine* e) {
   hipFree(e->d_rg_state); hipFree(e->d_rg_nz); hipFree(e->d_rg_src); hipFree(e->d_rg_pay); hipFree(e->d_rg_dk); hipFree(e->d_rg_ds);
   hipFree(e->d_rg_dp);
   hipFree(e->d_ring_next); hipFree(e->d_ring_free); hipFree(e->d_ring_total);
-  hipFree(e->d_orw); hipFree(e->d_orm); hipFree(e->d_orw_n);
+  hipFree(e->d_orw); hipFree(e->d_orm); hipFree(e->d_orw_n); hipFree(e->d_lww_step0);
   hipFree(e->d_ptab);
   hipFree(e->d_stash);
   hipFree(e->d_timers);
@@ -4055,7 +4099,13 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
   AGX_TRY(ensure_dev(e));
   AGX_TRY(sync_mirrors(e));  // device state is authoritative after a run
   const bool compiled = kind >= AGX_KIND_COMPILED && kind < AGX_KIND_COMPILED + AGX_MAX_BEHAVIORS;
-  if (first_id + count > e->n_global || (kind >= AGX_KIND_MAX && !compiled)) return set_err(AGX_EINVAL, "bad range or kind");
+  const bool lww = kind == AGX_KIND_LWWMAP;
+  if (first_id + count > e->n_global || (kind >= AGX_KIND_MAX && !compiled && !lww)) return set_err(AGX_EINVAL, "bad range or kind");
+  if (lww && e->R > 1) return set_err(AGX_EINVAL, "LWWMap replicas need a single-rank engine (n_ranks %u)", e->R);
+  // an LWWMap engine holds LWWMap replicas only (unregistering, AGX_KIND_NONE, stays possible)
+  if (count && kind != AGX_KIND_NONE && (lww ? (e->kinds_mask & ~(kb(AGX_KIND_NONE) | kb(AGX_KIND_LWWMAP))) != 0
+                                             : (e->kinds_mask & kb(AGX_KIND_LWWMAP)) != 0))
+    return set_err(AGX_EINVAL, "LWWMap replicas and actors of another kind (%u) need separate engines", lww ? 0u : kind);
   const uint32_t kCrdtMask = kb(AGX_KIND_GCOUNTER) | kb(AGX_KIND_PNCOUNTER) | kb(AGX_KIND_ORSET);
   if (count && ((compiled && (e->kinds_mask & kCrdtMask)) ||
                 (kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET && (e->kinds_mask & kb(AGX_KIND_COMPILED)))))
@@ -4077,7 +4127,7 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
                      "its entities are started by their first message", (unsigned long long)first_id,
                      (unsigned long long)(first_id + count), (unsigned long long)c0, (unsigned long long)c1);
   }
-  if (kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET) AGX_TRY(enable_crdt(e, kind));
+  if ((kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET) || lww) AGX_TRY(enable_crdt(e, kind));
   if (count && !(e->kinds_mask & kb(kind))) {  // the apply variant is captured in the superstep graphs
     e->kinds_mask |= kb(kind);
     drop_graphs(e);
@@ -5720,10 +5770,27 @@ agx_status agx_set_delta_crdt(agx_engine* e, uint32_t max_delta_size) {
   if (max_delta_size && e->kmax < 4) return set_err(AGX_EINVAL, "delta-CRDT replicas need max_emit >= 4");
   if (max_delta_size && e->n_global >= (1ull << 30)) return set_err(AGX_EINVAL, "delta-CRDT needs n_actors < 2^30");
   if (e->started && max_delta_size != e->delta_max) return set_err(AGX_ESTATE, "set delta-CRDT mode before agx_run");
+  if (max_delta_size && (e->kinds_mask & kb(AGX_KIND_LWWMAP)))
+    return set_err(AGX_EINVAL, "delta-CRDT replication on an engine with LWWMap replicas: they gossip their full state "
+                   "(ORMap delta ops are left out)");
   e->delta_max = max_delta_size;
   for (uint32_t k = AGX_KIND_GCOUNTER; k <= AGX_KIND_ORSET; ++k)
     if (e->kinds_mask & kb(k)) AGX_TRY(enable_crdt(e, k));
   drop_graphs(e);
+  return AGX_OK;
+}
+
+agx_status agx_set_lwwmap(agx_engine* e, uint32_t clock, uint64_t base) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  if (!(e->kinds_mask & kb(AGX_KIND_LWWMAP)))
+    return set_err(AGX_EINVAL, "agx_set_lwwmap: the engine has no LWWMap replicas (register them first)");
+  if (clock != AGX_LWW_CLOCK_DEFAULT && clock != AGX_LWW_CLOCK_REVERSE)
+    return set_err(AGX_EINVAL, "agx_set_lwwmap: unknown clock %u (AGX_LWW_CLOCK_DEFAULT, AGX_LWW_CLOCK_REVERSE)", clock);
+  if (base >= (1ull << 62)) return set_err(AGX_EINVAL, "agx_set_lwwmap: base must be < 2^62");
+  if (e->started) return set_err(AGX_ESTATE, "set the LWWMap clock before the first agx_run");
+  e->lww_clock = clock;
+  e->lww_base = base;
+  drop_graphs(e);  // (kernel arguments of the captured supersteps)
   return AGX_OK;
 }
 

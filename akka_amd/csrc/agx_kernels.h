@@ -27,6 +27,7 @@
 // Envelopes are SoA u32 {key, src, payload} = 12 B.
 #pragma once
 #include "agx_crdt.h"
+#include "agx_lwwmap.h"
 #include "agx_device.h"
 
 namespace agx {
@@ -2376,12 +2377,16 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     // message at the whole pitch, so a mixed delta population, whose counter groups have no length
     // word, never reads one (tests/test_gpu_delta_mixed.py)
     constexpr bool kBigRows = kWide && (KM & kb(AGX_KIND_ORSET)) != 0;
+    // LWWMap populations (V_LWWMAP, up to 2944-B rows): the wave copies too, each row by the used length it
+    // carries (kLwRowLen, agx_lwwmap.h)
+    constexpr bool kLwRows = kWide && KM == kb(AGX_KIND_LWWMAP);
+    constexpr bool kWaveRows = kBigRows || kLwRows;
     static_assert(!kBigRows || !(KM & kDeltaKM) || (KM & ~kDeltaKM) == kb(AGX_KIND_ORSET),
                   "a delta variant that copies rows by their used length holds ORSet groups only: counter groups "
                   "write no length word (dl_group_row)");
-    const uint32_t qstart = kBigRows ? (uint32_t)tid - lane_id() : (uint32_t)tid;
+    const uint32_t qstart = kWaveRows ? (uint32_t)tid - lane_id() : (uint32_t)tid;
     for (uint32_t qb = qstart; qb < cnt; qb += kBThreads) {  // queued messages, in actor order
-      const uint32_t q = kBigRows ? qb + lane_id() : qb;
+      const uint32_t q = kWaveRows ? qb + lane_id() : qb;
       const bool valid = q < cnt;
       const uint32_t key = valid ? ikey(q) : 0u;
       const uint32_t la = key & ((1u << a.bb) - 1u);
@@ -2418,7 +2423,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)leader);
           const uint32_t h = base + (uint32_t)__popcll(m & lanemask_lt());
           if (need && h >= H.rows) atomicOr((unsigned long long*)&a.stats[ST_ERROR], (unsigned long long)kErrCapacity);
-          if (!kBigRows && need && h < H.rows) {  // counter rows: each lane its own
+          if (!kWaveRows && need && h < H.rows) {  // counter rows: each lane its own
             const uint4* s = reinterpret_cast<const uint4*>(H.row(pv & kHandleMask));
             uint4* d = reinterpret_cast<uint4*>(H.wrow(h));
             for (uint32_t k2 = 0; k2 < H.pw / 4; ++k2) d[k2] = s[k2];
@@ -2426,7 +2431,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
           // ORSet rows (2 KB): the wave copies them one after the other, 16 B per lane -- whole
           // lines per instruction instead of each lane walking its own row in a load-store chain
           // (same-box A/B: C4 ORSet +10 %, ORSet delta +18 %)
-          for (uint64_t mm = kBigRows ? m : 0ull; mm; mm &= mm - 1) {
+          for (uint64_t mm = kWaveRows ? m : 0ull; mm; mm &= mm - 1) {
             const int i = __builtin_ctzll(mm);
             const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)h, i);
             const uint32_t pi = (uint32_t)__builtin_amdgcn_readlane((int)pv, i), si = pi & kHandleMask;
@@ -2442,6 +2447,8 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
                 n4 = min(q4, (used + 3u) / 4u);
                 if (lane == 0 && n4 < q4) d[q4 - 1] = s[q4 - 1];  // (the length word travels too)
               }
+              if constexpr (kLwRows)  // (the length word lies in the row's header: it travels with the copy)
+                n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kLwRowLen] + 3u) / 4u);
               for (uint32_t k2 = lane; k2 < n4; k2 += kWave) d[k2] = s[k2];
             }
           }
@@ -3542,6 +3549,10 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       mbox_limits(P, L.alive[la], Ca, Ta);
       const uint32_t nd = min(len, Ta);
       uint32_t kd = L.kind[la];
+      constexpr bool kLwWaveA = kWide && KM == kb(AGX_KIND_LWWMAP);  // (an LWWMap engine holds LWWMap replicas only)
+      if constexpr (kLwWaveA) {
+        for (uint32_t q = 0; q < nd; ++q) em.count(lwwmap_count(P, isrc(s0 + q), ipay(s0 + q), &nrows_t));
+      } else
       if (kWide && is_crdt(kd)) {
         DeltaSim ds;
         ds.on = false;
@@ -3611,12 +3622,15 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     // (ORSet-only full-state variant: the state effects of each replica's run are applied by
     // k_orset_merge after the apply; L.ecnt[la] = the run's first snapshot row, or ~0)
     constexpr bool kOrWave = kWide && KM == kb(AGX_KIND_ORSET);
+    // (LWWMap-only variant: the same split, lwwmap_protocol here and k_lwwmap_merge after the apply)
+    constexpr bool kLwWave = kWide && KM == kb(AGX_KIND_LWWMAP);
+    constexpr bool kWaveList = kOrWave || kLwWave;
   #pragma unroll 1
     for (int j = 0; j < kBAct; ++j) {
       const uint32_t la = j * kBThreads + tid;
       const uint32_t s0 = L.seg[la], len = L.seg[la + 1] - s0;
       if (la >= na || !len || !(L.alive[la] & 1u)) {
-        if constexpr (kOrWave) L.ecnt[la] = 0xFFFFFFFFu;
+        if constexpr (kWaveList) L.ecnt[la] = 0xFFFFFFFFu;
         continue;
       }
       const uint32_t l = a0 + la;
@@ -3628,6 +3642,13 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       const uint32_t nd = min(len, Ta);
       uint32_t kd = L.kind[la];
       ++nact;
+      if constexpr (kLwWave) {  // protocol here, state effects by k_lwwmap_merge (agx_lwwmap.h)
+        bool work = false;
+        const uint32_t rc0 = row_cursor;
+        nunh += lwwmap_protocol(P, self, s0, nd, isrc, ipay, row_cursor, em, &work);
+        ndel += nd;
+        L.ecnt[la] = work ? rc0 : 0xFFFFFFFFu;  // (this actor's tell offset is no longer needed)
+      } else
       if (kWide && is_crdt(kd)) {
         if constexpr (kOrWave) {  // protocol here, state effects by k_orset_merge (agx_crdt.h)
           bool work = false;
@@ -3715,7 +3736,7 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
                em.n_all, em.n_valid, nall, (unsigned long long)em.pos, (unsigned long long)(embase + L.ecnt[la]));
 #endif
     }
-    if constexpr (kOrWave) {  // the runs with state work -> k_orset_merge's list (wave-aggregated slots)
+    if constexpr (kWaveList) {  // the runs with state work -> k_orset_merge's / k_lwwmap_merge's list (wave-aggregated slots)
       const uint32_t lane = lane_id();
   #pragma unroll 1
       for (int j = 0; j < kBAct; ++j) {
@@ -7166,6 +7187,25 @@ static __global__ void __launch_bounds__(kThreads) k_orset_merge(DevParams P, co
     const uint2* msg = orm + w.z;
     orset_merge_wave(P, H, w.x, w.y & 0xFFu, 0u, w.y >> 8, w.w, [&](uint32_t q) { return msg[q].x; },
                      [&](uint32_t q) { return msg[q].y; });
+  }
+}
+
+// LWWMap-only populations: the state effects of every replica run the apply listed (lwwmap_protocol did
+// its tells and snapshot-row allocation): one wave per replica, lane = key (lwwmap_merge_wave).  The
+// LWWRegister clock's logical time is base + the superstep's number: *step0 supersteps with mail ran
+// before this replay (written by the host, stream-ordered), `slot` = the superstep's place in the replay.
+static __global__ void __launch_bounds__(kThreads) k_lwwmap_merge(DevParams P, const uint4* orw, const uint2* orm,
+                                                              const uint32_t* orw_n, const uint32_t* step0, uint32_t slot,
+                                                              uint32_t clock, long long base) {
+  const uint32_t n = orw_n[0];
+  const CrdtHeap H = crdt_heap(P);
+  const int64_t now = (int64_t)base + (int64_t)((uint64_t)*step0 + slot + 1ull);
+  const uint32_t nw = gridDim.x * (kThreads / kWave);
+  for (uint32_t it = blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave; it < n; it += nw) {
+    const uint4 w = orw[it];
+    const uint2* msg = orm + w.z;
+    lwwmap_merge_wave(P, H, w.x, w.y & 0xFFu, w.y >> 8, w.w, clock, now, [&](uint32_t q) { return msg[q].x; },
+                      [&](uint32_t q) { return msg[q].y; });
   }
 }
 

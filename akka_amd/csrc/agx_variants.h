@@ -22,6 +22,7 @@ enum : uint32_t {
   V_GC_DELTA = 0, V_PN_DELTA, V_OR_DELTA, V_ALL_DELTA,
   V_GC, V_PN, V_OR, V_CRDT, V_ALL_WIDE,
   V_RING, V_FWD, V_FANOUT, V_COUNTER, V_COMPILED, V_ALL_COMPILED, V_ALL,
+  V_LWWMAP,  // LWWMap replicas only (agx_lwwmap.h); appended: the ids above do not move
   V_N
 };
 constexpr ApplyVariant kVariants[V_N] = {
@@ -33,7 +34,10 @@ constexpr ApplyVariant kVariants[V_N] = {
     {false, kb(AGX_KIND_FORWARD_RR)},         {false, kb(AGX_KIND_FANOUT)},
     {false, kb(AGX_KIND_COUNTER)},            {false, kb(AGX_KIND_COMPILED)},
     {false, KM_ALL | kb(AGX_KIND_COMPILED)},  {false, KM_ALL},
+    {true, kb(AGX_KIND_LWWMAP)},
 };
+static_assert((kb(AGX_KIND_LWWMAP) & (KM_ALL | kCrdtKM | kb(AGX_KIND_COMPILED))) == 0 && kb(AGX_KIND_LWWMAP) < kBackoffKM,
+              "the LWWMap kind has a mask bit of its own");
 
 // pipeline modes: fused single-rank gather (kGather), multi-rank owner grouping (kOwner),
 // single-rank multi-pass with the backlog in place (neither)
@@ -41,10 +45,12 @@ enum : uint32_t { M_FUSED = 0, M_OWNER = 1, M_BYPASS = 2, M_PERSIST = 3 /* dense
 
 // variant groups = translation units (agx_apply.hip built with -DAGX_VGROUP=0..kVGroups-1);
 // the heavy CRDT variants are spread so the units take similar time
-constexpr uint32_t kVGroups = 9;
+constexpr uint32_t kVGroups = 10;
 // the last group holds no variant of the table: it is the unit of the kSuperKM | kBackoffKM feature launches alone
 constexpr uint32_t kBackoffGroup = 8;
-constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7};
+// V_LWWMAP and k_lwwmap_merge are a unit of their own too, so that every other unit compiles what it compiled before
+constexpr uint32_t kLwwmapGroup = 9;
+constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7, kLwwmapGroup};
 
 // launch k_bucket_apply<variant vid, mode, skew> with `grid` x kBThreads threads on `s`
 // (defined in agx_apply.hip; returns hipErrorInvalidValue for an unknown combination)
@@ -58,6 +64,10 @@ hipError_t agx_launch_apply(uint32_t vid, uint32_t mode, bool skew, dim3 grid, h
 // (hipErrorInvalidValue otherwise)
 hipError_t agx_launch_apply_feature(uint32_t vid, uint32_t mode, uint32_t km_flags, bool prio, dim3 grid, hipStream_t s,
                                     const BucketArgs& ba);
+// launch k_lwwmap_merge after V_LWWMAP's apply (defined in kLwwmapGroup's unit): the runs the apply listed in
+// orw / orm / orw_n; the clock's logical time is base + *step0 + slot + 1 (agx_kernels.h)
+hipError_t agx_launch_lwwmap_merge(dim3 grid, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
+                                   const uint32_t* orw_n, const uint32_t* step0, uint32_t slot, uint32_t clock, int64_t base);
 // launch k_tiny_apply<variant vid's kinds> (plain / compiled variants only: hipErrorInvalidValue otherwise)
 hipError_t agx_launch_tiny(uint32_t vid, dim3 grid, hipStream_t s, const BucketArgs& ba);
 // launch k_dense_apply<variant vid's kinds> (mode M_FUSED / M_OWNER: k_dense_fused) (plain / compiled variants only)

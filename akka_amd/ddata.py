@@ -1,0 +1,101 @@
+"""Read side of the replicated data types the engine holds: decode a replica's state words.
+
+    from akka_amd.ddata import LWWMap
+    words, _ = eng.read_state()
+    m = LWWMap.from_words(words[replica])
+    m.entries            # {key: value}
+    m.get(3), m.contains(3), m.size, m.timestamp(3), m.updated_by(3)
+
+The layout is include/akka_gpu.h "LWWMap replicas": the ORSet key set (64 keys x 8 u32 dots, 8 u32
+version vector), 64 int64 timestamps, 64 u32 registers (updatedBy node << 24 | value).  Writes go
+through the engine (Op.put, Op.REMOVE); `to_words` exists to seed replicas (register_range).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from .engine import CRDT_NODES, CRDT_WORDS, Kind, LWW_VALUE_MAX, ORSET_ELEMS
+
+LWWMAP_WORDS = CRDT_WORDS[Kind.LWWMAP]
+_VV = ORSET_ELEMS * CRDT_NODES          # u32 index of the version vector
+_TS = CRDT_WORDS[Kind.ORSET]            # u64 index of key 0's timestamp
+_REG = 2 * (_TS + ORSET_ELEMS)          # u32 index of key 0's register
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+@dataclass
+class LWWMap:
+    """One replica's LWWMap: per live key its dots {node: version}, and its LWWRegister
+    (updatedBy node, value, timestamp); the key set's version vector {node: version}."""
+    dots: dict = field(default_factory=dict)        # key -> {node: version}, live keys only
+    vvector: dict = field(default_factory=dict)     # node -> version
+    registers: dict = field(default_factory=dict)   # key -> (node, value, timestamp)
+
+    @classmethod
+    def from_words(cls, row) -> "LWWMap":
+        w = np.ascontiguousarray(np.asarray(row, np.uint64)[:LWWMAP_WORDS])
+        if w.size != LWWMAP_WORDS:
+            raise ValueError(f"an LWWMap replica has {LWWMAP_WORDS} state words, got {w.size}")
+        u = w.view(np.uint32)
+        ts = w[_TS:_TS + ORSET_ELEMS].view(np.int64)
+        m = cls()
+        for k in range(ORSET_ELEMS):
+            d = {n: int(u[k * CRDT_NODES + n]) for n in range(CRDT_NODES) if u[k * CRDT_NODES + n]}
+            r = int(u[_REG + k])
+            if d:
+                m.dots[k] = d
+                m.registers[k] = (r >> 24, r & 0xFFFFFF, int(ts[k]))
+            elif r or ts[k]:
+                raise ValueError(f"key {k} has no live dot but a register ({r:#x}, {int(ts[k])}): not canonical")
+        m.vvector = {n: int(u[_VV + n]) for n in range(CRDT_NODES) if u[_VV + n]}
+        return m
+
+    def to_words(self) -> np.ndarray:
+        w = np.zeros(LWWMAP_WORDS, np.uint64)
+        u = w.view(np.uint32)
+        ts = w[_TS:_TS + ORSET_ELEMS].view(np.int64)
+        if set(self.dots) != set(self.registers):
+            raise ValueError("every live key has exactly one register")
+        for k, d in self.dots.items():
+            if not 0 <= k < ORSET_ELEMS or not d:
+                raise ValueError(f"key {k}: outside the 64-key universe, or without a dot")
+            for n, v in d.items():
+                if not (0 <= n < CRDT_NODES and 0 < v < 1 << 32):
+                    raise ValueError(f"dot ({k}, {n}) -> {v} does not fit the layout")
+                u[k * CRDT_NODES + n] = v
+            node, value, t = self.registers[k]
+            if not (0 <= node < CRDT_NODES and 0 <= value <= LWW_VALUE_MAX and INT64_MIN <= t <= INT64_MAX):
+                raise ValueError(f"register of key {k} {self.registers[k]} does not fit the layout")
+            u[_REG + k] = (node << 24) | value
+            ts[k] = t
+        for n, v in self.vvector.items():
+            if not (0 <= n < CRDT_NODES and 0 < v < 1 << 32):
+                raise ValueError(f"version vector entry {n} -> {v} does not fit the layout")
+            u[_VV + n] = v
+        return w
+
+    @property
+    def entries(self) -> dict:
+        """LWWMap.entries: {key: value}."""
+        return {k: r[1] for k, r in sorted(self.registers.items())}
+
+    def get(self, key: int):
+        r = self.registers.get(key)
+        return None if r is None else r[1]
+
+    def contains(self, key: int) -> bool:
+        return key in self.registers
+
+    @property
+    def size(self) -> int:
+        return len(self.registers)
+
+    def timestamp(self, key: int):
+        r = self.registers.get(key)
+        return None if r is None else r[2]
+
+    def updated_by(self, key: int):
+        r = self.registers.get(key)
+        return None if r is None else r[0]

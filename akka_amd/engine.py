@@ -29,14 +29,18 @@ class Kind:
     GCOUNTER = 8      # Replicator-style replicas (akka-distributed-data), include/akka_gpu.h "CRDT behaviours"
     PNCOUNTER = 9
     ORSET = 10
+    LWWMAP = 11       # LWWMap = ORMap of LWWRegister (AGX_KIND_LWWMAP, not in the enum), "LWWMap replicas"
 
 
 CRDT_NODES = 8
 ORSET_ELEMS = 64
-CRDT_WORDS = {Kind.GCOUNTER: 8, Kind.PNCOUNTER: 16, Kind.ORSET: 260}
+CRDT_WORDS = {Kind.GCOUNTER: 8, Kind.PNCOUNTER: 16, Kind.ORSET: 260, Kind.LWWMAP: 356}
 # delta-CRDT mode (agx_set_delta_crdt): data + envelope/selector area + delta log (include/akka_gpu.h)
 DELTA_ENV_WORDS, DELTA_LOG = 12, 64
-CRDT_DELTA_WORDS = {k: w + DELTA_ENV_WORDS + (DELTA_LOG * 6 if k == Kind.ORSET else 4) for k, w in CRDT_WORDS.items()}
+CRDT_DELTA_WORDS = {k: w + DELTA_ENV_WORDS + (DELTA_LOG * 6 if k == Kind.ORSET else 4) for k, w in CRDT_WORDS.items()
+                    if k != Kind.LWWMAP}  # (LWWMap replicas gossip their full state only)
+LWW_VALUE_MAX = 0x3FFFF
+LWW_CLOCKS = {"default": 0, "reverse": 1}  # AGX_LWW_CLOCK_DEFAULT / AGX_LWW_CLOCK_REVERSE
 DELTA_WRITE = 0x800000
 WIDE_BIT = 0x80000000
 
@@ -50,10 +54,20 @@ class Op:
     CLEAR = 5
     GOSSIP = 6
     DELTA_TICK = 7
+    PUT = 8
 
     @staticmethod
     def make(op: int, arg: int = 0) -> int:
         return ((op & 0xFF) << 24) | (arg & 0xFFFFFF)
+
+    @staticmethod
+    def put(key: int, value: int) -> int:
+        """LWWMap.put(key, value) on an LWWMap replica: key < 64, value < 2^18 (AGX_OP_PUT_ARG)."""
+        if not 0 <= key < ORSET_ELEMS:
+            raise ValueError(f"LWWMap key {key} outside the 64-key universe")
+        if not 0 <= value <= LWW_VALUE_MAX:
+            raise ValueError(f"LWWMap value {value} does not fit 18 bits")
+        return Op.make(Op.PUT, key | (value << 6))
 
 
 @dataclass
@@ -607,6 +621,15 @@ class GpuEngine:
     def set_delta_crdt(self, max_delta_size: int) -> None:
         """Replicator delta-crdt.enabled / max-delta-size (0 = off)."""
         check(self.lib.agx_set_delta_crdt(self._h, max_delta_size))
+
+    def set_lwwmap(self, clock: str = "default", base: int = 0) -> None:
+        """The LWWRegister clock of an LWWMap engine: "default" (last write wins) or "reverse" (first write
+        wins), logical time base + superstep number.  After registering the replicas, before the first run."""
+        if clock not in LWW_CLOCKS:
+            raise ValueError(f"unknown LWWMap clock {clock!r} (one of {sorted(LWW_CLOCKS)})")
+        if not 0 <= base < 1 << 64:
+            raise ValueError("LWWMap clock base must be an unsigned 64-bit integer")
+        check(self.lib.agx_set_lwwmap(self._h, LWW_CLOCKS[clock], base))
 
     def set_fanout(self, k: int, seed: int, cdf, perm) -> None:
         cdf = _u32(cdf)

@@ -38,6 +38,7 @@ class Workload:
     ring_stride: int | None = None
     gossip: tuple | None = None  # (fanout, seed)
     delta_crdt: int = 0          # Replicator max-delta-size (0 = full-state gossip only)
+    lwwmap: tuple | None = None  # (clock, base) of an LWWMap engine (agx_set_lwwmap)
     behaviors: object = None     # compiled behaviour tables (akka_amd.typed.Tables)
     fanout: tuple | None = None  # (k, seed, cdf, perm)
     graph: tuple | None = None   # (row_ptr, col)
@@ -110,6 +111,8 @@ class Workload:
             target.set_gossip(*self.gossip)
         if self.delta_crdt:
             target.set_delta_crdt(self.delta_crdt)
+        if self.lwwmap is not None:
+            target.set_lwwmap(*self.lwwmap)
         if self.behaviors is not None:
             target.set_behaviors(self.behaviors)
         if self.receptionist:  # (empty: targets without the calls are unaffected)
@@ -263,6 +266,45 @@ def crdt_gossip(n: int = 1_000_000, kind: int = Kind.GCOUNTER, rounds: int = 32,
     # the ~3 x 512 messages in one 2048-message apply tile (the fast path)
     return Workload(f"crdt_gossip_{kind}", n, CRDT_WORDS[kind], fanout + 1, throughput, capacity,
                     [(0, n, kind, None)], gossip=(fanout, seed), tells=(dst, src, pay), bucket_actors=512)
+
+
+def lwwmap_ops(nw: int, puts: int, removes: int, keys: int = 12, seed: int = SEED) -> np.ndarray:
+    """Round-0 local updates of the `nw` writers of an LWWMap population, one row per writer: `puts` seeded puts
+    with `removes` removes spread among them, all over the first `keys` keys, so that writers collide on keys."""
+    per = puts + removes
+    out = np.zeros((nw, per), np.uint32)
+    a = np.arange(nw, dtype=np.uint64)
+    rm_at = set((np.arange(removes) * per // max(removes, 1) + per // (2 * max(removes, 1))).tolist()) if removes else set()
+    for j in range(per):
+        r = splitmix64_np((a << np.uint64(8)) ^ np.uint64(j) ^ np.uint64(seed * 13))
+        key = (r % np.uint64(keys)).astype(np.uint32)
+        val = ((r >> np.uint64(20)) & np.uint64(0x3FFFF)).astype(np.uint32)
+        if j in rm_at:
+            out[:, j] = (np.uint32(Op.REMOVE) << np.uint32(24)) | key
+        else:
+            out[:, j] = (np.uint32(Op.PUT) << np.uint32(24)) | key | (val << np.uint32(6))
+    return out
+
+
+def crdt_lwwmap(n: int = 1_000_000, rounds: int = 32, fanout: int = 2, puts_per_writer: int = 16, removes: int = 4,
+                throughput: int = 5, seed: int = SEED, capacity: int = 0, clock: str = "default", base: int = 0,
+                bucket_actors: int = 512) -> Workload:
+    """LWWMap replicas (LWWMap = ORMap of LWWRegister) in crdt_gossip's shape: replicas 0..7 are the writers, one
+    per node slot, and first apply seeded puts and removes over a dozen keys (host tells), so that writers collide
+    on keys; then every replica runs `rounds` GossipTicks.  The population converges to the merge of the writers'
+    maps; the LWWRegister timestamps are logical time (`base` + superstep number) under `clock`."""
+    nw = min(n, CRDT_NODES)
+    per = puts_per_writer + removes
+    ops = lwwmap_ops(nw, puts_per_writer, removes, seed=seed).reshape(-1)
+    odst = np.repeat(np.arange(nw, dtype=np.uint32), per)
+    tdst = np.arange(n, dtype=np.uint32)
+    tick = np.full(n, Op.make(Op.GOSSIP, rounds - 1), np.uint32)
+    dst = np.concatenate([odst, tdst])
+    pay = np.concatenate([ops, tick])
+    src = np.full(dst.size, NO_SENDER, np.uint32)
+    return Workload("crdt_lwwmap", n, CRDT_WORDS[Kind.LWWMAP], fanout + 1, throughput, capacity,
+                    [(0, n, Kind.LWWMAP, None)], gossip=(fanout, seed), lwwmap=(clock, base), tells=(dst, src, pay),
+                    bucket_actors=bucket_actors)
 
 
 def crdt_delta(n: int = 1_000_000, kind: int = Kind.ORSET, rounds: int = 32, write: bool = True,

@@ -125,6 +125,10 @@ enum agx_behavior_kind {
  * (payload >> 24), its argument (payload & 0xFFFFFF), state word `word`, the sender id or
  * the actor's own id.  Comparisons are unsigned 64-bit.                              */
 #define AGX_KIND_COMPILED 16u
+/* an LWWMap replica (see "LWWMap replicas" below).  Not in enum agx_behavior_kind and above
+ * AGX_KIND_MAX: agx_register_range accepts it explicitly, and code that only knows the enum keeps
+ * refusing it. */
+#define AGX_KIND_LWWMAP 11u
 #define AGX_MAX_BEHAVIORS 64u
 #define AGX_MAX_CASES 1024u
 #define AGX_MAX_ACTS 4096u
@@ -368,6 +372,51 @@ typedef struct agx_act {
 #define AGX_PNCOUNTER_DELTA_WORDS (AGX_PNCOUNTER_WORDS + AGX_DELTA_ENV_WORDS + AGX_COUNTER_DELTA_U32 / 2u)
 #define AGX_ORSET_DELTA_WORDS (AGX_ORSET_WORDS + AGX_DELTA_ENV_WORDS + AGX_DELTA_LOG * 6u)
 
+/* --- LWWMap replicas (AGX_KIND_LWWMAP) -------------------------------------------------------
+ * LWWMap[A, B] = ORMap[A, LWWRegister[B]] over the 64-key universe (DD/LWWMap.scala:144-150,175-187;
+ * DD/ORMap.scala:254-265 put, :361-366 remove, :379-409 merge; DD/LWWRegister.scala:24-38 clocks,
+ * :192-199 withValue / merge).  node = id % AGX_CRDT_NODES as for the other CRDT kinds.
+ * State, AGX_LWWMAP_WORDS u64 per replica:
+ *   w[0..259]              ORMap.keys: bit for bit the AGX_KIND_ORSET layout (64 keys x 8 u32 dots, the
+ *                          8 u32 version vector)
+ *   w[260 + k]             key k's LWWRegister.timestamp, an int64 in two's complement, compared signed
+ *   u32 view, 648 + k      key k's (updatedBy node << 24) | value, value < 2^18   (w[324..355])
+ * Canonical form: a key without a live dot has timestamp 0 and register word 0 (ORMap `values - key`);
+ * every operation leaves this form, so states compare bit for bit.
+ * Ops (control tells):
+ *   AGX_OP_PUT     arg = key | value << 6   LWWMap.put(node, key, value, clock): timestamp' =
+ *                  clock(timestamp) if the key is present, else clock(0); register = (node, value,
+ *                  timestamp'); the key is added as AGX_OP_ADD adds an ORSet element (vvector + 1,
+ *                  one birth dot).  (AGX_OP_PUT_ARG packs the argument: every 24-bit argument is a put.)
+ *   AGX_OP_REMOVE  arg = key < 64           ORMap.remove: dots cleared as in the ORSet kind, register
+ *                  cleared; key >= 64 is Behaviors.unhandled
+ *   AGX_OP_GOSSIP  as for the other kinds; the state gossip's payload carries data type 3
+ *   every other op (INCREMENT, DECREMENT, ADD, CLEAR, DELTA_TICK, unknown) is Behaviors.unhandled.
+ * Merge of a received snapshot: the keys merge by ORSet.merge; a key of the merged set present on both
+ * sides takes LWWRegister.merge (the higher timestamp wins, on a tie the lower node, else `this`
+ * stays), a key present on one side takes that side's register, a key absent from the merged set has
+ * its register cleared.
+ * Clock (agx_set_lwwmap; logical time, so that runs are reproducible): now = base + s, where s is
+ * the number of supersteps with mail the engine has run so far, the one that drains the put included
+ * (agx_stats.supersteps at that superstep: 1 for the first superstep of a fresh engine).  A run
+ * without mail executes no superstep with mail and does not advance s; the empty supersteps a
+ * replayed batch may run after quiescence do not count either.
+ *   AGX_LWW_CLOCK_DEFAULT  max(now, timestamp + 1)     LWWRegister.defaultClock
+ *   AGX_LWW_CLOCK_REVERSE  min(-now, timestamp - 1)    LWWRegister.reverseClock (first write wins)
+ * A timestamp that would pass the int64 range raises AGX_ERANGE (the reference's Long would wrap),
+ * as a wrapping ORSet version does.
+ * An LWWMap engine holds LWWMap replicas only, on one rank, with full-state gossip.  Left out:
+ * LWWRegister as a kind of its own, PNCounterMap, ORMultiMap, GSet, Flag, ORMap delta ops, pruning,
+ * multi-rank engines, custom clocks, the JVM shim.                                               */
+#define AGX_LWWMAP_WORDS 356u /* 260 (keys) + 64 (timestamps) + 32 (64 u32 registers) */
+#define AGX_LWWMAP_TS_WORD 260u
+#define AGX_LWWMAP_REG_U32 648u
+#define AGX_LWWMAP_VALUE_MAX 0x3FFFFu
+#define AGX_OP_PUT 8u
+#define AGX_OP_PUT_ARG(key, value) (((uint32_t)(key) & 63u) | ((uint32_t)(value) << 6))
+#define AGX_LWW_CLOCK_DEFAULT 0u
+#define AGX_LWW_CLOCK_REVERSE 1u
+
 typedef struct agx_cfg {
   uint32_t abi_version;   /* must be AGX_ABI_VERSION                                   */
   uint32_t device;        /* HIP device ordinal                                        */
@@ -430,6 +479,11 @@ agx_status agx_set_gossip(agx_engine* eng, uint32_t fanout, uint64_t seed);
  * (see "delta-CRDT replication" above).  Call before the first agx_run; CRDT actors then need
  * n_words >= the *_DELTA_WORDS of their kind.                                               */
 agx_status agx_set_delta_crdt(agx_engine* eng, uint32_t max_delta_size);
+/* The LWWRegister clock of an LWWMap engine (see "LWWMap replicas" above): clock =
+ * AGX_LWW_CLOCK_DEFAULT / AGX_LWW_CLOCK_REVERSE, base < 2^62.  Optional (default clock, base 0);
+ * call after registering the LWWMap replicas and before the first agx_run (AGX_ESTATE afterwards).
+ * AGX_EINVAL: an engine without LWWMap replicas, an unknown clock, base >= 2^62.                  */
+agx_status agx_set_lwwmap(agx_engine* eng, uint32_t clock, uint64_t base);
 /* Compiled behaviours (see "compiled behaviours" above): behaviour b = cases
  * [first[b], first[b+1]); first has n_behaviors + 1 entries.  Replaces the tables of an
  * earlier call; call before agx_run.  Register actors with kind AGX_KIND_COMPILED + b.      */
