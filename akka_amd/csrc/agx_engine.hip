@@ -893,6 +893,7 @@ uint32_t apply_variant(const agx_engine* e) {
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN;
     if (km == kb(AGX_KIND_ORSET)) return V_OR;
     if (km == kb(AGX_KIND_LWWMAP)) return V_LWWMAP;  // (an LWWMap engine holds nothing else: agx_register_range)
+    if (km == kb(AGX_KIND_PNCOUNTERMAP)) return V_PNCMAP;  // (nor does a PNCounterMap engine)
     if ((km & ~kCrdtKM) == 0) return V_CRDT;  // CRDT kinds only: no plain-behaviour code
     return V_ALL_WIDE;
   }
@@ -1522,7 +1523,8 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
   {
     const uint32_t vid = apply_variant(e);
     const bool lwm = vid == V_LWWMAP;       // LWWMap-only: state effects in k_lwwmap_merge
-    const bool orm = vid == V_OR || lwm;  // ORSet-only full state: state effects in k_orset_merge
+    const bool pnm = vid == V_PNCMAP;       // PNCounterMap-only: state effects in k_pncmap_merge
+    const bool orm = vid == V_OR || lwm || pnm;  // ORSet-only full state: state effects in k_orset_merge
     if (orm) {
       if (!e->d_orw || (lwm && !e->d_lww_step0)) return set_err(AGX_ESTATE, "ORSet work list not allocated (setup_orset)");
       ba.orw = e->d_orw;
@@ -1619,6 +1621,10 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       HIP_TRY(agx_launch_lwwmap_merge(dim3(grid_for(e->n_local / 4 + 1, 4096)), e->stream, ba.P, (const uint4*)e->d_orw,
                                       (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n, e->d_lww_step0, e->cur_slot,
                                       e->lww_clock, (int64_t)e->lww_base));
+    } else if (pnm) {
+      Scope s(e, K_APPLY);
+      HIP_TRY(agx_launch_pncmap_merge(dim3(grid_for(e->n_local / 4 + 1, 4096)), e->stream, ba.P, (const uint4*)e->d_orw,
+                                      (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n));
     } else if (orm) {
       Scope s(e, K_APPLY);
       hipLaunchKernelGGL(k_orset_merge, dim3(grid_for(e->n_local / 4 + 1, 4096)), dim3(kThreads), 0, e->stream, ba.P,
@@ -1749,7 +1755,7 @@ agx_status setup_ring_apply(agx_engine* e) {
 // ORSet-only full-state populations: k_orset_merge's work list (before any graph capture)
 agx_status setup_orset(agx_engine* e) {
   const uint32_t vid = apply_variant(e);
-  if (e->d_orw || (vid != V_OR && vid != V_LWWMAP)) return AGX_OK;
+  if (e->d_orw || (vid != V_OR && vid != V_LWWMAP && vid != V_PNCMAP)) return AGX_OK;
   if (vid == V_LWWMAP) {
     AGX_TRY(dalloc(&e->d_lww_step0, 1));
     HIP_TRY(hipMemset(e->d_lww_step0, 0, 4));
@@ -2485,6 +2491,7 @@ agx_status prepare_run(agx_engine* e) {
     // are read whole).  AGX_CRDT_LAYOUT=actor|word overrides.
     const char* lay = getenv("AGX_CRDT_LAYOUT");
     const bool word_major = apply_variant(e) != V_OR && apply_variant(e) != V_LWWMAP &&  // (k_orset_merge / k_lwwmap_merge walk actor-major rows)
+                            apply_variant(e) != V_PNCMAP &&                              // (k_pncmap_merge too)
                             (lay ? lay[0] == 'w' : (e->delta_max && !(e->kinds_mask & kb(AGX_KIND_ORSET))));
     if (e->pw && !e->pitch && !word_major) {
       const uint32_t pitch = e->W <= 16 ? (e->W + 1u) & ~1u : (e->W + 15u) & ~15u;
@@ -2760,8 +2767,8 @@ agx_status read_counters(agx_engine* e, uint64_t* s) {
 // still fills its counters); destroy the engine and start over.
 agx_status error_status(const agx_engine* e, uint64_t err) {
   if (err & kErrRange)
-    return set_err(AGX_ERANGE, "a GCounter/PNCounter slot exceeded 2^64 - 1 (u64 slots; the reference uses BigInt) or an "
-                   "ORSet / LWWMap replica's own version exceeded 2^32 - 1 (u32 versions; the reference uses Long) or an LWWMap "
+    return set_err(AGX_ERANGE, "a GCounter/PNCounter/PNCounterMap slot exceeded 2^64 - 1 (u64 slots; the reference uses BigInt) or an "
+                   "ORSet / LWWMap / PNCounterMap replica's own version exceeded 2^32 - 1 (u32 versions; the reference uses Long) or an LWWMap "
                    "timestamp would pass the int64 range (the reference's Long would wrap)");
   if (err & kErrPrioTile)
     return set_err(AGX_ECAPACITY, "a bucket of %u actors that holds a priority-mailbox actor received more than one "
@@ -2848,6 +2855,7 @@ agx_status collect_stats(agx_engine* e, agx_stats* out, bool check) {
   if (km & kb(AGX_KIND_PNCOUNTER)) sw = std::max<uint64_t>(sw, AGX_PNCOUNTER_WORDS);
   if (km & kb(AGX_KIND_ORSET)) sw = std::max<uint64_t>(sw, e->delta_max ? AGX_DELTA_ENV_WORDS + 4 : AGX_ORSET_WORDS);
   if (km & kb(AGX_KIND_LWWMAP)) sw = std::max<uint64_t>(sw, AGX_LWWMAP_WORDS);
+  if (km & kb(AGX_KIND_PNCOUNTERMAP)) sw = std::max<uint64_t>(sw, AGX_PNCMAP_WORDS);
   st.bytes_alg = 12ull * st.delivered + 12ull * st.emitted + (16ull * std::min<uint64_t>(sw, e->W) + 2ull) * bs[4];
   if (out) *out = st;
   return est;
@@ -3632,12 +3640,20 @@ void drop_graphs(agx_engine* e) {
 agx_status enable_crdt(agx_engine* e, uint32_t kind) {
   static_assert((2 * AGX_LWWMAP_WORDS + kRowAlign - 1) / kRowAlign * kRowAlign >= kLwRowMax,
                 "the row pitch of an LWWMap engine holds the widest LWWMap snapshot row (agx_lwwmap.h)");
+  static_assert((2 * AGX_PNCMAP_WORDS + kRowAlign - 1) / kRowAlign * kRowAlign >= kPnRowMax && kPnRowMax == 2592u,
+                "the row pitch of a PNCounterMap engine holds the widest PNCounterMap snapshot row (agx_pncmap.h)");
+  static_assert(AGX_PNCMAP_WORDS == 1296u && AGX_PNCMAP_WORDS % 16u == 0 && AGX_PNCMAP_WORDS <= AGX_MAX_WORDS,
+                "a PNCounterMap state is 81 lines of 128 B: the actor-major pitch (prepare_run) is exact");
+  if (kind == AGX_KIND_PNCOUNTERMAP && e->delta_max)
+    return set_err(AGX_EINVAL, "PNCounterMap replicas gossip their full state: not on an engine with delta-CRDT "
+                   "replication (agx_set_delta_crdt; ORMap delta ops are left out)");
   if (kind == AGX_KIND_LWWMAP && e->delta_max)
     return set_err(AGX_EINVAL, "LWWMap replicas gossip their full state: not on an engine with delta-CRDT replication "
                    "(agx_set_delta_crdt; ORMap delta ops are left out)");
   const uint32_t words = kind == AGX_KIND_GCOUNTER ? AGX_GCOUNTER_WORDS
                          : kind == AGX_KIND_PNCOUNTER ? AGX_PNCOUNTER_WORDS
-                         : kind == AGX_KIND_LWWMAP ? AGX_LWWMAP_WORDS : AGX_ORSET_WORDS;
+                         : kind == AGX_KIND_LWWMAP ? AGX_LWWMAP_WORDS
+                         : kind == AGX_KIND_PNCOUNTERMAP ? AGX_PNCMAP_WORDS : AGX_ORSET_WORDS;
   const uint32_t need = !e->delta_max ? words
                         : kind == AGX_KIND_GCOUNTER ? AGX_GCOUNTER_DELTA_WORDS
                         : kind == AGX_KIND_PNCOUNTER ? AGX_PNCOUNTER_DELTA_WORDS : AGX_ORSET_DELTA_WORDS;
@@ -4100,7 +4116,13 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
   AGX_TRY(sync_mirrors(e));  // device state is authoritative after a run
   const bool compiled = kind >= AGX_KIND_COMPILED && kind < AGX_KIND_COMPILED + AGX_MAX_BEHAVIORS;
   const bool lww = kind == AGX_KIND_LWWMAP;
-  if (first_id + count > e->n_global || (kind >= AGX_KIND_MAX && !compiled && !lww)) return set_err(AGX_EINVAL, "bad range or kind");
+  const bool pnm = kind == AGX_KIND_PNCOUNTERMAP;
+  if (first_id + count > e->n_global || (kind >= AGX_KIND_MAX && !compiled && !lww && !pnm)) return set_err(AGX_EINVAL, "bad range or kind");
+  if (pnm && e->R > 1) return set_err(AGX_EINVAL, "PNCounterMap replicas need a single-rank engine (n_ranks %u)", e->R);
+  // a PNCounterMap engine holds PNCounterMap replicas only (unregistering, AGX_KIND_NONE, stays possible)
+  if (count && kind != AGX_KIND_NONE && (pnm ? (e->kinds_mask & ~(kb(AGX_KIND_NONE) | kb(AGX_KIND_PNCOUNTERMAP))) != 0
+                                             : (e->kinds_mask & kb(AGX_KIND_PNCOUNTERMAP)) != 0))
+    return set_err(AGX_EINVAL, "PNCounterMap replicas and actors of another kind (%u) need separate engines", pnm ? 0u : kind);
   if (lww && e->R > 1) return set_err(AGX_EINVAL, "LWWMap replicas need a single-rank engine (n_ranks %u)", e->R);
   // an LWWMap engine holds LWWMap replicas only (unregistering, AGX_KIND_NONE, stays possible)
   if (count && kind != AGX_KIND_NONE && (lww ? (e->kinds_mask & ~(kb(AGX_KIND_NONE) | kb(AGX_KIND_LWWMAP))) != 0
@@ -4127,7 +4149,7 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
                      "its entities are started by their first message", (unsigned long long)first_id,
                      (unsigned long long)(first_id + count), (unsigned long long)c0, (unsigned long long)c1);
   }
-  if ((kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET) || lww) AGX_TRY(enable_crdt(e, kind));
+  if ((kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET) || lww || pnm) AGX_TRY(enable_crdt(e, kind));
   if (count && !(e->kinds_mask & kb(kind))) {  // the apply variant is captured in the superstep graphs
     e->kinds_mask |= kb(kind);
     drop_graphs(e);
@@ -5773,6 +5795,9 @@ agx_status agx_set_delta_crdt(agx_engine* e, uint32_t max_delta_size) {
   if (max_delta_size && (e->kinds_mask & kb(AGX_KIND_LWWMAP)))
     return set_err(AGX_EINVAL, "delta-CRDT replication on an engine with LWWMap replicas: they gossip their full state "
                    "(ORMap delta ops are left out)");
+  if (max_delta_size && (e->kinds_mask & kb(AGX_KIND_PNCOUNTERMAP)))
+    return set_err(AGX_EINVAL, "delta-CRDT replication on an engine with PNCounterMap replicas: they gossip their full "
+                   "state (ORMap delta ops are left out)");
   e->delta_max = max_delta_size;
   for (uint32_t k = AGX_KIND_GCOUNTER; k <= AGX_KIND_ORSET; ++k)
     if (e->kinds_mask & kb(k)) AGX_TRY(enable_crdt(e, k));

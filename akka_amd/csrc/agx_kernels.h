@@ -28,6 +28,7 @@
 #pragma once
 #include "agx_crdt.h"
 #include "agx_lwwmap.h"
+#include "agx_pncmap.h"
 #include "agx_device.h"
 
 namespace agx {
@@ -2380,7 +2381,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     // LWWMap populations (V_LWWMAP, up to 2944-B rows): the wave copies too, each row by the used length it
     // carries (kLwRowLen, agx_lwwmap.h)
     constexpr bool kLwRows = kWide && KM == kb(AGX_KIND_LWWMAP);
-    constexpr bool kWaveRows = kBigRows || kLwRows;
+    // PNCounterMap populations (V_PNCMAP, up to 10368-B rows): likewise (kPnRowLen, agx_pncmap.h)
+    constexpr bool kPnRows = kWide && KM == kb(AGX_KIND_PNCOUNTERMAP);
+    constexpr bool kWaveRows = kBigRows || kLwRows || kPnRows;
     static_assert(!kBigRows || !(KM & kDeltaKM) || (KM & ~kDeltaKM) == kb(AGX_KIND_ORSET),
                   "a delta variant that copies rows by their used length holds ORSet groups only: counter groups "
                   "write no length word (dl_group_row)");
@@ -2449,6 +2452,8 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
               }
               if constexpr (kLwRows)  // (the length word lies in the row's header: it travels with the copy)
                 n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kLwRowLen] + 3u) / 4u);
+              if constexpr (kPnRows)  // (likewise; the used length is a multiple of 4 u32)
+                n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kPnRowLen] + 3u) / 4u);
               for (uint32_t k2 = lane; k2 < n4; k2 += kWave) d[k2] = s[k2];
             }
           }
@@ -3553,6 +3558,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       if constexpr (kLwWaveA) {
         for (uint32_t q = 0; q < nd; ++q) em.count(lwwmap_count(P, isrc(s0 + q), ipay(s0 + q), &nrows_t));
       } else
+      if constexpr (kWide && KM == kb(AGX_KIND_PNCOUNTERMAP)) {  // (a PNCounterMap engine holds nothing else either)
+        for (uint32_t q = 0; q < nd; ++q) em.count(pncmap_count(P, isrc(s0 + q), ipay(s0 + q), &nrows_t));
+      } else
       if (kWide && is_crdt(kd)) {
         DeltaSim ds;
         ds.on = false;
@@ -3624,7 +3632,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     constexpr bool kOrWave = kWide && KM == kb(AGX_KIND_ORSET);
     // (LWWMap-only variant: the same split, lwwmap_protocol here and k_lwwmap_merge after the apply)
     constexpr bool kLwWave = kWide && KM == kb(AGX_KIND_LWWMAP);
-    constexpr bool kWaveList = kOrWave || kLwWave;
+    // (PNCounterMap-only variant: pncmap_protocol here and k_pncmap_merge after the apply)
+    constexpr bool kPnWave = kWide && KM == kb(AGX_KIND_PNCOUNTERMAP);
+    constexpr bool kWaveList = kOrWave || kLwWave || kPnWave;
   #pragma unroll 1
     for (int j = 0; j < kBAct; ++j) {
       const uint32_t la = j * kBThreads + tid;
@@ -3648,6 +3658,13 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         nunh += lwwmap_protocol(P, self, s0, nd, isrc, ipay, row_cursor, em, &work);
         ndel += nd;
         L.ecnt[la] = work ? rc0 : 0xFFFFFFFFu;  // (this actor's tell offset is no longer needed)
+      } else
+      if constexpr (kPnWave) {  // protocol here, state effects by k_pncmap_merge (agx_pncmap.h)
+        bool work = false;
+        const uint32_t rc0 = row_cursor;
+        nunh += pncmap_protocol(P, self, s0, nd, isrc, ipay, row_cursor, em, &work);
+        ndel += nd;
+        L.ecnt[la] = work ? rc0 : 0xFFFFFFFFu;
       } else
       if (kWide && is_crdt(kd)) {
         if constexpr (kOrWave) {  // protocol here, state effects by k_orset_merge (agx_crdt.h)
@@ -7205,6 +7222,22 @@ static __global__ void __launch_bounds__(kThreads) k_lwwmap_merge(DevParams P, c
     const uint4 w = orw[it];
     const uint2* msg = orm + w.z;
     lwwmap_merge_wave(P, H, w.x, w.y & 0xFFu, w.y >> 8, w.w, clock, now, [&](uint32_t q) { return msg[q].x; },
+                      [&](uint32_t q) { return msg[q].y; });
+  }
+}
+
+// PNCounterMap-only populations: the state effects of every replica run the apply listed (pncmap_protocol
+// did its tells and snapshot-row allocation): one wave per replica, lane = key (pncmap_merge_wave).  The
+// launch bound is the block size: a lane holds 32 VGPRs of its own slots and 32 of a row's.
+static __global__ void __launch_bounds__(kThreads) k_pncmap_merge(DevParams P, const uint4* orw, const uint2* orm,
+                                                              const uint32_t* orw_n) {
+  const uint32_t n = orw_n[0];
+  const CrdtHeap H = crdt_heap(P);
+  const uint32_t nw = gridDim.x * (kThreads / kWave);
+  for (uint32_t it = blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave; it < n; it += nw) {
+    const uint4 w = orw[it];
+    const uint2* msg = orm + w.z;
+    pncmap_merge_wave(P, H, w.x, w.y & 0xFFu, w.y >> 8, w.w, [&](uint32_t q) { return msg[q].x; },
                       [&](uint32_t q) { return msg[q].y; });
   }
 }

@@ -9,6 +9,14 @@
 The layout is include/akka_gpu.h "LWWMap replicas": the ORSet key set (64 keys x 8 u32 dots, 8 u32
 version vector), 64 int64 timestamps, 64 u32 registers (updatedBy node << 24 | value).  Writes go
 through the engine (Op.put, Op.REMOVE); `to_words` exists to seed replicas (register_range).
+
+    from akka_amd.ddata import PNCounterMap
+    c = PNCounterMap.from_words(words[replica])
+    c.entries            # {key: signed value}
+    c.get(3), c.contains(3), c.size, c.increments(3), c.decrements(3)
+
+"PNCounterMap replicas": the same key set, 12 words of padding, then 16 u64 slots per key (8 increments, 8
+decrements, one per node).  Writes: Op.increment_key, Op.decrement_key, Op.REMOVE.
 """
 from __future__ import annotations
 
@@ -23,6 +31,9 @@ _VV = ORSET_ELEMS * CRDT_NODES          # u32 index of the version vector
 _TS = CRDT_WORDS[Kind.ORSET]            # u64 index of key 0's timestamp
 _REG = 2 * (_TS + ORSET_ELEMS)          # u32 index of key 0's register
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+PNCMAP_WORDS = CRDT_WORDS[Kind.PNCOUNTERMAP]
+_CTR = 272                              # u64 index of key 0's slots (AGX_PNCMAP_CTR_WORD)
+_SLOTS = 2 * CRDT_NODES                 # u64 slots per key: increments, then decrements
 
 
 @dataclass
@@ -99,3 +110,80 @@ class LWWMap:
     def updated_by(self, key: int):
         r = self.registers.get(key)
         return None if r is None else r[0]
+
+
+@dataclass
+class PNCounterMap:
+    """One replica's PNCounterMap: per live key its dots {node: version} and its PNCounter as 16 slots
+    (increments of node 0..7, then decrements of node 0..7); the key set's version vector {node: version}."""
+    dots: dict = field(default_factory=dict)        # key -> {node: version}, live keys only
+    vvector: dict = field(default_factory=dict)     # node -> version
+    slots: dict = field(default_factory=dict)       # key -> tuple of 16 ints
+
+    @classmethod
+    def from_words(cls, row) -> "PNCounterMap":
+        w = np.ascontiguousarray(np.asarray(row, np.uint64)[:PNCMAP_WORDS])
+        if w.size != PNCMAP_WORDS:
+            raise ValueError(f"a PNCounterMap replica has {PNCMAP_WORDS} state words, got {w.size}")
+        u = w.view(np.uint32)
+        if w[_TS:_CTR].any():
+            raise ValueError("the padding words 260..271 are not zero: not canonical")
+        m = cls()
+        for k in range(ORSET_ELEMS):
+            d = {n: int(u[k * CRDT_NODES + n]) for n in range(CRDT_NODES) if u[k * CRDT_NODES + n]}
+            sl = tuple(int(x) for x in w[_CTR + _SLOTS * k:_CTR + _SLOTS * (k + 1)])
+            if d:
+                m.dots[k] = d
+                m.slots[k] = sl
+            elif any(sl):
+                raise ValueError(f"key {k} has no live dot but non-zero slots: not canonical")
+        m.vvector = {n: int(u[_VV + n]) for n in range(CRDT_NODES) if u[_VV + n]}
+        return m
+
+    def to_words(self) -> np.ndarray:
+        w = np.zeros(PNCMAP_WORDS, np.uint64)
+        u = w.view(np.uint32)
+        if set(self.dots) != set(self.slots):
+            raise ValueError("every live key has exactly one counter")
+        for k, d in self.dots.items():
+            if not 0 <= k < ORSET_ELEMS or not d:
+                raise ValueError(f"key {k}: outside the 64-key universe, or without a dot")
+            for n, v in d.items():
+                if not (0 <= n < CRDT_NODES and 0 < v < 1 << 32):
+                    raise ValueError(f"dot ({k}, {n}) -> {v} does not fit the layout")
+                u[k * CRDT_NODES + n] = v
+            sl = self.slots[k]
+            if len(sl) != _SLOTS or not all(0 <= x < 1 << 64 for x in sl):
+                raise ValueError(f"counter of key {k} does not fit 16 u64 slots")
+            w[_CTR + _SLOTS * k:_CTR + _SLOTS * (k + 1)] = np.array(sl, np.uint64)
+        for n, v in self.vvector.items():
+            if not (0 <= n < CRDT_NODES and 0 < v < 1 << 32):
+                raise ValueError(f"version vector entry {n} -> {v} does not fit the layout")
+            u[_VV + n] = v
+        return w
+
+    def increments(self, key: int):
+        """Key's GCounter of increments, {node: count} (None: no such key)."""
+        sl = self.slots.get(key)
+        return None if sl is None else {n: sl[n] for n in range(CRDT_NODES) if sl[n]}
+
+    def decrements(self, key: int):
+        sl = self.slots.get(key)
+        return None if sl is None else {n: sl[CRDT_NODES + n] for n in range(CRDT_NODES) if sl[CRDT_NODES + n]}
+
+    def get(self, key: int):
+        """PNCounterMap.get: the key's value, a signed Python int (None: no such key)."""
+        sl = self.slots.get(key)
+        return None if sl is None else sum(sl[:CRDT_NODES]) - sum(sl[CRDT_NODES:])
+
+    @property
+    def entries(self) -> dict:
+        """PNCounterMap.entries: {key: value}."""
+        return {k: self.get(k) for k in sorted(self.slots)}
+
+    def contains(self, key: int) -> bool:
+        return key in self.slots
+
+    @property
+    def size(self) -> int:
+        return len(self.slots)

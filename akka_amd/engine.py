@@ -30,16 +30,19 @@ class Kind:
     PNCOUNTER = 9
     ORSET = 10
     LWWMAP = 11       # LWWMap = ORMap of LWWRegister (AGX_KIND_LWWMAP, not in the enum), "LWWMap replicas"
+    PNCOUNTERMAP = 12  # PNCounterMap = ORMap of PNCounter (AGX_KIND_PNCOUNTERMAP), "PNCounterMap replicas"
 
 
 CRDT_NODES = 8
 ORSET_ELEMS = 64
-CRDT_WORDS = {Kind.GCOUNTER: 8, Kind.PNCOUNTER: 16, Kind.ORSET: 260, Kind.LWWMAP: 356}
+CRDT_WORDS = {Kind.GCOUNTER: 8, Kind.PNCOUNTER: 16, Kind.ORSET: 260, Kind.LWWMAP: 356,
+              Kind.PNCOUNTERMAP: 1296}
 # delta-CRDT mode (agx_set_delta_crdt): data + envelope/selector area + delta log (include/akka_gpu.h)
 DELTA_ENV_WORDS, DELTA_LOG = 12, 64
 CRDT_DELTA_WORDS = {k: w + DELTA_ENV_WORDS + (DELTA_LOG * 6 if k == Kind.ORSET else 4) for k, w in CRDT_WORDS.items()
-                    if k != Kind.LWWMAP}  # (LWWMap replicas gossip their full state only)
+                    if k not in (Kind.LWWMAP, Kind.PNCOUNTERMAP)}  # (map replicas gossip their full state only)
 LWW_VALUE_MAX = 0x3FFFF
+PNCMAP_COUNT_MAX = 0x3FFFF  # AGX_PNCMAP_COUNT_MAX
 LWW_CLOCKS = {"default": 0, "reverse": 1}  # AGX_LWW_CLOCK_DEFAULT / AGX_LWW_CLOCK_REVERSE
 DELTA_WRITE = 0x800000
 WIDE_BIT = 0x80000000
@@ -68,6 +71,24 @@ class Op:
         if not 0 <= value <= LWW_VALUE_MAX:
             raise ValueError(f"LWWMap value {value} does not fit 18 bits")
         return Op.make(Op.PUT, key | (value << 6))
+
+    @staticmethod
+    def _count(op: int, key: int, n: int) -> int:
+        if not 0 <= key < ORSET_ELEMS:
+            raise ValueError(f"PNCounterMap key {key} outside the 64-key universe")
+        if not 0 <= n <= PNCMAP_COUNT_MAX:
+            raise ValueError(f"PNCounterMap delta {n} does not fit 18 bits (a negative delta is the other op)")
+        return Op.make(op, key | (n << 6))
+
+    @staticmethod
+    def increment_key(key: int, n: int = 1) -> int:
+        """PNCounterMap.increment(key, n) on a PNCounterMap replica: key < 64, 0 <= n < 2^18 (AGX_OP_COUNT_ARG)."""
+        return Op._count(Op.INCREMENT, key, n)
+
+    @staticmethod
+    def decrement_key(key: int, n: int = 1) -> int:
+        """PNCounterMap.decrement(key, n) on a PNCounterMap replica: key < 64, 0 <= n < 2^18 (AGX_OP_COUNT_ARG)."""
+        return Op._count(Op.DECREMENT, key, n)
 
 
 @dataclass

@@ -307,6 +307,48 @@ def crdt_lwwmap(n: int = 1_000_000, rounds: int = 32, fanout: int = 2, puts_per_
                     bucket_actors=bucket_actors)
 
 
+def pncountermap_ops(nw: int, incs: int, removes: int, keys: int = 12, seed: int = SEED) -> np.ndarray:
+    """Round-0 local updates of the `nw` writers of a PNCounterMap population, one row per writer: `incs` seeded
+    counts (about one in four a decrement, now and then by 0) with `removes` removes spread among them, all over the
+    first `keys` keys, so that writers collide on keys."""
+    per = incs + removes
+    out = np.zeros((nw, per), np.uint32)
+    a = np.arange(nw, dtype=np.uint64)
+    rm_at = set((np.arange(removes) * per // max(removes, 1) + per // (2 * max(removes, 1))).tolist()) if removes else set()
+    for j in range(per):
+        r = splitmix64_np((a << np.uint64(8)) ^ np.uint64(j) ^ np.uint64(seed * 17))
+        key = (r % np.uint64(keys)).astype(np.uint32)
+        by = ((r >> np.uint64(20)) & np.uint64(0x3FFFF)).astype(np.uint32)
+        by = np.where(((r >> np.uint64(40)) & np.uint64(15)) == 0, np.uint32(0), by)
+        op = np.where(((r >> np.uint64(44)) & np.uint64(3)) == 0, np.uint32(Op.DECREMENT), np.uint32(Op.INCREMENT))
+        if j in rm_at:
+            out[:, j] = (np.uint32(Op.REMOVE) << np.uint32(24)) | key
+        else:
+            out[:, j] = (op << np.uint32(24)) | key | (by << np.uint32(6))
+    return out
+
+
+def crdt_pncountermap(n: int = 1_000_000, rounds: int = 32, fanout: int = 2, incs_per_writer: int = 16, removes: int = 4,
+                      throughput: int = 5, seed: int = SEED, capacity: int = 0, bucket_actors: int = 512) -> Workload:
+    """PNCounterMap replicas (PNCounterMap = ORMap of PNCounter) in crdt_lwwmap's shape: replicas 0..7 are the
+    writers, one per node slot, and first apply seeded increments, decrements and removes over a dozen keys (host
+    tells), so that writers collide on keys; then every replica runs `rounds` GossipTicks.  The population converges
+    to the merge of the writers' maps.  A replica's snapshot row is up to 10 KB: pass `msg_capacity` to the engine
+    explicitly (the default sizes the row heap for max(4n, 65536) messages)."""
+    nw = min(n, CRDT_NODES)
+    per = incs_per_writer + removes
+    ops = pncountermap_ops(nw, incs_per_writer, removes, seed=seed).reshape(-1)
+    odst = np.repeat(np.arange(nw, dtype=np.uint32), per)
+    tdst = np.arange(n, dtype=np.uint32)
+    tick = np.full(n, Op.make(Op.GOSSIP, rounds - 1), np.uint32)
+    dst = np.concatenate([odst, tdst])
+    pay = np.concatenate([ops, tick])
+    src = np.full(dst.size, NO_SENDER, np.uint32)
+    return Workload("crdt_pncountermap", n, CRDT_WORDS[Kind.PNCOUNTERMAP], fanout + 1, throughput, capacity,
+                    [(0, n, Kind.PNCOUNTERMAP, None)], gossip=(fanout, seed), tells=(dst, src, pay),
+                    bucket_actors=bucket_actors)
+
+
 def crdt_delta(n: int = 1_000_000, kind: int = Kind.ORSET, rounds: int = 32, write: bool = True,
                ops_per_replica: int = 0, gossip_rounds: int = 0, fanout: int = 1, max_delta_size: int = 50,
                throughput: int = 5, seed: int = SEED, capacity: int = 0, bucket_actors: int = 0) -> Workload:

@@ -129,6 +129,8 @@ enum agx_behavior_kind {
  * AGX_KIND_MAX: agx_register_range accepts it explicitly, and code that only knows the enum keeps
  * refusing it. */
 #define AGX_KIND_LWWMAP 11u
+/* a PNCounterMap replica (see "PNCounterMap replicas" below); outside the enum for the same reason */
+#define AGX_KIND_PNCOUNTERMAP 12u
 #define AGX_MAX_BEHAVIORS 64u
 #define AGX_MAX_CASES 1024u
 #define AGX_MAX_ACTS 4096u
@@ -281,7 +283,7 @@ typedef struct agx_act {
   int64_t k, dk;
 } agx_act; /* 32 B */
 
-#define AGX_MAX_WORDS 656u /* = AGX_ORSET_DELTA_WORDS (the widest layout) */
+#define AGX_MAX_WORDS 1296u /* = AGX_PNCMAP_WORDS (the widest layout) */
 #define AGX_MAX_RANKS 16u
 
 /* --- CRDT behaviours ---------------------------------------------------------
@@ -406,8 +408,8 @@ typedef struct agx_act {
  * A timestamp that would pass the int64 range raises AGX_ERANGE (the reference's Long would wrap),
  * as a wrapping ORSet version does.
  * An LWWMap engine holds LWWMap replicas only, on one rank, with full-state gossip.  Left out:
- * LWWRegister as a kind of its own, PNCounterMap, ORMultiMap, GSet, Flag, ORMap delta ops, pruning,
- * multi-rank engines, custom clocks, the JVM shim.                                               */
+ * LWWRegister as a kind of its own, ORMultiMap, GSet, Flag, ORMap delta ops, pruning, multi-rank
+ * engines, custom clocks, the JVM shim.  (PNCounterMap is a kind of its own, below.)             */
 #define AGX_LWWMAP_WORDS 356u /* 260 (keys) + 64 (timestamps) + 32 (64 u32 registers) */
 #define AGX_LWWMAP_TS_WORD 260u
 #define AGX_LWWMAP_REG_U32 648u
@@ -416,6 +418,50 @@ typedef struct agx_act {
 #define AGX_OP_PUT_ARG(key, value) (((uint32_t)(key) & 63u) | ((uint32_t)(value) << 6))
 #define AGX_LWW_CLOCK_DEFAULT 0u
 #define AGX_LWW_CLOCK_REVERSE 1u
+
+/* --- PNCounterMap replicas (AGX_KIND_PNCOUNTERMAP) -------------------------------------------
+ * PNCounterMap[A] = ORMap[A, PNCounter] over the 64-key universe (DD/PNCounterMap.scala:105-106 increment,
+ * :139-141 decrement; DD/ORMap.scala:308-334 updated, :361-366 remove, :379-409 merge;
+ * DD/PNCounter.scala:173-178 change, :180-183 merge).  node = id % AGX_CRDT_NODES as for the other CRDT kinds.
+ * State, AGX_PNCMAP_WORDS u64 per replica (81 lines of 128 B):
+ *   w[0..259]              ORMap.keys: bit for bit the AGX_KIND_ORSET layout (64 keys x 8 u32 dots, the
+ *                          8 u32 version vector)
+ *   w[260..271]            always 0 (padding: every key's counters start on a 128-B line)
+ *   w[272 + 16k + n]       key k's increments of node n      (AGX_PNCMAP_CTR_WORD = 272)
+ *   w[272 + 16k + 8 + n]   key k's decrements of node n
+ * so each key's 16 words are an AGX_KIND_PNCOUNTER replica's 16 words; key k's value is the sum of its
+ * increments less the sum of its decrements.
+ * Canonical form: a key without a live dot has all 16 slots 0 (ORMap `values - key`); every operation
+ * leaves this form, so states compare bit for bit.
+ * Ops (control tells):
+ *   AGX_OP_INCREMENT  arg = key | n << 6   PNCounterMap.increment(node, key, n), n < 2^18:
+ *                     ORMap.updated(node, key, PNCounter())(_.increment(node, n)) -- the present counter,
+ *                     or a fresh one, with node's increments slot raised by n (n = 0 leaves the counter as
+ *                     it is, PNCounter.change); the key is added as AGX_OP_ADD adds an ORSet element
+ *                     (vvector + 1, one birth dot), so an increment by 0 creates the key with value 0.
+ *   AGX_OP_DECREMENT  arg = key | n << 6   PNCounterMap.decrement: likewise on node's decrements slot.
+ *                     (AGX_OP_COUNT_ARG packs the argument: every 24-bit argument is valid.  A negative
+ *                     delta cannot be expressed: decrement by n instead of incrementing by -n.)
+ *   AGX_OP_REMOVE     arg = key < 64       ORMap.remove: dots cleared as in the ORSet kind, the 16 slots
+ *                     cleared; key >= 64 is Behaviors.unhandled
+ *   AGX_OP_GOSSIP     as for the other kinds; the state gossip's payload carries data type 3
+ *                     (3 = the engine's ORMap-based map: a map engine holds one map kind only, so LWWMap
+ *                     and PNCounterMap share the code)
+ *   every other op (ADD, CLEAR, PUT, DELTA_TICK, unknown) is Behaviors.unhandled.
+ * Merge of a received snapshot: the keys merge by ORSet.merge; a key of the merged set present on both
+ * sides takes PNCounter.merge (the slot-wise maximum of all 16 slots), a key present on one side takes
+ * that side's counter, a key absent from the merged set has its slots cleared.  As in the reference,
+ * the values merge before it is known which dots survive: a key removed and counted again on one
+ * replica gets its old slots back from a peer that still holds them.
+ * AGX_ERANGE: a slot would pass 2^64 - 1 (the reference's BigInt would not wrap; as for
+ * AGX_KIND_PNCOUNTER), or a replica's own version would pass 2^32 - 1 (as for ORSet and LWWMap).
+ * A PNCounterMap engine holds PNCounterMap replicas only, on one rank, with full-state gossip and
+ * n_words = AGX_PNCMAP_WORDS.  Left out: ORMap delta ops, ORMultiMap, pruning, multi-rank engines,
+ * mixed populations, the JVM shim.                                                              */
+#define AGX_PNCMAP_WORDS 1296u /* 260 (keys) + 12 (padding) + 64 * 16 (slots) = 81 lines of 128 B */
+#define AGX_PNCMAP_CTR_WORD 272u
+#define AGX_PNCMAP_COUNT_MAX 0x3FFFFu
+#define AGX_OP_COUNT_ARG(key, n) (((uint32_t)(key) & 63u) | ((uint32_t)(n) << 6))
 
 typedef struct agx_cfg {
   uint32_t abi_version;   /* must be AGX_ABI_VERSION                                   */
