@@ -24,8 +24,8 @@ struct GroupLaunch {
   hipError_t (*ring)(uint32_t vid, bool tiny, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
   hipError_t (*persist_occupancy)(uint32_t vid, int*);
 };
-#define AGX_GROUPS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
-static_assert(kVGroups == 11, "AGX_GROUPS names every group");
+#define AGX_GROUPS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11)
+static_assert(kVGroups == 12, "AGX_GROUPS names every group");
 #define AGX_GROUP_DECL(g) const GroupLaunch& agx_group_##g();
 AGX_GROUPS(AGX_GROUP_DECL)
 
@@ -36,16 +36,16 @@ hipError_t launch_v(uint32_t mode, bool skew, dim3 g, hipStream_t s, const Bucke
   constexpr bool W = kVariants[V].wide;
   constexpr uint32_t M = kVariants[V].km;
   const dim3 blk(kBThreads);
-  if constexpr (V == V_LWWMAP || V == V_PNCMAP)  // (single-rank engines only: no owner-mode instantiation)
+  if constexpr (V == V_LWWMAP || V == V_PNCMAP || V == V_ORMM)  // (single-rank engines only: no owner-mode instantiation)
     if (mode == M_OWNER) return hipErrorInvalidValue;
   switch (mode * 2 + (skew ? 1u : 0u)) {
     case M_FUSED * 2: hipLaunchKernelGGL((k_bucket_apply<W, M, true, false, false>), g, blk, 0, s, ba); break;
     case M_FUSED * 2 + 1: hipLaunchKernelGGL((k_bucket_apply<W, M, true, true, false>), g, blk, 0, s, ba); break;
     case M_OWNER * 2:
-      if constexpr (V != V_LWWMAP && V != V_PNCMAP) hipLaunchKernelGGL((k_bucket_apply<W, M, false, false, true>), g, blk, 0, s, ba);
+      if constexpr (V != V_LWWMAP && V != V_PNCMAP && V != V_ORMM) hipLaunchKernelGGL((k_bucket_apply<W, M, false, false, true>), g, blk, 0, s, ba);
       break;
     case M_OWNER * 2 + 1:
-      if constexpr (V != V_LWWMAP && V != V_PNCMAP) hipLaunchKernelGGL((k_bucket_apply<W, M, false, true, true>), g, blk, 0, s, ba);
+      if constexpr (V != V_LWWMAP && V != V_PNCMAP && V != V_ORMM) hipLaunchKernelGGL((k_bucket_apply<W, M, false, true, true>), g, blk, 0, s, ba);
       break;
     case M_BYPASS * 2: hipLaunchKernelGGL((k_bucket_apply<W, M, false, false, false>), g, blk, 0, s, ba); break;
     case M_BYPASS * 2 + 1: hipLaunchKernelGGL((k_bucket_apply<W, M, false, true, false>), g, blk, 0, s, ba); break;
@@ -206,6 +206,15 @@ static_assert(kPncmapGroup == 10, "k_pncmap_merge lives in V_PNCMAP's unit");
 hipError_t agx_launch_pncmap_merge(dim3 g, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
                                    const uint32_t* orw_n) {
   hipLaunchKernelGGL(k_pncmap_merge, g, dim3(kThreads), 0, s, P, orw, orm, orw_n);
+  return hipGetLastError();
+}
+#endif
+
+#if AGX_VGROUP == 11
+static_assert(kOrmmGroup == 11, "k_ormm_merge lives in V_ORMM's unit");
+hipError_t agx_launch_ormm_merge(dim3 g, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
+                                 const uint32_t* orw_n) {
+  hipLaunchKernelGGL(k_ormm_merge, g, dim3(kThreads), 0, s, P, orw, orm, orw_n);
   return hipGetLastError();
 }
 #endif

@@ -894,6 +894,7 @@ uint32_t apply_variant(const agx_engine* e) {
     if (km == kb(AGX_KIND_ORSET)) return V_OR;
     if (km == kb(AGX_KIND_LWWMAP)) return V_LWWMAP;  // (an LWWMap engine holds nothing else: agx_register_range)
     if (km == kb(AGX_KIND_PNCOUNTERMAP)) return V_PNCMAP;  // (nor does a PNCounterMap engine)
+    if (km == kb(AGX_KIND_ORMULTIMAP)) return V_ORMM;      // (nor an ORMultiMap engine)
     if ((km & ~kCrdtKM) == 0) return V_CRDT;  // CRDT kinds only: no plain-behaviour code
     return V_ALL_WIDE;
   }
@@ -1524,7 +1525,8 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
     const uint32_t vid = apply_variant(e);
     const bool lwm = vid == V_LWWMAP;       // LWWMap-only: state effects in k_lwwmap_merge
     const bool pnm = vid == V_PNCMAP;       // PNCounterMap-only: state effects in k_pncmap_merge
-    const bool orm = vid == V_OR || lwm || pnm;  // ORSet-only full state: state effects in k_orset_merge
+    const bool mmm = vid == V_ORMM;         // ORMultiMap-only: state effects in k_ormm_merge
+    const bool orm = vid == V_OR || lwm || pnm || mmm;  // ORSet-only full state: state effects in k_orset_merge
     if (orm) {
       if (!e->d_orw || (lwm && !e->d_lww_step0)) return set_err(AGX_ESTATE, "ORSet work list not allocated (setup_orset)");
       ba.orw = e->d_orw;
@@ -1625,6 +1627,10 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       Scope s(e, K_APPLY);
       HIP_TRY(agx_launch_pncmap_merge(dim3(grid_for(e->n_local / 4 + 1, 4096)), e->stream, ba.P, (const uint4*)e->d_orw,
                                       (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n));
+    } else if (mmm) {
+      Scope s(e, K_APPLY);
+      HIP_TRY(agx_launch_ormm_merge(dim3(grid_for(e->n_local / 4 + 1, 4096)), e->stream, ba.P, (const uint4*)e->d_orw,
+                                    (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n));
     } else if (orm) {
       Scope s(e, K_APPLY);
       hipLaunchKernelGGL(k_orset_merge, dim3(grid_for(e->n_local / 4 + 1, 4096)), dim3(kThreads), 0, e->stream, ba.P,
@@ -1755,7 +1761,7 @@ agx_status setup_ring_apply(agx_engine* e) {
 // ORSet-only full-state populations: k_orset_merge's work list (before any graph capture)
 agx_status setup_orset(agx_engine* e) {
   const uint32_t vid = apply_variant(e);
-  if (e->d_orw || (vid != V_OR && vid != V_LWWMAP && vid != V_PNCMAP)) return AGX_OK;
+  if (e->d_orw || (vid != V_OR && vid != V_LWWMAP && vid != V_PNCMAP && vid != V_ORMM)) return AGX_OK;
   if (vid == V_LWWMAP) {
     AGX_TRY(dalloc(&e->d_lww_step0, 1));
     HIP_TRY(hipMemset(e->d_lww_step0, 0, 4));
@@ -2492,6 +2498,7 @@ agx_status prepare_run(agx_engine* e) {
     const char* lay = getenv("AGX_CRDT_LAYOUT");
     const bool word_major = apply_variant(e) != V_OR && apply_variant(e) != V_LWWMAP &&  // (k_orset_merge / k_lwwmap_merge walk actor-major rows)
                             apply_variant(e) != V_PNCMAP &&                              // (k_pncmap_merge too)
+                            apply_variant(e) != V_ORMM &&                                // (and k_ormm_merge)
                             (lay ? lay[0] == 'w' : (e->delta_max && !(e->kinds_mask & kb(AGX_KIND_ORSET))));
     if (e->pw && !e->pitch && !word_major) {
       const uint32_t pitch = e->W <= 16 ? (e->W + 1u) & ~1u : (e->W + 15u) & ~15u;
@@ -2768,7 +2775,8 @@ agx_status read_counters(agx_engine* e, uint64_t* s) {
 agx_status error_status(const agx_engine* e, uint64_t err) {
   if (err & kErrRange)
     return set_err(AGX_ERANGE, "a GCounter/PNCounter/PNCounterMap slot exceeded 2^64 - 1 (u64 slots; the reference uses BigInt) or an "
-                   "ORSet / LWWMap / PNCounterMap replica's own version exceeded 2^32 - 1 (u32 versions; the reference uses Long) or an LWWMap "
+                   "ORSet / LWWMap / PNCounterMap / ORMultiMap replica's own version (an ORMultiMap value set's included) exceeded 2^32 - 1 "
+                   "(u32 versions; the reference uses Long) or an LWWMap "
                    "timestamp would pass the int64 range (the reference's Long would wrap)");
   if (err & kErrPrioTile)
     return set_err(AGX_ECAPACITY, "a bucket of %u actors that holds a priority-mailbox actor received more than one "
@@ -2856,6 +2864,7 @@ agx_status collect_stats(agx_engine* e, agx_stats* out, bool check) {
   if (km & kb(AGX_KIND_ORSET)) sw = std::max<uint64_t>(sw, e->delta_max ? AGX_DELTA_ENV_WORDS + 4 : AGX_ORSET_WORDS);
   if (km & kb(AGX_KIND_LWWMAP)) sw = std::max<uint64_t>(sw, AGX_LWWMAP_WORDS);
   if (km & kb(AGX_KIND_PNCOUNTERMAP)) sw = std::max<uint64_t>(sw, AGX_PNCMAP_WORDS);
+  if (km & kb(AGX_KIND_ORMULTIMAP)) sw = std::max<uint64_t>(sw, AGX_ORMM_WORDS);
   st.bytes_alg = 12ull * st.delivered + 12ull * st.emitted + (16ull * std::min<uint64_t>(sw, e->W) + 2ull) * bs[4];
   if (out) *out = st;
   return est;
@@ -3644,6 +3653,15 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
                 "the row pitch of a PNCounterMap engine holds the widest PNCounterMap snapshot row (agx_pncmap.h)");
   static_assert(AGX_PNCMAP_WORDS == 1296u && AGX_PNCMAP_WORDS % 16u == 0 && AGX_PNCMAP_WORDS <= AGX_MAX_WORDS,
                 "a PNCounterMap state is 81 lines of 128 B: the actor-major pitch (prepare_run) is exact");
+  static_assert((2 * AGX_ORMM_WORDS + kRowAlign - 1) / kRowAlign * kRowAlign == kMmRowMax && kMmRowMax == 5152u,
+                "the row pitch of an ORMultiMap engine is exactly the widest ORMultiMap snapshot row (agx_ormm.h)");
+  static_assert(AGX_ORMM_WORDS == 2576u && AGX_ORMM_WORDS % 16u == 0 && AGX_ORMM_WORDS <= AGX_MAX_WORDS,
+                "an ORMultiMap state is 161 lines of 128 B: the actor-major pitch (prepare_run) is exact");
+  if (kind == AGX_KIND_ORMULTIMAP && e->delta_max)
+    return set_err(AGX_EINVAL, "ORMultiMap replicas gossip their full state: not on an engine with delta-CRDT "
+                   "replication (agx_set_delta_crdt; ORMap delta ops are left out)");
+  if (kind == AGX_KIND_ORMULTIMAP && e->W != AGX_ORMM_WORDS)
+    return set_err(AGX_EINVAL, "ORMultiMap replicas need an engine with n_words = %u (got %u)", AGX_ORMM_WORDS, e->W);
   if (kind == AGX_KIND_PNCOUNTERMAP && e->delta_max)
     return set_err(AGX_EINVAL, "PNCounterMap replicas gossip their full state: not on an engine with delta-CRDT "
                    "replication (agx_set_delta_crdt; ORMap delta ops are left out)");
@@ -3653,7 +3671,8 @@ agx_status enable_crdt(agx_engine* e, uint32_t kind) {
   const uint32_t words = kind == AGX_KIND_GCOUNTER ? AGX_GCOUNTER_WORDS
                          : kind == AGX_KIND_PNCOUNTER ? AGX_PNCOUNTER_WORDS
                          : kind == AGX_KIND_LWWMAP ? AGX_LWWMAP_WORDS
-                         : kind == AGX_KIND_PNCOUNTERMAP ? AGX_PNCMAP_WORDS : AGX_ORSET_WORDS;
+                         : kind == AGX_KIND_PNCOUNTERMAP ? AGX_PNCMAP_WORDS
+                         : kind == AGX_KIND_ORMULTIMAP ? AGX_ORMM_WORDS : AGX_ORSET_WORDS;
   const uint32_t need = !e->delta_max ? words
                         : kind == AGX_KIND_GCOUNTER ? AGX_GCOUNTER_DELTA_WORDS
                         : kind == AGX_KIND_PNCOUNTER ? AGX_PNCOUNTER_DELTA_WORDS : AGX_ORSET_DELTA_WORDS;
@@ -3694,7 +3713,13 @@ agx_status validate_cfg(const agx_cfg* c) {
   if (!c) return set_err(AGX_EINVAL, "null cfg");
   if (c->abi_version != AGX_ABI_VERSION) return set_err(AGX_EINVAL, "abi_version %u != %u", c->abi_version, AGX_ABI_VERSION);
   if (c->n_actors == 0 || c->n_actors >= (1ull << 31)) return set_err(AGX_EINVAL, "n_actors out of range");
-  if (c->n_words == 0 || c->n_words > AGX_MAX_WORDS) return set_err(AGX_EINVAL, "n_words must be 1..%u", AGX_MAX_WORDS);
+  // every layout but an ORMultiMap replica's fits AGX_MAX_GENERAL_WORDS; the widths between that and
+  // AGX_ORMM_WORDS belong to no kind (an ORMultiMap engine takes exactly AGX_ORMM_WORDS: enable_crdt)
+  static_assert(AGX_MAX_GENERAL_WORDS == AGX_PNCMAP_WORDS && AGX_MAX_WORDS == AGX_ORMM_WORDS && AGX_MAX_GENERAL_WORDS < AGX_MAX_WORDS,
+                "n_words: 1..AGX_MAX_GENERAL_WORDS, or AGX_MAX_WORDS for an ORMultiMap engine");
+  if (c->n_words == 0 || (c->n_words > AGX_MAX_GENERAL_WORDS && c->n_words != AGX_MAX_WORDS))
+    return set_err(AGX_EINVAL, "n_words must be 1..%u, or %u for an engine of ORMultiMap replicas", AGX_MAX_GENERAL_WORDS,
+                   AGX_MAX_WORDS);
   uint32_t R = c->n_ranks ? c->n_ranks : 1;
   if (R > AGX_MAX_RANKS || c->rank >= R) return set_err(AGX_EINVAL, "bad rank %u / n_ranks %u", c->rank, R);
   if (c->num_shards > (uint32_t)INT32_MAX) return set_err(AGX_EINVAL, "num_shards must be < 2^31 (maxNumberOfShards is an Int)");
@@ -4117,7 +4142,13 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
   const bool compiled = kind >= AGX_KIND_COMPILED && kind < AGX_KIND_COMPILED + AGX_MAX_BEHAVIORS;
   const bool lww = kind == AGX_KIND_LWWMAP;
   const bool pnm = kind == AGX_KIND_PNCOUNTERMAP;
-  if (first_id + count > e->n_global || (kind >= AGX_KIND_MAX && !compiled && !lww && !pnm)) return set_err(AGX_EINVAL, "bad range or kind");
+  const bool mmm = kind == AGX_KIND_ORMULTIMAP;
+  if (first_id + count > e->n_global || (kind >= AGX_KIND_MAX && !compiled && !lww && !pnm && !mmm)) return set_err(AGX_EINVAL, "bad range or kind");
+  if (mmm && e->R > 1) return set_err(AGX_EINVAL, "ORMultiMap replicas need a single-rank engine (n_ranks %u)", e->R);
+  // an ORMultiMap engine holds ORMultiMap replicas only (unregistering, AGX_KIND_NONE, stays possible)
+  if (count && kind != AGX_KIND_NONE && (mmm ? (e->kinds_mask & ~(kb(AGX_KIND_NONE) | kb(AGX_KIND_ORMULTIMAP))) != 0
+                                             : (e->kinds_mask & kb(AGX_KIND_ORMULTIMAP)) != 0))
+    return set_err(AGX_EINVAL, "ORMultiMap replicas and actors of another kind (%u) need separate engines", mmm ? 0u : kind);
   if (pnm && e->R > 1) return set_err(AGX_EINVAL, "PNCounterMap replicas need a single-rank engine (n_ranks %u)", e->R);
   // a PNCounterMap engine holds PNCounterMap replicas only (unregistering, AGX_KIND_NONE, stays possible)
   if (count && kind != AGX_KIND_NONE && (pnm ? (e->kinds_mask & ~(kb(AGX_KIND_NONE) | kb(AGX_KIND_PNCOUNTERMAP))) != 0
@@ -4149,7 +4180,7 @@ agx_status agx_register_range(agx_engine* e, uint64_t first_id, uint64_t count, 
                      "its entities are started by their first message", (unsigned long long)first_id,
                      (unsigned long long)(first_id + count), (unsigned long long)c0, (unsigned long long)c1);
   }
-  if ((kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET) || lww || pnm) AGX_TRY(enable_crdt(e, kind));
+  if ((kind >= AGX_KIND_GCOUNTER && kind <= AGX_KIND_ORSET) || lww || pnm || mmm) AGX_TRY(enable_crdt(e, kind));
   if (count && !(e->kinds_mask & kb(kind))) {  // the apply variant is captured in the superstep graphs
     e->kinds_mask |= kb(kind);
     drop_graphs(e);
@@ -5795,6 +5826,9 @@ agx_status agx_set_delta_crdt(agx_engine* e, uint32_t max_delta_size) {
   if (max_delta_size && (e->kinds_mask & kb(AGX_KIND_LWWMAP)))
     return set_err(AGX_EINVAL, "delta-CRDT replication on an engine with LWWMap replicas: they gossip their full state "
                    "(ORMap delta ops are left out)");
+  if (max_delta_size && (e->kinds_mask & kb(AGX_KIND_ORMULTIMAP)))
+    return set_err(AGX_EINVAL, "delta-CRDT replication on an engine with ORMultiMap replicas: they gossip their full "
+                   "state (ORMap delta ops are left out)");
   if (max_delta_size && (e->kinds_mask & kb(AGX_KIND_PNCOUNTERMAP)))
     return set_err(AGX_EINVAL, "delta-CRDT replication on an engine with PNCounterMap replicas: they gossip their full "
                    "state (ORMap delta ops are left out)");

@@ -29,6 +29,7 @@
 #include "agx_crdt.h"
 #include "agx_lwwmap.h"
 #include "agx_pncmap.h"
+#include "agx_ormm.h"
 #include "agx_device.h"
 
 namespace agx {
@@ -2383,7 +2384,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     constexpr bool kLwRows = kWide && KM == kb(AGX_KIND_LWWMAP);
     // PNCounterMap populations (V_PNCMAP, up to 10368-B rows): likewise (kPnRowLen, agx_pncmap.h)
     constexpr bool kPnRows = kWide && KM == kb(AGX_KIND_PNCOUNTERMAP);
-    constexpr bool kWaveRows = kBigRows || kLwRows || kPnRows;
+    // ORMultiMap populations (V_ORMM, up to 20608-B rows): likewise (kMmRowLen, agx_ormm.h)
+    constexpr bool kMmRows = kWide && KM == kb(AGX_KIND_ORMULTIMAP);
+    constexpr bool kWaveRows = kBigRows || kLwRows || kPnRows || kMmRows;
     static_assert(!kBigRows || !(KM & kDeltaKM) || (KM & ~kDeltaKM) == kb(AGX_KIND_ORSET),
                   "a delta variant that copies rows by their used length holds ORSet groups only: counter groups "
                   "write no length word (dl_group_row)");
@@ -2454,6 +2457,8 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
                 n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kLwRowLen] + 3u) / 4u);
               if constexpr (kPnRows)  // (likewise; the used length is a multiple of 4 u32)
                 n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kPnRowLen] + 3u) / 4u);
+              if constexpr (kMmRows)  // (likewise)
+                n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kMmRowLen] + 3u) / 4u);
               for (uint32_t k2 = lane; k2 < n4; k2 += kWave) d[k2] = s[k2];
             }
           }
@@ -3561,6 +3566,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       if constexpr (kWide && KM == kb(AGX_KIND_PNCOUNTERMAP)) {  // (a PNCounterMap engine holds nothing else either)
         for (uint32_t q = 0; q < nd; ++q) em.count(pncmap_count(P, isrc(s0 + q), ipay(s0 + q), &nrows_t));
       } else
+      if constexpr (kWide && KM == kb(AGX_KIND_ORMULTIMAP)) {  // (nor does an ORMultiMap engine)
+        for (uint32_t q = 0; q < nd; ++q) em.count(ormm_count(P, isrc(s0 + q), ipay(s0 + q), &nrows_t));
+      } else
       if (kWide && is_crdt(kd)) {
         DeltaSim ds;
         ds.on = false;
@@ -3634,7 +3642,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     constexpr bool kLwWave = kWide && KM == kb(AGX_KIND_LWWMAP);
     // (PNCounterMap-only variant: pncmap_protocol here and k_pncmap_merge after the apply)
     constexpr bool kPnWave = kWide && KM == kb(AGX_KIND_PNCOUNTERMAP);
-    constexpr bool kWaveList = kOrWave || kLwWave || kPnWave;
+    // (ORMultiMap-only variant: ormm_protocol here and k_ormm_merge after the apply)
+    constexpr bool kMmWave = kWide && KM == kb(AGX_KIND_ORMULTIMAP);
+    constexpr bool kWaveList = kOrWave || kLwWave || kPnWave || kMmWave;
   #pragma unroll 1
     for (int j = 0; j < kBAct; ++j) {
       const uint32_t la = j * kBThreads + tid;
@@ -3663,6 +3673,13 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
         bool work = false;
         const uint32_t rc0 = row_cursor;
         nunh += pncmap_protocol(P, self, s0, nd, isrc, ipay, row_cursor, em, &work);
+        ndel += nd;
+        L.ecnt[la] = work ? rc0 : 0xFFFFFFFFu;
+      } else
+      if constexpr (kMmWave) {  // protocol here, state effects by k_ormm_merge (agx_ormm.h)
+        bool work = false;
+        const uint32_t rc0 = row_cursor;
+        nunh += ormm_protocol(P, self, s0, nd, isrc, ipay, row_cursor, em, &work);
         ndel += nd;
         L.ecnt[la] = work ? rc0 : 0xFFFFFFFFu;
       } else
@@ -7239,6 +7256,23 @@ static __global__ void __launch_bounds__(kThreads) k_pncmap_merge(DevParams P, c
     const uint2* msg = orm + w.z;
     pncmap_merge_wave(P, H, w.x, w.y & 0xFFu, w.y >> 8, w.w, [&](uint32_t q) { return msg[q].x; },
                       [&](uint32_t q) { return msg[q].y; });
+  }
+}
+
+// ORMultiMap-only populations: the state effects of every replica run the apply listed (ormm_protocol did
+// its tells and snapshot-row allocation): one wave per replica, lane = key (ormm_merge_wave).  The launch
+// bound is the block size: a lane holds 88 VGPRs of its own key (8 key dots, 72 of the value set, the key
+// set's version vector) and streams a row's value set 8 dots at a time.
+static __global__ void __launch_bounds__(kThreads) k_ormm_merge(DevParams P, const uint4* orw, const uint2* orm,
+                                                            const uint32_t* orw_n) {
+  const uint32_t n = orw_n[0];
+  const CrdtHeap H = crdt_heap(P);
+  const uint32_t nw = gridDim.x * (kThreads / kWave);
+  for (uint32_t it = blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave; it < n; it += nw) {
+    const uint4 w = orw[it];
+    const uint2* msg = orm + w.z;
+    ormm_merge_wave(P, H, w.x, w.y & 0xFFu, w.y >> 8, w.w, [&](uint32_t q) { return msg[q].x; },
+                    [&](uint32_t q) { return msg[q].y; });
   }
 }
 

@@ -24,6 +24,7 @@ enum : uint32_t {
   V_RING, V_FWD, V_FANOUT, V_COUNTER, V_COMPILED, V_ALL_COMPILED, V_ALL,
   V_LWWMAP,  // LWWMap replicas only (agx_lwwmap.h); appended: the ids above do not move
   V_PNCMAP,  // PNCounterMap replicas only (agx_pncmap.h); appended likewise
+  V_ORMM,    // ORMultiMap replicas only (agx_ormm.h); appended likewise
   V_N
 };
 constexpr ApplyVariant kVariants[V_N] = {
@@ -37,12 +38,17 @@ constexpr ApplyVariant kVariants[V_N] = {
     {false, KM_ALL | kb(AGX_KIND_COMPILED)},  {false, KM_ALL},
     {true, kb(AGX_KIND_LWWMAP)},
     {true, kb(AGX_KIND_PNCOUNTERMAP)},
+    {true, kb(AGX_KIND_ORMULTIMAP)},
 };
 static_assert((kb(AGX_KIND_LWWMAP) & (KM_ALL | kCrdtKM | kb(AGX_KIND_COMPILED))) == 0 && kb(AGX_KIND_LWWMAP) < kBackoffKM,
               "the LWWMap kind has a mask bit of its own");
 static_assert((kb(AGX_KIND_PNCOUNTERMAP) & (KM_ALL | kCrdtKM | kb(AGX_KIND_COMPILED) | kb(AGX_KIND_LWWMAP))) == 0 &&
                   kb(AGX_KIND_PNCOUNTERMAP) < kBackoffKM,
               "the PNCounterMap kind has a mask bit of its own");
+static_assert((kb(AGX_KIND_ORMULTIMAP) & (KM_ALL | kCrdtKM | kb(AGX_KIND_COMPILED) | kb(AGX_KIND_LWWMAP) |
+                                          kb(AGX_KIND_PNCOUNTERMAP))) == 0 &&
+                  kb(AGX_KIND_ORMULTIMAP) < kBackoffKM,
+              "the ORMultiMap kind has a mask bit of its own");
 
 // pipeline modes: fused single-rank gather (kGather), multi-rank owner grouping (kOwner),
 // single-rank multi-pass with the backlog in place (neither)
@@ -50,14 +56,16 @@ enum : uint32_t { M_FUSED = 0, M_OWNER = 1, M_BYPASS = 2, M_PERSIST = 3 /* dense
 
 // variant groups = translation units (agx_apply.hip built with -DAGX_VGROUP=0..kVGroups-1);
 // the heavy CRDT variants are spread so the units take similar time
-constexpr uint32_t kVGroups = 11;
+constexpr uint32_t kVGroups = 12;
 // the last group holds no variant of the table: it is the unit of the kSuperKM | kBackoffKM feature launches alone
 constexpr uint32_t kBackoffGroup = 8;
 // V_LWWMAP and k_lwwmap_merge are a unit of their own too, so that every other unit compiles what it compiled before
 constexpr uint32_t kLwwmapGroup = 9;
 // and so are V_PNCMAP and k_pncmap_merge
 constexpr uint32_t kPncmapGroup = 10;
-constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7, kLwwmapGroup, kPncmapGroup};
+// and V_ORMM and k_ormm_merge
+constexpr uint32_t kOrmmGroup = 11;
+constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7, kLwwmapGroup, kPncmapGroup, kOrmmGroup};
 
 // launch k_bucket_apply<variant vid, mode, skew> with `grid` x kBThreads threads on `s`
 // (defined in agx_apply.hip; returns hipErrorInvalidValue for an unknown combination)
@@ -79,6 +87,10 @@ hipError_t agx_launch_lwwmap_merge(dim3 grid, hipStream_t s, const DevParams& P,
 // orw / orm / orw_n
 hipError_t agx_launch_pncmap_merge(dim3 grid, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
                                    const uint32_t* orw_n);
+// launch k_ormm_merge after V_ORMM's apply (defined in kOrmmGroup's unit): the runs the apply listed in
+// orw / orm / orw_n
+hipError_t agx_launch_ormm_merge(dim3 grid, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
+                                 const uint32_t* orw_n);
 // launch k_tiny_apply<variant vid's kinds> (plain / compiled variants only: hipErrorInvalidValue otherwise)
 hipError_t agx_launch_tiny(uint32_t vid, dim3 grid, hipStream_t s, const BucketArgs& ba);
 // launch k_dense_apply<variant vid's kinds> (mode M_FUSED / M_OWNER: k_dense_fused) (plain / compiled variants only)

@@ -17,6 +17,15 @@ through the engine (Op.put, Op.REMOVE); `to_words` exists to seed replicas (regi
 
 "PNCounterMap replicas": the same key set, 12 words of padding, then 16 u64 slots per key (8 increments, 8
 decrements, one per node).  Writes: Op.increment_key, Op.decrement_key, Op.REMOVE.
+
+    from akka_amd.ddata import ORMultiMap
+    m = ORMultiMap.from_words(words[replica])
+    m.entries            # {key: frozenset of value indices}
+    m.get(3), m.get_or_else(3, frozenset()), m.contains(3), m.size, m.is_empty
+
+"ORMultiMap replicas": the same key set and padding, then 72 u32 per key: the value set's own version vector
+(8 u32) and 8 values x 8 node dots.  Writes: Op.add_binding, Op.remove_binding, Op.put_set, Op.replace_binding,
+Op.REMOVE.
 """
 from __future__ import annotations
 
@@ -24,7 +33,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .engine import CRDT_NODES, CRDT_WORDS, Kind, LWW_VALUE_MAX, ORSET_ELEMS
+from .engine import ORMM_VALUES, CRDT_NODES, CRDT_WORDS, Kind, LWW_VALUE_MAX, ORSET_ELEMS
 
 LWWMAP_WORDS = CRDT_WORDS[Kind.LWWMAP]
 _VV = ORSET_ELEMS * CRDT_NODES          # u32 index of the version vector
@@ -34,6 +43,9 @@ INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 PNCMAP_WORDS = CRDT_WORDS[Kind.PNCOUNTERMAP]
 _CTR = 272                              # u64 index of key 0's slots (AGX_PNCMAP_CTR_WORD)
 _SLOTS = 2 * CRDT_NODES                 # u64 slots per key: increments, then decrements
+ORMM_WORDS = CRDT_WORDS[Kind.ORMULTIMAP]
+_SET = 2 * 272                          # u32 index of key 0's value set (AGX_ORMM_SET_WORD)
+_SET_U32 = CRDT_NODES + ORMM_VALUES * CRDT_NODES  # AGX_ORMM_SET_U32: version vector, then 8 values x 8 node dots
 
 
 @dataclass
@@ -187,3 +199,93 @@ class PNCounterMap:
     @property
     def size(self) -> int:
         return len(self.slots)
+
+
+@dataclass
+class ORMultiMap:
+    """One replica's ORMultiMap: per live key its key dots {node: version} and its value set -- that set's own
+    version vector {node: version} and per bound value its dots {node: version}; the key set's version vector."""
+    dots: dict = field(default_factory=dict)        # key -> {node: version}, live keys only
+    vvector: dict = field(default_factory=dict)     # node -> version (the key set's)
+    sets: dict = field(default_factory=dict)        # key -> (vvector {node: version}, {value: {node: version}})
+
+    @classmethod
+    def from_words(cls, row) -> "ORMultiMap":
+        w = np.ascontiguousarray(np.asarray(row, np.uint64)[:ORMM_WORDS])
+        if w.size != ORMM_WORDS:
+            raise ValueError(f"an ORMultiMap replica has {ORMM_WORDS} state words, got {w.size}")
+        u = w.view(np.uint32)
+        if w[_TS:272].any():
+            raise ValueError("the padding words 260..271 are not zero: not canonical")
+        m = cls()
+        for k in range(ORSET_ELEMS):
+            d = {n: int(u[k * CRDT_NODES + n]) for n in range(CRDT_NODES) if u[k * CRDT_NODES + n]}
+            b = u[_SET + _SET_U32 * k:_SET + _SET_U32 * (k + 1)]
+            if d:
+                m.dots[k] = d
+                vv = {n: int(b[n]) for n in range(CRDT_NODES) if b[n]}
+                vals = {}
+                for v in range(ORMM_VALUES):
+                    e = b[CRDT_NODES * (1 + v):CRDT_NODES * (2 + v)]
+                    if e.any():
+                        vals[v] = {n: int(e[n]) for n in range(CRDT_NODES) if e[n]}
+                m.sets[k] = (vv, vals)
+            elif b.any():
+                raise ValueError(f"key {k} has no live dot but a non-zero value set: not canonical")
+        m.vvector = {n: int(u[_VV + n]) for n in range(CRDT_NODES) if u[_VV + n]}
+        return m
+
+    def to_words(self) -> np.ndarray:
+        w = np.zeros(ORMM_WORDS, np.uint64)
+        u = w.view(np.uint32)
+        if set(self.dots) != set(self.sets):
+            raise ValueError("every live key has exactly one value set")
+
+        def put(i, n, v, what):
+            if not (0 <= n < CRDT_NODES and 0 < v < 1 << 32):
+                raise ValueError(f"{what} {n} -> {v} does not fit the layout")
+            u[i + n] = v
+
+        for k, d in self.dots.items():
+            if not 0 <= k < ORSET_ELEMS or not d:
+                raise ValueError(f"key {k}: outside the 64-key universe, or without a dot")
+            for n, v in d.items():
+                put(k * CRDT_NODES, n, v, f"dot of key {k}")
+            vv, vals = self.sets[k]
+            base = _SET + _SET_U32 * k
+            for n, v in vv.items():
+                put(base, n, v, f"version vector entry of key {k}'s set")
+            for val, e in vals.items():
+                if not 0 <= val < ORMM_VALUES or not e:
+                    raise ValueError(f"value {val} of key {k}: outside the 8-value universe, or without a dot")
+                for n, v in e.items():
+                    put(base + CRDT_NODES * (1 + val), n, v, f"dot of value {val} of key {k}")
+        for n, v in self.vvector.items():
+            put(_VV, n, v, "version vector entry")
+        return w
+
+    def get(self, key: int):
+        """ORMultiMap.get: the key's set of value indices, a frozenset (None: no such key)."""
+        s = self.sets.get(key)
+        return None if s is None else frozenset(s[1])
+
+    def get_or_else(self, key: int, default):
+        s = self.get(key)
+        return default if s is None else s
+
+    @property
+    def entries(self) -> dict:
+        """ORMultiMap.entries: {key: frozenset of value indices}."""
+        return {k: frozenset(self.sets[k][1]) for k in sorted(self.sets)}
+
+    def contains(self, key: int) -> bool:
+        """ORMultiMap.contains reads the key set (DD/ORMultiMap.scala:131)."""
+        return key in self.dots
+
+    @property
+    def size(self) -> int:
+        return len(self.dots)
+
+    @property
+    def is_empty(self) -> bool:
+        return not self.dots

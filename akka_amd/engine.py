@@ -31,18 +31,20 @@ class Kind:
     ORSET = 10
     LWWMAP = 11       # LWWMap = ORMap of LWWRegister (AGX_KIND_LWWMAP, not in the enum), "LWWMap replicas"
     PNCOUNTERMAP = 12  # PNCounterMap = ORMap of PNCounter (AGX_KIND_PNCOUNTERMAP), "PNCounterMap replicas"
+    ORMULTIMAP = 13   # ORMultiMap = ORMap of ORSet (AGX_KIND_ORMULTIMAP), "ORMultiMap replicas"
 
 
 CRDT_NODES = 8
 ORSET_ELEMS = 64
 CRDT_WORDS = {Kind.GCOUNTER: 8, Kind.PNCOUNTER: 16, Kind.ORSET: 260, Kind.LWWMAP: 356,
-              Kind.PNCOUNTERMAP: 1296}
+              Kind.PNCOUNTERMAP: 1296, Kind.ORMULTIMAP: 2576}
 # delta-CRDT mode (agx_set_delta_crdt): data + envelope/selector area + delta log (include/akka_gpu.h)
 DELTA_ENV_WORDS, DELTA_LOG = 12, 64
 CRDT_DELTA_WORDS = {k: w + DELTA_ENV_WORDS + (DELTA_LOG * 6 if k == Kind.ORSET else 4) for k, w in CRDT_WORDS.items()
-                    if k not in (Kind.LWWMAP, Kind.PNCOUNTERMAP)}  # (map replicas gossip their full state only)
+                    if k not in (Kind.LWWMAP, Kind.PNCOUNTERMAP, Kind.ORMULTIMAP)}  # (map replicas gossip their full state only)
 LWW_VALUE_MAX = 0x3FFFF
 PNCMAP_COUNT_MAX = 0x3FFFF  # AGX_PNCMAP_COUNT_MAX
+ORMM_VALUES = 8             # AGX_ORMM_VALUES: the value universe of an ORMultiMap key's set
 LWW_CLOCKS = {"default": 0, "reverse": 1}  # AGX_LWW_CLOCK_DEFAULT / AGX_LWW_CLOCK_REVERSE
 DELTA_WRITE = 0x800000
 WIDE_BIT = 0x80000000
@@ -58,6 +60,8 @@ class Op:
     GOSSIP = 6
     DELTA_TICK = 7
     PUT = 8
+    REMOVE_BINDING = 9
+    REPLACE_BINDING = 10
 
     @staticmethod
     def make(op: int, arg: int = 0) -> int:
@@ -89,6 +93,43 @@ class Op:
     def decrement_key(key: int, n: int = 1) -> int:
         """PNCounterMap.decrement(key, n) on a PNCounterMap replica: key < 64, 0 <= n < 2^18 (AGX_OP_COUNT_ARG)."""
         return Op._count(Op.DECREMENT, key, n)
+
+
+    @staticmethod
+    def _binding(key: int, *values: int) -> None:
+        if not 0 <= key < ORSET_ELEMS:
+            raise ValueError(f"ORMultiMap key {key} outside the 64-key universe")
+        for v in values:
+            if not 0 <= v < ORMM_VALUES:
+                raise ValueError(f"ORMultiMap value {v} outside the {ORMM_VALUES}-value universe")
+
+    @staticmethod
+    def add_binding(key: int, value: int) -> int:
+        """ORMultiMap.addBinding(key, value) on an ORMultiMap replica: key < 64, value < 8 (AGX_OP_BINDING_ARG)."""
+        Op._binding(key, value)
+        return Op.make(Op.ADD, key | (value << 6))
+
+    @staticmethod
+    def remove_binding(key: int, value: int) -> int:
+        """ORMultiMap.removeBinding(key, value): a set left empty takes its key with it (AGX_OP_BINDING_ARG)."""
+        Op._binding(key, value)
+        return Op.make(Op.REMOVE_BINDING, key | (value << 6))
+
+    @staticmethod
+    def put_set(key: int, values) -> int:
+        """ORMultiMap.put(key, set): `values` is an iterable of value indices < 8, possibly empty (AGX_OP_PUT_SET_ARG)."""
+        values = list(values)
+        Op._binding(key, *values)
+        mask = 0
+        for v in values:
+            mask |= 1 << v
+        return Op.make(Op.PUT, key | (mask << 6))
+
+    @staticmethod
+    def replace_binding(key: int, old: int, new: int) -> int:
+        """ORMultiMap.replaceBinding(key, old, new): nothing at all when old == new (AGX_OP_REPLACE_ARG)."""
+        Op._binding(key, old, new)
+        return Op.make(Op.REPLACE_BINDING, key | (old << 6) | (new << 9))
 
 
 @dataclass

@@ -349,6 +349,55 @@ def crdt_pncountermap(n: int = 1_000_000, rounds: int = 32, fanout: int = 2, inc
                     bucket_actors=bucket_actors)
 
 
+def ormultimap_ops(nw: int, binds: int, removes: int, keys: int = 12, seed: int = SEED) -> np.ndarray:
+    """Round-0 local updates of the `nw` writers of an ORMultiMap population, one row per writer -- a service
+    registry: `binds` seeded binding ops (of 16, ten bind an instance to a service, three unbind one, one puts a
+    whole set, two replace an instance) with `removes` removes of a whole service spread among them, all over the
+    first `keys` services and the 8 instances, so that writers collide on keys and values."""
+    per = binds + removes
+    out = np.zeros((nw, per), np.uint32)
+    a = np.arange(nw, dtype=np.uint64)
+    rm_at = set((np.arange(removes) * per // max(removes, 1) + per // (2 * max(removes, 1))).tolist()) if removes else set()
+    for j in range(per):
+        r = splitmix64_np((a << np.uint64(8)) ^ np.uint64(j) ^ np.uint64(seed * 19))
+        key = (r % np.uint64(keys)).astype(np.uint32)
+        val = ((r >> np.uint64(20)) & np.uint64(7)).astype(np.uint32)
+        new = ((r >> np.uint64(24)) & np.uint64(7)).astype(np.uint32)
+        mask = ((r >> np.uint64(28)) & np.uint64(255)).astype(np.uint32)
+        sel = ((r >> np.uint64(40)) & np.uint64(15)).astype(np.uint32)
+        bind = (np.uint32(Op.ADD) << np.uint32(24)) | key | (val << np.uint32(6))
+        unbind = (np.uint32(Op.REMOVE_BINDING) << np.uint32(24)) | key | (val << np.uint32(6))
+        put = (np.uint32(Op.PUT) << np.uint32(24)) | key | (mask << np.uint32(6))
+        repl = (np.uint32(Op.REPLACE_BINDING) << np.uint32(24)) | key | (val << np.uint32(6)) | (new << np.uint32(9))
+        if j in rm_at:
+            out[:, j] = (np.uint32(Op.REMOVE) << np.uint32(24)) | key
+        else:
+            out[:, j] = np.where(sel < 10, bind, np.where(sel < 13, unbind, np.where(sel < 14, put, repl)))
+    return out
+
+
+def crdt_ormultimap(n: int = 1_000_000, rounds: int = 32, fanout: int = 2, binds_per_writer: int = 16, removes: int = 4,
+                    throughput: int = 5, seed: int = SEED, capacity: int = 0, bucket_actors: int = 512) -> Workload:
+    """ORMultiMap replicas (ORMultiMap = ORMap of ORSet) as a service registry, in crdt_pncountermap's shape:
+    replicas 0..7 are the writers, one per node slot, and first bind and unbind instances (8 values) to a dozen
+    services (keys) with seeded host tells, so that writers collide on keys and values; then every replica runs
+    `rounds` GossipTicks.  The population converges to the merge of the writers' maps.  A replica's snapshot row is
+    up to 20 KB: pass `msg_capacity` to the engine explicitly (the default sizes the row heap for max(4n, 65536)
+    messages)."""
+    nw = min(n, CRDT_NODES)
+    per = binds_per_writer + removes
+    ops = ormultimap_ops(nw, binds_per_writer, removes, seed=seed).reshape(-1)
+    odst = np.repeat(np.arange(nw, dtype=np.uint32), per)
+    tdst = np.arange(n, dtype=np.uint32)
+    tick = np.full(n, Op.make(Op.GOSSIP, rounds - 1), np.uint32)
+    dst = np.concatenate([odst, tdst])
+    pay = np.concatenate([ops, tick])
+    src = np.full(dst.size, NO_SENDER, np.uint32)
+    return Workload("crdt_ormultimap", n, CRDT_WORDS[Kind.ORMULTIMAP], fanout + 1, throughput, capacity,
+                    [(0, n, Kind.ORMULTIMAP, None)], gossip=(fanout, seed), tells=(dst, src, pay),
+                    bucket_actors=bucket_actors)
+
+
 def crdt_delta(n: int = 1_000_000, kind: int = Kind.ORSET, rounds: int = 32, write: bool = True,
                ops_per_replica: int = 0, gossip_rounds: int = 0, fanout: int = 1, max_delta_size: int = 50,
                throughput: int = 5, seed: int = SEED, capacity: int = 0, bucket_actors: int = 0) -> Workload:

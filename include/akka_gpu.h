@@ -131,6 +131,8 @@ enum agx_behavior_kind {
 #define AGX_KIND_LWWMAP 11u
 /* a PNCounterMap replica (see "PNCounterMap replicas" below); outside the enum for the same reason */
 #define AGX_KIND_PNCOUNTERMAP 12u
+/* an ORMultiMap replica (see "ORMultiMap replicas" below); outside the enum for the same reason */
+#define AGX_KIND_ORMULTIMAP 13u
 #define AGX_MAX_BEHAVIORS 64u
 #define AGX_MAX_CASES 1024u
 #define AGX_MAX_ACTS 4096u
@@ -283,7 +285,9 @@ typedef struct agx_act {
   int64_t k, dk;
 } agx_act; /* 32 B */
 
-#define AGX_MAX_WORDS 1296u /* = AGX_PNCMAP_WORDS (the widest layout) */
+#define AGX_MAX_WORDS 2576u /* = AGX_ORMM_WORDS (the widest layout: an engine of ORMultiMap replicas, exactly this) */
+#define AGX_MAX_GENERAL_WORDS 1296u /* = AGX_PNCMAP_WORDS: n_words of every other engine is 1..this; the widths
+                                     * between the two fit no layout and are refused                            */
 #define AGX_MAX_RANKS 16u
 
 /* --- CRDT behaviours ---------------------------------------------------------
@@ -408,8 +412,8 @@ typedef struct agx_act {
  * A timestamp that would pass the int64 range raises AGX_ERANGE (the reference's Long would wrap),
  * as a wrapping ORSet version does.
  * An LWWMap engine holds LWWMap replicas only, on one rank, with full-state gossip.  Left out:
- * LWWRegister as a kind of its own, ORMultiMap, GSet, Flag, ORMap delta ops, pruning, multi-rank
- * engines, custom clocks, the JVM shim.  (PNCounterMap is a kind of its own, below.)             */
+ * LWWRegister as a kind of its own, GSet, Flag, ORMap delta ops, pruning, multi-rank engines,
+ * custom clocks, the JVM shim.  (PNCounterMap and ORMultiMap are kinds of their own, below.)     */
 #define AGX_LWWMAP_WORDS 356u /* 260 (keys) + 64 (timestamps) + 32 (64 u32 registers) */
 #define AGX_LWWMAP_TS_WORD 260u
 #define AGX_LWWMAP_REG_U32 648u
@@ -456,12 +460,73 @@ typedef struct agx_act {
  * AGX_ERANGE: a slot would pass 2^64 - 1 (the reference's BigInt would not wrap; as for
  * AGX_KIND_PNCOUNTER), or a replica's own version would pass 2^32 - 1 (as for ORSet and LWWMap).
  * A PNCounterMap engine holds PNCounterMap replicas only, on one rank, with full-state gossip and
- * n_words = AGX_PNCMAP_WORDS.  Left out: ORMap delta ops, ORMultiMap, pruning, multi-rank engines,
- * mixed populations, the JVM shim.                                                              */
+ * n_words = AGX_PNCMAP_WORDS.  Left out: ORMap delta ops, pruning, multi-rank engines, mixed
+ * populations, the JVM shim.  (ORMultiMap is a kind of its own, below.)                         */
 #define AGX_PNCMAP_WORDS 1296u /* 260 (keys) + 12 (padding) + 64 * 16 (slots) = 81 lines of 128 B */
 #define AGX_PNCMAP_CTR_WORD 272u
 #define AGX_PNCMAP_COUNT_MAX 0x3FFFFu
 #define AGX_OP_COUNT_ARG(key, n) (((uint32_t)(key) & 63u) | ((uint32_t)(n) << 6))
+
+/* --- ORMultiMap replicas (AGX_KIND_ORMULTIMAP) -----------------------------------------------
+ * ORMultiMap[A, B] = ORMap[A, ORSet[B]] over the 64-key universe, each key's set over a universe of
+ * AGX_ORMM_VALUES = 8 values; the plain ORMultiMap.empty (withValueDeltas = false)
+ * (DD/ORMultiMap.scala:78-91 merge, :182-189 put, :216-225 remove, :248-252 addBinding, :277-290
+ * removeBinding, :310-318 replaceBinding; DD/ORMap.scala:308-334 updated, :361-366 remove, :379-409
+ * dryMerge and merge; DD/ORSet.scala:339 add, :380 remove, :404 clear, :427- merge).
+ * node = id % AGX_CRDT_NODES as for the other CRDT kinds.
+ * State, AGX_ORMM_WORDS u64 per replica (161 lines of 128 B):
+ *   w[0..259]              ORMap.keys: bit for bit the AGX_KIND_ORSET layout (64 keys x 8 u32 dots, the
+ *                          8 u32 version vector)
+ *   w[260..271]            always 0 (padding, as in a PNCounterMap replica)
+ *   w[272 + 36k .. + 35]   key k's value ORSet[B] as 72 u32 (AGX_ORMM_SET_WORD = 272, AGX_ORMM_SET_U32 = 72):
+ *                          u32 [0..7] the value set's own version vector, u32 [8 + 8v + n] the dot of
+ *                          value v by node n, 0 = no dot.  Every block is 16-B aligned.
+ * Canonical form: a key without a live key-dot has 72 zero u32 (ORMap `values - key`); every operation
+ * leaves this form, so states compare bit for bit.  A live key may hold an empty set (put(key, Set())).
+ * Ops (control tells):
+ *   AGX_OP_ADD             arg = key | value << 6 < 512    addBinding(node, key, value):
+ *                          ORMap.updated(node, key, ORSet.empty)(_.add(node, value)) -- the key is added as
+ *                          AGX_OP_ADD adds an ORSet element (key-set vvector + 1, one birth dot); the
+ *                          present set, or an empty one with a zero version vector, gets its own version
+ *                          vector + 1 at node and the value's dots replaced by that one dot.
+ *   AGX_OP_REMOVE_BINDING  arg = key | value << 6 < 512    removeBinding: the same `updated` with
+ *                          ORSet.remove (the value's dots dropped, the set's version vector untouched); a
+ *                          set left empty -- the value or the key may have been absent -- is followed by
+ *                          ORMap.remove(node, key): key dots and the 72 u32 cleared, the key-set version
+ *                          vector keeps the + 1.
+ *   AGX_OP_PUT             arg = key | mask << 6, mask < 256 (bit v = value v)   put(node, key, set):
+ *                          `updated` with clear() (all dots dropped, the version vector kept), then add of
+ *                          every value of the mask in ascending value index.  (The reference folds over a
+ *                          Scala Set in its iteration order; the order only decides which of the
+ *                          consecutive versions each value gets, never `entries`.)  Mask 0 leaves a live
+ *                          key with an empty set.
+ *   AGX_OP_REPLACE_BINDING arg = key | old << 6 | new << 9 < 4096   replaceBinding: old == new returns
+ *                          `this` (handled, no state change at all); otherwise addBinding(new) then
+ *                          removeBinding(old) in one message.
+ *   AGX_OP_REMOVE          arg = key < 64       remove(node, key) = ORMap.remove
+ *   AGX_OP_GOSSIP          as for the other kinds; the state gossip's payload carries data type 3
+ *   every other op, and every argument out of range, is Behaviors.unhandled.
+ * Merge of a received snapshot: the keys merge by ORSet.merge; a key of the merged set present on both
+ * sides takes ORSet.merge of the two value sets with their own version vectors, a key present on one
+ * side takes that side's set, a key absent from the merged set has its 72 u32 cleared.  The reference's
+ * anomalies are kept: a removeBinding concurrent with another node's addBinding to the same set can be
+ * lost ("removals can be lost", ORMultiMap.scala:65), and a key removed and bound again starts a set with
+ * a zero version vector, so it gets stale dots back from a peer that still holds the old set.
+ * AGX_ERANGE: the key set's version or a value set's version at the node would pass 2^32 - 1.
+ * An ORMultiMap engine holds ORMultiMap replicas only, on one rank, with full-state gossip and
+ * n_words = AGX_ORMM_WORDS.  A snapshot row is up to 20 608 B: pass msg_capacity explicitly.  Left out:
+ * ORMultiMap.emptyWithValueDeltas, ORMap delta ops, pruning, multi-rank engines, mixed populations, the
+ * JVM shim.                                                                                      */
+#define AGX_ORMM_VALUES 8u
+#define AGX_ORMM_SET_U32 72u   /* 8 (version vector) + 8 values x 8 nodes */
+#define AGX_ORMM_SET_WORD 272u
+#define AGX_ORMM_WORDS 2576u /* 260 (keys) + 12 (padding) + 64 * 36 (value sets) = 161 lines of 128 B */
+#define AGX_OP_REMOVE_BINDING 9u
+#define AGX_OP_REPLACE_BINDING 10u
+#define AGX_OP_BINDING_ARG(key, value) (((uint32_t)(key) & 63u) | (((uint32_t)(value) & 7u) << 6))
+#define AGX_OP_PUT_SET_ARG(key, mask) (((uint32_t)(key) & 63u) | (((uint32_t)(mask) & 255u) << 6))
+#define AGX_OP_REPLACE_ARG(key, old_value, new_value) \
+  (((uint32_t)(key) & 63u) | (((uint32_t)(old_value) & 7u) << 6) | (((uint32_t)(new_value) & 7u) << 9))
 
 typedef struct agx_cfg {
   uint32_t abi_version;   /* must be AGX_ABI_VERSION                                   */
@@ -469,7 +534,7 @@ typedef struct agx_cfg {
   uint64_t n_actors;      /* global actor population (ids 0..n_actors-1), < 2^31       */
   uint32_t throughput;    /* dispatcher `throughput` (RC:541); <=0 behaves as 1 (Mailbox.scala:261) */
   uint32_t capacity;      /* bounded mailbox capacity C (Mailboxes.scala:212-216); 0 = unbounded */
-  uint32_t n_words;       /* u64 state words per actor, 1..AGX_MAX_WORDS               */
+  uint32_t n_words;       /* u64 state words: 1..AGX_MAX_GENERAL_WORDS, or AGX_MAX_WORDS */
   uint32_t max_emit;      /* max tells one message may emit (kmax)                     */
   uint32_t n_ranks;       /* GPUs the population is hash-sharded over (1 = single GPU) */
   uint32_t rank;          /* this engine's rank                                        */
