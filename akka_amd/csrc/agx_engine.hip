@@ -2739,6 +2739,9 @@ agx_status sync_mirrors(agx_engine* e) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
   AGX_TRY(copy_sync(e, e->h_alive.data(), e->d_alive, e->n_local, hipMemcpyDeviceToHost));
+  // (the kinds too: become, unstash_all, a restart, a child's Create and an entity's start change them on the
+  // device, and the next upload writes the whole mirror back; h_init keeps the registered kinds)
+  AGX_TRY(copy_sync(e, e->h_kind.data(), e->d_kind, e->n_local, hipMemcpyDeviceToHost));
   if (e->pitch) {  // actor-major rows -> word-major mirror
     std::vector<uint64_t> rows((size_t)e->n_local * e->pitch);
     AGX_TRY(copy_sync(e, rows.data(), e->d_state, rows.size() * 8, hipMemcpyDeviceToHost));

@@ -752,6 +752,11 @@ void bsp_read_state(bsp_sim* s, uint64_t first, uint64_t count, uint64_t* words,
   }
 }
 
+/* agx_read_kinds: each actor's behaviour kind now (a compiled behaviour's become changes it) */
+void bsp_read_kinds(const bsp_sim* s, uint64_t first, uint64_t count, uint8_t* kinds) {
+  memcpy(kinds, s->kind + first, count);
+}
+
 /* ------------------------------------------------ CRDT restatements (KATs) */
 
 /* GCounter over R node slots (node index 0..R-1 in UniqueAddress order,

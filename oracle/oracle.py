@@ -91,6 +91,7 @@ def _load_bsp():
             "bsp_stage": (ctypes.c_int, [vp, P32, P32, P32, u64]),
             "bsp_run": (ctypes.c_int, [vp, u32, ctypes.POINTER(Stats)]),
             "bsp_read_state": (None, [vp, u64, u64, P64, P8]),
+            "bsp_read_kinds": (None, [vp, u64, u64, P8]),
             "bsp_delta_backlog_census": (None, [vp, P64]),
             "bsp_orset_backlog_census": (None, [vp, P64]),
             "bsp_java_hash_decimal": (ctypes.c_int32, [u32]),
@@ -251,6 +252,15 @@ class BspOracle(_Base):
         a = np.zeros(count, np.uint8)
         self.lib.bsp_read_state(self.h, first, count, _p(w, ctypes.c_uint64), _p(a, ctypes.c_uint8))
         return w, a
+
+    def read_kinds(self, first=0, count=None):
+        """Each actor's behaviour kind now (GpuEngine.read_kinds): the registered kind until a become."""
+        count = self.n - first if count is None else count
+        if first + count > self.n:
+            raise ValueError("bad actor range")
+        k = np.zeros(count, np.uint8)
+        self.lib.bsp_read_kinds(self.h, first, count, _p(k, ctypes.c_uint8))
+        return k
 
     def delta_backlog_census(self):
         """(gcounter, pncounter, orset): the envelope-supersteps that DeltaPropagations of each data
