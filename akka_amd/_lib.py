@@ -138,6 +138,7 @@ SIGNATURES = {
     "agx_set_gossip": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]),
     "agx_set_delta_crdt": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32]),
     "agx_set_lwwmap": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]),
+    "agx_set_lwwmap_delta": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32]),
     "agx_set_behaviors": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                            ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]),
     "agx_set_fanout": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, c_u32p, c_u32p,
@@ -181,7 +182,7 @@ SIGNATURES = {
 OPTIONAL = {"agx_tell", "agx_pump_idle", "agx_pump_cancel", "agx_exchange_info", "agx_run_timed", "agx_build_hash",
             "agx_persist_info", "agx_set_router_logics", "agx_router_info", "agx_read_hash_ring", "agx_set_sharding",
             "agx_sharding_info", "agx_read_entities", "agx_set_backoff", "agx_backoff_info", "agx_read_backoff",
-            "agx_set_lwwmap"}
+            "agx_set_lwwmap", "agx_set_lwwmap_delta"}
 
 
 def load():

@@ -24,8 +24,8 @@ struct GroupLaunch {
   hipError_t (*ring)(uint32_t vid, bool tiny, dim3, hipStream_t, const BucketArgs&, const RingArgs&);
   hipError_t (*persist_occupancy)(uint32_t vid, int*);
 };
-#define AGX_GROUPS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11)
-static_assert(kVGroups == 12, "AGX_GROUPS names every group");
+#define AGX_GROUPS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
+static_assert(kVGroups == 13, "AGX_GROUPS names every group");
 #define AGX_GROUP_DECL(g) const GroupLaunch& agx_group_##g();
 AGX_GROUPS(AGX_GROUP_DECL)
 
@@ -36,16 +36,16 @@ hipError_t launch_v(uint32_t mode, bool skew, dim3 g, hipStream_t s, const Bucke
   constexpr bool W = kVariants[V].wide;
   constexpr uint32_t M = kVariants[V].km;
   const dim3 blk(kBThreads);
-  if constexpr (V == V_LWWMAP || V == V_PNCMAP || V == V_ORMM)  // (single-rank engines only: no owner-mode instantiation)
+  if constexpr (V == V_LWWMAP || V == V_PNCMAP || V == V_ORMM || V == V_LWWMAP_DELTA)  // (single-rank engines only: no owner-mode instantiation)
     if (mode == M_OWNER) return hipErrorInvalidValue;
   switch (mode * 2 + (skew ? 1u : 0u)) {
     case M_FUSED * 2: hipLaunchKernelGGL((k_bucket_apply<W, M, true, false, false>), g, blk, 0, s, ba); break;
     case M_FUSED * 2 + 1: hipLaunchKernelGGL((k_bucket_apply<W, M, true, true, false>), g, blk, 0, s, ba); break;
     case M_OWNER * 2:
-      if constexpr (V != V_LWWMAP && V != V_PNCMAP && V != V_ORMM) hipLaunchKernelGGL((k_bucket_apply<W, M, false, false, true>), g, blk, 0, s, ba);
+      if constexpr (V != V_LWWMAP && V != V_PNCMAP && V != V_ORMM && V != V_LWWMAP_DELTA) hipLaunchKernelGGL((k_bucket_apply<W, M, false, false, true>), g, blk, 0, s, ba);
       break;
     case M_OWNER * 2 + 1:
-      if constexpr (V != V_LWWMAP && V != V_PNCMAP && V != V_ORMM) hipLaunchKernelGGL((k_bucket_apply<W, M, false, true, true>), g, blk, 0, s, ba);
+      if constexpr (V != V_LWWMAP && V != V_PNCMAP && V != V_ORMM && V != V_LWWMAP_DELTA) hipLaunchKernelGGL((k_bucket_apply<W, M, false, true, true>), g, blk, 0, s, ba);
       break;
     case M_BYPASS * 2: hipLaunchKernelGGL((k_bucket_apply<W, M, false, false, false>), g, blk, 0, s, ba); break;
     case M_BYPASS * 2 + 1: hipLaunchKernelGGL((k_bucket_apply<W, M, false, true, false>), g, blk, 0, s, ba); break;
@@ -215,6 +215,39 @@ static_assert(kOrmmGroup == 11, "k_ormm_merge lives in V_ORMM's unit");
 hipError_t agx_launch_ormm_merge(dim3 g, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
                                  const uint32_t* orw_n) {
   hipLaunchKernelGGL(k_ormm_merge, g, dim3(kThreads), 0, s, P, orw, orm, orw_n);
+  return hipGetLastError();
+}
+#endif
+
+#if AGX_VGROUP == 12
+static_assert(kLwwmapDeltaGroup == 12, "k_lwwmap_delta_merge lives in V_LWWMAP_DELTA's unit");
+namespace {
+// LWWMap populations with delta replication (agx_set_lwwmap_delta): the state effects of every replica run the
+// apply listed (lwd_protocol did the tells, the row allocation and the placeholder decisions): one wave per
+// replica, lane = key = ring slot (lwwmap_delta_merge_wave).  The clock arguments as k_lwwmap_merge's.  Defined here, not in
+// agx_kernels.h: only this unit launches it, so only this unit compiles it.
+__global__ void __launch_bounds__(kThreads) k_lwwmap_delta_merge(DevParams P, const uint4* orw, const uint2* orm,
+                                                                    const uint32_t* orw_n, const uint32_t* step0,
+                                                                    uint32_t slot, uint32_t clock, long long base) {
+  const uint32_t n = orw_n[0];
+  const CrdtHeap H = crdt_heap(P);
+  const int64_t now = (int64_t)base + (int64_t)((uint64_t)*step0 + slot + 1ull);
+  const uint32_t nw = gridDim.x * (kThreads / kWave);
+  // the wave's index through readfirstlane: the compiler then knows the run, its messages and the replica's
+  // version vector, deltaVersions and selector words to be wave-uniform (scalar registers, scalar branches)
+  const uint32_t it0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave));
+  for (uint32_t it = it0; it < n; it += nw) {
+    const uint4 w = orw[it];
+    const uint2* msg = orm + w.z;
+    lwwmap_delta_merge_wave(P, H, w.x, w.y & 0xFFu, w.y >> 8, w.w, clock, now, [&](uint32_t q) { return msg[q].x; },
+                            [&](uint32_t q) { return msg[q].y; });
+  }
+}
+}  // namespace
+hipError_t agx_launch_lwwmap_delta_merge(dim3 g, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
+                                         const uint32_t* orw_n, const uint32_t* step0, uint32_t slot, uint32_t clock,
+                                         int64_t base) {
+  hipLaunchKernelGGL(k_lwwmap_delta_merge, g, dim3(kThreads), 0, s, P, orw, orm, orw_n, step0, slot, clock, (long long)base);
   return hipGetLastError();
 }
 #endif

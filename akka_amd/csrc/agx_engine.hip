@@ -399,6 +399,7 @@ struct agx_engine {
   // LWWMap engines (agx_set_lwwmap): the LWWRegister clock; d_lww_step0 = the supersteps with mail that ran
   // before the replay being launched (k_lwwmap_merge's logical time; written stream-ordered, run_single)
   uint32_t lww_clock = AGX_LWW_CLOCK_DEFAULT;
+  uint32_t lww_delta_max = 0;  // LWWMap delta replication (agx_set_lwwmap_delta): max-delta-size, 0 = off (delta_max stays 0)
   uint64_t lww_base = 0;
   uint32_t* d_lww_step0 = nullptr;
   unsigned long long* d_ring_total = nullptr;
@@ -722,7 +723,7 @@ DevParams make_params(agx_engine* e) {
   P.pw = e->pw;
   P.gossip_f = e->gossip_f;
   P.gossip_seed = e->gossip_seed;
-  P.delta_max = e->delta_max;
+  P.delta_max = e->delta_max ? e->delta_max : e->lww_delta_max;  // (never both: agx_set_lwwmap_delta)
   P.bcase = e->d_bcase;
   P.bact = e->d_bact;
   P.bfirst = e->d_bfirst;
@@ -892,7 +893,8 @@ uint32_t apply_variant(const agx_engine* e) {
     if (km == kb(AGX_KIND_GCOUNTER)) return V_GC;
     if (km == kb(AGX_KIND_PNCOUNTER)) return V_PN;
     if (km == kb(AGX_KIND_ORSET)) return V_OR;
-    if (km == kb(AGX_KIND_LWWMAP)) return V_LWWMAP;  // (an LWWMap engine holds nothing else: agx_register_range)
+    if (km == kb(AGX_KIND_LWWMAP))  // (an LWWMap engine holds nothing else: agx_register_range)
+      return e->lww_delta_max ? V_LWWMAP_DELTA : V_LWWMAP;
     if (km == kb(AGX_KIND_PNCOUNTERMAP)) return V_PNCMAP;  // (nor does a PNCounterMap engine)
     if (km == kb(AGX_KIND_ORMULTIMAP)) return V_ORMM;      // (nor an ORMultiMap engine)
     if ((km & ~kCrdtKM) == 0) return V_CRDT;  // CRDT kinds only: no plain-behaviour code
@@ -1523,7 +1525,8 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
   }
   {
     const uint32_t vid = apply_variant(e);
-    const bool lwm = vid == V_LWWMAP;       // LWWMap-only: state effects in k_lwwmap_merge
+    const bool lwd = vid == V_LWWMAP_DELTA;  // LWWMap with delta replication: state effects in k_lwwmap_delta_merge
+    const bool lwm = vid == V_LWWMAP || lwd;  // LWWMap-only: state effects in k_lwwmap_merge
     const bool pnm = vid == V_PNCMAP;       // PNCounterMap-only: state effects in k_pncmap_merge
     const bool mmm = vid == V_ORMM;         // ORMultiMap-only: state effects in k_ormm_merge
     const bool orm = vid == V_OR || lwm || pnm || mmm;  // ORSet-only full state: state effects in k_orset_merge
@@ -1618,7 +1621,12 @@ agx_status launch_apply(agx_engine* e, const DevMsgs& sorted) {
       Scope s(e, K_SKEW);
       HIP_TRY(agx_launch_apply(vid, mode, true, gs, e->stream, ba));
     }
-    if (lwm) {
+    if (lwd) {
+      Scope s(e, K_APPLY);
+      HIP_TRY(agx_launch_lwwmap_delta_merge(dim3(grid_for(e->n_local / 4 + 1, 4096)), e->stream, ba.P, (const uint4*)e->d_orw,
+                                            (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n, e->d_lww_step0, e->cur_slot,
+                                            e->lww_clock, (int64_t)e->lww_base));
+    } else if (lwm) {
       Scope s(e, K_APPLY);
       HIP_TRY(agx_launch_lwwmap_merge(dim3(grid_for(e->n_local / 4 + 1, 4096)), e->stream, ba.P, (const uint4*)e->d_orw,
                                       (const uint2*)e->d_orm, (const uint32_t*)e->d_orw_n, e->d_lww_step0, e->cur_slot,
@@ -1761,8 +1769,8 @@ agx_status setup_ring_apply(agx_engine* e) {
 // ORSet-only full-state populations: k_orset_merge's work list (before any graph capture)
 agx_status setup_orset(agx_engine* e) {
   const uint32_t vid = apply_variant(e);
-  if (e->d_orw || (vid != V_OR && vid != V_LWWMAP && vid != V_PNCMAP && vid != V_ORMM)) return AGX_OK;
-  if (vid == V_LWWMAP) {
+  if (e->d_orw || (vid != V_OR && vid != V_LWWMAP && vid != V_PNCMAP && vid != V_ORMM && vid != V_LWWMAP_DELTA)) return AGX_OK;
+  if (vid == V_LWWMAP || vid == V_LWWMAP_DELTA) {
     AGX_TRY(dalloc(&e->d_lww_step0, 1));
     HIP_TRY(hipMemset(e->d_lww_step0, 0, 4));
   }
@@ -2499,6 +2507,7 @@ agx_status prepare_run(agx_engine* e) {
     const bool word_major = apply_variant(e) != V_OR && apply_variant(e) != V_LWWMAP &&  // (k_orset_merge / k_lwwmap_merge walk actor-major rows)
                             apply_variant(e) != V_PNCMAP &&                              // (k_pncmap_merge too)
                             apply_variant(e) != V_ORMM &&                                // (and k_ormm_merge)
+                            apply_variant(e) != V_LWWMAP_DELTA &&                        // (and k_lwwmap_delta_merge)
                             (lay ? lay[0] == 'w' : (e->delta_max && !(e->kinds_mask & kb(AGX_KIND_ORSET))));
     if (e->pw && !e->pitch && !word_major) {
       const uint32_t pitch = e->W <= 16 ? (e->W + 1u) & ~1u : (e->W + 15u) & ~15u;
@@ -5853,6 +5862,36 @@ agx_status agx_set_lwwmap(agx_engine* e, uint32_t clock, uint64_t base) {
   e->lww_clock = clock;
   e->lww_base = base;
   drop_graphs(e);  // (kernel arguments of the captured supersteps)
+  return AGX_OK;
+}
+
+agx_status agx_set_lwwmap_delta(agx_engine* e, uint32_t max_delta_size) {
+  if (!e) return set_err(AGX_EINVAL, "null engine");
+  // (first: a multi-rank engine cannot register LWWMap replicas at all)
+  if (e->R > 1) return set_err(AGX_EINVAL, "agx_set_lwwmap_delta: LWWMap replicas need a single-rank engine (n_ranks %u)", e->R);
+  if (!(e->kinds_mask & kb(AGX_KIND_LWWMAP)))
+    return set_err(AGX_EINVAL, "agx_set_lwwmap_delta: the engine has no LWWMap replicas (register them first)");
+  if (max_delta_size == 0 || max_delta_size > AGX_DELTA_MAX_SIZE)
+    return set_err(AGX_EINVAL, "agx_set_lwwmap_delta: max_delta_size %u is not in 1..%u (DeltaPropagation rows are sized for it)",
+                   max_delta_size, AGX_DELTA_MAX_SIZE);
+  if (e->kmax < 4) return set_err(AGX_EINVAL, "agx_set_lwwmap_delta: delta-CRDT replicas need max_emit >= 4");
+  if (e->W < AGX_LWWMAP_DELTA_WORDS)
+    return set_err(AGX_EINVAL, "agx_set_lwwmap_delta: LWWMap delta replication needs n_words >= %u (got %u)",
+                   AGX_LWWMAP_DELTA_WORDS, e->W);
+  if (e->started) return set_err(AGX_ESTATE, "set LWWMap delta replication before the first agx_run");
+  // the row pitch of the mode: full-state rows carry the deltaVersions behind their data, and both row forms
+  // stay below the length word of a DeltaPropagation (agx_lwwmap_delta.h kLdPitch)
+  static_assert(kLdPitch % kRowAlign == 0 && kLdPitch > (2 * AGX_LWWMAP_WORDS + kRowAlign - 1) / kRowAlign * kRowAlign,
+                "the row pitch of LWWMap delta replication is wider than the full-state engine's");
+  if (e->pw < kLdPitch) {
+    uint32_t* heap = nullptr;  // (the new heap first: a failed allocation leaves the engine as it was)
+    AGX_TRY(dalloc_rows(&heap, 2 * e->heap_rows * kLdPitch));
+    hipFree(e->d_heap);
+    e->d_heap = heap;
+    e->pw = kLdPitch;
+  }
+  e->lww_delta_max = max_delta_size;
+  drop_graphs(e);  // (the apply variant and the row pitch are captured in the superstep graphs)
   return AGX_OK;
 }
 

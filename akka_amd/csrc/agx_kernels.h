@@ -28,6 +28,7 @@
 #pragma once
 #include "agx_crdt.h"
 #include "agx_lwwmap.h"
+#include "agx_lwwmap_delta.h"
 #include "agx_pncmap.h"
 #include "agx_ormm.h"
 #include "agx_device.h"
@@ -2386,7 +2387,10 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     constexpr bool kPnRows = kWide && KM == kb(AGX_KIND_PNCOUNTERMAP);
     // ORMultiMap populations (V_ORMM, up to 20608-B rows): likewise (kMmRowLen, agx_ormm.h)
     constexpr bool kMmRows = kWide && KM == kb(AGX_KIND_ORMULTIMAP);
-    constexpr bool kWaveRows = kBigRows || kLwRows || kPnRows || kMmRows;
+    // LWWMap delta populations (V_LWWMAP_DELTA): full-state rows by the used length they carry (kLwRowLen, the
+    // deltaVersions included), DeltaPropagation rows by the length in their last word (agx_lwwmap_delta.h)
+    constexpr bool kLdRows = kWide && KM == (kb(AGX_KIND_LWWMAP) | kDeltaKM);
+    constexpr bool kWaveRows = kBigRows || kLwRows || kPnRows || kMmRows || kLdRows;
     static_assert(!kBigRows || !(KM & kDeltaKM) || (KM & ~kDeltaKM) == kb(AGX_KIND_ORSET),
                   "a delta variant that copies rows by their used length holds ORSet groups only: counter groups "
                   "write no length word (dl_group_row)");
@@ -2455,6 +2459,8 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
               }
               if constexpr (kLwRows)  // (the length word lies in the row's header: it travels with the copy)
                 n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kLwRowLen] + 3u) / 4u);
+              if constexpr (kLdRows)
+                if (!(pi & AGX_DELTA_ROW_BIT)) n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kLwRowLen] + 3u) / 4u);
               if constexpr (kPnRows)  // (likewise; the used length is a multiple of 4 u32)
                 n4 = min(q4, (reinterpret_cast<const uint32_t*>(s)[kPnRowLen] + 3u) / 4u);
               if constexpr (kMmRows)  // (likewise)
@@ -3560,6 +3566,11 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       const uint32_t nd = min(len, Ta);
       uint32_t kd = L.kind[la];
       constexpr bool kLwWaveA = kWide && KM == kb(AGX_KIND_LWWMAP);  // (an LWWMap engine holds LWWMap replicas only)
+      if constexpr (kWide && KM == (kb(AGX_KIND_LWWMAP) | kDeltaKM)) {  // (LWWMap delta replication: the selector simulated)
+        DeltaSim ds;
+        ds.on = false;
+        for (uint32_t q = 0; q < nd; ++q) em.count(lwd_count(P, self, l, isrc(s0 + q), ipay(s0 + q), &nrows_t, ds));
+      } else
       if constexpr (kLwWaveA) {
         for (uint32_t q = 0; q < nd; ++q) em.count(lwwmap_count(P, isrc(s0 + q), ipay(s0 + q), &nrows_t));
       } else
@@ -3644,7 +3655,9 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
     constexpr bool kPnWave = kWide && KM == kb(AGX_KIND_PNCOUNTERMAP);
     // (ORMultiMap-only variant: ormm_protocol here and k_ormm_merge after the apply)
     constexpr bool kMmWave = kWide && KM == kb(AGX_KIND_ORMULTIMAP);
-    constexpr bool kWaveList = kOrWave || kLwWave || kPnWave || kMmWave;
+    // (LWWMap delta variant: lwd_protocol here and k_lwwmap_delta_merge after the apply)
+    constexpr bool kLdWave = kWide && KM == (kb(AGX_KIND_LWWMAP) | kDeltaKM);
+    constexpr bool kWaveList = kOrWave || kLwWave || kPnWave || kMmWave || kLdWave;
   #pragma unroll 1
     for (int j = 0; j < kBAct; ++j) {
       const uint32_t la = j * kBThreads + tid;
@@ -3662,6 +3675,13 @@ __device__ __forceinline__ void bucket_finish(const BucketArgs& a, const BucketL
       const uint32_t nd = min(len, Ta);
       uint32_t kd = L.kind[la];
       ++nact;
+      if constexpr (kLdWave) {  // protocol here, state effects by k_lwwmap_delta_merge (agx_lwwmap_delta.h)
+        bool work = false;
+        const uint32_t rc0 = row_cursor;
+        nunh += lwd_protocol(P, self, l, s0, nd, isrc, ipay, row_cursor, em, &work);
+        ndel += nd;
+        L.ecnt[la] = work ? rc0 : 0xFFFFFFFFu;
+      } else
       if constexpr (kLwWave) {  // protocol here, state effects by k_lwwmap_merge (agx_lwwmap.h)
         bool work = false;
         const uint32_t rc0 = row_cursor;
@@ -7242,6 +7262,9 @@ static __global__ void __launch_bounds__(kThreads) k_lwwmap_merge(DevParams P, c
                       [&](uint32_t q) { return msg[q].y; });
   }
 }
+
+// (k_lwwmap_delta_merge, the wave kernel of LWWMap delta replication, is defined in agx_apply.hip, in the one unit that
+// launches it: kLwwmapDeltaGroup)
 
 // PNCounterMap-only populations: the state effects of every replica run the apply listed (pncmap_protocol
 // did its tells and snapshot-row allocation): one wave per replica, lane = key (pncmap_merge_wave).  The

@@ -25,6 +25,7 @@ enum : uint32_t {
   V_LWWMAP,  // LWWMap replicas only (agx_lwwmap.h); appended: the ids above do not move
   V_PNCMAP,  // PNCounterMap replicas only (agx_pncmap.h); appended likewise
   V_ORMM,    // ORMultiMap replicas only (agx_ormm.h); appended likewise
+  V_LWWMAP_DELTA,  // LWWMap replicas with delta replication (agx_lwwmap_delta.h); appended likewise
   V_N
 };
 constexpr ApplyVariant kVariants[V_N] = {
@@ -39,6 +40,7 @@ constexpr ApplyVariant kVariants[V_N] = {
     {true, kb(AGX_KIND_LWWMAP)},
     {true, kb(AGX_KIND_PNCOUNTERMAP)},
     {true, kb(AGX_KIND_ORMULTIMAP)},
+    {true, kb(AGX_KIND_LWWMAP) | kDeltaKM},
 };
 static_assert((kb(AGX_KIND_LWWMAP) & (KM_ALL | kCrdtKM | kb(AGX_KIND_COMPILED))) == 0 && kb(AGX_KIND_LWWMAP) < kBackoffKM,
               "the LWWMap kind has a mask bit of its own");
@@ -56,7 +58,7 @@ enum : uint32_t { M_FUSED = 0, M_OWNER = 1, M_BYPASS = 2, M_PERSIST = 3 /* dense
 
 // variant groups = translation units (agx_apply.hip built with -DAGX_VGROUP=0..kVGroups-1);
 // the heavy CRDT variants are spread so the units take similar time
-constexpr uint32_t kVGroups = 12;
+constexpr uint32_t kVGroups = 13;
 // the last group holds no variant of the table: it is the unit of the kSuperKM | kBackoffKM feature launches alone
 constexpr uint32_t kBackoffGroup = 8;
 // V_LWWMAP and k_lwwmap_merge are a unit of their own too, so that every other unit compiles what it compiled before
@@ -65,7 +67,10 @@ constexpr uint32_t kLwwmapGroup = 9;
 constexpr uint32_t kPncmapGroup = 10;
 // and V_ORMM and k_ormm_merge
 constexpr uint32_t kOrmmGroup = 11;
-constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7, kLwwmapGroup, kPncmapGroup, kOrmmGroup};
+// and V_LWWMAP_DELTA and k_lwwmap_delta_merge
+constexpr uint32_t kLwwmapDeltaGroup = 12;
+constexpr uint32_t kVariantGroup[V_N] = {0, 1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7, kLwwmapGroup, kPncmapGroup, kOrmmGroup,
+                                         kLwwmapDeltaGroup};
 
 // launch k_bucket_apply<variant vid, mode, skew> with `grid` x kBThreads threads on `s`
 // (defined in agx_apply.hip; returns hipErrorInvalidValue for an unknown combination)
@@ -83,6 +88,11 @@ hipError_t agx_launch_apply_feature(uint32_t vid, uint32_t mode, uint32_t km_fla
 // orw / orm / orw_n; the clock's logical time is base + *step0 + slot + 1 (agx_kernels.h)
 hipError_t agx_launch_lwwmap_merge(dim3 grid, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
                                    const uint32_t* orw_n, const uint32_t* step0, uint32_t slot, uint32_t clock, int64_t base);
+// launch k_lwwmap_delta_merge after V_LWWMAP_DELTA's apply (defined in kLwwmapDeltaGroup's unit): the arguments of
+// agx_launch_lwwmap_merge
+hipError_t agx_launch_lwwmap_delta_merge(dim3 grid, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,
+                                         const uint32_t* orw_n, const uint32_t* step0, uint32_t slot, uint32_t clock,
+                                         int64_t base);
 // launch k_pncmap_merge after V_PNCMAP's apply (defined in kPncmapGroup's unit): the runs the apply listed in
 // orw / orm / orw_n
 hipError_t agx_launch_pncmap_merge(dim3 grid, hipStream_t s, const DevParams& P, const uint4* orw, const uint2* orm,

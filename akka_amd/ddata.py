@@ -8,7 +8,9 @@
 
 The layout is include/akka_gpu.h "LWWMap replicas": the ORSet key set (64 keys x 8 u32 dots, 8 u32
 version vector), 64 int64 timestamps, 64 u32 registers (updatedBy node << 24 | value).  Writes go
-through the engine (Op.put, Op.REMOVE); `to_words` exists to seed replicas (register_range).
+through the engine (Op.put, Op.REMOVE); `to_words` exists to seed replicas (register_range).  A row of an
+engine with delta replication (set_lwwmap_delta) is wider: `from_words` decodes its first 356 words as before
+and `delta_versions` reads the 8 DataEnvelope.deltaVersions behind them.
 
     from akka_amd.ddata import PNCounterMap
     c = PNCounterMap.from_words(words[replica])
@@ -55,10 +57,14 @@ class LWWMap:
     dots: dict = field(default_factory=dict)        # key -> {node: version}, live keys only
     vvector: dict = field(default_factory=dict)     # node -> version
     registers: dict = field(default_factory=dict)   # key -> (node, value, timestamp)
+    # DataEnvelope.deltaVersions per node (the seqNr last applied from it) of a delta-width row, else None;
+    # not part of the data: `entries` and `to_words` ignore it
+    delta_versions: tuple | None = field(default=None, compare=False)
 
     @classmethod
     def from_words(cls, row) -> "LWWMap":
-        w = np.ascontiguousarray(np.asarray(row, np.uint64)[:LWWMAP_WORDS])
+        full = np.ascontiguousarray(np.asarray(row, np.uint64))
+        w = np.ascontiguousarray(full[:LWWMAP_WORDS])
         if w.size != LWWMAP_WORDS:
             raise ValueError(f"an LWWMap replica has {LWWMAP_WORDS} state words, got {w.size}")
         u = w.view(np.uint32)
@@ -73,6 +79,8 @@ class LWWMap:
             elif r or ts[k]:
                 raise ValueError(f"key {k} has no live dot but a register ({r:#x}, {int(ts[k])}): not canonical")
         m.vvector = {n: int(u[_VV + n]) for n in range(CRDT_NODES) if u[_VV + n]}
+        if full.size >= LWWMAP_WORDS + CRDT_NODES // 2:  # (a delta-width row: the envelope area follows the data)
+            m.delta_versions = tuple(int(x) for x in full[LWWMAP_WORDS:LWWMAP_WORDS + CRDT_NODES // 2].view(np.uint32))
         return m
 
     def to_words(self) -> np.ndarray:

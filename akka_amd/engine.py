@@ -42,6 +42,10 @@ CRDT_WORDS = {Kind.GCOUNTER: 8, Kind.PNCOUNTER: 16, Kind.ORSET: 260, Kind.LWWMAP
 DELTA_ENV_WORDS, DELTA_LOG = 12, 64
 CRDT_DELTA_WORDS = {k: w + DELTA_ENV_WORDS + (DELTA_LOG * 6 if k == Kind.ORSET else 4) for k, w in CRDT_WORDS.items()
                     if k not in (Kind.LWWMAP, Kind.PNCOUNTERMAP, Kind.ORMULTIMAP)}  # (map replicas gossip their full state only)
+# LWWMap delta replication (agx_set_lwwmap_delta): data + envelope/selector area + a ring of 64 entries of 16 u32
+LWWMAP_DELTA_LOG_U32 = 16
+LWWMAP_DELTA_WORDS = CRDT_WORDS[Kind.LWWMAP] + DELTA_ENV_WORDS + DELTA_LOG * LWWMAP_DELTA_LOG_U32 // 2  # AGX_LWWMAP_DELTA_WORDS = 880
+DELTA_MAX_SIZE = 50  # AGX_DELTA_MAX_SIZE
 LWW_VALUE_MAX = 0x3FFFF
 PNCMAP_COUNT_MAX = 0x3FFFF  # AGX_PNCMAP_COUNT_MAX
 ORMM_VALUES = 8             # AGX_ORMM_VALUES: the value universe of an ORMultiMap key's set
@@ -683,6 +687,15 @@ class GpuEngine:
     def set_delta_crdt(self, max_delta_size: int) -> None:
         """Replicator delta-crdt.enabled / max-delta-size (0 = off)."""
         check(self.lib.agx_set_delta_crdt(self._h, max_delta_size))
+
+    def set_lwwmap_delta(self, max_delta_size: int = DELTA_MAX_SIZE) -> None:
+        """Delta replication for an LWWMap engine (ORMap.DeltaOp: PutDeltaOp / RemoveDeltaOp groups, causal delivery,
+        full-state gossip as the repair path): max_delta_size 1..50; needs n_words >= LWWMAP_DELTA_WORDS and
+        max_emit >= 4.  After the LWWMap replicas are registered, before the first run."""
+        fn = getattr(self.lib, "agx_set_lwwmap_delta", None)
+        if fn is None:
+            raise RuntimeError("this libakka_gpu.so has no agx_set_lwwmap_delta (an older build)")
+        check(fn(self._h, max_delta_size))
 
     def set_lwwmap(self, clock: str = "default", base: int = 0) -> None:
         """The LWWRegister clock of an LWWMap engine: "default" (last write wins) or "reverse" (first write

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .engine import CRDT_DELTA_WORDS, CRDT_NODES, CRDT_WORDS, DELTA_WRITE, Kind, NO_SENDER, Op
+from .engine import CRDT_DELTA_WORDS, CRDT_NODES, CRDT_WORDS, DELTA_WRITE, LWWMAP_DELTA_WORDS, Kind, NO_SENDER, Op
 
 SEED = 0x5EED
 M64 = (1 << 64) - 1
@@ -39,6 +39,7 @@ class Workload:
     gossip: tuple | None = None  # (fanout, seed)
     delta_crdt: int = 0          # Replicator max-delta-size (0 = full-state gossip only)
     lwwmap: tuple | None = None  # (clock, base) of an LWWMap engine (agx_set_lwwmap)
+    lwwmap_delta: int = 0        # max-delta-size of an LWWMap engine with delta replication (agx_set_lwwmap_delta; 0 = off)
     behaviors: object = None     # compiled behaviour tables (akka_amd.typed.Tables)
     fanout: tuple | None = None  # (k, seed, cdf, perm)
     graph: tuple | None = None   # (row_ptr, col)
@@ -113,6 +114,8 @@ class Workload:
             target.set_delta_crdt(self.delta_crdt)
         if self.lwwmap is not None:
             target.set_lwwmap(*self.lwwmap)
+        if self.lwwmap_delta:
+            target.set_lwwmap_delta(self.lwwmap_delta)
         if self.behaviors is not None:
             target.set_behaviors(self.behaviors)
         if self.receptionist:  # (empty: targets without the calls are unaffected)
@@ -427,6 +430,35 @@ def crdt_delta(n: int = 1_000_000, kind: int = Kind.ORSET, rounds: int = 32, wri
     return Workload(f"crdt_delta_{kind}", n, CRDT_DELTA_WORDS[kind], max(4, fanout + 1), throughput, capacity,
                     [(0, n, kind, None)], gossip=(fanout, seed), delta_crdt=max_delta_size, tells=(dst, src, pay),
                     bucket_actors=bucket_actors)
+
+
+def crdt_lwwmap_delta(n: int = 1_000_000, rounds: int = 32, write: bool = True, ops_per_replica: int = 0,
+                      gossip_rounds: int = 0, fanout: int = 1, max_delta_size: int = 50, throughput: int = 5,
+                      seed: int = SEED, capacity: int = 0, clock: str = "default", base: int = 0,
+                      bucket_actors: int = 512) -> Workload:
+    """LWWMap replicas with delta replication (ORMap.DeltaOp; agx_set_lwwmap_delta) in crdt_delta's shape: keys of
+    8 replicas (id = 8 * key + node).  Each replica first applies `ops_per_replica` host puts and removes
+    (lwwmap_ops: about one remove in five, over a dozen keys), then runs `rounds` DeltaPropagationTicks (`write`:
+    each tick also tells the replica one seeded put or remove, a writer client) and, if `gossip_rounds`, that many
+    full-state GossipTicks to `fanout` random replicas of its key."""
+    ids = np.arange(n, dtype=np.uint32)
+    dsts, pays = [], []
+    if ops_per_replica:
+        removes = ops_per_replica // 5
+        dsts.append(np.repeat(ids, ops_per_replica))
+        pays.append(lwwmap_ops(n, ops_per_replica - removes, removes, seed=seed).reshape(-1))
+    if rounds:
+        dsts.append(ids)
+        pays.append(np.full(n, Op.make(Op.DELTA_TICK, (rounds - 1) | (DELTA_WRITE if write else 0)), np.uint32))
+    if gossip_rounds:
+        dsts.append(ids)
+        pays.append(np.full(n, Op.make(Op.GOSSIP, gossip_rounds - 1), np.uint32))
+    dst = np.concatenate(dsts)
+    pay = np.concatenate(pays)
+    src = np.full(dst.size, NO_SENDER, np.uint32)
+    return Workload("crdt_lwwmap_delta", n, LWWMAP_DELTA_WORDS, max(4, fanout + 1), throughput, capacity,
+                    [(0, n, Kind.LWWMAP, None)], gossip=(fanout, seed), lwwmap=(clock, base), lwwmap_delta=max_delta_size,
+                    tells=(dst, src, pay), bucket_actors=bucket_actors)
 
 
 def crdt_delta_mixed(counts=(320, 320, 320), rounds: int = 8, throughput: int = 1, capacity: int = 0,

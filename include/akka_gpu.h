@@ -411,8 +411,9 @@ typedef struct agx_act {
  *   AGX_LWW_CLOCK_REVERSE  min(-now, timestamp - 1)    LWWRegister.reverseClock (first write wins)
  * A timestamp that would pass the int64 range raises AGX_ERANGE (the reference's Long would wrap),
  * as a wrapping ORSet version does.
- * An LWWMap engine holds LWWMap replicas only, on one rank, with full-state gossip.  Left out:
- * LWWRegister as a kind of its own, GSet, Flag, ORMap delta ops, pruning, multi-rank engines,
+ * An LWWMap engine holds LWWMap replicas only, on one rank, with full-state gossip -- and, after
+ * agx_set_lwwmap_delta, delta replication ("LWWMap delta replication" below).  Left out:
+ * LWWRegister as a kind of its own, GSet, Flag, pruning, multi-rank engines,
  * custom clocks, the JVM shim.  (PNCounterMap and ORMultiMap are kinds of their own, below.)     */
 #define AGX_LWWMAP_WORDS 356u /* 260 (keys) + 64 (timestamps) + 32 (64 u32 registers) */
 #define AGX_LWWMAP_TS_WORD 260u
@@ -422,6 +423,55 @@ typedef struct agx_act {
 #define AGX_OP_PUT_ARG(key, value) (((uint32_t)(key) & 63u) | ((uint32_t)(value) << 6))
 #define AGX_LWW_CLOCK_DEFAULT 0u
 #define AGX_LWW_CLOCK_REVERSE 1u
+
+/* --- LWWMap delta replication (agx_set_lwwmap_delta; ORMap.DeltaOp, DD/ORMap.scala:30-164) -----
+ * An LWWMap engine in this mode follows the delta contract of "delta-CRDT replication" above: keys
+ * of AGX_CRDT_NODES consecutive replicas, the DeltaPropagationSelector (slice size, round robin,
+ * deltaSentToNode), causal delivery (ORMap.DeltaOp is RequiresCausalDeliveryOfDeltas), full-state
+ * gossip among the replicas of a key carrying the sender's deltaVersions.  LWWMap.put goes through
+ * ORMap.put (DD/LWWMap.scala:144-150, DD/ORMap.scala:254-265), so the deltas are PutDeltaOp (the
+ * ORSet.AddDeltaOp of the key and the full register) and RemoveDeltaOp only.
+ * State, AGX_LWWMAP_DELTA_WORDS u64 per replica (u32 view):
+ *   u32[0 .. 711]          the AGX_LWWMAP_WORDS data words, as above
+ *   u32[712 + 0..7]        DataEnvelope.deltaVersions
+ *   u32[712 + 8]           deltaCounter            u32[712 + 9]  deltaNodeRoundRobinCounter
+ *   u32[712 + 10..17]      deltaSentToNode per node            (u32[712 + 18..23] always 0)
+ *   u32[736 + 16 * (seq % AGX_DELTA_LOG) ..+ 15], a ring of AGX_DELTA_LOG entries of
+ *   AGX_LWWMAP_DELTA_LOG_U32 u32, one per seqNr:
+ *     PutDeltaOp     {seq, 1 | key << 8, the key's new dot version, register word, timestamp lo, hi, 0 x 10}
+ *     RemoveDeltaOp  {seq, 2 | key << 8, 0 x 6, the remover's version vector[8]}   (DD/ORSet.scala:382)
+ *   A local update that would overwrite a seqNr some node of the key has not been sent raises
+ *   AGX_ECAPACITY, as for ORSet.
+ * Local updates: every AGX_OP_PUT records one PutDeltaOp under the next seqNr, every AGX_OP_REMOVE
+ * with key < 64 one RemoveDeltaOp (ORSet.add and ORSet.remove always yield a delta: no placeholder
+ * comes from a local op).
+ * AGX_OP_DELTA_TICK arg = k | AGX_DELTA_WRITE?: with AGX_DELTA_WRITE the replica first tells itself one
+ * seeded update, r = fanout_rand(seed, self, k | 0x04000000, 0):
+ *     ((r >> 40) & 3) != 0 ? AGX_OP_PUT, arg = AGX_OP_PUT_ARG((r >> 48) & 7, (r >> 8) & AGX_LWWMAP_VALUE_MAX)
+ *                          : AGX_OP_REMOVE, arg = (r >> 48) & 7
+ * then for each node of the slice with seqNrs after deltaSentToNode it folds those entries with
+ * ORMap.DeltaOp.merge (DD/ORMap.scala:62-65,76-91,140-158): a put merges into the group's last op only
+ * when that op is a put of the same key (the merged op keeps the later register and the later dot; the
+ * merged one-node version vector is that dot, DD/ORSet.scala:57-76), everything else is appended.  A
+ * group of two or more seqNrs with deltaSize (its ops) >= max_delta_size is a NoDeltaPlaceholder: not
+ * told, deltaSentToNode advances all the same.  If k > 0, DELTA_TICK(k - 1) to itself.
+ * DeltaPropagation row (payload data type 3 | AGX_DELTA_ROW_BIT), u32: the 12-u32 header of the other
+ * delta kinds ([0] ops, [1] from node, [2] fromSeqNr, [3] toSeqNr, [4..11] the sender's deltaVersions),
+ * then per op  PutDeltaOp {1 | key << 8, dot version, register word, timestamp lo, hi}  or
+ * RemoveDeltaOp {2 | key << 8, version vector[8]}.  A group has at most AGX_DELTA_MAX_SIZE - 1 ops:
+ * at most 12 + 9 * 49 = 453 u32 (AGX_LWWMAP_DELTA_ROW_U32); the row's last word (pitch - 1) holds
+ * its used length.  A full-state row carries the 8 deltaVersions behind its data and counts them in
+ * its length word: at most 736 + 8 u32 (AGX_LWWMAP_DELTA_STATE_ROW_U32), within the pitch of 768.
+ * Receipt: skipped if toSeqNr <= deltaVersions(from) or fromSeqNr > deltaVersions(from) + 1; else
+ * ORMap.mergeDelta (DD/ORMap.scala:425-503) -- dryMergeDelta walks the ops in order over a copy (a put:
+ * keys.mergeDelta(AddDeltaOp), the value overwritten; a remove: the value dropped, mergeRemoveDelta),
+ * then this.merge(copy) -- and deltaVersions(from) = toSeqNr.  The canonical form holds afterwards.
+ * Left out: PNCounterMap and ORMultiMap deltas (UpdateDeltaOp, RemoveKeyDeltaOp, value deltas), mixed
+ * populations, multi-rank engines, pruning, an unbounded delta log, the JVM shim.                   */
+#define AGX_LWWMAP_DELTA_LOG_U32 16u
+#define AGX_LWWMAP_DELTA_WORDS (AGX_LWWMAP_WORDS + AGX_DELTA_ENV_WORDS + AGX_DELTA_LOG * AGX_LWWMAP_DELTA_LOG_U32 / 2u) /* 880 */
+#define AGX_LWWMAP_DELTA_ROW_U32 453u
+#define AGX_LWWMAP_DELTA_STATE_ROW_U32 744u
 
 /* --- PNCounterMap replicas (AGX_KIND_PNCOUNTERMAP) -------------------------------------------
  * PNCounterMap[A] = ORMap[A, PNCounter] over the 64-key universe (DD/PNCounterMap.scala:105-106 increment,
@@ -595,6 +645,12 @@ agx_status agx_set_delta_crdt(agx_engine* eng, uint32_t max_delta_size);
  * call after registering the LWWMap replicas and before the first agx_run (AGX_ESTATE afterwards).
  * AGX_EINVAL: an engine without LWWMap replicas, an unknown clock, base >= 2^62.                  */
 agx_status agx_set_lwwmap(agx_engine* eng, uint32_t clock, uint64_t base);
+/* Delta replication for an LWWMap engine (see "LWWMap delta replication" above): max_delta_size =
+ * 1..AGX_DELTA_MAX_SIZE.  Call after registering the LWWMap replicas and before the first agx_run
+ * (AGX_ESTATE afterwards); agx_set_lwwmap keeps working, in either order.  AGX_EINVAL: an engine without
+ * LWWMap replicas, max_delta_size out of range, max_emit < 4, more than one rank, n_words <
+ * AGX_LWWMAP_DELTA_WORDS.  (agx_set_delta_crdt stays refused on an LWWMap engine.)                  */
+agx_status agx_set_lwwmap_delta(agx_engine* eng, uint32_t max_delta_size);
 /* Compiled behaviours (see "compiled behaviours" above): behaviour b = cases
  * [first[b], first[b+1]); first has n_behaviors + 1 entries.  Replaces the tables of an
  * earlier call; call before agx_run.  Register actors with kind AGX_KIND_COMPILED + b.      */

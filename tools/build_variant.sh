@@ -9,7 +9,8 @@ OUT=$ROOT/akka_amd/lib/var/$NAME; mkdir -p "$OUT"
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -Wno-unused-value -I/opt/rocm/include $*"
 pids=()
 /opt/rocm/bin/hipcc $F -c -o "$OUT/e.o" "$SRC/akka_amd/csrc/agx_engine.hip" & pids+=($!)
-for g in 0 1 2 3 4 5 6 7 8 9 10 11; do
+NG=$(sed -n 's/^constexpr uint32_t kVGroups = \([0-9]*\);.*/\1/p' "$SRC/akka_amd/csrc/agx_variants.h")  # (the checkout's own group count)
+for g in $(seq 0 $((NG - 1))); do
   /opt/rocm/bin/hipcc $F -DAGX_VGROUP=$g -c -o "$OUT/a$g.o" "$SRC/akka_amd/csrc/agx_apply.hip" & pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
